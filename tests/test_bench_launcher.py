@@ -107,3 +107,40 @@ def test_bench_oracle_fixture_check_logic():
     assert r3["applicable"] and not r3["ok"] and r3["first_timed_batch"]["images_differing_outside_the_fragile_set"] == [victim]
     # another batch size than the fixture's
     assert not bench.oracle_fixture_check(args, 128, {"first": (first[:128], keys[0]), "last": (last[:128], keys[1])})["applicable"]
+
+
+def test_steps_and_warmup_are_checked_before_anything_runs():
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        p = _run(bad)
+        assert p.returncode != 0 and "--steps" in p.stderr and p.stdout.strip() == ""
+
+
+def test_dump_outputs_writer(tmp_path):
+    """``--dump-outputs DIR``'s writer, host logic only: float32 (float64 kept; integers beyond float32's exact range as float64),
+    shapes kept (0-d too), and over 64 MB one fixed seeded subset of rows shared by every batch-shaped array."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    tok = (np.arange(256 * 49, dtype=np.int64) % 128).reshape(256, 7, 7)
+    img = (np.arange(256 * 784) % 256).astype(np.uint8).reshape(256, 1, 28, 28)
+    s = bench.dump_outputs(str(tmp_path / "a"), {"tokens": tok, "images": img, "loss": np.float64(0.25),
+                                                 "wide": np.array([(1 << 40) + 1])})
+    assert not s["sampled"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("tokens", "images", "loss", "wide")}
+    assert got["tokens"].dtype == np.float32 and np.array_equal(got["tokens"], tok)
+    assert got["images"].dtype == np.float32 and np.array_equal(got["images"], img)
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == () and float(got["loss"]) == 0.25
+    assert got["wide"].dtype == np.float64 and int(got["wide"][0]) == (1 << 40) + 1
+    n = 40000                                                    # 40000 x 3 x 32 x 32 fp32 = 492 MB: sampled
+    big = {"images": np.broadcast_to(np.arange(n, dtype=np.uint8)[:, None, None, None], (n, 3, 32, 32)),
+           "tokens": np.broadcast_to(np.arange(n, dtype=np.int64)[:, None, None], (n, 8, 8))}
+    for d in ("b", "c"):
+        s = bench.dump_outputs(str(tmp_path / d), big)
+        assert s["sampled"]
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64 << 20
+    rows = np.load(tmp_path / "b" / "tokens.rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "images.rows.npy"))
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "tokens.rows.npy"))          # fixed from run to run
+    assert np.array_equal(np.load(tmp_path / "b" / "tokens.npy")[:, 0, 0], rows)
