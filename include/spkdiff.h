@@ -10,8 +10,7 @@
  * Contract (all functions):
  *   - plain C types only; every pointer is a DEVICE pointer owned by the caller (PyTorch); the library never
  *     allocates or frees device memory, reads no environment variable and keeps no mutable global state (the launch-shape
- *     options of earlier rounds are compile-time constants here; only a `make variants` build -- include/spkdiff_variants.h --
- *     keeps them settable, for repeating the recorded A/B measurements);
+ *     choices of earlier rounds are fixed in the sources);
  *   - work is enqueued asynchronously on ``stream`` (a hipStream_t; pass torch.cuda.current_stream().cuda_stream);
  *   - returns 0 on success, SPK_ERR_* (< 0) for argument errors, a positive hipError_t for launch failures;
  *   - reentrant across streams and host threads.

@@ -27,8 +27,7 @@
 // rows.
 //
 // Sides of one to four channels (the 1 -> 32 / 3 -> 32 first layer, the 32 -> 1 / 32 -> 3 read-out layer) are vector kernels: there is no
-// matrix in them.  Every variant that was built and measured slower stays behind a knob below, with its numbers
-// (profiles/r5_ab_conv_train.txt holds the A/B records, ablations, counters and phase stamps).
+// matrix in them.  The variants that were built and measured slower, and the ablations, are recorded in profiles/r5_ab_conv_train.txt.
 #include "spk_common.h"
 #include "../../include/spkdiff.h"
 #include <mutex>
@@ -37,44 +36,11 @@ namespace {
 
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-#ifndef CT_STAGE_A
-#define CT_STAGE_A 0                               // 1: the gather kernel's input records go through a per-wave LDS transpose (coalesced 16-byte
-#endif                                             // requests: LPR lanes per row instead of one).  Built because "lane = row" touches 32 - 64 cache
-                                                   // lines per request; measured SLOWER (same box, N = 512: dec.convT2 forward 80.3 against 66.0 us,
-                                                   // sum of the ten matrix-path launches of a VQ-VAE iteration 289 against 265 us,
-                                                   // profiles/r5_ab_conv_train.txt): the LDS tiles cost a workgroup per CU, and the address unit
-                                                   // was not what set the pace (the no-load ablation, CT_DBG 4, runs the same launch in 72 us)
-#ifndef CT_WGRAD_LDS
-#define CT_WGRAD_LDS 1                             // 0: the weight gradient always reads its operands from global memory (the first form)
-#endif
-#ifndef CT_C1_ROWS_CAP
-#define CT_C1_ROWS_CAP 4096                        // workgroups of the few-channel gather kernels (at most; each walks output rows)
-#endif
-#ifndef CT_C1W_CAP
-#define CT_C1W_CAP 1024                            // workgroups of the few-channel weight gradient (at most)
-#endif
-#ifndef CT_WL_FUSE_BIAS
-#define CT_WL_FUSE_BIAS 1                          // LDS-staged weight gradient: bias column sums from the staged rows (0: a second pass over gy)
-#endif
-#ifndef CT_WL_PINGPONG
-#define CT_WL_PINGPONG 0                           // 1: LDS-staged weight gradient with the two halves of a workgroup alternating between their MFMA
-#endif                                             // phase and their request / LDS-write phase (one buffer per half, two barriers per block).  Built
-                                                   // because the in-step form's parts add up; measured SLOWER (same box: dec.convT2 109.5 against 87.2 us,
-                                                   // enc.conv2 46.8 against 40.6, dec.convT1 53.9 against 45.7): a wave alone on its SIMD does not
-                                                   // issue its MFMAs twice as fast -- every step waits for its own LDS reads with nobody to fill in
-#ifndef CT_SUBPIXEL
-#define CT_SUBPIXEL 0                              // 1: the stride-2 transposed form takes ALL FOUR sub-pixel classes of 32 coarse positions per item
-                                                   // (conv_train_gather_sub_kernel).  Built to amortise the per-item index arithmetic; measured SLOWER
-                                                   // (same box, us per call: dec.convT2 forward 69.1 against 64.4, enc.conv2 data gradient 35.6 against
-                                                   // 29.6, dec.convT1 forward 33.0 against 23.4): 182 registers put one workgroup on a CU instead of two
-#endif
-#ifndef CT_BIG_ITEMS
-#define CT_BIG_ITEMS 2048                          // a wave takes all column tiles of its 32 rows from this many items on (below: one column tile)
-#endif
-#ifndef CT_DBG
-#define CT_DBG 0                                   // timing experiments only (results are wrong; 32 / 64 / 128: the LDS-staged weight gradient without
-                                                   // its bias sums / MFMAs / global requests): 1 wgrad without operand loads, 2 wgrad without
-#endif                                             // MFMAs, 4 gather without input loads, 8 gather without MFMAs, 16 gather without stores
+// (a per-wave LDS transpose of the gather kernel's input records for coalesced requests measured slower: dec.convT2 forward 80.3
+//  against 66.0 us, profiles/r5_ab_conv_train.txt (3))
+constexpr int CT_C1_ROWS_CAP = 4096;               // workgroups of the few-channel gather kernels (at most; each walks output rows)
+constexpr int CT_C1W_CAP = 1024;                   // workgroups of the few-channel weight gradient (at most)
+constexpr int CT_BIG_ITEMS = 2048;                 // a wave takes all column tiles of its 32 rows from this many items on (below: one column tile)
 constexpr int MAX_TAPS = 16;                       // k <= 4
 constexpr int GATHER_LDS_MAX = 150 * 1024;
 
@@ -110,7 +76,6 @@ template <int J, int CN, int NTH>
 __device__ __forceinline__ void stage_weights(const GArgs& a, float4* sB, const int co0, const int tid) {
   constexpr int CP = CN * 32, CRED = J * 8;
   const int ntap = a.k * a.k;
-  if (CT_DBG & 256) return;                        // (timing experiment: no weight staging)
   // staging: 16-byte loads along whichever weight dimension is contiguous, SB requests in flight per thread (the weights are
   // L2-resident; one request at a time cost 30+ us per launch)
   constexpr int SB = 6;
@@ -196,19 +161,12 @@ __global__ __launch_bounds__(512) void conv_train_gather_kernel(GArgs a, ClassTa
   __shared__ ClassTab ct;                           // (LDS copy of the host-built table: published by the barrier behind the weight staging)
   if (threadIdx.x < sizeof(ClassTab) / 4) reinterpret_cast<int*>(&ct)[threadIdx.x] = reinterpret_cast<const int*>(&ct_arg)[threadIdx.x];
   constexpr int CP = CN * 32, CRED = J * 8, ROWS = RM * 32;
-  constexpr bool STAGE = CT_STAGE_A && (J == 1 || J == 2 || J == 4 || J == 8);       // (a power of two lanes per row)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int cs = a.form ? a.stride : 1;            // output step per class-grid step
   const int ai = a.form ? 1 : a.stride;            // input step per class-grid step
   const int co0 = blockIdx.y * CP;                 // first output channel of this workgroup
-  unsigned long long stamp[4] = {0, 0, 0, 0};      // (CT_DBG 512: s_memrealtime at start / tables built / weights staged / items done -> a.out)
-  if (CT_DBG & 512) stamp[0] = __builtin_amdgcn_s_memrealtime();
-  const int ntap = a.k * a.k;
-  float4* const sA = sB + ntap * J * 2 * CP;          // STAGE: [8 waves][32 rows][Cred / 4] operand tiles behind the weights
-  if (CT_DBG & 512) stamp[1] = __builtin_amdgcn_s_memrealtime();
   stage_weights<J, CN, NTH>(a, sB, co0, tid);
   __syncthreads();
-  if (CT_DBG & 512) stamp[2] = __builtin_amdgcn_s_memrealtime();
 
   const int nitems = ct.first[cs * cs];
   const int r = lane & 31, h = lane >> 5;
@@ -271,63 +229,19 @@ __global__ __launch_bounds__(512) void conv_train_gather_kernel(GArgs a, ClassTa
             for (int cn = 0; cn < CN; ++cn) {
               const float av = q == 0 ? src[rm][j].x : q == 1 ? src[rm][j].y : q == 2 ? src[rm][j].z : src[rm][j].w;
               const float bv = q == 0 ? B[cn].x : q == 1 ? B[cn].y : q == 2 ? B[cn].z : B[cn].w;
-              if (CT_DBG & 8) acc[rm][cn][0] += av + bv;
-              else acc[rm][cn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[rm][cn], 0, 0, 0);
+              acc[rm][cn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[rm][cn], 0, 0, 0);
             }
       }
     };
-    if constexpr (STAGE) {
-      // Coalesced requests + a per-wave LDS transpose.  With "lane = row" a 16-byte request per lane touches 32 - 64 cache lines
-      // per instruction and the CU's one texture-address unit, not the matrix pipe, set the pace (measured: 2x the MFMA time).
-      // Here LPR = Cred / 4 consecutive lanes cover one row's record (8 full lines per instruction), the wave writes the 32 rows
-      // to its own LDS tile (chunks XOR-swizzled by row: conflict-free both ways) and reads its operands back row-wise.  LDS
-      // operations of a wave execute in order; the asm statements only keep the compiler from reordering across them.
-      static_assert(RM == 1, "staged form: one row tile per wave");
-      constexpr int LPR = 2 * J, RPI = 64 / LPR, SH = LPR >= 8 ? 0 : (LPR == 4 ? 1 : 2), MASK = LPR >= 8 ? 7 : LPR - 1;
-      float4* const sAw = sA + wave * (32 * LPR);
-      const int wrow = lane / LPR, wchunk = lane % LPR;
-      float4 G[J];
-      auto gload = [&](int t) {
-        const int iy = qy_[0] * ai + tl.dy[t], ix = qx_[0] * ai + tl.dx[t];
-        const bool ok = rv[0] && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
-        const int off = ok ? ((n_[0] * a.Hi + iy) * a.Wi + ix) * CRED : -1;
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-          const int o = __shfl(off, i * RPI + wrow);
-          if (CT_DBG & 4) G[i] = make_float4((float)o, 1.f, 2.f, (float)lane);
-          else
-          G[i] = o >= 0 ? *reinterpret_cast<const float4*>(a.in + o + 4 * wchunk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      };
-      auto stage = [&]() {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < J; ++i) {
-          const int row = i * RPI + wrow;
-          sAw[row * LPR + (wchunk ^ ((row >> SH) & MASK))] = G[i];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < J; ++j) A[0][0][j] = sAw[r * LPR + ((2 * j + h) ^ ((r >> SH) & MASK))];
-        asm volatile("" ::: "memory");
-      };
-      if (nt > 0) gload(0);
-      for (int t = 0; t < nt; ++t) {
-        stage();
-        if (t + 1 < nt) gload(t + 1);
-        mma(t, A[0]);
-      }
-    } else {
-      if (nt > 0) load_a(0, A[0]);
-      int t = 0;
-      for (; t + 1 < nt; t += 2) {
-        load_a(t + 1, A[1]);
-        mma(t, A[0]);
-        if (t + 2 < nt) load_a(t + 2, A[0]);
-        mma(t + 1, A[1]);
-      }
-      if (t < nt) mma(t, A[0]);
+    if (nt > 0) load_a(0, A[0]);
+    int t = 0;
+    for (; t + 1 < nt; t += 2) {
+      load_a(t + 1, A[1]);
+      mma(t, A[0]);
+      if (t + 2 < nt) load_a(t + 2, A[0]);
+      mma(t + 1, A[1]);
     }
+    if (t < nt) mma(t, A[0]);
 
     // D[i][j]: j = lane & 31, i = 8 * (reg / 4) + 4 * (lane / 32) + reg % 4
 #pragma unroll
@@ -342,140 +256,7 @@ __global__ __launch_bounds__(512) void conv_train_gather_kernel(GArgs a, ClassTa
         if (co < a.Cout) {
 #pragma unroll
           for (int i = 0; i < 16; ++i)
-            if (orow[i] >= 0 && (!(CT_DBG & 16) || acc[rm][cn][i] == 12345.f)) a.out[(long long)orow[i] * a.Cout + co] = acc[rm][cn][i] + bv;
-        }
-      }
-    }
-  }
-  if (CT_DBG & 512) {
-    __syncthreads();
-    stamp[3] = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(a.out) + 4 * (blockIdx.y * gridDim.x + blockIdx.x);
-      o[0] = stamp[0]; o[1] = stamp[1]; o[2] = stamp[2]; o[3] = stamp[3];
-    }
-  }
-}
-
-// The transposed form at stride 2 with ALL FOUR sub-pixel classes of a coarse position in one item.  Class (py, px) of coarse
-// position q reads in[q + d] for the taps with (p + pad - k) even, d = (p + pad - k) / 2: over the four classes the k * k taps meet
-// only a handful of DISTINCT offsets d (four for k = 3: every input record feeds one tap of up to four classes).  An item = 32 coarse
-// positions: per distinct offset one 16-byte-per-lane read of the input records and, for every class that has a tap there, the
-// 4 J MFMAs of that tap into the class's accumulator -- 9 taps x 4 J MFMAs per four input tiles and ONE set of index arithmetic,
-// where the class-per-item form above spends a tile, a prologue and an epilogue per 1 - 4 taps (550 vector instructions per 72
-// MFMAs: 28 % of the matrix pipe, profiles/r5_ab_conv_train.txt (2)).
-constexpr int SUB_MAXOFF = 9;
-struct SubTab { int noff; int dy[SUB_MAXOFF], dx[SUB_MAXOFF]; int tap[SUB_MAXOFF][4]; };
-
-inline void build_sub_tab(SubTab& tb, const GArgs& a) {
-  int n = 0;
-  for (int c = 0; c < 4; ++c) {
-    const int py = c >> 1, px = c & 1;
-    for (int ky = 0; ky < a.k; ++ky)
-      for (int kx = 0; kx < a.k; ++kx) {
-        const int ty = py + a.pad - ky, tx = px + a.pad - kx;
-        if ((ty & 1) || (tx & 1)) continue;
-        const int dy = ty / 2, dx = tx / 2;
-        int o = 0;
-        while (o < n && !(tb.dy[o] == dy && tb.dx[o] == dx)) ++o;
-        if (o == n) {
-          tb.dy[n] = dy; tb.dx[n] = dx;
-          for (int q = 0; q < 4; ++q) tb.tap[n][q] = -1;
-          ++n;
-        }
-        tb.tap[o][c] = ky * a.k + kx;
-      }
-  }
-  tb.noff = n;
-}
-
-template <int J, int CN>
-__global__ __launch_bounds__(512) void conv_train_gather_sub_kernel(GArgs a, SubTab tb) {
-  constexpr int NTH = 512, NWV = 8;
-  extern __shared__ __attribute__((aligned(16))) float4 sB[];       // [tap][J][2][CN * 32]
-  constexpr int CP = CN * 32, CRED = J * 8;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int co0 = blockIdx.y * CP;
-  stage_weights<J, CN, NTH>(a, sB, co0, tid);
-  __syncthreads();
-
-  const int Qh = (a.Ho + 1) >> 1, Qw = (a.Wo + 1) >> 1;
-  const long long M = (long long)a.N * Qh * Qw;
-  const int nitems = (int)((M + 31) / 32);
-  const int r = lane & 31, h = lane >> 5;
-  const int noff = tb.noff;
-  for (int item = blockIdx.x * NWV + wave; item < nitems; item += gridDim.x * NWV) {
-    const long long R = (long long)item * 32 + r;
-    const bool rv = R < M;
-    const int Rc = rv ? (int)R : 0;
-    const int qx = Rc % Qw, t1 = Rc / Qw, qy = t1 % Qh, n = t1 / Qh;
-    const int opos = rv ? (n * a.Ho + 2 * qy) * a.Wo + 2 * qx : -1;           // class (0, 0); class (py, px) is py * Wo + px further
-    const int edge = (2 * qy + 1 < a.Ho ? 1 : 0) | (2 * qx + 1 < a.Wo ? 2 : 0);   // bit 0: the odd row exists, bit 1: the odd column
-    v16f acc[4][CN];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int cn = 0; cn < CN; ++cn)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[c][cn][i] = 0.f;
-    float4 A[2][J];
-    auto load_a = [&](int o, float4 (&dst)[J]) {
-      const int iy = qy + tb.dy[o], ix = qx + tb.dx[o];
-      const bool ok = rv && iy >= 0 && iy < a.Hi && ix >= 0 && ix < a.Wi;
-      const float4* p = reinterpret_cast<const float4*>(a.in + (((long long)n * a.Hi + iy) * a.Wi + ix) * CRED + 4 * h);
-#pragma unroll
-      for (int j = 0; j < J; ++j) dst[j] = ok ? p[2 * j] : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto mma = [&](int o, const float4 (&src)[J]) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int tap = tb.tap[o][c];                  // (wave-uniform)
-        if (tap < 0) continue;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-          float4 B[CN];
-#pragma unroll
-          for (int cn = 0; cn < CN; ++cn) B[cn] = sB[((tap * J + j) * 2 + h) * CP + cn * 32 + r];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int cn = 0; cn < CN; ++cn) {
-              const float av = q == 0 ? src[j].x : q == 1 ? src[j].y : q == 2 ? src[j].z : src[j].w;
-              const float bv = q == 0 ? B[cn].x : q == 1 ? B[cn].y : q == 2 ? B[cn].z : B[cn].w;
-              acc[c][cn] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[c][cn], 0, 0, 0);
-            }
-        }
-      }
-    };
-    if (noff > 0) load_a(0, A[0]);
-    int o = 0;
-    for (; o + 1 < noff; o += 2) {
-      load_a(o + 1, A[1]);
-      mma(o, A[0]);
-      if (o + 2 < noff) load_a(o + 2, A[0]);
-      mma(o + 1, A[1]);
-    }
-    if (o < noff) mma(o, A[0]);
-
-    int orow[16], oedge[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int src = 8 * (i >> 2) + 4 * h + (i & 3);
-      orow[i] = __shfl(opos, src);
-      oedge[i] = __shfl(edge, src);
-    }
-#pragma unroll
-    for (int cn = 0; cn < CN; ++cn) {
-      const int co = co0 + cn * 32 + r;
-      if (co < a.Cout) {
-        const float bv = a.bias ? a.bias[co] : 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int need = (c >> 1) | ((c & 1) << 1);                 // the edge bits class c needs
-          float* const oc = a.out + ((long long)(c >> 1) * a.Wo + (c & 1)) * a.Cout + co;
-#pragma unroll
-          for (int i = 0; i < 16; ++i)
-            if (orow[i] >= 0 && (oedge[i] & need) == need) oc[(long long)orow[i] * a.Cout] = acc[c][cn][i] + bv;
+            if (orow[i] >= 0) a.out[(long long)orow[i] * a.Cout + co] = acc[rm][cn][i] + bv;
         }
       }
     }
@@ -657,11 +438,6 @@ __global__ __launch_bounds__(256 * SPLIT) void conv_train_wgrad_kernel(WArgs a) 
           const int qx = qx0 + 2 * u + kk;
           const bool pv = qx < a.Wv;
           const int xo = qx * sCu, xb = qx * a.stride;
-          if (CT_DBG & 1) {
-#pragma unroll
-            for (int i = 0; i < NTW; ++i) { av[u][i] = (float)(lane + u); bv[u][i] = (float)(qx + i); }
-            continue;
-          }
           if (a_shared) {
             const float x = (pv && t_cv[0] < a.Cv) ? vb[qx * a.Cv + t_cv[0]] : 0.f;
 #pragma unroll
@@ -682,8 +458,7 @@ __global__ __launch_bounds__(256 * SPLIT) void conv_train_wgrad_kernel(WArgs a) 
         if (qx0 + 2 * u < a.Wv) {
 #pragma unroll
           for (int i = 0; i < NTW; ++i) {
-            if (CT_DBG & 2) acc[i][0] += av[u][i] + bv[u][i];
-            else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][i], bv[u][i], acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][i], bv[u][i], acc[i], 0, 0, 0);
           }
         }
     }
@@ -793,7 +568,7 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
   const int r0 = (blockIdx.x * 2 + half) * g.rows_per;
   const int r1 = r0 + g.rows_per < NR ? r0 + g.rows_per : NR;
   const int bufsz = g.svb + g.sub;
-  constexpr int NBUF = CT_WL_PINGPONG ? 1 : 2;
+  constexpr int NBUF = 2;
   float* const sh = s_l + half * NBUF * bufsz;
   // zero both buffers of this half once: the padding columns are never written again
   for (int i = th; i < NBUF * bufsz / 4; i += 256) reinterpret_cast<float4*>(sh)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -878,7 +653,7 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
   // bias gradient from the staged rows (every gy row passes through LDS exactly once: as a v row, or -- gy on the finer grid -- as
   // the input rows ky in [pad, pad + s) of its coarse row): no second pass over gy in global memory (9 us of an 87 us launch)
   const int Cb = a.bias_from == 1 ? a.Cv : a.Cu;
-  const bool fuse_bias = CT_WL_FUSE_BIAS && a.bias_from != 0 && (256 % Cb) == 0 &&
+  const bool fuse_bias = a.bias_from != 0 && (256 % Cb) == 0 &&
                          (a.bias_from == 1 || (a.k >= a.pad + a.stride && a.Hu == a.stride * a.Hv));
   float bsum = 0.f;
   auto bias_rows = [&](const float* sv) {
@@ -915,8 +690,7 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
     auto multiply = [&](const float av, const float (&bv)[NTW]) {
 #pragma unroll
       for (int i = 0; i < NTW; ++i) {
-        if (CT_DBG & 64) acc[i][0] += av + bv[i];
-        else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[i], acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[i], acc[i], 0, 0, 0);
       }
     };
     fetch(0, 0, av0, bv0);
@@ -934,40 +708,17 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  if (CT_WL_PINGPONG) {
-    // ONE buffer per half and two barriers per block: while half 0 multiplies block b, half 1 writes its block b to LDS and
-    // requests the next one; then they swap.  The two waves of a SIMD are never in their MFMA phase together (together they
-    // only share the pipe: the phase takes twice as long), and a half's requests / LDS writes run beside the other half's MFMAs
-    // instead of in front of its own.  (Off by default: see the knob.)
-    request(0);
-    if (half == 0) deposit(0);
+  // (a ping-pong schedule of the two halves with one buffer each measured slower: dec.convT2 109.5 against 87.2 us,
+  //  profiles/r5_ab_conv_train.txt (4))
+  request(0);
+  deposit(0);
+  __syncthreads();
+  for (int b = 0; b < g.nb; ++b) {
+    const bool more = r0 + (b + 1) * g.RB < r1;
+    if (more) request(b + 1);
+    if (r0 + b * g.RB < r1) compute(sh + (b & 1) * bufsz);
+    if (more) deposit((b + 1) & 1);
     __syncthreads();
-    for (int b = 0; b < g.nb; ++b) {
-      const bool cur = r0 + b * g.RB < r1, more = r0 + (b + 1) * g.RB < r1;
-      if (half == 0) {
-        if (more && !(CT_DBG & 128)) request(b + 1);
-        if (cur) compute(sh);
-      } else if (cur) deposit(0);
-      __syncthreads();
-      if (half == 0) {
-        if (more) deposit(0);
-      } else {
-        if (more && !(CT_DBG & 128)) request(b + 1);
-        if (cur) compute(sh);
-      }
-      __syncthreads();
-    }
-  } else {
-    request(0);
-    deposit(0);
-    __syncthreads();
-    for (int b = 0; b < g.nb; ++b) {
-      const bool more = r0 + (b + 1) * g.RB < r1;
-      if (more && !(CT_DBG & 128)) request(b + 1);
-      if (r0 + b * g.RB < r1) compute(sh + (b & 1) * bufsz);
-      if (more) deposit((b + 1) & 1);
-      __syncthreads();
-    }
   }
   // second half's tiles through LDS (aliases the operand buffers: every wave is behind the last block's barrier)
   float* const s_x = s_l;
@@ -987,7 +738,7 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
         for (int r = 0; r < 16; ++r) part[(long long)(wq + 4 * i) * 1024 + r * 64 + lane] = acc[i][r] + s_x[((wq * NTW + i) * 16 + r) * 64 + lane];
       }
   }
-  if (fuse_bias && !(CT_DBG & 32)) {
+  if (fuse_bias) {
     __syncthreads();
     s_x[tid] = bsum;                                 // (tid & 255) % Cb is the thread's channel, in either half
     __syncthreads();
@@ -996,7 +747,7 @@ __global__ __launch_bounds__(512) void conv_train_wgrad_lds_kernel(WArgs a, WLGe
       for (int q = tid; q < 512; q += Cb) tot += s_x[q];
       part[(long long)ntile * 1024 + tid] = tot;
     }
-  } else if (a.bias_from && !(CT_DBG & 32)) {
+  } else if (a.bias_from) {
     __syncthreads();
     constexpr int NT = 512;
     const float* gq = a.bias_from == 1 ? a.v : a.u;
@@ -1197,7 +948,7 @@ int gather_kind(int Cred, int Cout, int k, int stride, int form) {
     return (Cred == 8 || Cred == 16 || Cred == 32 || Cred == 64) ? 2 : 0;
   }
   if (Cred % 8 != 0 || Cred > 64 || Cout > 64) return 0;
-  if (stride > 4 || (form && stride > 2) || (long long)k * k * Cred * 32 * 4 + (CT_STAGE_A ? 8 * 32 * Cred * 4 : 0) > GATHER_LDS_MAX) return 0;    // (one column tile per workgroup always fits then)
+  if (stride > 4 || (form && stride > 2) || (long long)k * k * Cred * 32 * 4 > GATHER_LDS_MAX) return 0;    // (one column tile per workgroup always fits then)
   return 1;
 }
 
@@ -1259,46 +1010,16 @@ extern "C" int spk_conv_train_gather(const float* in_cl, const float* w, const f
     const int cs = form ? stride : 1;
     if (cs * cs > MAX_CLASSES) return SPK_ERR_UNSUPPORTED;
     const int CNT = (Cout + 31) / 32, J = Cred / 8;
-    if (CT_SUBPIXEL && form && stride == 2 && k <= 3 && (J == 1 || J == 2 || J == 4 || J == 8)) {
-      // all four sub-pixel classes of 32 coarse positions per item
-      const long long items = ((long long)N * ((Ho + 1) / 2) * ((Wo + 1) / 2) + 31) / 32;
-      const bool big = CNT == 1 || (items >= CT_BIG_ITEMS / 4 && (size_t)k * k * Cred * CNT * 32 * 4 <= 150 * 1024);
-      const int CN = big ? CNT : 1, gy = big ? 1 : CNT;
-      const size_t lds = (size_t)k * k * Cred * CN * 32 * 4;
-      int gx = (int)((items + 7) / 8);
-      const int per_cu = lds > 76 * 1024 ? 1 : 2;
-      const int cap = 256 * per_cu / gy > 0 ? 256 * per_cu / gy : 1;
-      gx = gx < cap ? gx : cap;
-      SubTab tb;
-      build_sub_tab(tb, a);
-#define SPK_SUB_LAUNCH(J_, CN_)                                                                                        \
-  do {                                                                                                                 \
-    static std::once_flag once_;                                                                                       \
-    std::call_once(once_, [] {                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_train_gather_sub_kernel<J_, CN_>),                                                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);                               \
-    });                                                                                                                \
-    hipLaunchKernelGGL((conv_train_gather_sub_kernel<J_, CN_>), dim3(gx, gy), dim3(512), lds, s, a, tb);               \
-  } while (0)
-      if (CN == 2) {
-        if (J == 1) SPK_SUB_LAUNCH(1, 2); else if (J == 2) SPK_SUB_LAUNCH(2, 2); else if (J == 4) SPK_SUB_LAUNCH(4, 2); else SPK_SUB_LAUNCH(8, 2);
-      } else {
-        if (J == 1) SPK_SUB_LAUNCH(1, 1); else if (J == 2) SPK_SUB_LAUNCH(2, 1); else if (J == 4) SPK_SUB_LAUNCH(4, 1); else SPK_SUB_LAUNCH(8, 1);
-      }
-#undef SPK_SUB_LAUNCH
-      SPK_LAUNCH_CHECK();
-      return SPK_OK;
-    }
+    // (items of all four sub-pixel classes of 32 coarse positions measured slower: dec.convT2 forward 69.1 against 64.4 us,
+    //  profiles/r5_ab_conv_train.txt (5))
     // items of 32 rows x all column tiles when there are at least four per SIMD; otherwise 32 rows x one column tile
     long long items = 0;
     for (int c = 0; c < cs * cs; ++c)
       items += ((long long)N * ((Ho - c / cs + cs - 1) / cs) * ((Wo - c % cs + cs - 1) / cs) + 31) / 32;
-    const bool staged = CT_STAGE_A && (J == 1 || J == 2 || J == 4 || J == 8);
-    const size_t lds_a = staged ? (size_t)8 * 32 * Cred * 4 : 0;
-    const bool big = CNT == 1 || (items >= CT_BIG_ITEMS && (size_t)k * k * Cred * CNT * 32 * 4 + lds_a <= 150 * 1024);
+    const bool big = CNT == 1 || (items >= CT_BIG_ITEMS && (size_t)k * k * Cred * CNT * 32 * 4 <= 150 * 1024);
     const int CN = big ? CNT : 1, RM = 1;
     const int gy = big ? 1 : CNT;
-    const size_t lds = (size_t)k * k * Cred * CN * 32 * 4 + lds_a;
+    const size_t lds = (size_t)k * k * Cred * CN * 32 * 4;
     int gx = (int)((items + 7) / 8);
     const int per_cu = lds > 76 * 1024 ? 1 : 2;                      // workgroups per CU that fit the LDS
     const int cap = 256 * per_cu / gy > 0 ? 256 * per_cu / gy : 1;
@@ -1369,7 +1090,7 @@ extern "C" int spk_conv_train_wgrad(const float* u_cl, const float* v_cl, float*
     const int ntw = (ntile + 3) / 4;
     // LDS-staged form where its tiles fit (Cu, Cv multiples of 4, 16-byte aligned tensors, at most WL_MAXCH chunks per thread and block)
     bool lds_form = false;
-    if (CT_WGRAD_LDS && ntw <= 5 && (Cu & 3) == 0 && (Cv & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_cl) | reinterpret_cast<uintptr_t>(v_cl)) & 15) == 0) {
+    if (ntw <= 5 && (Cu & 3) == 0 && (Cv & 3) == 0 && ((reinterpret_cast<uintptr_t>(u_cl) | reinterpret_cast<uintptr_t>(v_cl)) & 15) == 0) {
       WLGeo g{};
       g.WP = Wv * stride + k;
       if (g.WP >= Wu + pad) {                        // (the row image holds every input column)
@@ -1383,7 +1104,7 @@ extern "C" int spk_conv_train_wgrad(const float* u_cl, const float* v_cl, float*
           g.sub = RB * k * g.WP * Cu;
           g.nv4 = RB * Wv * Cv / 4;
           g.nu4 = RB * k * Wu * Cu / 4;
-          const size_t need = (size_t)(CT_WL_PINGPONG ? 2 : 4) * (g.svb + g.sub) * 4;
+          const size_t need = (size_t)4 * (g.svb + g.sub) * 4;
           if (need <= 150 * 1024 && g.nv4 + g.nu4 <= 256 * WL_MAXCH) {
             g.nb = (g.rows_per + RB - 1) / RB;
             const size_t lds_ = need > comb ? need : comb;

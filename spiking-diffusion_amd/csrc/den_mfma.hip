@@ -52,11 +52,10 @@ struct MfmaArgs {
   uint8_t* out_cnt;   // optional per-neuron spike counts over T, [B][Cout/32][HW][32] (input of the time-collapsed conv6)
   int B, H, W, Cout, mode;
   const int* n_dyn;   // optional device-side batch count (<= B): only images [0, *n_dyn) are processed
-  int dbg;   // -DSPK_MFMA_ABLATION builds only (env SPK_MFMA_DEBUG): 1 = skip steady-state DMA, 2 = skip MFMAs, 4 = skip epilogue
 };
 
 // NT = row tiles per wave (7 for 7x7 latents, 8 for 8x8); NPA = A-slab DMA pieces per wave (H*ceil(W/2)/4, rounded up).
-template <int NT, int NPA, int MODE, int DBG>
+template <int NT, int NPA, int MODE>
 __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int HW = a.H * a.W, PW = a.W + 2;
@@ -141,13 +140,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
   }
   for (int item = blockIdx.x; item < total; item += gridDim.x) {
     v16i acc[NT][2];      // written (not accumulated) by tap 0 of the first chunk: no explicit zeroing
-#ifdef SPK_NO_PEEL
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][0][r] = 0; acc[i][1][r] = 0; }
-    }
-#endif
     // epilogue constants of this item's channel: loaded now, their latency hides under the K loop
     const int b = item / G, g = item - b * G;
     const int co = g * 16 + ch;
@@ -194,17 +186,13 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
           bn0 = *reinterpret_cast<const v4i*>(Wb + ((tap + 1) * 2 + 0) * 32 * CK);
           bn1 = *reinterpret_cast<const v4i*>(Wb + ((tap + 1) * 2 + 1) * 32 * CK);
         }
-        if (!(DBG & 2)) {
-          if (FIRST && tap == 0) {
-            const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            acc[i][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc0, z, 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc1, z, 0, 0, 0);
-          } else {
-            acc[i][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc1, acc[i][1], 0, 0, 0);
-          }
+        if (FIRST && tap == 0) {
+          const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+          acc[i][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc0, z, 0, 0, 0);
+          acc[i][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc1, z, 0, 0, 0);
         } else {
-          acc[i][0][0] += av[0] + bc0[1]; acc[i][1][0] += av[1] + bc1[0];
+          acc[i][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc0, acc[i][0], 0, 0, 0);
+          acc[i][1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bc1, acc[i][1], 0, 0, 0);
         }
         if (i == NT - 1) { bc0 = bn0; bc1 = bn1; }
         // DMA schedule: NPA + NPW pieces spread over the 9*NT steps (every DMA_EVERY-th step issues one piece)
@@ -212,115 +200,109 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
           constexpr int NPIECES = NPA + NPW;
           constexpr int DMA_EVERY = (9 * NT) / NPIECES;
           if (s % DMA_EVERY == 0 && s / DMA_EVERY < NPIECES) {
-            if (!(DBG & 1)) issue_piece(s / DMA_EVERY, n_aslab, n_wslab, n_dA, n_dW);
+            issue_piece(s / DMA_EVERY, n_aslab, n_wslab, n_dA, n_dW);
           }
         }
         __builtin_amdgcn_sched_barrier(0);     // keep the read-ahead distance: hipcc otherwise sinks every ds_read
       }                                         // to just before its MFMA (one exposed LDS latency per tile)
     };
-#ifdef SPK_NO_PEEL
-    compute(std::false_type{});
-#else
     if (c == 0) compute(std::true_type{}); else compute(std::false_type{});
-#endif
 
     }   // chunks
-    if (!(DBG & 4)) {
-      // ---------------- epilogue: exact recombination, BN, LIF scan over the 16 accumulator registers ----------
-      // Partner lanes (col, col ^ 16) hold digit planes {0,2} and {1,3} of the same channel.  recombine(i, x):
-      // v_permlane16_swap(A, B) gives A' = {even row: A.even, odd row: B.even}, B' = {even row: A.odd, odd row: B.odd};
-      // with A = acc[.][r] (t = r) and B = acc[.][r + 8] every lane ends up with both digits of ITS time step (even
-      // lane t = r, odd lane t = r + 8), recombines it in fp64, and a third swap hands both lanes all 16 fp32 values.
-      auto recombine = [&](int i, float (&x)[16]) {
+    // ---------------- epilogue: exact recombination, BN, LIF scan over the 16 accumulator registers ----------
+    // Partner lanes (col, col ^ 16) hold digit planes {0,2} and {1,3} of the same channel.  recombine(i, x):
+    // v_permlane16_swap(A, B) gives A' = {even row: A.even, odd row: B.even}, B' = {even row: A.odd, odd row: B.odd};
+    // with A = acc[.][r] (t = r) and B = acc[.][r + 8] every lane ends up with both digits of ITS time step (even
+    // lane t = r, odd lane t = r + 8), recombines it in fp64, and a third swap hands both lanes all 16 fp32 values.
+    auto recombine = [&](int i, float (&x)[16]) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][0][r], (unsigned)acc[i][0][r + 8], false, false);
-          const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][1][r], (unsigned)acc[i][1][r + 8], false, false);
-          const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
-          const double s = fma((double)hi, 65536.0, (double)lo);        // exact
-          const float xm = (float)fma(s, sc, bi);                        // the one rounding to fp32 (s*sc is exact)
-          const v2u xx = __builtin_amdgcn_permlane16_swap(__float_as_uint(xm), __float_as_uint(xm), false, false);
-          x[r] = __uint_as_float(xx[0]);                                 // t = r     (computed by the even lane)
-          x[r + 8] = __uint_as_float(xx[1]);                             // t = r + 8 (computed by the odd lane)
+      for (int r = 0; r < 8; ++r) {
+        const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][0][r], (unsigned)acc[i][0][r + 8], false, false);
+        const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][1][r], (unsigned)acc[i][1][r + 8], false, false);
+        const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
+        const double s = fma((double)hi, 65536.0, (double)lo);        // exact
+        const float xm = (float)fma(s, sc, bi);                        // the one rounding to fp32 (s*sc is exact)
+        const v2u xx = __builtin_amdgcn_permlane16_swap(__float_as_uint(xm), __float_as_uint(xm), false, false);
+        x[r] = __uint_as_float(xx[0]);                                 // t = r     (computed by the even lane)
+        x[r + 8] = __uint_as_float(xx[1]);                             // t = r + 8 (computed by the odd lane)
+      }
+    };
+    if (MODE == SPK_MODE_LIF) {
+      // The LIF scan runs on TWO row tiles at once: even lanes scan tile ip, odd lanes tile ip + 1.  Each lane collects
+      // its neuron's 16 spike bits; a DPP bit-matrix
+      // transpose inside every 16-lane row (= 16 channels of one position) turns them into per-time-step channel masks.
+#pragma unroll
+      for (int ip = 0; ip < NT; ip += 2) {
+        // Pairwise exchange (as in den_mfma_fp6.hip): v_permlane16_swap(acc[ip][ct][r], acc[ip + 1][ct][r]) leaves the
+        // even lane with both digits of column tile ct of tile ip and the odd lane with those of tile ip + 1, so 32
+        // swaps give every lane all four digits of ONE neuron for all 16 steps; the odd tile out of an odd NT is
+        // split over the lane parities by time steps (recombine()).
+        float xa[16];
+        const bool paired = ip + 1 < NT;
+        // keep this pair's accumulators in their AGPR tuples up to here: hipcc otherwise copies 16-register tuples
+        // to VGPRs at the top of the epilogue and spills (den_mfma_fp6.hip)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          asm volatile("" : "+a"(acc[ip][ct]));
+          if (paired) asm volatile("" : "+a"(acc[ip + 1][ct]));
         }
-      };
-      if (MODE == SPK_MODE_LIF) {
-        // The LIF scan runs on TWO row tiles at once: even lanes scan tile ip, odd lanes tile ip + 1.  Each lane collects
-        // its neuron's 16 spike bits; a DPP bit-matrix
-        // transpose inside every 16-lane row (= 16 channels of one position) turns them into per-time-step channel masks.
-#pragma unroll
-        for (int ip = 0; ip < NT; ip += 2) {
-          // Pairwise exchange (as in den_mfma_fp6.hip): v_permlane16_swap(acc[ip][ct][r], acc[ip + 1][ct][r]) leaves the
-          // even lane with both digits of column tile ct of tile ip and the odd lane with those of tile ip + 1, so 32
-          // swaps give every lane all four digits of ONE neuron for all 16 steps; the odd tile out of an odd NT is
-          // split over the lane parities by time steps (recombine()).
-          float xa[16];
-          const bool paired = ip + 1 < NT;
-          // keep this pair's accumulators in their AGPR tuples up to here: hipcc otherwise copies 16-register tuples
-          // to VGPRs at the top of the epilogue and spills (den_mfma_fp6.hip)
-#pragma unroll
-          for (int ct = 0; ct < 2; ++ct) {
-            asm volatile("" : "+a"(acc[ip][ct]));
-            if (paired) asm volatile("" : "+a"(acc[ip + 1][ct]));
-          }
-          if (paired) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][0][r], (unsigned)acc[paired ? ip + 1 : ip][0][r], false, false);
-              const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][1][r], (unsigned)acc[paired ? ip + 1 : ip][1][r], false, false);
-              const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
-              const double s = fma((double)hi, 65536.0, (double)lo);        // exact
-              xa[r] = (float)fma(s, sc, bi);                                 // the one rounding to fp32
-            }
-          } else {
-            recombine(ip, xa);
-          }
-          const int ti = wave + 4 * (ip + (paired ? odd : 0));
-          const int p = 2 * ti + half;                  // accumulator lane-half == position within the tile
-          const bool pos_ok = p < HW && (paired || !odd);
-          const long long vidx = ((long long)b * a.Cout + co) * HW + (pos_ok ? p : 0);
-          float v = a.v_io ? a.v_io[vidx] : 0.f;
-          unsigned mybits = 0;                    // bit r = this lane's neuron fired at t = r
+        if (paired) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const bool s = spk_lif_step_default(v, fmaf(xa[r], bn_a, bn_b)) && pos_ok;
-            mybits |= s ? (1u << r) : 0u;
+            const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][0][r], (unsigned)acc[paired ? ip + 1 : ip][0][r], false, false);
+            const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][1][r], (unsigned)acc[paired ? ip + 1 : ip][1][r], false, false);
+            const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
+            const double s = fma((double)hi, 65536.0, (double)lo);        // exact
+            xa[r] = (float)fma(s, sc, bi);                                 // the one rounding to fp32
           }
-          const unsigned cnt = __popc(mybits);
-          // lanes of a 16-lane row are the 16 channels of one (tile, position): transposing the 16x16 bit matrix gives
-          // lane t the 16 channel bits of time step t -- the 16 bytes it stores
-          const unsigned bitsv = spk_transpose16_rows(mybits, lane);
-          if (a.v_io && pos_ok) a.v_io[vidx] = v;
-          if (a.out_cnt && pos_ok)
-            a.out_cnt[(((long long)b * (a.Cout >> 5) + (co >> 5)) * HW + p) * CK + (co & 31)] = (uint8_t)cnt;
-          // every lane stores one (position, time step): 16 channels = 16 bytes
-          if (pos_ok) {
-            uint4 o;
-            o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.w = (((bitsv >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
-            const int co0 = g * 16;
-            uint8_t* dst = a.out + ((((long long)b * (a.Cout >> 5) + (co0 >> 5)) * HW + p) * T16 + (lane & 15)) * CK +
-                           (co0 & 31);
-            *reinterpret_cast<uint4*>(dst) = o;
-          }
-          __builtin_amdgcn_sched_barrier(0);        // keep the tile pairs from being interleaved (VGPR pressure)
+        } else {
+          recombine(ip, xa);
         }
-      } else {
+        const int ti = wave + 4 * (ip + (paired ? odd : 0));
+        const int p = 2 * ti + half;                  // accumulator lane-half == position within the tile
+        const bool pos_ok = p < HW && (paired || !odd);
+        const long long vidx = ((long long)b * a.Cout + co) * HW + (pos_ok ? p : 0);
+        float v = a.v_io ? a.v_io[vidx] : 0.f;
+        unsigned mybits = 0;                    // bit r = this lane's neuron fired at t = r
 #pragma unroll
-        for (int i = 0; i < NT; ++i) {
-          float x[16];
-          asm volatile("" : "+a"(acc[i][0]));
-          asm volatile("" : "+a"(acc[i][1]));
-          recombine(i, x);
-          const int p = 2 * (wave + 4 * i) + half;
-          float msum = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) msum = msum + x[r];                // torch.sum(x6, dim=0), t order
-          if (!odd && p < HW) a.out_f32[((long long)b * a.Cout + co) * HW + p] = msum / 16.0f;
-          __builtin_amdgcn_sched_barrier(0);
+        for (int r = 0; r < 16; ++r) {
+          const bool s = spk_lif_step_default(v, fmaf(xa[r], bn_a, bn_b)) && pos_ok;
+          mybits |= s ? (1u << r) : 0u;
         }
+        const unsigned cnt = __popc(mybits);
+        // lanes of a 16-lane row are the 16 channels of one (tile, position): transposing the 16x16 bit matrix gives
+        // lane t the 16 channel bits of time step t -- the 16 bytes it stores
+        const unsigned bitsv = spk_transpose16_rows(mybits, lane);
+        if (a.v_io && pos_ok) a.v_io[vidx] = v;
+        if (a.out_cnt && pos_ok)
+          a.out_cnt[(((long long)b * (a.Cout >> 5) + (co >> 5)) * HW + p) * CK + (co & 31)] = (uint8_t)cnt;
+        // every lane stores one (position, time step): 16 channels = 16 bytes
+        if (pos_ok) {
+          uint4 o;
+          o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
+          o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
+          o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
+          o.w = (((bitsv >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
+          const int co0 = g * 16;
+          uint8_t* dst = a.out + ((((long long)b * (a.Cout >> 5) + (co0 >> 5)) * HW + p) * T16 + (lane & 15)) * CK +
+                         (co0 & 31);
+          *reinterpret_cast<uint4*>(dst) = o;
+        }
+        __builtin_amdgcn_sched_barrier(0);        // keep the tile pairs from being interleaved (VGPR pressure)
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NT; ++i) {
+        float x[16];
+        asm volatile("" : "+a"(acc[i][0]));
+        asm volatile("" : "+a"(acc[i][1]));
+        recombine(i, x);
+        const int p = 2 * (wave + 4 * i) + half;
+        float msum = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) msum = msum + x[r];                // torch.sum(x6, dim=0), t order
+        if (!odd && p < HW) a.out_f32[((long long)b * a.Cout + co) * HW + p] = msum / 16.0f;
+        __builtin_amdgcn_sched_barrier(0);
       }
     }
   }   // items
@@ -597,19 +579,9 @@ int launch(const MfmaArgs& a, hipStream_t stream) {
   dim3 grid(total < cus ? total : cus), blk(256);          // persistent: one workgroup per CU
   const int npa = (a.H * ((a.W + 1) / 2) + 3) / 4;
   if (nt <= 7 && npa <= 7) {
-#ifdef SPK_MFMA_ABLATION
-    switch (a.dbg) {
-      case 1: hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 1>), grid, blk, lds, stream, a); break;
-      case 2: hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 2>), grid, blk, lds, stream, a); break;
-      case 3: hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 3>), grid, blk, lds, stream, a); break;
-      case 4: hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 4>), grid, blk, lds, stream, a); break;
-      default: hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 0>), grid, blk, lds, stream, a); break;
-    }
-#else
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE, 0>), grid, blk, lds, stream, a);
-#endif
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE>), grid, blk, lds, stream, a);
   } else if (nt <= 8 && npa <= 8) {
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<8, 8, MODE, 0>), grid, blk, lds, stream, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<8, 8, MODE>), grid, blk, lds, stream, a);
   } else {
     return SPK_ERR_UNSUPPORTED;
   }
@@ -647,11 +619,9 @@ extern "C" int spk_den_conv3x3_counts_mfma(const uint8_t* cnt0, int nch0, const 
   const long long tiles = ((long long)B * H * W + 31) / 32;
   dim3 grid((unsigned)tiles, Cout / 16), blk(256);
   // batches of more than 160 row tiles: shared weight tiles and count records
-  const bool shared_w = spk_opt(SPK_OPT_CONV6_SHARED) != 0;
   // (also the sampler's active-set calls: its register-staged stream of two chunks beats the K split of the first kernel even at
-  //  a few dozen images -- elimination + position lists 35.4 -> 34.4 ms; option conv6_shared_dyn = 0: the first kernel there)
-  const bool shared_dyn = spk_opt(SPK_OPT_CONV6_SHARED_DYN) != 0;
-  if ((!n_dyn_or_null || shared_dyn) && (long long)B * H * W > 32 * 160 && H * W >= 43 && H * W <= 64 && shared_w) {
+  //  a few dozen images -- elimination + position lists 35.4 -> 34.4 ms)
+  if ((long long)B * H * W > 32 * 160 && H * W >= 43 && H * W <= 64) {
     hipLaunchKernelGGL(conv3x3_counts_mfma_shared_kernel, dim3((unsigned)((tiles + 3) / 4), Cout / 16), blk, 0, stream, a);
     SPK_LAUNCH_CHECK();
     return SPK_OK;
@@ -674,11 +644,6 @@ extern "C" int spk_den_conv3x3_mfma(const uint8_t* in0_cptc, int nch0, const uin
   a.in0 = in0_cptc; a.in1 = in1_cptc; a.nch0 = nch0; a.nch1 = nch1; a.wq = wq; a.scale = scale; a.bias = bias_d;
   a.bn_a = bn_a; a.bn_b = bn_b; a.out = out_cptc; a.out_f32 = out_f32; a.v_io = v_inout; a.out_cnt = out_counts; a.B = B; a.H = H; a.W = W;
   a.Cout = Cout; a.mode = mode; a.n_dyn = n_dyn_or_null;
-  a.dbg = 0;
-#ifdef SPK_MFMA_ABLATION
-  // (timing experiments only; read once per process: the launch path makes no environment look-ups)
-  a.dbg = spk_opt(SPK_OPT_MFMA_DEBUG);
-#endif
   if (mode == SPK_MODE_LIF) {
     if (!bn_a || !bn_b || !out_cptc) return SPK_ERR_ARG;
     return launch<SPK_MODE_LIF>(a, stream);

@@ -55,9 +55,7 @@ struct Fp6Args {
 // D = A(32 x 64 fp4) * B(64 x 32 fp6) + C, accumulator in AGPRs ("a") or VGPRs ("v"); *_Z: C = 0 (first MFMA of an item).
 // s_nop 1: the two wait states between a VALU write of an operand register (the B fragment hand-over is v_mov) and
 // the MFMA that reads it, which hipcc's hazard recognizer cannot insert around inline assembly.
-#ifndef SPK_FP6_PRE
 #define SPK_FP6_PRE "s_nop 1\n\t"
-#endif
 #define SPK_MFMA_FP6(CLS, acc, av, bv, sa, sb)                                                                       \
   asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"  \
                : "+" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
@@ -65,15 +63,8 @@ struct Fp6Args {
   asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"   \
                : "=&" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
 
-#ifndef SPK_FP6_DBG
-#define SPK_FP6_DBG 0           // timing experiments only: 1 = no steady-state DMA, 4 = no epilogue (results are wrong)
-#endif
-#ifndef SPK_FP6_PF
-#define SPK_FP6_PF 4
-#endif
-#ifndef SPK_FP6_DMA_EVERY
-#define SPK_FP6_DMA_EVERY 2     // one piece every second step: all 18 are issued in the first 60 % of a chunk and land before its end
-#endif
+constexpr int SPK_FP6_PF = 4;         // A fragments in flight ahead of the MFMA that consumes them
+constexpr int SPK_FP6_DMA_EVERY = 2;  // one piece every second step: all 18 are issued in the first 60 % of a chunk and land before its end
 // NT = row tiles per wave: 6 when H*W is odd and H*W / 2 <= 24 (7x7: 24 tiles of 2 positions, no padding rows; the last
 // position of every image is left to conv3x3_fp6_lastpos_kernel), else 7 (up to 56 positions, padded to 28 tiles)
 constexpr int NPA = 7;         // A-slab DMA pieces per wave
@@ -85,16 +76,10 @@ constexpr int N_AGPR = 16;     // accumulators (row tile i, column tile j: index
 // H / 2 + 1 input rows: one halo row from the other band).  Both bands sit in LDS rows 1..H/2+1 of a (H/2 + 3)-row padded
 // image whose rows 0 and H/2 + 2 stay zero; the top band's outputs are centred on LDS rows 1.., the bottom band's on
 // rows 2.. -- one row offset added to the fragment addresses per item.
-// NWV = waves per workgroup: 4 (one per SIMD, NT = 6 / 7 / 4 tiles each) or 8 (two per SIMD with NT = 3 tiles each: the same
-// item, LDS plan and DMA volume; meant to let the second wave of a SIMD fill the matrix pipe while the first reads
-// fragments, issues copies or runs its epilogue).  Measured (SPKDIFF_FP6_WAVES=8, correct, same results): 7 % SLOWER on
-// conv4 / conv5 (620 vs 580 us, 531 vs 501 us), with or without de-phasing the two waves -- the kernel is not starved
-// for issue slots but limited by the power the matrix pipe may draw; kept as an experiment, not the default.
-template <int NT, bool RAW = false, bool SPLIT = false, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
-  constexpr int NPA_ = NWV == 8 ? 4 : NPA;                    // A pieces per wave
-  constexpr int NAG = NWV == 8 ? 8 : N_AGPR;                  // accumulators kept in AGPRs (two waves per SIMD: 256 registers each)
-  constexpr int NPW_ = (W_PIECES + NWV - 1) / NWV;            // W pieces per wave (wave w copies pieces w, w + NWV, ...)
+// Four waves, one per SIMD (eight waves, two per SIMD with three tiles each, measured 7 % slower on conv4 / conv5: 620 vs 580 us,
+// 531 vs 501 us -- the kernel is limited by the power the matrix pipe may draw, not by issue slots).
+template <int NT, bool RAW = false, bool SPLIT = false>
+__global__ __launch_bounds__(256, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int HW = a.H * a.W, PW = a.W + 1;
   const int Hb = SPLIT ? a.H / 2 : a.H;               // output rows of an item
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   const int total = Bn * G * (SPLIT ? 2 : 1);
 
   // zero both A images once: the borders stay zero for the whole kernel, interiors are overwritten by DMA
-  for (int i = tid; i < 2 * A_BYTES / 16; i += NWV * 64) reinterpret_cast<uint4*>(sA)[i] = make_uint4(0, 0, 0, 0);
+  for (int i = tid; i < 2 * A_BYTES / 16; i += 256) reinterpret_cast<uint4*>(sA)[i] = make_uint4(0, 0, 0, 0);
 
   // per-lane LDS byte offsets of this wave's A fragments (tile ti = wave + 4*i); absent tiles read garbage that the
   // epilogue discards
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   int a_off[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
-    const int p = 2 * (wave + NWV * i) + hsel;
+    const int p = 2 * (wave + 4 * i) + hsel;
     const int pp = p < HWb ? (p / a.W + 1) * PW + (p % a.W) + 1 : PW + 1;
     a_off[i] = pp * POS_BYTES + tt * 32 + 16 * (half ^ (tt >> 3));   // 16-B halves swapped for t >= 8: bank-conflict-free
   }
@@ -134,10 +119,10 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int pprow = (a.W + 1) >> 1;
   const int nA = Hin * pprow;
-  unsigned pa_pk[NPA_];
+  unsigned pa_pk[NPA];
 #pragma unroll
-  for (int j = 0; j < NPA_; ++j) {
-    int id = wave_s * NPA_ + j;
+  for (int j = 0; j < NPA; ++j) {
+    int id = wave_s * NPA + j;
     id = id < nA ? id : nA - 1;
     const int y = id / pprow, px = id - y * pprow;
     const unsigned src = (unsigned)((y * a.W + 2 * px) * POS_BYTES), dst = (unsigned)(((y + 1) * PW + 1 + 2 * px) * POS_BYTES);
@@ -149,13 +134,13 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
 
   // piece q of this wave: q < NPA -> A piece q, else W piece wave + 4 * (q - NPA) (the 42nd..44th repeat an earlier one)
   auto issue_piece = [&](int q, const uint8_t* aslab, const uint8_t* wslab, unsigned dA, unsigned dW) {
-    if (q < NPA_) {
+    if (q < NPA) {
       const unsigned pk = pa_pk[q];
       const unsigned long long mask = (pk >> 31) ? ~0ull : 0xffffffffull;
       spk_dma16s_masked(aslab + (pk & 0x7fffu), lane_a, dA + ((pk >> 15) & 0xffffu), mask);
     } else {
-      unsigned ko = wave_k + (unsigned)NWV * 1024u * (unsigned)(q - NPA_);
-      if (NWV * (q - NPA_) + NWV - 1 >= W_PIECES) ko = ko < (unsigned)W_PIECES * 1024u ? ko : ko - (unsigned)NWV * 1024u;
+      unsigned ko = wave_k + 4096u * (unsigned)(q - NPA);
+      if (4 * (q - NPA) + 3 >= W_PIECES) ko = ko < (unsigned)W_PIECES * 1024u ? ko : ko - 4096u;
       spk_dma16s(wslab + ko, lane_w, dW + ko);
     }
   };
@@ -193,13 +178,12 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   const int sc_a = 0x7f7f7f7f;             // e8m0 block scales: spikes x 1
   const int sc_b = (int)0x82828282u;       //                    digits x 8 (e2m3 value d/8 -> d)
 
-  long long dbg_t[4] = {0, 0, 0, 0};               // SPK_FP6_DBG & 64: cycles in DMA wait / barrier / K loop, chunk count
   int it = 0;                                      // running chunk counter: LDS buffer = it & 1
   if ((int)blockIdx.x < total) {
     const uint8_t *as0, *ws0;
     slabs(blockIdx.x, 0, as0, ws0);
 #pragma unroll
-    for (int q = 0; q < NPA_ + NPW_; ++q) issue_piece(q, as0, ws0, sA_addr, sW_addr);
+    for (int q = 0; q < NPA + NPW; ++q) issue_piece(q, as0, ws0, sA_addr, sW_addr);
   }
   for (int item = blockIdx.x; item < total; item += gridDim.x) {
     v16f acc[NT][3];      // written (not accumulated) by tap 0 of the first chunk: no explicit zeroing
@@ -214,19 +198,14 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
     const float bn_a = RAW ? 1.0f : a.bn_a[co], bn_b = RAW ? 0.0f : a.bn_b[co];
     for (int c = 0; c < nchunks; ++c, ++it) {
       const int buf = it & 1;
-      long long tq0 = 0, tq1 = 0, tq2 = 0;
-      if (SPK_FP6_DBG & 64) tq0 = __builtin_amdgcn_s_memtime();
       spk_dma_wait_all();  // this wave's share of the chunk's DMA has landed ...
-      if (SPK_FP6_DBG & 64) tq1 = __builtin_amdgcn_s_memtime();
       __syncthreads();     // ... and so has everyone else's; everyone is done with the other buffer
-      if (SPK_FP6_DBG & 64) tq2 = __builtin_amdgcn_s_memtime();
       // next chunk (possibly of the next item): its DMA pieces are issued between the MFMA groups below
       int nitem = item, nc = c + 1;
       if (nc == nchunks) { nc = 0; nitem = item + gridDim.x; }
       const bool have_next = nitem < total;      // otherwise the last chunk is copied once more (never read)
       const uint8_t *n_aslab, *n_wslab;
       slabs(have_next ? nitem : item, nc, n_aslab, n_wslab);
-      if (SPK_FP6_DBG & 128) { n_aslab = a.in0; n_wslab = a.wq; }      // timing experiment: L2-hot, tiny DMA footprint
       const unsigned n_dA = sA_addr + (buf ^ 1) * A_BYTES;            // LDS byte addresses of the DMA destinations
       const unsigned n_dW = sW_addr + (buf ^ 1) * W_CHUNK_BYTES;
 
@@ -253,10 +232,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
         v6i bc[3], bn[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) { bc[j] = ldb(0, j); bn[j] = bc[j]; }
-        // A fragments in flight ahead of the MFMA that consumes them; with two waves per SIMD the other wave covers the
-        // latency instead of registers (no second set of weight fragments either)
-        constexpr int PF = NWV == 8 ? 2 : SPK_FP6_PF;
-        constexpr bool BPF = NWV != 8;
+        constexpr int PF = SPK_FP6_PF;
         v4i af[PF];
 #pragma unroll
         for (int s = 0; s < PF; ++s) af[s] = lda(s);
@@ -266,14 +242,11 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
           const v4i av = af[s % PF];
           if (s + PF < 9 * NT) af[s % PF] = lda(s + PF);
           auto mfma = [&](int j) {
-#ifdef SPK_FP6_KEEP
-            if (i >= SPK_FP6_KEEP) return;        // bound experiment: only the first KEEP row tiles of a wave are computed
-#endif
             if (FIRST && tap == 0) {
-              if (3 * i + j < NAG) SPK_MFMA_FP6_Z("a", acc[i][j], av, bc[j], sc_a, sc_b);
+              if (3 * i + j < N_AGPR) SPK_MFMA_FP6_Z("a", acc[i][j], av, bc[j], sc_a, sc_b);
               else SPK_MFMA_FP6_Z("v", acc[i][j], av, bc[j], sc_a, sc_b);
             } else {
-              if (3 * i + j < NAG) SPK_MFMA_FP6("a", acc[i][j], av, bc[j], sc_a, sc_b);
+              if (3 * i + j < N_AGPR) SPK_MFMA_FP6("a", acc[i][j], av, bc[j], sc_a, sc_b);
               else SPK_MFMA_FP6("v", acc[i][j], av, bc[j], sc_a, sc_b);
             }
           };
@@ -283,55 +256,32 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
           __builtin_amdgcn_sched_barrier(0);
           {
             // DMA schedule: NPA + NPW pieces spread over the 9*NT steps (every DMA_EVERY-th step issues one piece)
-            constexpr int NPIECES = NPA_ + NPW_;
+            constexpr int NPIECES = NPA + NPW;
             constexpr int DMA_EVERY = SPK_FP6_DMA_EVERY;
             if (s % DMA_EVERY == 0 && s / DMA_EVERY < NPIECES) {
-              const int q = s / DMA_EVERY;
-              const bool skip = ((SPK_FP6_DBG & 8) && q >= NPA_) || ((SPK_FP6_DBG & 16) && q < NPA_);
-              if (!(SPK_FP6_DBG & 1) && !skip) issue_piece(q, n_aslab, n_wslab, n_dA, n_dW);
+              issue_piece(s / DMA_EVERY, n_aslab, n_wslab, n_dA, n_dW);
             }
           }
           mfma(1);
           __builtin_amdgcn_sched_barrier(0);
-          if (BPF && i == 0 && tap + 1 < 9) {
+          if (i == 0 && tap + 1 < 9) {
 #pragma unroll
             for (int j = 0; j < 3; ++j) bn[j] = ldb(tap + 1, j);
           }
           mfma(2);
           if (i == NT - 1) {
-            if constexpr (BPF) {
 #pragma unroll
-              for (int j = 0; j < 3; ++j) bc[j] = bn[j];
-            } else if (tap + 1 < 9) {
-#pragma unroll
-              for (int j = 0; j < 3; ++j) bc[j] = ldb(tap + 1, j);
-            }
+            for (int j = 0; j < 3; ++j) bc[j] = bn[j];
           }
           __builtin_amdgcn_sched_barrier(0);     // keep the read-ahead distance (see den_mfma.hip)
         }
       };
       if (c == 0) compute(std::true_type{}); else compute(std::false_type{});
-      if (SPK_FP6_DBG & 64) {
-        const long long tq3 = __builtin_amdgcn_s_memtime();
-        dbg_t[0] += tq1 - tq0; dbg_t[1] += tq2 - tq1; dbg_t[2] += tq3 - tq2; dbg_t[3] += 1;
-      }
     }   // chunks
 
     // The MFMAs are opaque to hipcc's hazard recognizer: an accumulator may be read 18 wait states after the (16-pass)
     // MFMA that wrote it was issued.
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    if (SPK_FP6_DBG & 4) {
-      float sacc = 0.f;
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          if (3 * i + j < NAG) asm volatile("" : "+a"(acc[i][j]));
-          sacc += acc[i][j][0];
-        }
-      if (sacc == 12345.f) a.out[0] = 1;
-      continue;
-    }
 
     // ---------------- epilogue: exact recombination, BN, LIF scan over the 16 accumulator registers ----------------
     // Partner lanes (col, col ^ 16) hold digit planes {0,2,4} and {1,3,5} of the same channel, for every row tile.
@@ -350,13 +300,10 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
       const int ia = k == 0 ? NT - 2 : (((NT & 1) && k == (NT + 1) / 2 - 1) ? NT - 3 : 2 * (k - 1));
       const bool paired = !((NT & 1) && k == (NT + 1) / 2 - 1);
       const int ib = paired ? ia + 1 : ia;
-#ifdef SPK_FP6_KEEP
-      if (ia >= SPK_FP6_KEEP) continue;
-#endif
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        if (3 * ia + j < NAG) asm volatile("" : "+a"(acc[ia][j]));
-        if (paired && 3 * ib + j < NAG) asm volatile("" : "+a"(acc[ib][j]));
+        if (3 * ia + j < N_AGPR) asm volatile("" : "+a"(acc[ia][j]));
+        if (paired && 3 * ib + j < N_AGPR) asm volatile("" : "+a"(acc[ib][j]));
       }
       float x[16];
       auto recombine3 = [&](const float (&pr)[3]) -> float {
@@ -394,7 +341,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
           x[r + 8] = __uint_as_float(xx[1]);                             // t = r + 8 (computed by the odd lane)
         }
       }
-      const int ti = wave + NWV * (odd ? ib : ia);
+      const int ti = wave + 4 * (odd ? ib : ia);
       const int pl = 2 * ti + half;                 // accumulator lane-half == position within the tile
       const int p = pl + band * HWb;                // position in the image
       const bool pos_ok = pl < HWb && (paired || !odd);
@@ -442,10 +389,6 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6_kernel(Fp6Args a) {
     }
   }   // items
   spk_dma_wait_all();     // the copy issued during the very last chunk must not outlive the workgroup's LDS allocation
-  if ((SPK_FP6_DBG & 64) && lane == 0 && blockIdx.x < 4) {
-    long long* o = reinterpret_cast<long long*>(a.out) + (blockIdx.x * 4 + wave) * 4;
-    o[0] = dbg_t[0]; o[1] = dbg_t[1]; o[2] = dbg_t[2]; o[3] = dbg_t[3];
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ the odd position out
@@ -767,10 +710,9 @@ int launch_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* s
   // 4 MB L2, if the shape tiles exactly (see decode() in the kernel)
   // Measured on the conv4 shape (B = 256): L2-miss reads 206 -> 111 MB and HBM-side writes 218 -> 56 MB per launch at
   // the same launch time (with 7 tiles per wave it was ~2 % slower; rotating the chunk order per workgroup to spread the
-  // slab requests of an XCD made it slower still).  option fp6_xcd_walk = 0 selects the image-major walk.
-  const bool xcd_walk = spk_opt(SPK_OPT_FP6_XCD_WALK) != 0;
+  // slab requests of an XCD made it slower still).
   a.gx = 0;
-  if (xcd_walk && !n_dyn && !bands && (grid.x & 7) == 0) {      // (a device-side batch count / row bands walk image-major)
+  if (!n_dyn && !bands && (grid.x & 7) == 0) {      // (a device-side batch count / row bands walk image-major)
     const int S = grid.x / 8;
     int gx = 1;
     while (gx * 2 <= G && (long long)gx * 2 * nch * W_CHUNK_BYTES <= 1536 * 1024) gx *= 2;
@@ -780,11 +722,7 @@ int launch_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* s
   if (bands) {
     hipLaunchKernelGGL((conv3x3_fp6_kernel<4, RAW, true>), grid, blk, lds, stream, a);
   } else if (split_last) {
-    const bool eight = spk_opt(SPK_OPT_FP6_WAVES) == 8;
-    if (eight && (H * ((W + 1) / 2) + 7) / 8 <= 4)
-      hipLaunchKernelGGL((conv3x3_fp6_kernel<3, RAW, false, 8>), grid, dim3(512), lds, stream, a);
-    else
-      hipLaunchKernelGGL((conv3x3_fp6_kernel<6, RAW>), grid, blk, lds, stream, a);
+    hipLaunchKernelGGL((conv3x3_fp6_kernel<6, RAW>), grid, blk, lds, stream, a);
     SPK_LAUNCH_CHECK();
     hipLaunchKernelGGL(conv3x3_fp6_lastpos_kernel<RAW>, dim3((B + 2 * LP_TILES - 1) / (2 * LP_TILES), G / 4), blk, 0, stream, a);
   } else {

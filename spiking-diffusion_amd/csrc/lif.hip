@@ -18,18 +18,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ------------------------------------------------------------------------------------------ LIF
 // One thread owns VEC consecutive neurons and walks T with stride N.  Loads of a chunk of TU steps are
 // issued back to back (TU x 16 B in flight per lane) before the dependent scan consumes them.
-#ifndef SPK_LIF_TU
-#define SPK_LIF_TU 8            // time steps whose loads are in flight together (x 16 B per lane)
-#endif
-#ifndef SPK_LIF_BLOCK
-#define SPK_LIF_BLOCK 256
-#endif
-#ifndef SPK_LIF_GRID_PER_CU
-#define SPK_LIF_GRID_PER_CU 32  // workgroups per CU at most (grid-stride beyond)
-#endif
-#ifndef SPK_LIF_NT
-#define SPK_LIF_NT 3            // bit 0: non-temporal loads, bit 1: non-temporal stores
-#endif
+// Loads and f32 stores are non-temporal (streamed once).
+constexpr int SPK_LIF_TU = 8;            // time steps whose loads are in flight together (x 16 B per lane)
+constexpr int SPK_LIF_BLOCK = 256;
+constexpr int SPK_LIF_GRID_PER_CU = 32;  // workgroups per CU at most (grid-stride beyond)
 template <int VEC, int OUT, bool DIV>
 __global__ __launch_bounds__(SPK_LIF_BLOCK) void lif_fwd_kernel(const float* __restrict__ x, float* __restrict__ v_io,
                                                       void* __restrict__ out, int T, long long N, float tau,
@@ -58,8 +50,7 @@ __global__ __launch_bounds__(SPK_LIF_BLOCK) void lif_fwd_kernel(const float* __r
           if constexpr (VEC >= 4) {
 #pragma unroll
             for (int q = 0; q < VEC / 4; ++q) {
-              f32x4 t4 = (SPK_LIF_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + q)
-                                          : reinterpret_cast<const f32x4*>(p)[q];
+              f32x4 t4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p) + q);
               xv[i][4 * q] = t4.x; xv[i][4 * q + 1] = t4.y; xv[i][4 * q + 2] = t4.z; xv[i][4 * q + 3] = t4.w;
             }
           } else {
@@ -80,8 +71,7 @@ __global__ __launch_bounds__(SPK_LIF_BLOCK) void lif_fwd_kernel(const float* __r
 #pragma unroll
               for (int q = 0; q < VEC / 4; ++q) {
                 f32x4 r = {s[4 * q] ? 1.f : 0.f, s[4 * q + 1] ? 1.f : 0.f, s[4 * q + 2] ? 1.f : 0.f, s[4 * q + 3] ? 1.f : 0.f};
-                if (SPK_LIF_NT & 2) __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(po) + q);
-                else reinterpret_cast<f32x4*>(po)[q] = r;
+                __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(po) + q);
               }
             } else {
               po[0] = s[0] ? 1.f : 0.f;
@@ -306,20 +296,10 @@ extern "C" int spk_lif_fwd(const float* x_seq, float* v_inout, void* spike_out, 
   const bool f32 = spike_dtype == SPK_SPIKE_F32;
   const uintptr_t al = (uintptr_t)x_seq | (uintptr_t)v_inout | (uintptr_t)spike_out;
   const bool vec = (N % 4 == 0) && (al % 16 == 0);
-#ifndef SPK_LIF_VEC8
-#define SPK_LIF_VEC8 0          // 1: eight neurons per thread (two 16-byte requests per lane and step) where N % 8 == 0.  Round 6, same box:
-                                // 3.7-3.8 TB/s against 6.4 (a wave's request then covers every other 16 bytes of 2 KB): not instantiated
-#endif
-  [[maybe_unused]] const bool vec8 = SPK_LIF_VEC8 && vec && (N % 8 == 0) && (al % 32 == 0);
+  // (eight neurons per thread where N % 8 == 0: 3.7-3.8 TB/s against 6.4, profiles/r6_ab_kernel_variants.txt)
 #define SPK_LIF_LAUNCH(VEC, OUT, DIV)                                                                              \
   hipLaunchKernelGGL((lif_fwd_kernel<VEC, OUT, DIV>), dim3(lif_grid((N + VEC - 1) / VEC)), dim3(SPK_LIF_BLOCK), 0, stream, \
                      x_seq, v_inout, spike_out, T, N, tau, inv_tau, v_threshold, v_reset)
-#if SPK_LIF_VEC8
-  if (vec8) {
-    if (f32) { if (pow2) SPK_LIF_LAUNCH(8, SPK_SPIKE_F32, false); else SPK_LIF_LAUNCH(8, SPK_SPIKE_F32, true); }
-    else     { if (pow2) SPK_LIF_LAUNCH(8, SPK_SPIKE_U8, false);  else SPK_LIF_LAUNCH(8, SPK_SPIKE_U8, true); }
-  } else
-#endif
   if (vec) {
     if (f32) { if (pow2) SPK_LIF_LAUNCH(4, SPK_SPIKE_F32, false); else SPK_LIF_LAUNCH(4, SPK_SPIKE_F32, true); }
     else     { if (pow2) SPK_LIF_LAUNCH(4, SPK_SPIKE_U8, false);  else SPK_LIF_LAUNCH(4, SPK_SPIKE_U8, true); }

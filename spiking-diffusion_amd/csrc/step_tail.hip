@@ -28,15 +28,7 @@ constexpr int TCK = 32;                           // channels per K chunk
 constexpr int TW_CHUNK = 9 * 2 * 32 * TCK;        // 18432 B of packed weights per (channel group, chunk)
 constexpr int TNCH = 10;                          // 8 chunks of conv5 counts + 2 of conv1 counts (256 + 64 channels)
 constexpr int TK_MAX = 512;                       // classes = conv6 output channels (KG = groups per wave = ceil(K / 128) <= 4)
-#ifndef SPK_TAIL_PF
-#define SPK_TAIL_PF 8                             // weight tiles are requested this many taps ahead of their MFMAs
-#endif
-#ifndef SPK_TAIL_ROT
-#define SPK_TAIL_ROT 1
-#endif
-#ifndef SPK_TAIL_DBG
-#define SPK_TAIL_DBG 0                            // timing experiments only (wrong results): 1 no K loop, 2 no token update, 4 no conv1
-#endif
+constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested this many taps ahead of their MFMAs
 
 struct TailArgs {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
@@ -88,7 +80,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
   const int8_t* wg = a.wq + (long long)(wave < ng ? wave : 0) * TNCH * TW_CHUNK + boff;
   // every workgroup reads the same 1.4 MB of packed weights: workgroups of one XCD (blocks k, k + 8, ...) start at different
   // chunks so that they do not all ask the L2 for the same lines at the same time (exact integer sums: any order)
-  const int rot = SPK_TAIL_ROT ? (int)((blockIdx.x >> 3) % TNCH) : 0;
+  const int rot = (int)((blockIdx.x >> 3) % TNCH);
   auto chunk_of = [&](int i) -> int { const int c = i / 9 + rot; return c >= TNCH ? c - TNCH : c; };
   constexpr int NIT = TNCH * 9, D = SPK_TAIL_PF;
   v4i bq[D][2];
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[rt][j][r] = 0;
 #pragma unroll
-    for (int i = 0; i < ((SPK_TAIL_DBG & 1) ? D : NIT); ++i) {
+    for (int i = 0; i < NIT; ++i) {
       const int c = chunk_g(i), tap = i % 9;
       const int dy = tap / 3 - 1, dx = tap % 3 - 1;
       const v4i b0 = bq[i % D][0], b1 = bq[i % D][1];
@@ -227,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
   __syncthreads();
 
   // ---- p_sample: wave w takes positions w, w + 8, ...; only positions that change at this step consume a sample (:140)
-  for (int p = wave; p < ((SPK_TAIL_DBG & 2) ? 0 : HW); p += 8) {
+  for (int p = wave; p < HW; p += 8) {
     const long long pi = (long long)bi * HW + p;
     if (!s_chg[p]) continue;                                            // (wave-uniform; s_tok[p] holds the token it keeps)
     // (classes k >= K -- the zero-padded output channels of conv6 and the lanes beyond them -- are masked exactly as
@@ -279,7 +271,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
       s_tok[p] = (float)besti;
     }
   }
-  if (!a.x1_out || (SPK_TAIL_DBG & 4)) return;                         // (uniform: the last reverse step has no successor)
+  if (!a.x1_out) return;                         // (uniform: the last reverse step has no successor)
   __syncthreads();
 
   // ---- the next step's first layer: conv1(cat(x_t, t - 1)) + BN + LIF from the reset state -> S32 spikes + spike counts

@@ -4,7 +4,7 @@
 // accumulator through the per-block scales, every spike decision certified against an error bound, the few neurons that come
 // within the bound of the threshold recomputed exactly (all six digits, 64-bit sums, fp64 recombination, one rounding) by a
 // tail launch.  Unflagged neurons provably emit the exact path's spikes; the result is the one spk_conv_mfma_fused_fwd (int8
-// gather kernel) produces for the same layer.  Round 4: FOUR digits on the matrix cores (SPK_VT_D4: two accumulators per tile,
+// gather kernel) produces for the same layer.  Round 4: FOUR digits on the matrix cores (two accumulators per tile,
 // 4 / 2 instead of 5 / 3 MFMAs and weight-tile reads per tap and chunk) behind the COUNTED bound of den_mfma_fp6v2.hip -- the
 // active inputs of every input record are popcounted once per item, then per class and output position the maximum over the
 // steps of the sum over the class's taps multiplies the per-input bound of the two dropped digits.  Measured at B = 1024 (same
@@ -68,60 +68,23 @@ __device__ __forceinline__ void tfor(F&& f) {
 }
 
 constexpr float CERT_4EPS = 4.0f * 2.38418579e-07f;
-#ifndef SPK_VT_EXEC_SCAN
-#define SPK_VT_EXEC_SCAN 1      // 0: the collapsed-output scan handles a spike with compare + selects (the compiler's form)
-#endif
-#ifndef SPK_VT_NWV
-#define SPK_VT_NWV 16           // waves per workgroup.  Round 4: SIXTEEN (four per SIMD) with one tile per pass: the four-digit form needs ~100
-                                // registers at SPK_VT_TPP = 1, four waves issue vector instructions at 2.0 instead of 3.1 cycles each
-                                // (tools/coexec_probe.hip) and overlap one another's multiply phases: encode -> decode at B = 1024
-                                // 1.577 -> 1.632-1.640 M images/s, convT2 0.225 -> 0.213 ms (same box; 12 waves: 1.61 M).  Round 3 (five
-                                // digits): 16 waves x 1 tile 253-255 us against 259-267 for convT2 and spills in the nine-tap layer
-#endif
-#ifndef SPK_VT_PIPE
-#define SPK_VT_PIPE 0           // 1: software-pipelined LDS reads in the multiply phase (weight tile two steps ahead, next tap's spike
-                                // fragments one tap ahead, schedule pinned); measured equal (264-267 against 267 us): hipcc already defers the
-                                // second tile's MFMAs to after the first tile's scan and runs them back to back from registers
-#endif
-#ifndef SPK_VT_PFB
-#define SPK_VT_PFB 2            // (SPK_VT_PIPE) how many steps ahead a weight tile is requested
-#endif
-#ifndef SPK_VT_STAGGER
-#define SPK_VT_STAGGER 0        // s_sleep argument (x 64 cycles) of waves 4..7 after every item barrier.  Measured (convT2, B = 1024): 8 / 16 / 24 /
-                                // 32 / 48 -> 273 / 270-274 / 273 / 273 / 275 us against 266-267: a wave that scans while its partner multiplies
-                                // issues its vector instructions at the single-wave rate (6.3 instead of 3.1 cycles): nothing is gained
-#endif
-#ifndef SPK_VT_D4
-#define SPK_VT_D4 1             // round 4: FOUR digits on the matrix cores (two accumulators per tile, 4 / 2 instead of 5 / 3 MFMAs and
-                                // weight-tile reads per tap) behind the COUNTED certification bound of den_mfma_fp6v2.hip: the two dropped
-                                // digits move a pre-activation by at most 528 units of 2^-s per ACTIVE input, and the active inputs of
-                                // every output row are counted once per item (popcounts of the input records, then per class and
-                                // position the maximum over the steps of the sum over the class's taps).  0: five digits, static bound
-#endif
-#ifndef SPK_VT_TPP
-#define SPK_VT_TPP (SPK_VT_NWV >= 12 ? 1 : 2)   // row tiles per pass (a weight tile read from LDS serves all of them)
-#endif
-#ifndef SPK_VT_TPP_T
-#define SPK_VT_TPP_T SPK_VT_TPP // ... of the transposed (1 / 2 / 2 / 4-tap) layers.  Round 4 (four digits): three tiles per pass fit (256 registers,
-                                // 16 B of scratch) and measure the same as two (dec2 0.2275 against 0.2219 / 0.2249 ms): two
-#endif
-#ifndef SPK_VT_SIGNBITS
-#define SPK_VT_SIGNBITS 1       // spike-bit outputs: the sixteen bits of a lane shifted in from the sign of h - 1 (den_mfma_fp6v2.hip, SPK_V2_SIGNBITS):
-                                // same speed here (encode -> decode 1.667-1.685 against 1.677-1.678 M images/s), ten registers fewer in the
-                                // spike-bit layers and no scratch left in the CIFAR-shaped 8x8 -> 16x16 layer.  0: the select form
-#endif
-#ifndef SPK_VT_HOIST
-#define SPK_VT_HOIST 1          // the weight fragments of a class's FIRST tap stay in registers over the wave's passes of that class within an
-                                // item (24 registers with two chunks, 12 with one): the multiply phase of these layers is bound by LDS reads,
-                                // 1.5 KB of weight fragments per MFMA (profiles/r4_ab_kernel_variants.txt (11)); 0: every pass reads them
-#endif
-#ifndef SPK_VT_NHOLD
-#define SPK_VT_NHOLD 1          // how many of a class's leading taps are held that way (SPK_VT_HOIST).  All four taps of the four-tap class need
-                                // 96 registers with two chunks: twelve waves (168 registers each) hold three, sixteen (128) hold one
-#endif
-#ifndef SPK_VT_DBG
-#define SPK_VT_DBG 0            // timing experiments only (results are wrong): 1 = no MFMAs, 2 = no LIF scan, 4 = no weight-tile reads from LDS
-#endif
+constexpr int SPK_VT_NWV = 16;          // waves per workgroup.  Round 4: SIXTEEN (four per SIMD) with one tile per pass: the four-digit form needs ~100
+                                        // registers at one tile per pass, four waves issue vector instructions at 2.0 instead of 3.1 cycles each
+                                        // (tools/coexec_probe.hip) and overlap one another's multiply phases: encode -> decode at B = 1024
+                                        // 1.577 -> 1.632-1.640 M images/s, convT2 0.225 -> 0.213 ms (same box; 12 waves: 1.61 M).  Round 3 (five
+                                        // digits): 16 waves x 1 tile 253-255 us against 259-267 for convT2 and spills in the nine-tap layer
+constexpr int SPK_VT_TPP = 1;           // row tiles per pass (a weight tile read from LDS serves all of them)
+// FOUR digits on the matrix cores (two accumulators per tile, 4 / 2 MFMAs and weight-tile reads per tap) behind the COUNTED certification
+// bound of den_mfma_fp6v2.hip: the two dropped digits move a pre-activation by at most 528 units of 2^-s per ACTIVE input, and the active
+// inputs of every output row are counted once per item (popcounts of the input records, then per class and position the maximum over the
+// steps of the sum over the class's taps).  Spike-bit outputs: the sixteen bits of a lane shifted in from the sign of h - 1 (as in
+// den_mfma_fp6v2.hip).  The weight fragments of a class's leading SPK_VT_NHOLD taps stay in registers over the wave's passes of that class
+// within an item: the multiply phase of these layers is bound by LDS reads, 1.5 KB of weight fragments per MFMA
+// (profiles/r4_ab_kernel_variants.txt (11)).
+// (Measured and dropped: software-pipelined LDS reads in the multiply phase, 264-267 against 267 us; a 512-2048-cycle s_sleep stagger of
+//  waves 4..7, 270-275 against 266-267 us on convT2.)
+constexpr int SPK_VT_NHOLD = 1;         // held taps per class.  All four taps of the four-tap class need 96 registers with two chunks: twelve waves
+                                        // (168 registers each) hold three, sixteen (128) hold one
 
 __device__ __forceinline__ unsigned spread8_v(unsigned x) {        // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
   x = (x | (x << 12)) & 0x000f000fu;
@@ -155,57 +118,19 @@ __host__ __device__ constexpr int on_tap(int k) {
   return 0;
 }
 
-#ifndef SPK_VT_DYN
-#define SPK_VT_DYN 1            // round 5: the passes of an item are HANDED OUT (an LDS counter, class-major order kept) instead of dealt
-                                // round-robin.  tools/vae_phase.py: of the four waves of a SIMD the oldest issues its scan's vector
-                                // instructions first -- waves 0-3 scan a pass in 1 280 cycles, waves 12-15 in 2 410 -- so with equal
-                                // shares the first four waited 31 % of the launch at the item's end barrier (mean over the waves: 19 %)
-#endif
-#ifndef SPK_VT_PREFETCH
-#define SPK_VT_PREFETCH 0       // 1 (single-slab layers): one dword of every 128-byte line of the NEXT item's input rows is requested at the start of
-                                // this item's passes, so that the copy behind the end barrier finds them in the L2
-#endif
-#ifndef SPK_VT_PRIO
-#define SPK_VT_PRIO 0           // s_setprio of a wave in its multiply phase (0 in the scan): the MFMAs and their LDS reads go first
-#endif
-#ifndef SPK_VT_STAMP
-#define SPK_VT_STAMP 0          // 1 (timing builds only): workgroup 0 accumulates shader-clock cycles per wave and phase into g_vt_stamp
-                                // (spk_vt_stamps reads and clears it; tools/vae_phase.py)
-#endif
-#if SPK_VT_STAMP
-__device__ unsigned long long g_vt_stamp[SPK_VT_NWV][8];
-#define VT_CLK() ((long long)__builtin_readcyclecounter())
-#define VT_ACC(slot, t0) do { const long long t1_ = VT_CLK(); st_acc[slot] += t1_ - (t0); (t0) = t1_; } while (0)
-#else
-#define VT_ACC(slot, t0) do { } while (0)
-#endif
-
-#ifndef SPK_VT_INWAVE_FIX
-#define SPK_VT_INWAVE_FIX 0     // 1 (round 6 experiment, measured SLOWER): a wave recomputes the neurons IT flags, exactly, right behind the tile's
-                                // stores (an out-of-line call on a path 0.6 % of the tiles take) -- no id list, no repair launch.  Bit-equal (28
-                                // vae_fp6 tests), and the three repair launches (8 + 8 + 6 us) go away, but the main launches grow by more:
-                                // convT2 198.8 -> 209.8, convT1 105.9 -> 110.5, conv2 65.3 -> 79.7 us; encode -> decode 0.555 -> 0.575 ms, same
-                                // box (profiles/r6_ab_kernel_variants.txt (3)).  0: id list + overflow bitmap + vae_fp6_fixup_kernel
-#endif
-// (the out-of-line form of vae_fix_neuron: the hot kernel then pays for the call only on the rare path)
-template <int GEO, int H, int W, int NCH, int OUT>
-__device__ __attribute__((noinline)) void vae_fix_neuron_call(const uint8_t* in, const int* qtab, const double* scale, const double* bias,
-                                                              const float* bn_a, const float* bn_b, const float* coef, void* out,
-                                                              int Cin, int Cout, long long nid, int lane);
-
+// The passes of an item are HANDED OUT (an LDS counter, class-major order kept) instead of dealt round-robin: of the four waves of a SIMD
+// the oldest issues its scan's vector instructions first -- waves 0-3 scan a pass in 1 280 cycles, waves 12-15 in 2 410 -- so with equal
+// shares the first four waited 31 % of the launch at the item's end barrier (mean over the waves: 19 %).
+// (A wave recomputing the neurons IT flags right behind the tile's stores, instead of the id list + repair launch, measured slower:
+//  convT2 198.8 -> 209.8, conv2 65.3 -> 79.7 us, profiles/r6_ab_kernel_variants.txt (3).)
 template <int GEO, int H, int W, int NCH, int OUT, int SPLIT, bool DB>
 __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
-#if SPK_VT_STAMP
-  long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // 0 stage+wait+barrier, 1 popcount phases, 2 multiply, 3 scan+store, 4 end barrier, 5 hold reads, 6 passes
-  long long st_t = VT_CLK();
-  const long long st_begin = st_t;
-#endif
   constexpr int TPT = tiles_per_tap(NCH), W_BYTES = 9 * TPT * WT;
-  constexpr int TPL = SPK_VT_D4 ? TPT - 1 : TPT;            // tiles per tap kept in LDS (the fifth-digit tile stays in memory)
+  constexpr int TPL = TPT - 1;                              // tiles per tap kept in LDS (the fifth-digit tile stays in memory)
   constexpr int WL_BYTES = 9 * TPL * WT;
   constexpr int RQ = GEO == 0 ? H / SPLIT : H / 2;          // rows of positions per item (class rows / output rows)
   constexpr int CW = GEO == 0 ? W : W / 2;                  // positions per row
-  constexpr int NPOS = RQ * CW, NTC = (NPOS + 1) / 2, TPP = GEO == 0 ? SPK_VT_TPP_T : SPK_VT_TPP, NPASS = (NTC + TPP - 1) / TPP,
+  constexpr int NPOS = RQ * CW, NTC = (NPOS + 1) / 2, TPP = SPK_VT_TPP, NPASS = (NTC + TPP - 1) / TPP,
                 NCLS = GEO == 0 ? 4 : 1;
   constexpr int SROWS = GEO == 0 ? RQ + 1 : H + 1, SCOLS = W + 1;
   constexpr int A_CH = SROWS * SCOLS * POSB, A_BYTES = NCH * A_CH, NBUF = DB ? 2 : 1;
@@ -216,13 +141,13 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   uint8_t* const sA = lds;
   uint8_t* const sW = lds + NBUF * A_BYTES;
-  // four-digit form: active inputs per input cell and step (u8, borders zero) and, per class and position, their maximum over
+  // active inputs per input cell and step (u8, borders zero) and, per class and position, their maximum over
   // the steps of the sum over the class's taps
   constexpr int NCELL = SROWS * SCOLS;
   uint8_t* const s_cin = lds + NBUF * A_BYTES + WL_BYTES;                       // [NCELL][16]
   int* const s_nmax = reinterpret_cast<int*>(s_cin + ((NCELL * 16 + 15) & ~15));   // [NCLS][NPOS]
-  constexpr bool DYN = SPK_VT_DYN && GEO == 0;              // (the 25 passes of the plain stride-2 layer's item: dealt; handed out it measured 3 us slower)
-  int* const s_ctr = SPK_VT_D4 ? s_nmax + NCLS * NPOS : reinterpret_cast<int*>(s_cin);   // the item's next pass (SPK_VT_DYN)
+  constexpr bool DYN = GEO == 0;                           // (the 25 passes of the plain stride-2 layer's item: dealt; handed out it measured 3 us slower)
+  int* const s_ctr = s_nmax + NCLS * NPOS;                  // the item's next pass (DYN)
   const unsigned sA_addr = spk_lds_addr(sA);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -242,19 +167,9 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
   const int co = g * 32 + (lane & 31);
   const float scale_f = (float)a.scale[co], bias_f = (float)a.bias[co];
   const float bna = a.bn_a[co], bnb = a.bn_b[co];
-  const float Ac = 32.0f * scale_f * bna;                   // z = Q5 * Ac + Bc,  Q5 = P01 * 2^15 + P23 * 2^5 + P4
-  const float Ac0 = Ac * 32768.0f, Ac1 = Ac * 32.0f;        // (powers of two: exact)
   const float Bc = fmaf(bias_f, bna, bnb);
-  // Certification (den_mfma_fp6v2.hip): the approximate and the exact pre-activation differ by at most cE + 2 eps |z|:
-  // the dropped sixth digit moves a pre-activation by at most 16 units of 2^-s per active input (at most KMAX taps x Cin
-  // inputs reach an output), and the three-term fp32 recombination z = P01 * Ac0 + (P23 * Ac1 + (P4 * Ac + Bc)) rounds partial
-  // sums bounded by the middle / low digit groups (|32 d2 + d3| <= 528, |d4| <= 16 per input) rather than by |z|.
-  const float kin = (float)(Geo<GEO, H, W>::KMAX * a.Cin);
-  const float E5 = 16.0f * kin * scale_f;
-  const float part_max = (528.0f * fabsf(Ac1) + 16.0f * fabsf(Ac)) * kin + fabsf(Bc);
-  const float cE = SPK_VT_D4 ? 2.0f * 2.38418579e-07f * (fabsf(bnb) + fabsf(Bc)) + 1e-30f
-                             : fabsf(bna) * E5 + 2.0f * 2.38418579e-07f * (fabsf(bnb) + fabsf(Bc) + 2.0f * part_max) + 1e-30f;
-  // four digits (den_mfma_fp6v2.hip, "Certification"): z = Q4 * Ac4 + Bc, Q4 = P01 * 2^10 + P23; the dropped digits move z_t by at
+  const float cE = 2.0f * 2.38418579e-07f * (fabsf(bnb) + fabsf(Bc)) + 1e-30f;
+  // certification (den_mfma_fp6v2.hip, "Certification"): z = Q4 * Ac4 + Bc, Q4 = P01 * 2^10 + P23; the dropped digits move z_t by at
   // most cT * n_t (|32 d4 + d5| <= 528 units of 2^-s per active input), every fp32 rounding is inside the eps terms
   const float cT = 528.0f * scale_f * fabsf(bna) * 1.000001f;
   const float Ac4 = 1024.0f * scale_f * bna;
@@ -266,7 +181,6 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
   const int hsel = (row >> 2) & 1, tt = (row & 3) + 4 * (row >> 3);
   const int sc_a = 0x7f7f7f7f;
   const int sc_p = half ? (int)0x82828282u : (int)0x87878787u;     // even digit (K half 0) x 2^8, odd digit x 2^3
-  const int sc_4 = (int)0x82828282u;                                // fifth digit x 2^3
   const unsigned lane16 = (unsigned)lane * 16u;
   const int nitems = SPLIT * a.B;
 
@@ -306,74 +220,52 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
       // (every wave took its last pass number of the previous item before the barrier above; the first one of this item is taken
       //  behind the barriers of the counting phases below)
       if (tid == 0) *s_ctr = SPK_VT_NWV;
-      if constexpr (!SPK_VT_D4) __syncthreads();
     }
-    VT_ACC(0, st_t);
-#if SPK_VT_STAGGER > 0
-    // The two waves of a SIMD run the same pass list from the same barrier, so both are in their multiply phase together (each
-    // then sees the matrix pipe at half rate: stamped 65-70 cycles per MFMA) and in their scans together.  The second wave
-    // starts every item this many x 64 cycles late: its multiply phases then fall into the first one's scans.
-    if (wave >= SPK_VT_NWV / 2) __builtin_amdgcn_s_sleep(SPK_VT_STAGGER);
-#endif
     const uint8_t* const A0 = sA + buf * A_BYTES;
 
-    if constexpr (SPK_VT_D4) {
-      // (A) active inputs of every input record (cell, step), summed over the chunks: a spike is the nibble 0x2 = one set bit
-      for (int r = tid; r < NCELL * 16; r += SPK_VT_NWV * 64) {
-        int n = 0;
+    // (A) active inputs of every input record (cell, step), summed over the chunks: a spike is the nibble 0x2 = one set bit
+    for (int r = tid; r < NCELL * 16; r += SPK_VT_NWV * 64) {
+      int n = 0;
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const v4i q = *reinterpret_cast<const v4i*>(A0 + c * A_CH + r * 16);
-          n += __builtin_popcount((unsigned)q[0]) + __builtin_popcount((unsigned)q[1]) + __builtin_popcount((unsigned)q[2]) +
-               __builtin_popcount((unsigned)q[3]);
-        }
-        s_cin[r] = (uint8_t)n;                                 // <= 64
+      for (int c = 0; c < NCH; ++c) {
+        const v4i q = *reinterpret_cast<const v4i*>(A0 + c * A_CH + r * 16);
+        n += __builtin_popcount((unsigned)q[0]) + __builtin_popcount((unsigned)q[1]) + __builtin_popcount((unsigned)q[2]) +
+             __builtin_popcount((unsigned)q[3]);
       }
-      __syncthreads();
-      // (B) per class and output position: max over the steps of the sum over the class's taps (what the bound multiplies cT by)
-      for (int e = tid; e < NCLS * NPOS; e += SPK_VT_NWV * 64) {
-        const int cls = e / NPOS, p = e - cls * NPOS, ry = p / CW, rx = p - ry * CW;
-        const int cell0 = GEO == 0 ? ry * SCOLS + rx : 2 * ry * SCOLS + 2 * rx;
-        const int py = cls >> 1, px = cls & 1;
-        unsigned lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};   // sixteen 16-bit sums (even / odd bytes of the four words)
+      s_cin[r] = (uint8_t)n;                                 // <= 64
+    }
+    __syncthreads();
+    // (B) per class and output position: max over the steps of the sum over the class's taps (what the bound multiplies cT by)
+    for (int e = tid; e < NCLS * NPOS; e += SPK_VT_NWV * 64) {
+      const int cls = e / NPOS, p = e - cls * NPOS, ry = p / CW, rx = p - ry * CW;
+      const int cell0 = GEO == 0 ? ry * SCOLS + rx : 2 * ry * SCOLS + 2 * rx;
+      const int py = cls >> 1, px = cls & 1;
+      unsigned lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};   // sixteen 16-bit sums (even / odd bytes of the four words)
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-          const int ky = tap / 3, kx = tap % 3;
-          const bool on = GEO == 1 || ((py == 0 ? ky == 1 : ky != 1) && (px == 0 ? kx == 1 : kx != 1));
-          const int dy = GEO == 1 ? ky : ((py == 1 && ky == 0) ? 1 : 0), dx = GEO == 1 ? kx : ((px == 1 && kx == 0) ? 1 : 0);
-          if (on) {
-            const v4i q = *reinterpret_cast<const v4i*>(s_cin + (cell0 + dy * SCOLS + dx) * 16);
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap % 3;
+        const bool on = GEO == 1 || ((py == 0 ? ky == 1 : ky != 1) && (px == 0 ? kx == 1 : kx != 1));
+        const int dy = GEO == 1 ? ky : ((py == 1 && ky == 0) ? 1 : 0), dx = GEO == 1 ? kx : ((px == 1 && kx == 0) ? 1 : 0);
+        if (on) {
+          const v4i q = *reinterpret_cast<const v4i*>(s_cin + (cell0 + dy * SCOLS + dx) * 16);
 #pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-              lo[w4] += (unsigned)q[w4] & 0x00ff00ffu;
-              hi[w4] += ((unsigned)q[w4] >> 8) & 0x00ff00ffu;
-            }
+          for (int w4 = 0; w4 < 4; ++w4) {
+            lo[w4] += (unsigned)q[w4] & 0x00ff00ffu;
+            hi[w4] += ((unsigned)q[w4] >> 8) & 0x00ff00ffu;
           }
         }
-        unsigned mx = 0;
+      }
+      unsigned mx = 0;
 #pragma unroll
-        for (int w4 = 0; w4 < 4; ++w4) {
-          mx = max(mx, max(lo[w4] & 0xffffu, lo[w4] >> 16));
-          mx = max(mx, max(hi[w4] & 0xffffu, hi[w4] >> 16));
-        }
-        s_nmax[e] = (int)mx;
+      for (int w4 = 0; w4 < 4; ++w4) {
+        mx = max(mx, max(lo[w4] & 0xffffu, lo[w4] >> 16));
+        mx = max(mx, max(hi[w4] & 0xffffu, hi[w4] >> 16));
       }
-      __syncthreads();
+      s_nmax[e] = (int)mx;
     }
-    VT_ACC(1, st_t);
-    if constexpr (SPK_VT_PREFETCH && !DB) {
-      if (itm + lanes < nitems) {
-        const int nb_ = (itm + lanes) / SPLIT, np_ = (itm + lanes) - nb_ * SPLIT;
-        const int iy0 = GEO == 0 ? np_ * RQ : 0;
-        const int nrows = (iy0 + DROWS <= H ? DROWS : H - iy0), lpc = nrows * (W * POSB / 128);   // rows are contiguous within a chunk
-        for (int l = tid; l < NCH * lpc; l += SPK_VT_NWV * 64) {
-          const int c = l / lpc, o = l - c * lpc;
-          (void)*reinterpret_cast<const volatile unsigned*>(a.in + (((long long)nb_ * NCH + c) * H * W + iy0 * W) * POSB + (long long)o * 128);
-        }
-      }
-    }
+    __syncthreads();
 
-    // hb: the weight fragments of the class's first tap, read once per class by the caller (SPK_VT_HOIST)
+    // hb: the weight fragments of the class's first tap, read once per class by the caller
     auto run_pass = [&](auto cls_tag, int k, const v6i (&hb)[SPK_VT_NHOLD][NCH * 2]) __attribute__((always_inline)) {
       constexpr int CLS = decltype(cls_tag)::value, PY = CLS >> 1, PX = CLS & 1;
       constexpr int NHELD = n_on_taps<GEO, CLS>() < SPK_VT_NHOLD ? n_on_taps<GEO, CLS>() : SPK_VT_NHOLD;
@@ -397,8 +289,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         const int ry = p / CW, rx = p - ry * CW;
         base[i] = (GEO == 0 ? ry * SCOLS + rx : 2 * ry * SCOLS + 2 * rx) * POSB + tt * 16;
       }
-      if (SPK_VT_PRIO) __builtin_amdgcn_s_setprio(SPK_VT_PRIO);
-      constexpr int NACC = SPK_VT_D4 ? 2 : 3;
+      constexpr int NACC = 2;
       v16f acc[TPP][NACC];
 #pragma unroll
       for (int i = 0; i < TPP; ++i)
@@ -407,7 +298,6 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
       auto ldb = [&](int tile) -> v6i {
-        if (SPK_VT_DBG & 4) return v6i{lane + tile, lane, tile, 0x11111111, lane * 3, 0x01010101};   // (timing only: no weight reads)
         const uint8_t* p = sW + tile * WT;
         const v4i x = *reinterpret_cast<const v4i*>(p + lane * 16);
         const v2i y = *reinterpret_cast<const v2i*>(p + 1024 + lane * 8);
@@ -420,58 +310,6 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         const v8i b8 = {bv[0], bv[1], bv[2], bv[3], bv[4], bv[5], 0, 0};
         d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, d, 4, 2, 0, sc_a, 0, sb);
       };
-#if SPK_VT_PIPE
-      // The pass's products as ONE compile-time list of steps (an active tap of the class x one weight tile), software pipelined:
-      // the weight tile of step s + PFB and the spike fragments of the NEXT tap are requested from LDS while the MFMAs of step s run
-      // (tap by tap -- read, wait, multiply -- a pass spends 1 000 - 1 500 cycles on 288 cycles of matrix time: tools/vae_phase.py).
-      // Steps of a held tap (SPK_VT_HOIST) take their tile from hb and request nothing.
-      constexpr int NON = n_on_taps<GEO, CLS>(), TS = TPL, NSTEP = NON * TS, PFB = SPK_VT_PFB, RB = PFB + 1;
-      auto toff = [&](auto k_tag) {
-        constexpr int TAP = on_tap<GEO, CLS>(decltype(k_tag)::value), KY = TAP / 3, KX = TAP % 3;
-        constexpr int DY = GEO == 1 ? KY : ((PY == 1 && KY == 0) ? 1 : 0), DX = GEO == 1 ? KX : ((PX == 1 && KX == 0) ? 1 : 0);
-        return std::integral_constant<int, (DY * SCOLS + DX) * POSB>{};
-      };
-      auto step_held = [](int st) constexpr {                 // the held set of step st's tap (-1: its tile comes from LDS)
-        if (!(SPK_VT_HOIST && SPK_VT_D4)) return -1;
-        for (int h = 0; h < NHELD; ++h)
-          if (h == st / TS) return h;                          // (the held taps are the class's leading ones)
-        return -1;
-      };
-      v4i av[2][TPP][NCH];
-      v6i bq[RB];
-      auto lda = [&](auto k_tag) {
-        constexpr int k = decltype(k_tag)::value, TOFF = decltype(toff(k_tag))::value;
-#pragma unroll
-        for (int i = 0; i < TPP; ++i)
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) av[k & 1][i][c] = *reinterpret_cast<const v4i*>(A0 + c * A_CH + base[i] + TOFF);
-      };
-      lda(std::integral_constant<int, 0>{});
-      tfor<(PFB < NSTEP ? PFB : NSTEP)>([&](auto s_tag) {
-        constexpr int st = decltype(s_tag)::value;
-        if constexpr (step_held(st) < 0) bq[st % RB] = ldb(on_tap<GEO, CLS>(st / TS) * TPL + st % TS);
-      });
-      tfor<NSTEP>([&](auto s_tag) {
-        constexpr int st = decltype(s_tag)::value, k = st / TS, j = st % TS;
-        if constexpr (st + PFB < NSTEP && step_held(st + PFB) < 0)
-          bq[(st + PFB) % RB] = ldb(on_tap<GEO, CLS>((st + PFB) / TS) * TPL + (st + PFB) % TS);
-        if constexpr (j == 0 && k + 1 < NON) lda(std::integral_constant<int, k + 1>{});
-        asm volatile("" ::: "memory");                       // (every read stays where it is written)
-        constexpr int HS = step_held(st);
-        const v6i bv = HS >= 0 ? hb[HS >= 0 ? HS : 0][j] : bq[st % RB];
-#pragma unroll
-        for (int i = 0; i < TPP; ++i) {
-          if (SPK_VT_DBG & 1) continue;
-          if constexpr (NCH == 2) {
-            if constexpr (j < 4) mm(acc[i][j & 1], av[k & 1][i][j >> 1], bv, sc_p);
-            else mm(acc[i][NACC - 1], half ? av[k & 1][i][1] : av[k & 1][i][0], bv, sc_4);
-          } else {
-            mm(acc[i][j < 2 ? j : NACC - 1], av[k & 1][i][0], bv, j < 2 ? sc_p : sc_4);
-          }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-#else
       tfor<9>([&](auto tap_tag) {
         constexpr int TAP = decltype(tap_tag)::value, KY = TAP / 3, KX = TAP % 3;
         // GEO 0: oy = 2 iy - 1 + ky: class parity PY takes ky = 1 (iy = qy) when even, ky = 0 (iy = qy + 1) and ky = 2 (iy = qy) when odd
@@ -487,54 +325,33 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
               av[i][1] = *reinterpret_cast<const v4i*>(A0 + A_CH + base[i] + TOFF);
             }
             constexpr int HS = held_slot(TAP);
-            constexpr bool HB = SPK_VT_HOIST && SPK_VT_D4 && HS >= 0;
+            constexpr bool HB = HS >= 0;
             constexpr int HQ = HB ? HS : 0;
             const v6i b0 = HB ? hb[HQ][0] : ldb(TAP * TPL + 0), b1 = HB ? hb[HQ][1] : ldb(TAP * TPL + 1),
                       b2 = HB ? hb[HQ][2] : ldb(TAP * TPL + 2), b3 = HB ? hb[HQ][3] : ldb(TAP * TPL + 3);
-            v6i b4 = b0;
-            if constexpr (!SPK_VT_D4) b4 = ldb(TAP * TPL + 4);
 #pragma unroll
             for (int i = 0; i < TPP; ++i) {
-              if (SPK_VT_DBG & 1) continue;
               mm(acc[i][0], av[i][0], b0, sc_p);
               mm(acc[i][1], av[i][0], b1, sc_p);
               mm(acc[i][0], av[i][1], b2, sc_p);
               mm(acc[i][1], av[i][1], b3, sc_p);
-              if constexpr (!SPK_VT_D4) {
-                const v4i a4 = half ? av[i][1] : av[i][0];
-                mm(acc[i][NACC - 1], a4, b4, sc_4);
-              }
             }
           } else {
             v4i av[TPP];
 #pragma unroll
             for (int i = 0; i < TPP; ++i) av[i] = *reinterpret_cast<const v4i*>(A0 + base[i] + TOFF);
             constexpr int HS = held_slot(TAP);
-            constexpr bool HB = SPK_VT_HOIST && SPK_VT_D4 && HS >= 0;
+            constexpr bool HB = HS >= 0;
             constexpr int HQ = HB ? HS : 0;
             const v6i b0 = HB ? hb[HQ][0] : ldb(TAP * TPL + 0), b1 = HB ? hb[HQ][1] : ldb(TAP * TPL + 1);
-            v6i b4 = b0;
-            if constexpr (!SPK_VT_D4) b4 = ldb(TAP * TPL + 2);
 #pragma unroll
             for (int i = 0; i < TPP; ++i) {
-              if (SPK_VT_DBG & 1) continue;
               mm(acc[i][0], av[i], b0, sc_p);
               mm(acc[i][1], av[i], b1, sc_p);
-              if constexpr (!SPK_VT_D4) mm(acc[i][NACC - 1], av[i], b4, sc_4);
             }
           }
         }
       });
-#endif
-      if (SPK_VT_PRIO) __builtin_amdgcn_s_setprio(0);
-#if SPK_VT_STAMP
-      {
-        float sink = acc[0][0][15] + acc[0][NACC - 1][15];
-        asm volatile("" : "+v"(sink));
-        VT_ACC(2, st_t);
-        st_acc[6] += 1;
-      }
-#endif
       // ---- epilogue: fp32 recombination, BN, LIF scan with certification, output
 #pragma unroll
       for (int i = 0; i < TPP; ++i) {
@@ -542,23 +359,12 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         // track max |z| and min |h - 1| (two instructions per step instead of five) and compare once
         float v = 0.f, m = 0.f, zmax = 0.f, dmin = 3.0e38f;
         unsigned mybits = 0;
-        if (SPK_VT_DBG & 2) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) m += acc[i][0][r] + acc[i][1][r] + acc[i][NACC - 1][r];
-        } else
 #pragma unroll
         for (int r2 = 0; r2 < 16; r2 += 2) {
           // the recombination of two steps at a time on the packed fp32 pipe (adjacent accumulator registers)
-          const v2f p0 = {acc[i][0][r2], acc[i][0][r2 + 1]}, p1 = {acc[i][1][r2], acc[i][1][r2 + 1]},
-                    p2 = {acc[i][NACC - 1][r2], acc[i][NACC - 1][r2 + 1]};
-          v2f z2;
-          if constexpr (SPK_VT_D4) {
-            const v2f q4 = __builtin_elementwise_fma(p0, (v2f){1024.0f, 1024.0f}, p1);
-            z2 = __builtin_elementwise_fma(q4, (v2f){Ac4, Ac4}, (v2f){Bc, Bc});
-          } else {
-            z2 = __builtin_elementwise_fma(p0, (v2f){Ac0, Ac0},
-                 __builtin_elementwise_fma(p1, (v2f){Ac1, Ac1}, __builtin_elementwise_fma(p2, (v2f){Ac, Ac}, (v2f){Bc, Bc})));
-          }
+          const v2f p0 = {acc[i][0][r2], acc[i][0][r2 + 1]}, p1 = {acc[i][1][r2], acc[i][1][r2 + 1]};
+          const v2f q4 = __builtin_elementwise_fma(p0, (v2f){1024.0f, 1024.0f}, p1);
+          const v2f z2 = __builtin_elementwise_fma(q4, (v2f){Ac4, Ac4}, (v2f){Bc, Bc});
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
             const int r = r2 + e;
@@ -567,7 +373,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             const float h = fmaf(z - v, 0.5f, v);            // == v + (z - v) * 0.5f: the product is exact
             const float hm = h - 1.0f;
             dmin = fminf(dmin, fabsf(hm));
-            if constexpr (OUT == OUT_COLLAPSED && SPK_VT_EXEC_SCAN) {
+            if constexpr (OUT == OUT_COLLAPSED) {
               // spike = h >= 1: reset v and add the step's coefficient UNDER THE SPIKE MASK (v_cmpx narrows exec, two plain
               // instructions, exec restored): three vector instructions instead of compare + two selects + add (convT2 -5 %;
               // the spike-bit outputs measured slower in this form -- hipcc keeps their sixteen masks in SGPRs -- and keep the C form)
@@ -579,20 +385,16 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             } else {
               const bool s = h >= 1.0f;
               v = s ? 0.0f : h;
-              if (OUT == OUT_COLLAPSED) m = m + (s ? coef[r] : 0.f);
-              else if constexpr (SPK_VT_SIGNBITS) mybits = __builtin_amdgcn_alignbit(mybits, __float_as_uint(hm), 31);   // (mybits << 1) | sign(h - 1)
-              else mybits |= s ? (1u << r) : 0u;
+              mybits = __builtin_amdgcn_alignbit(mybits, __float_as_uint(hm), 31);   // (mybits << 1) | sign(h - 1)
             }
           }
         }
-        if constexpr (SPK_VT_SIGNBITS && OUT != OUT_COLLAPSED) {
-          if (!(SPK_VT_DBG & 2)) mybits = ~(__builtin_bitreverse32(mybits) >> 16) & 0xffffu;      // bit r = NOT sign(h_r - 1)
-        }
+        if constexpr (OUT != OUT_COLLAPSED) mybits = ~(__builtin_bitreverse32(mybits) >> 16) & 0xffffu;   // bit r = NOT sign(h_r - 1)
         const int p = 2 * tl[i] + half;                       // accumulator lane half == position within the tile
         const bool ok = tv[i] && p < NPOS;
         const int pc = p < NPOS ? p : NPOS - 1;
-        // dh <= c + 8 eps max |z| (10 eps: a little to spare); c = cE (five digits, every input active) or cE + cT max_t n_t
-        const float cb = SPK_VT_D4 ? fmaf((float)s_nmax[CLS * NPOS + pc], cT, cE) : cE;
+        // dh <= c + 8 eps max |z| (10 eps: a little to spare); c = cE + cT max_t n_t
+        const float cb = fmaf((float)s_nmax[CLS * NPOS + pc], cT, cE);
         const bool flg = dmin <= fmaf(zmax, 2.5f * CERT_4EPS, cb);
         const int ry = pc / CW, rx = pc - ry * CW;
         const int oy = GEO == 0 ? 2 * (part * RQ + ry) + PY : ry, ox = GEO == 0 ? 2 * rx + PX : rx;
@@ -600,10 +402,8 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         const long long nid_f = pos * a.Cout + co;
         if (flg && ok) {
           const unsigned idx = atomicAdd(a.flags, 1u);            // (the count of flagged neurons: statistics, tests)
-          if constexpr (!SPK_VT_INWAVE_FIX) {
-            if (idx < a.flag_cap) a.flags[2 + idx] = (unsigned)nid_f;
-            else atomicOr(a.flags + 2 + FLAG_CAP + (nid_f >> 5), 1u << (nid_f & 31));
-          }
+          if (idx < a.flag_cap) a.flags[2 + idx] = (unsigned)nid_f;
+          else atomicOr(a.flags + 2 + FLAG_CAP + (nid_f >> 5), 1u << (nid_f & 31));
         }
         if (OUT == OUT_COLLAPSED) {
           if (ok) reinterpret_cast<float*>(a.out)[pos * a.Cout + co] = m;
@@ -627,27 +427,12 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.out) + (pos * T16 + t) * a.Cout + g * 32 + 16 * hi) = o;
           }
         }
-        if constexpr (SPK_VT_INWAVE_FIX) {
-          unsigned long long fm = __builtin_amdgcn_ballot_w64(flg && ok);
-          if (fm) {                                             // (wave-uniform; 0.6 % of the tiles)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the tile's own stores first: the exact values overwrite them
-            while (fm) {
-              const int l = __builtin_ctzll(fm);
-              fm &= fm - 1;
-              const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(nid_f & 0xffffffffll), l);
-              const unsigned hi32 = (unsigned)__builtin_amdgcn_readlane((int)(nid_f >> 32), l);
-              vae_fix_neuron_call<GEO, H, W, NCH, OUT>(a.in, a.qtab, a.scale, a.bias, a.bn_a, a.bn_b, a.coef, a.out, a.Cin, a.Cout,
-                                                       (long long)(((unsigned long long)hi32 << 32) | lo), lane);
-            }
-          }
-        }
       }
-      VT_ACC(3, st_t);
     };
 
     // the item's passes, class-major, dealt round-robin over the waves (every wave gets a mix of cheap and expensive classes); a
     // wave's passes of one class follow one another, so the class's first-tap weight fragments are read once for all of them
-    [[maybe_unused]] int Pdyn = wave;                          // (SPK_VT_DYN) the wave's pass: the first NWV are dealt, the rest handed out
+    [[maybe_unused]] int Pdyn = wave;                          // (DYN) the wave's pass: the first NWV are dealt, the rest handed out
     tfor<NCLS>([&](auto cls_tag) {
       constexpr int CLS = decltype(cls_tag)::value;
       constexpr int NHELD = n_on_taps<GEO, CLS>() < SPK_VT_NHOLD ? n_on_taps<GEO, CLS>() : SPK_VT_NHOLD;
@@ -658,25 +443,16 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         for (int h = 0; h < SPK_VT_NHOLD; ++h)
 #pragma unroll
           for (int j = 0; j < NCH * 2; ++j) hb[h][j] = v6i{0, 0, 0, 0, 0, 0};
-        if constexpr (SPK_VT_HOIST && SPK_VT_D4) {
-          tfor<NHELD>([&](auto h_tag) {
-            constexpr int h = decltype(h_tag)::value, TAPH = on_tap<GEO, CLS>(h);
+        tfor<NHELD>([&](auto h_tag) {
+          constexpr int h = decltype(h_tag)::value, TAPH = on_tap<GEO, CLS>(h);
 #pragma unroll
-            for (int j = 0; j < NCH * 2; ++j) {
-              const uint8_t* p = sW + (TAPH * TPL + j) * WT;
-              const v4i x = *reinterpret_cast<const v4i*>(p + lane * 16);
-              const v2i y = *reinterpret_cast<const v2i*>(p + 1024 + lane * 8);
-              hb[h][j] = v6i{x[0], x[1], x[2], x[3], y[0], y[1]};
-            }
-          });
-        }
-#if SPK_VT_STAMP
-        {
-          int sink = hb[0][0][0];
-          asm volatile("" : "+v"(sink));
-          VT_ACC(5, st_t);
-        }
-#endif
+          for (int j = 0; j < NCH * 2; ++j) {
+            const uint8_t* p = sW + (TAPH * TPL + j) * WT;
+            const v4i x = *reinterpret_cast<const v4i*>(p + lane * 16);
+            const v2i y = *reinterpret_cast<const v2i*>(p + 1024 + lane * 8);
+            hb[h][j] = v6i{x[0], x[1], x[2], x[3], y[0], y[1]};
+          }
+        });
         if constexpr (DYN) {
           while (P < (CLS + 1) * NPASS) {
             int nxt = 0;
@@ -691,15 +467,8 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
       }
     });
     if (!DB) __syncthreads();                                  // everyone is done with the slab before the next copy lands
-    VT_ACC(4, st_t);
   }
   spk_dma_wait_all();
-#if SPK_VT_STAMP
-  if (blockIdx.x == 0 && lane == 0) {
-    for (int k = 0; k < 7; ++k) atomicAdd(&g_vt_stamp[wave][k], (unsigned long long)st_acc[k]);
-    atomicAdd(&g_vt_stamp[wave][7], (unsigned long long)(VT_CLK() - st_begin));
-  }
-#endif
   // hand-over to the repair launch: the workgroup that finishes last publishes the count and re-arms the live counter (the
   // workgroups finish at different times, so this ticket costs nothing; a ticket in the repair launch, whose workgroups all
   // arrive at once, cost 16 us, a separate reset launch 5)
@@ -937,21 +706,19 @@ __global__ void ptc_to_s32_kernel(const uint8_t* __restrict__ in, uint8_t* __res
 
 template <int GEO, int H, int W, int NCH, int OUT, int SPLIT, bool DB>
 int launch_vae(const TArgs& a, long long n_words, hipStream_t stream) {
-  constexpr int TPT = tiles_per_tap(NCH), TPL = SPK_VT_D4 ? TPT - 1 : TPT;
+  constexpr int TPT = tiles_per_tap(NCH), TPL = TPT - 1;
   constexpr int SROWS = GEO == 0 ? H / SPLIT + 1 : H + 1;
   constexpr int NPOS = GEO == 0 ? (H / SPLIT) * W : (H / 2) * (W / 2), NCLS = GEO == 0 ? 4 : 1;
   // (+ the four-digit form's counters: u8 [cells][16] and int [classes][positions])
   const size_t lds = (size_t)(DB ? 2 : 1) * NCH * SROWS * (W + 1) * POSB + 9 * TPL * WT +
-                     (SPK_VT_D4 ? (size_t)((SROWS * (W + 1) * 16 + 15) & ~15) + (size_t)NCLS * NPOS * 4 : 0) + 16;
+                     (size_t)((SROWS * (W + 1) * 16 + 15) & ~15) + (size_t)NCLS * NPOS * 4 + 16;
   if (lds > 160 * 1024) return SPK_ERR_UNSUPPORTED;
   const int cus = spk_cu_count(), G = a.Cout / 32;
   const int grid = cus >= G ? (cus / G) * G : G;
   hipLaunchKernelGGL((vae_fp6_kernel<GEO, H, W, NCH, OUT, SPLIT, DB>), dim3(grid), dim3(SPK_VT_NWV * 64), lds, stream, a);
   SPK_LAUNCH_CHECK();
-  if constexpr (!SPK_VT_INWAVE_FIX) {
-    hipLaunchKernelGGL((vae_fp6_fixup_kernel<GEO, H, W, NCH, OUT>), dim3(4 * cus), dim3(256), 0, stream, a, n_words);
-    SPK_LAUNCH_CHECK();
-  }
+  hipLaunchKernelGGL((vae_fp6_fixup_kernel<GEO, H, W, NCH, OUT>), dim3(4 * cus), dim3(256), 0, stream, a, n_words);
+  SPK_LAUNCH_CHECK();
   return SPK_OK;
 }
 
@@ -1005,13 +772,9 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
   const long long n_words = (neurons + 31) / 32;
   a.ticket_idx = 2 + (long long)FLAG_CAP + n_words;
   if (transposed && Cin == 64 && out_kind == OUT_COLLAPSED) {                                // decoder convT2
-#ifndef SPK_VT_T2_SPLIT
-#define SPK_VT_T2_SPLIT 2       // items per image of the 14x14 -> 28x28 layer: 2 = half images, one input slab (two do not fit beside the weights);
-                                // 7 = two class rows per item, two slabs (the copy of the next item runs under this one's passes): 231 against
-                                // 195 us -- 28 items per workgroup pay the counting phases' barriers 28 times (15 % of the launch) and the waves
-                                // then wait for one another at the item's first barrier instead (profiles/r5_ab_kernel_variants.txt (7))
-#endif
-    if (H == 14 && W == 14) return launch_vae<0, 14, 14, 2, OUT_COLLAPSED, SPK_VT_T2_SPLIT, (SPK_VT_T2_SPLIT > 2)>(a, n_words, stream);
+    // half images per item, one input slab (two do not fit beside the weights); two class rows per item with two slabs measured
+    // 231 against 195 us (profiles/r5_ab_kernel_variants.txt (7))
+    if (H == 14 && W == 14) return launch_vae<0, 14, 14, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
     if (H == 16 && W == 16) return launch_vae<0, 16, 16, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
   }
   if (transposed && Cin == 16 && out_kind == OUT_S32) {                                      // decoder convT1
@@ -1024,14 +787,3 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
   }
   return SPK_ERR_UNSUPPORTED;
 }
-
-#if SPK_VT_STAMP
-// (timing builds only) the accumulated phase cycles of workgroup 0, [wave][8]; cleared on read
-extern "C" int spk_vt_stamps(unsigned long long* out, int* n_waves) {
-  unsigned long long z[SPK_VT_NWV][8] = {};
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_vt_stamp), sizeof(z)) != hipSuccess) return -1;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(g_vt_stamp), z, sizeof(z)) != hipSuccess) return -1;
-  *n_waves = SPK_VT_NWV;
-  return 0;
-}
-#endif

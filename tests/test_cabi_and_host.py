@@ -18,7 +18,7 @@ def header_functions():
     return sorted(set(re.findall(r"\b(spk_[a-z0-9_]+)\s*\(", txt)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_exactly_the_declared_symbols():
     from spkdiff import _lib
     names = header_functions()
     assert len(names) >= 18
@@ -27,13 +27,11 @@ def test_library_exports_every_declared_symbol():
         assert n in _lib.EXPORTS, f"{n} has no ctypes signature in spkdiff/_lib.py"
     assert set(_lib.EXPORTS) == set(names)
     assert _lib.version() == _lib.EXPECTED_VERSION == 105
-    # the shipped library keeps no process-wide state: the option entry points exist only in a `make variants` build
-    # (include/spkdiff_variants.h), and its launch-shape options read as their compiled-in defaults
+    # the shipped library keeps no process-wide state: no option entry points, no settable launch shapes in the binding
     if not os.environ.get("SPKDIFF_LIB"):
-        assert not _lib.HAS_OPTIONS and not hasattr(_lib.lib, "spk_set_option") and not hasattr(_lib.lib, "spk_get_option")
-        assert _lib.get_option("v2_waves") == 8 and _lib.get_option("v2_duo") == 0
-        with pytest.raises(NotImplementedError):
-            _lib.set_option("v2_duo", 1)
+        assert not hasattr(_lib.lib, "spk_set_option") and not hasattr(_lib.lib, "spk_get_option")
+        assert _lib.HAS_OPTIONS is False
+        assert not any(hasattr(_lib, n) for n in ("OPTIONS", "OPTION_DEFAULTS", "set_option", "get_option"))
     assert _lib.lib.spk_error_string(-1).decode().startswith("spkdiff: invalid argument")
 
 
@@ -109,10 +107,8 @@ def test_workspace_sizes_and_shape_support_are_host_side():
     assert lib.spk_select_needed_bytes(B, R) == (lists + 63) // 64 * 64 + R * B * 64
     assert lib.spk_select_needed_bytes(0, 3) == -1 and lib.spk_select_needed_bytes(4, 9) == -1
     cap = 1 << 20
-    # (count, published count, id list, overflow bitmap, hand-over ticket; a `make variants` library adds the duo form's
-    #  counters and the deferred-scan form's staging slabs behind the ticket)
-    extra = (2048 + 128 + 256 * 24576) if _lib.HAS_OPTIONS else 0
-    assert lib.spk_den_fp6v2_flag_words(2, 64, 7, 7) == 2 + cap + (2 * 64 * 49 + 31) // 32 + 1 + extra
+    # (count, published count, id list, overflow bitmap, hand-over ticket)
+    assert lib.spk_den_fp6v2_flag_words(2, 64, 7, 7) == 2 + cap + (2 * 64 * 49 + 31) // 32 + 1
     assert lib.spk_vae_fp6_flag_words(2, 32, 28, 28) == 2 + cap + (2 * 32 * 784 + 31) // 32 + 1
     assert lib.spk_vae_fp6_packed_bytes(32, 64) == 9 * 5 * 1536 and lib.spk_vae_fp6_packed_bytes(64, 16) == 2 * 9 * 3 * 1536
     assert lib.spk_vae_fp6_packed_bytes(32, 128) == -1 and lib.spk_vae_fp6_packed_bytes(48, 64) == -1
@@ -255,14 +251,13 @@ def test_synthetic_checkpoint_cache_is_safe_under_concurrent_ranks(tmp_path):
     assert len([f for f in left if f.endswith(".pt")]) == 2 and not any(f.endswith((".lock", ".tmp")) for f in left), left
 
 
-def test_header_is_plain_c(tmp_path):
+def test_header_compiles_alone_as_plain_c(tmp_path):
     """include/spkdiff.h is the boundary a C / cgo / JNI binding includes: it must compile as C without any HIP header."""
     import shutil, subprocess
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
     src = tmp_path / "inc.c"
-    # (spkdiff_variants.h: the two option entry points of the separate `make variants` library -- plain C as well)
-    src.write_text('#include "spkdiff.h"\n#include "spkdiff_variants.h"\n'
+    src.write_text('#include "spkdiff.h"\n'
                    'int main(void) { return spk_conv_out_size(7, 3, 1, 1, 0, 0) == 7 ? 0 : 1; }\n')
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-I", os.path.join(root, "include"), str(src)],
@@ -271,21 +266,33 @@ def test_header_is_plain_c(tmp_path):
 
 
 
-def test_shipped_library_has_no_settable_state_and_variant_sources_stay_out_of_it():
-    """the measured-and-dropped launch forms and the process-wide options are NOT in libspkdiff.so.  The forms' source is
-    an include file only a -DSPK_V2_VARIANTS=1 build pulls in; the default Makefile target compiles csrc/*.hip and nothing under
-    csrc/variants/; the variants header declares exactly the two option entry points."""
+def test_shipped_library_has_no_settable_state_and_no_variant_sources():
+    """the measured-and-dropped launch forms and the process-wide options are NOT in libspkdiff.so.  The library
+    exports no option entry point and reads no environment variable; the sources hold only the shipped forms: no variants
+    directory, no spk_opt switch and no -D override guard (#ifndef SPK_... / CT_...) -- include guards are the only #ifndef."""
+    import shutil, subprocess
+    from spkdiff import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "spiking-diffusion_amd", "csrc")
-    assert os.path.exists(os.path.join(csrc, "variants", "fp6v2_forms.inc"))
-    assert not [f for f in os.listdir(os.path.join(csrc, "variants")) if f.endswith(".hip")]
-    main = open(os.path.join(csrc, "den_mfma_fp6v2.hip")).read()
-    assert '#if SPK_V2_VARIANTS\n#include "variants/fp6v2_forms.inc"' in main
-    assert "duo_kernel" not in main.split('#include "variants/fp6v2_forms.inc"')[0]
-    assert len(main.splitlines()) < 2000
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "spkdiff_variants.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(spk_[a-z0-9_]+)\s*\(", txt))) == ["spk_get_option", "spk_set_option"]
-    assert "spk_set_option" not in re.sub(r"/\*.*?\*/", "", open(os.path.join(root, "include", "spkdiff.h")).read(), flags=re.S)
+    so = os.path.join(root, "spiking-diffusion_amd", "spkdiff", "libspkdiff.so")
+    assert os.path.exists(so), so
+    if shutil.which("nm") is None:
+        pytest.skip("no nm")
+    syms = subprocess.run(["nm", "-D", so], capture_output=True, text=True, check=True).stdout
+    for bad in ("spk_set_option", "spk_get_option", "getenv"):
+        assert bad not in syms, bad
+    assert not hasattr(_lib, "set_option")
+    assert not os.path.exists(os.path.join(csrc, "variants"))
+    assert not os.path.exists(os.path.join(root, "include", "spkdiff_variants.h"))
+    srcs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc"))]
+    srcs += [os.path.join(root, "include", f) for f in sorted(os.listdir(os.path.join(root, "include")))]
+    for path in srcs:
+        txt = open(path).read()
+        assert "spk_opt" not in txt and "SPK_V2_VARIANTS" not in txt, path
+        for m in re.finditer(r"^\s*#\s*ifndef\s+((?:SPK|CT)_\w+)", txt, re.M):
+            nxt = txt[m.end():].lstrip().splitlines()[0] if txt[m.end():].strip() else ""
+            assert re.match(r"#\s*define\s+" + m.group(1) + r"\s*$", nxt) and m.group(1).endswith("_H"), (path, m.group(1))
+    assert len(open(os.path.join(csrc, "den_mfma_fp6v2.hip")).read().splitlines()) < 2000
 
 
 def test_synth_cache_takes_over_a_stale_lock(tmp_path, monkeypatch):

@@ -1,10 +1,10 @@
 """ONE parametrised same-box A/B driver (replaces the per-experiment r4_run*.sh / r4_ab*.sh batches).
 
-usage: python tools/ab.py [--passes 2] [--what layers,dense,elim,tests] <label>[:KEY=VAL[,KEY=VAL...]] ...
+usage: python tools/ab.py [--passes 2] [--what layers,dense,elim,tests] <label>[:LIB=<path>] ...
 
-Every configuration is a label plus environment settings for a fresh child process: SPKDIFF_<OPTION>=<int> (forwarded to
-spk_set_option by spkdiff/_lib.py: v2_duo, v2_waves, ...) and/or LIB=<path of a library variant built by tools/build_variant.sh>
-(exported as SPKDIFF_LIB).  Per pass and configuration it runs
+Every configuration is a label plus, optionally, the path of a libspkdiff.so built from another tree (e.g. the parent commit of a
+change: `git worktree add`, `make -C <tree>/spiking-diffusion_amd/csrc`), exported to a fresh child process as SPKDIFF_LIB.
+Per pass and configuration it runs
   layers: tools/fp6v2_time.py  -- per-layer time of spk_den_conv3x3_mfma_fp6v2 (main + tail launch) at B = 256 with the spike
           mismatch count against the six-plane kernel (bit-equality check),
   dense / elim: tools/listed_time.py -- the 100-step reverse process, dense (the bench line's mode) / elimination + lists,
@@ -31,12 +31,11 @@ def main():
     for spec in args:
         label, _, kv = spec.partition(":")
         env = {}
-        for item in filter(None, kv.split(",")):
-            k, _, v = item.partition("=")
-            if k == "LIB":
-                env["SPKDIFF_LIB"] = os.path.join(ROOT, v) if not os.path.isabs(v) else v
-            else:
-                env[k] = v
+        if kv:
+            k, _, v = kv.partition("=")
+            if k != "LIB":
+                raise SystemExit(__doc__)
+            env["SPKDIFF_LIB"] = os.path.join(ROOT, v) if not os.path.isabs(v) else v
         cfgs.append((label, env))
     if not cfgs:
         raise SystemExit(__doc__)

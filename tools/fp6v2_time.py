@@ -1,7 +1,7 @@
 """Time the second-generation fp6 denoiser convolution (spk_den_conv3x3_mfma_fp6v2) next to the first-generation kernel at
 the four denoiser shapes (B=256, 7x7), for every libspkdiff variant given on the command line (SPKDIFF_LIB, fresh process
 each).  Inputs fire at a few percent with BatchNorm terms that put the membrane potentials around the threshold; prints the
-spike mismatches between the two kernels and -- for a build with -DSPK_V2_DBG=64 -- the number of flagged neurons."""
+spike mismatches between the two kernels and the live flagged-neuron counter (zero: the tail launch re-arms it)."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
@@ -22,7 +22,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
             y1 = ops.den_conv3x3_mfma_fp6(x1, p1, Cout, bn_a=a, bn_b=b)
             y2 = ops.den_conv3x3_mfma_fp6v2(x2, p2, Cout, bn_a=a, bn_b=b)
         torch.cuda.synchronize()
-        flagged = sum(int(v[0]) for v in ops._FLAG_DEFAULT.values())      # non-zero only for a -DSPK_V2_DBG=64 build
+        flagged = sum(int(v[0]) for v in ops._FLAG_DEFAULT.values())      # (the live counter: re-armed by the tail launch)
         for v in ops._FLAG_DEFAULT.values():
             v[:2].zero_()
         s1, s2 = ops.c4_to_spikes(y1), ops.s32_to_spikes(y2)

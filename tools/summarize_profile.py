@@ -17,7 +17,7 @@ for r in rows:
     d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
     if "conv3x3_mfma_kernel<" in name:
         targs = name.split("conv3x3_mfma_kernel<")[1].split(">")[0].split(",")
-        if int(targs[2]) == 0:          # template <NT, NPA, MODE, DBG>: MODE 0 = LIF (conv2..conv5, in launch order)
+        if int(targs[2]) == 0:          # template <NT, NPA, MODE>: MODE 0 = LIF (conv2..conv5, in launch order)
             name = f"conv3x3_mfma_kernel<LIF> den.conv{2 + k % 4}"
             k += 1
         else:
