@@ -34,7 +34,9 @@ typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
                            * training branch and the training convolutions: 102, the token-table spike generator: 103; round 6: `int flag_cap` (and `int form` for spk_den_conv3x3_mfma_fp6v2) in front of the
                            * stream of the four certified-kernel entry points, spk_set_option / spk_get_option left the shipped library: 104;
                            * `active` / `n_active` of spk_den_step_tail: 105); spkdiff/_lib.py refuses a library whose
-                           * spk_version() differs from the signatures it declares */
+                           * spk_version() differs from the signatures it declares.  Purely additive entry points (the SNN_VAE
+                           * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
+                           * symbol at import, so a library that lacks one fails there */
 
 /* fused-kernel epilogue modes (spk_conv_fused_fwd) */
 #define SPK_CHUNK_C4 (-64) /* chunk_out value: fp4 nibble-packed output, 64 channels per chunk */
@@ -597,6 +599,36 @@ int spk_checksum_multi(const unsigned long long* table_dev, int n, unsigned long
  * nonzero == ones  <=>  the tensor is binary). */
 int spk_count_spikes(const void* data, long long n_words, long long inner_words, int T, int kind, unsigned long long* out3,
                      spk_stream_t stream);
+
+/* ---- SNN_VAE baseline: spiking MLP layers and the autoregressive Bernoulli loops (eval) ------------------------------ */
+/* input / output layouts of spk_linear_lif_fwd */
+#define SPK_LIN_IN_F32 0  /* fp32 [T,B,in], any values                                                   */
+#define SPK_LIN_IN_U8 1   /* u8 {0,1} spikes [T,B,in]                                                    */
+#define SPK_LIN_IN_PTC 2  /* u8 PTC spikes [B,H,W,T,C], in = C*H*W read in flatten(C,H,W) order (c*H*W + h*W + w) */
+#define SPK_LIN_OUT_F32 0 /* the Linear's currents, fp32 [T,B,out]; no neuron, v unused                  */
+#define SPK_LIN_OUT_U8 1  /* LIF spikes u8 [T,B,out]; out may be NULL (state-only pass)                  */
+#define SPK_LIN_OUT_PTC 2 /* LIF spikes u8 PTC [B,H,W,T,C], out = C*H*W in flatten(C,H,W) order          */
+
+/* Multi-step layer.Linear followed by the models' LIFNode (tau 2, v_th 1, hard reset to 0, decay_input): replaces
+ * SJ/activation_based/layer.py Linear (nn.Linear over seq_to_ann_forward) + the eval LIF of neuron.py:799-811 for
+ * R/snn_model/vae_model.py:212-216 (before_latent_layer: PTC in), :224-228 (decoder_input: PTC out, consumed by the fused
+ * decoder, :256-260) and the prior's teacher-forced eval pass :365-403.  out = SPK_LIN_OUT_F32 is layer.Linear alone.
+ * w [out,in], bias [out] (may be NULL) fp32; v_inout [B,out] fp32, the neuron state before / after (LIF outputs only);
+ * ptc_c/h/w describe the PTC side.  Each output is an fp32 sum over the inputs in ascending order, then + bias. */
+int spk_linear_lif_fwd(const void* x, int in_kind, const float* w, const float* bias_or_null, float* v_inout_or_null,
+                       void* out_or_null, int out_kind, int T, int B, int in_features, int out_features, int ptc_c, int ptc_h,
+                       int ptc_w, spk_stream_t stream);
+/* One whole autoregressive loop of the SNN_VAE's Bernoulli latent model, every pass in one launch: with x (u8 spikes
+ * [T,B,cx]) PosteriorBernoulliSTBP.forward (R/snn_model/vae_model.py:470-546: T-1 passes over the prefixes of [x, z],
+ * then one full pass), with x NULL (cx 0) PriorBernoulliSTBP.sample (:405-423: T passes over the prefixes of z).  The MLP is
+ * w1 [h1, cx+cz], w2 [h2,h1], w3 [cz*k, h2] with biases, each layer followed by the LIF of spk_linear_lif_fwd with state
+ * v1/v2/v3 [B,h] carried in and out (no pass resets it); z0 = initial_input [cz].  idx int32 [T,B,cz] in [0,k): the host's
+ * draws (torch.randint(0, k, (B*cz,)) in the reference's order), z_t = spike[c*k + idx].  sampled_z_out fp32 [T,B,cz];
+ * q_z_out (posterior only, may be NULL) u8 [T,B,cz*k], the spikes of the final pass.  T <= 16. */
+int spk_svae_ar_fwd(const uint8_t* x_or_null, const float* z0, const float* w1, const float* b1, const float* w2,
+                    const float* b2, const float* w3, const float* b3, float* v1_inout, float* v2_inout, float* v3_inout,
+                    const int* idx, float* sampled_z_out, uint8_t* q_z_out_or_null, int T, int B, int cx, int cz, int h1,
+                    int h2, int k, spk_stream_t stream);
 
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every

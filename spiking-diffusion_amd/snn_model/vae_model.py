@@ -9,6 +9,10 @@ mode with autograd: native convolutions forward and backward (``csrc/conv_train.
 cover take the framework's operator), native BatchNorm+LIF block tails (``spk_bn_lif_train_*``), and the VectorQuantizer's
 read-out / code search / losses, the PSP losses and the reconstruction loss as fused operators (``csrc/vq_train.hip``).
 
+``SNN_VAE`` (R/snn_model/vae_model.py:198-546, the FSVAE-style baseline) runs its eval forward, ``encode``, ``decode`` and
+``sample`` on ``csrc/svae.hip``: Linear + LIF pairs fused, each autoregressive Bernoulli loop one launch; its training branch
+raises ``NotImplementedError``.
+
 Re-exported names match what ``from snn_model.vae_model import *`` gives R/main.py (``functional`` in particular,
 R/main.py:101-107,317).
 """
@@ -264,15 +268,212 @@ class SNN_VQVAE(nn.Module):
         return r['f32'], r['u8']
 
 
+# ---- SNN_VAE: the FSVAE-style baseline (R/snn_model/vae_model.py:198-546), eval path ---------------------------------------
+# Every Linear + LIFNode pair runs fused (spk_linear_lif_fwd) and each autoregressive Bernoulli loop is ONE launch
+# (spk_svae_ar_fwd); the modules keep the reference's children, state_dict keys and LIFNode states, so reset_net and
+# load_state_dict behave as there.  The random indices are drawn on the host with the reference's calls in its order.
+
+def _svae_node_v(node, B, n, device):
+    """The LIFNode's state as the [B, n] fp32 buffer the kernels update in place (the float reset value expanded on first
+    use, SJ/activation_based/neuron.py:260-263)."""
+    if not (node.v_reset == 0.0 and node.v_threshold == 1.0 and node.tau == 2.0 and node.decay_input
+            and not node.store_v_seq):
+        raise NotImplementedError('spkdiff: the SNN_VAE kernels implement the default LIFNode (tau 2, v_th 1, hard reset 0, '
+                                  'decay_input)')
+    v = node.v
+    if isinstance(v, float):
+        v = torch.full((B, n), v, dtype=torch.float32, device=device)
+    elif v.shape != (B, n) or v.dtype != torch.float32 or v.device != device or not v.is_contiguous():
+        raise ValueError(f'spkdiff: LIFNode state {tuple(v.shape)} on {v.device} does not fit a batch of {B} x {n} on '
+                         f'{device}; call functional.reset_net between batches of different sizes')
+    node.v = v
+    return v
+
+
+def _svae_linear_lif(seq, x, **kw):
+    """nn.Sequential(layer.Linear, LIFNode) on x (fp32 / u8 [T,B,in] or u8 PTC [B,H,W,T,C]) -> u8 spikes (or PTC / None)."""
+    lin, node = seq[0], seq[1]
+    B = x.shape[0] if x.dim() == 5 else x.shape[1]
+    return ops.linear_lif(x, lin.weight, lin.bias, _svae_node_v(node, B, lin.out_features, x.device), **kw)
+
+
+def _require_device(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"spkdiff: {what} is on '{t.device}'; there is no CPU path (move the module and tensors to a "
+                           "ROCm device)")
+
+
+class _BernoulliSTBP(nn.Module):
+    """The 3-layer spiking MLP shared by the prior (input z) and the posterior (input [x, z]) of R/snn_model/vae_model.py."""
+
+    def __init__(self, in_mult, k):
+        super().__init__()
+        self.channels = 28 * 2
+        self.k = k
+        self.n_steps = 16
+        self.layers = nn.Sequential(
+            layer.Linear(self.channels * in_mult, self.channels * 2),
+            neuron.LIFNode(surrogate_function=surrogate.ATan()),
+            layer.Linear(self.channels * 2, self.channels * 4),
+            neuron.LIFNode(surrogate_function=surrogate.ATan()),
+            layer.Linear(self.channels * 4, self.channels * k),
+            neuron.LIFNode(surrogate_function=surrogate.ATan()),
+        )
+        self.register_buffer('initial_input', torch.zeros(1, 1, self.channels))
+
+    def _draw_indices(self, batch_size, device):
+        """The n_steps draws torch.randint(0, k, (B*C,)) of the reference, in its order, on the CPU default generator."""
+        idx = torch.stack([torch.randint(0, self.k, (batch_size * self.channels,)) for _ in range(self.n_steps)])
+        return idx.view(self.n_steps, batch_size, self.channels).to(torch.int32).to(device)
+
+    def _ar(self, x, batch_size, want_q_z=False):
+        dev = self.initial_input.device
+        _require_device(self.initial_input, f'{type(self).__name__}')
+        idx = self._draw_indices(batch_size, dev)
+        lins = [self.layers[i] for i in (0, 2, 4)]
+        vs = [_svae_node_v(self.layers[i + 1], batch_size, lins[j].out_features, dev) for j, i in enumerate((0, 2, 4))]
+        return ops.svae_ar(x, self.initial_input, [(m.weight, m.bias) for m in lins], vs, idx, want_q_z=want_q_z)
+
+    def _teacher_forced(self, z, want_out=True):
+        """The eval pass over [initial_input, z_0 .. z_{T-2}] (one multi-step pass, state carried): u8 [T,B,C*k] or None."""
+        _require_device(z, 'z')
+        B = z.shape[1]
+        z_prev = torch.cat([self.initial_input.to(torch.float32).expand(1, B, self.channels), z[:-1].to(torch.float32)], 0)
+        h = _svae_linear_lif(self.layers[0:2], z_prev.contiguous())
+        h = _svae_linear_lif(self.layers[2:4], h)
+        return _svae_linear_lif(self.layers[4:6], h, want_out=want_out)
+
+
+class PriorBernoulliSTBP(_BernoulliSTBP):
+    """p(z_t | z_<t), R/snn_model/vae_model.py:306-423."""
+
+    def __init__(self, k=20) -> None:
+        super().__init__(1, k)
+
+    def forward(self, z, scheduled=True, p=None):
+        """Eval: p_z (T,B,C,k) of the pass over [initial_input, z_0 .. z_{T-2}] (both branches of the reference compute this
+        pass outside training, :338-403).  Advances the layers' LIF state."""
+        if self.training:
+            _training_oos('PriorBernoulliSTBP.forward in train() mode (scheduled sampling, :365-390)')
+        out = self._teacher_forced(z)
+        return out.to(torch.float32).view(self.n_steps, z.shape[1], self.channels, self.k)
+
+    def sample(self, batch_size=64):
+        """Autoregressive sampling of z (T,B,C): n_steps passes over the growing prefix, one launch (spk_svae_ar_fwd)."""
+        z, _ = self._ar(None, batch_size)
+        return z
+
+
+class PosteriorBernoulliSTBP(_BernoulliSTBP):
+    """q(z_t | x_<=t, z_<t), R/snn_model/vae_model.py:425-546."""
+
+    def __init__(self, k=20) -> None:
+        super().__init__(2, k)
+        self.is_true_scheduled_sampling = True
+
+    def forward(self, x, want_q_z=True):
+        """x: (T,B,C) spikes of before_latent_layer (u8 / bool, or fp32 0/1).  Returns (sampled_z (T,B,C) fp32,
+        q_z (T,B,C,k) fp32 -- the spikes of the final pass -- or None with want_q_z=False).  One launch."""
+        if self.training:
+            _training_oos('PosteriorBernoulliSTBP.forward in train() mode')
+        _require_device(x, 'x')
+        if x.dtype != torch.uint8 and x.dtype != torch.bool:
+            x = x.to(torch.uint8)
+        T, B = x.shape[0], x.shape[1]
+        z, q = self._ar(x.contiguous(), B, want_q_z=want_q_z)
+        if q is not None:
+            q = q.to(torch.float32).view(T, B, self.channels, self.k)
+        return z, q
+
+
+class SNN_VAE(nn.Module):
+    """The spiking VAE baseline, R/snn_model/vae_model.py:198-305 -- eval forward, encode, decode and sample on HIP."""
+
+    def __init__(self):
+        super().__init__()
+        latent_dim = 28 * 2
+        self.latent_dim = latent_dim
+        self.n_steps = 16
+        self.k = 20
+        self.encoder = Encoder()
+        self.before_latent_layer = nn.Sequential(
+            layer.Linear(in_features=784, out_features=latent_dim),
+            neuron.LIFNode(surrogate_function=surrogate.ATan()),
+        )
+        self.prior = PriorBernoulliSTBP(self.k)
+        self.posterior = PosteriorBernoulliSTBP(self.k)
+        self.decoder_input = nn.Sequential(
+            layer.Linear(in_features=latent_dim, out_features=16 * 7 * 7),
+            neuron.LIFNode(surrogate_function=surrogate.ATan()),
+        )
+        self.decoder = Decoder()
+        self.p = 0
+        self.membrane_output_layer = MembraneOutputLayer()
+        self.psp = PSP()
+
+    def _encode(self, x, scheduled=True, full=True):
+        if self.training:
+            _training_oos('SNN_VAE.encode in train() mode')
+        _require_device(x, 'x')
+        z_ptc = self.encoder.snn_convs.run(x, IN_SEQ, final='ptc')['ptc']            # u8 [B,7,7,T,16]
+        latent_x = _svae_linear_lif(self.before_latent_layer, z_ptc)                 # u8 [T,B,56], flatten(C,H,W) order
+        sampled_z, q_z = self.posterior(latent_x, want_q_z=full)
+        if full:
+            p_z = self.prior(sampled_z, scheduled, self.p)
+        else:
+            self.prior._teacher_forced(sampled_z, want_out=False)                    # output unused; advances the state
+            p_z = None
+        return sampled_z, q_z, p_z
+
+    def encode(self, x, scheduled=True):
+        """x (T,B,1,28,28) -> (sampled_z (T,B,C), q_z (T,B,C,k), p_z (T,B,C,k))."""
+        return self._encode(x, scheduled, full=True)
+
+    def decode(self, z):
+        """z (T,B,C) -> tanh(membrane read-out) (B,1,28,28): decoder_input writes the PTC spikes the fused decoder reads."""
+        _require_device(z, 'z')
+        ptc = _svae_linear_lif(self.decoder_input, z.to(torch.float32).contiguous(), out_ptc=(16, 7, 7))
+        return self.decoder.snn_convs.run(ptc, IN_PTC, final='memout', coef=self.membrane_output_layer.coef.flatten(),
+                                          apply_tanh=True)['f32']
+
+    def sample(self, batch_size=64):
+        sampled_z = self.prior.sample(batch_size)
+        sampled_x = self.decode(sampled_z)
+        return sampled_x, sampled_z
+
+    def loss_function_mmd(self, input_img, recons_img, q_z, p_z):
+        """q_z, p_z: (T,N,latent_dim,k) -> (mmd_loss, recons_loss)."""
+        recons_loss = F.mse_loss(recons_img, input_img)
+        q_z_ber = torch.mean(q_z, dim=-1)
+        p_z_ber = torch.mean(p_z, dim=-1)
+        mmd_loss = torch.mean((self.psp(q_z_ber) - self.psp(p_z_ber)) ** 2)
+        return mmd_loss, recons_loss
+
+    def weight_clipper(self):
+        with torch.no_grad():
+            for prm in self.parameters():
+                prm.data.clamp_(-4, 4)
+
+    def update_p(self, epoch, max_epoch):
+        init_p, last_p = 0.1, 0.3
+        self.p = (last_p - init_p) * epoch / max_epoch + init_p
+
+    def forward(self, x, image, scheduled=True):
+        """Eval: (sampled_z (T,B,C), x_recon (B,1,28,28)).  The training branch (MMD + reconstruction loss) is out of scope."""
+        if self.training:
+            _training_oos('SNN_VAE.forward in train() mode (MMD / reconstruction losses, R/snn_model/vae_model.py:299-305)')
+        sampled_z, _, _ = self._encode(x, scheduled, full=False)
+        return sampled_z, self.decode(sampled_z)
+
+
 def _not_in_scope(name):
     class _Stub(nn.Module):
         def __init__(self, *a, **k):
             raise NotImplementedError(f'spkdiff: {name} is a baseline model outside the named hot path '
-                                      '(SURVEY.md §2.1 #3); only SNN_VQVAE is implemented')
+                                      '(SURVEY.md §2.1 #3); only SNN_VQVAE and SNN_VAE are implemented')
     _Stub.__name__ = name
     return _Stub
 
 
-SNN_VAE = _not_in_scope('SNN_VAE')
 VQVAE = _not_in_scope('VQVAE')
 SNN_VQVAE_uni = _not_in_scope('SNN_VQVAE_uni')

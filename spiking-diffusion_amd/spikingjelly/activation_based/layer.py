@@ -1,4 +1,4 @@
-"""Step-mode wrappers of the stateless layers used by ``snn_model``: Conv2d, ConvTranspose2d, BatchNorm2d (+Linear).
+"""Step-mode wrappers of the stateless layers used by ``snn_model``: Conv2d, ConvTranspose2d, BatchNorm2d, Linear.
 
 Surface of SJ/activation_based/layer.py:125-173, :276-325, :423-465, :900-922.  They subclass the ``torch.nn``
 layers (parameters, ``state_dict`` keys and constructors are torch's), but ``forward`` runs the HIP kernels of
@@ -147,11 +147,26 @@ class BatchNorm2d(nn.BatchNorm2d, base.StepModule):
 
 
 class Linear(nn.Linear, base.StepModule):
-    """Declared for ``from ...layer import *`` completeness (used only by the out-of-scope SNN_VAE baseline)."""
+    """SJ/activation_based/layer.py:900-922: nn.Linear over the last dimension; 'm' mode folds T into the batch.  The
+    currents come from spk_linear_lif_fwd (fp32 sums in a fixed order, then + bias); the SNN_VAE model runs its
+    Linear + LIFNode pairs fused through the same kernel (snn_model/vae_model.py)."""
 
     def __init__(self, in_features, out_features, bias=True, step_mode='s'):
         super().__init__(in_features, out_features, bias)
         self.step_mode = step_mode
 
-    def forward(self, x):
-        raise NotImplementedError('spkdiff: layer.Linear belongs to the SNN_VAE baseline, outside the hot path')
+    def extra_repr(self):
+        return super().extra_repr() + f', step_mode={self.step_mode}'
+
+    def forward(self, x: torch.Tensor):
+        if not x.is_cuda:
+            raise RuntimeError(f"spkdiff: input is on '{x.device}'; there is no CPU path (move module and tensors to a ROCm "
+                               "device)")
+        if self.training and torch.is_grad_enabled():
+            raise NotImplementedError('spkdiff: layer.Linear training (the SNN_VAE training branch) is outside the '
+                                      'inference path; call .eval() or run under torch.no_grad()')
+        if self.step_mode == 'm' and x.dim() < 3:
+            raise ValueError(f'expected x with shape [T, N, *, {self.in_features}], but got x with shape {tuple(x.shape)}!')
+        lead = x.shape[:-1]
+        y = ops.linear(x.reshape(-1, self.in_features), self.weight, self.bias)
+        return y.view(tuple(lead) + (self.out_features,))

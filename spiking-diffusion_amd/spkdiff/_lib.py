@@ -142,6 +142,8 @@ _SIGS = {
     "spk_conv_train_wgrad_ws_bytes": (c_longlong, [c_int] * 6),
     "spk_conv_train_wgrad": (c_int, [P, P, P, c_longlong, P, P] + [c_int] * 10 + [c_longlong] * 3 + [c_int, P]),
     "spk_q_sample": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
+    "spk_linear_lif_fwd": (c_int, [P, c_int, P, P, P, P, c_int] + [c_int] * 7 + [P]),
+    "spk_svae_ar_fwd": (c_int, [P] * 14 + [c_int] * 7 + [P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -2020,3 +2020,125 @@ def select_active(unmasked, t, u=None, seed=0, offset=0, philox_state=None, out=
     check(lib.spk_select_active(_p(unmasked), int(t), _p(u), int(seed), int(offset), _p(philox_state), _p(out[0]),
                                 _p(out[1]), B, HW, int(K), _stream(unmasked)), "spk_select_active")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- SNN_VAE spiking MLP
+LIN_IN_F32, LIN_IN_U8, LIN_IN_PTC = 0, 1, 2
+LIN_OUT_F32, LIN_OUT_U8, LIN_OUT_PTC = 0, 1, 2
+
+
+def _linear_params(weight, bias, n_in):
+    w = _dev(weight, "weight", torch.float32)
+    if w.dim() != 2 or w.shape[1] != n_in:
+        raise ValueError(f"weight must be [out, {n_in}], got {tuple(w.shape)}")
+    b = None if bias is None else _dev(bias, "bias", torch.float32)
+    if b is not None and b.shape != (w.shape[0],):
+        raise ValueError(f"bias must be [{w.shape[0]}], got {tuple(b.shape)}")
+    return w, b
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias=None):
+    """layer.Linear's currents: x fp32 [N, in] -> fp32 [N, out] = x @ weight.T + bias (spk_linear_lif_fwd, LIN_OUT_F32);
+    each output an fp32 sum over the inputs in ascending order, then + bias."""
+    x = _dev(x, "x", torch.float32)
+    if x.dim() != 2:
+        raise ValueError(f"x must be [N, in], got {tuple(x.shape)}")
+    w, b = _linear_params(weight, bias, x.shape[1])
+    out = torch.empty((x.shape[0], w.shape[0]), dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return out
+    check(lib.spk_linear_lif_fwd(_p(x), LIN_IN_F32, _p(w), _p(b), None, _p(out), LIN_OUT_F32, 1, x.shape[0], x.shape[1],
+                                 w.shape[0], 0, 0, 0, _stream(x)), "spk_linear_lif_fwd")
+    return out
+
+
+def linear_lif(x: torch.Tensor, weight: torch.Tensor, bias, v: torch.Tensor, out_ptc=None, want_out=True):
+    """Multi-step Linear + default LIFNode (tau 2, v_th 1, hard reset 0), spk_linear_lif_fwd.
+
+    x: fp32 [T,B,in] (any values), u8/bool [T,B,in] (spikes), or u8 PTC [B,H,W,T,C] (spikes, in = C*H*W read in
+    flatten(C,H,W) order).  v: fp32 [B,out], updated in place.  Returns u8 spikes [T,B,out], or with ``out_ptc=(C,H,W)``
+    u8 PTC [B,H,W,T,C] (out = C*H*W); ``want_out=False``: state-only pass, returns None."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    x = _dev(x, "x")
+    if x.dtype == torch.bool:
+        x = x.view(torch.uint8)
+    if x.dtype == torch.float32 and x.dim() == 3:
+        in_kind, (T, B, n_in), pc = LIN_IN_F32, x.shape, (0, 0, 0)
+    elif x.dtype == torch.uint8 and x.dim() == 3:
+        in_kind, (T, B, n_in), pc = LIN_IN_U8, x.shape, (0, 0, 0)
+    elif x.dtype == torch.uint8 and x.dim() == 5:
+        B, H, W, T, C = x.shape
+        in_kind, n_in, pc = LIN_IN_PTC, C * H * W, (C, H, W)
+    else:
+        raise ValueError(f"x must be fp32/u8 [T,B,in] or u8 PTC [B,H,W,T,C], got {x.dtype} {tuple(x.shape)}")
+    w, b = _linear_params(weight, bias, n_in)
+    n_out = w.shape[0]
+    v = _dev(v, "v", torch.float32)
+    if v.shape != (B, n_out):
+        raise ValueError(f"v must be [{B}, {n_out}], got {tuple(v.shape)}")
+    out = None
+    if out_ptc is not None:
+        if in_kind == LIN_IN_PTC:
+            raise NotImplementedError("spkdiff: PTC input and PTC output in one call")
+        C, H, W = out_ptc
+        if C * H * W != n_out:
+            raise ValueError(f"out_ptc {tuple(out_ptc)} does not hold {n_out} outputs")
+        out_kind, pc = LIN_OUT_PTC, (C, H, W)
+        out = torch.empty((B, H, W, T, C), dtype=torch.uint8, device=x.device)
+    else:
+        out_kind = LIN_OUT_U8
+        if want_out:
+            out = torch.empty((T, B, n_out), dtype=torch.uint8, device=x.device)
+    check(lib.spk_linear_lif_fwd(_p(x), in_kind, _p(w), _p(b), _p(v), _p(out), out_kind, T, B, n_in, n_out, *pc,
+                                 _stream(x)), "spk_linear_lif_fwd")
+    return out
+
+
+def svae_ar(x, z0, layers, vs, idx, want_q_z=False):
+    """One autoregressive loop of the SNN_VAE latent model in one launch (spk_svae_ar_fwd).
+
+    x: u8/bool spikes [T,B,cx] -> PosteriorBernoulliSTBP.forward; None -> PriorBernoulliSTBP.sample (B from idx).
+    z0: initial_input ([1,1,cz] or [cz]); layers: ((w1, b1), (w2, b2), (w3, b3)) with w3 [cz*k, h2]; vs: the three layers'
+    v, fp32 [B,h], updated in place; idx: [T,B,cz] integer draws in [0,k).  Returns (sampled_z fp32 [T,B,cz],
+    q_z u8 [T,B,cz*k] of the final posterior pass, or None)."""
+    idx = _dev(idx, "idx")
+    if idx.dim() != 3 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"idx must be an integer [T,B,cz] tensor, got {idx.dtype} {tuple(idx.shape)}")
+    T, B, cz = idx.shape
+    if x is not None:
+        x = _dev(x, "x")
+        if x.dtype == torch.bool:
+            x = x.view(torch.uint8)
+        if x.dtype != torch.uint8 or x.dim() != 3 or x.shape[:2] != (T, B):
+            raise ValueError(f"x must be u8 spikes [{T}, {B}, cx], got {x.dtype} {tuple(x.shape)}")
+        cx = x.shape[2]
+    else:
+        cx = 0
+        if want_q_z:
+            raise ValueError("q_z belongs to the posterior (x given)")
+    z0 = _dev(z0, "initial_input", torch.float32)
+    if z0.numel() != cz:
+        raise ValueError(f"initial_input has {z0.numel()} elements, expected {cz}")
+    (w1, b1), (w2, b2), (w3, b3) = layers
+    w1, b1 = _linear_params(w1, b1, cx + cz)
+    h1 = w1.shape[0]
+    w2, b2 = _linear_params(w2, b2, h1)
+    h2 = w2.shape[0]
+    w3, b3 = _linear_params(w3, b3, h2)
+    h3 = w3.shape[0]
+    if h3 % cz:
+        raise ValueError(f"last layer has {h3} outputs, not a multiple of {cz} channels")
+    k = h3 // cz
+    bs = [torch.zeros(w.shape[0], dtype=torch.float32, device=w.device) if bb is None else bb
+          for w, bb in ((w1, b1), (w2, b2), (w3, b3))]
+    v1, v2, v3 = (_dev(v, "v", torch.float32) for v in vs)
+    for v, h in ((v1, h1), (v2, h2), (v3, h3)):
+        if v.shape != (B, h):
+            raise ValueError(f"v must be [{B}, {h}], got {tuple(v.shape)}")
+    idx32 = idx if idx.dtype == torch.int32 else idx.to(torch.int32)
+    z = torch.empty((T, B, cz), dtype=torch.float32, device=idx.device)
+    q = torch.empty((T, B, h3), dtype=torch.uint8, device=idx.device) if want_q_z else None
+    check(lib.spk_svae_ar_fwd(_p(x), _p(z0), _p(w1), _p(bs[0]), _p(w2), _p(bs[1]), _p(w3), _p(bs[2]), _p(v1), _p(v2), _p(v3),
+                              _p(idx32), _p(z), _p(q), T, B, cx, cz, h1, h2, k, _stream(idx)), "spk_svae_ar_fwd")
+    return z, q

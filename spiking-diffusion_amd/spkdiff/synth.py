@@ -185,6 +185,69 @@ def synth_denoiser_state(cfg: PathConfig = MNIST, seed: int = 4321, calib_batch:
     return {k: v.contiguous() for k, v in sd.items()}
 
 
+SVAE_LATENT, SVAE_K = 56, 20          # R/snn_model/vae_model.py:203-208 (latent_dim = 28*2, k = 20)
+
+
+def _dyadic(shape, bound_units, seed, key):
+    """Integers in [-bound_units, bound_units] times 2^-12, drawn uniformly (exact fp32 grid values)."""
+    n = torch.randint(-bound_units, bound_units + 1, shape, generator=_gen(seed, key), dtype=torch.int64)
+    return n.to(torch.float32) * 2.0 ** -12
+
+
+def _bn_eval(sd, prefix, y_seq):
+    c = y_seq.shape[2]
+    a = sd[prefix + ".weight"] / torch.sqrt(sd[prefix + ".running_var"] + 1e-5)
+    b = sd[prefix + ".bias"] - sd[prefix + ".running_mean"] * a
+    return y_seq * a.view(1, 1, c, 1, 1) + b.view(1, 1, c, 1, 1)
+
+
+def _linear_lif_calibrated(sd, prefix, x_seq, n_out, seed, rate=0.25):
+    """Dyadic Linear weights (|w| <= 0.25) for ``prefix`` and a bias = per-layer offset + small per-neuron jitter, all on the
+    2^-12 grid; the offset is bisected so that the LIF after the layer fires at ~``rate`` on x_seq [T,B,in] (spikes).
+    Returns the layer's spikes on x_seq."""
+    w = _dyadic((n_out, x_seq.shape[-1]), 1024, seed, prefix + ".weight")
+    jitter = _dyadic((n_out,), 256, seed, prefix + ".bias")
+    cur = x_seq @ w.t()                                        # exact: every partial sum is on the grid, |sum| < 2^8
+    lo, hi = -16.0, 16.0
+    for _ in range(30):
+        mid = 0.5 * (lo + hi)
+        if float(_lif(cur + mid + jitter).mean()) < rate:
+            lo = mid
+        else:
+            hi = mid
+    off = round(0.5 * (lo + hi) * 4096) / 4096
+    sd[prefix + ".weight"] = w
+    sd[prefix + ".bias"] = jitter + off
+    return _lif(cur + sd[prefix + ".bias"])
+
+
+def synth_svae_state(seed: int = 5678, calib_batch: int = 16) -> dict:
+    """Synthetic ``SNN_VAE`` state_dict (the 56 keys of R/snn_model/vae_model.py:198-234).  The encoder and decoder are those
+    of ``synth_vqvae_state`` (MNIST shapes); every Linear weight and bias is a multiple of 2^-12 with |w| <= 0.25, so each
+    spike-weighted sum (fan-in <= 784: |sum| <= 196 + |bias| < 2^8, 20 significant bits) is exact in fp32 in any summation
+    order and the HIP kernels must match the reference bit for bit.  Bias offsets are calibrated on a host pass (latent
+    inputs of the autoregressive models stood in for by Bernoulli spikes) so that each LIF layer fires at ~25 %."""
+    base = synth_vqvae_state(MNIST, seed=seed, calib_batch=calib_batch)
+    sd = {k: v for k, v in base.items() if k.startswith(("encoder.", "decoder."))}
+    T, C, k = MNIST.T, SVAE_LATENT, SVAE_K
+    img = torch.rand(calib_batch, 1, 28, 28, generator=_gen(seed, "svae.calib.images")) - 0.5
+    x = img.unsqueeze(0).repeat(T, 1, 1, 1, 1)
+    p = "encoder.snn_convs."
+    x = _lif(_bn_eval(sd, p + "1", _seq(lambda y: F.conv2d(y, sd[p + "0.weight"], sd[p + "0.bias"], 2, 1), x)))
+    x = _lif(_bn_eval(sd, p + "4", _seq(lambda y: F.conv2d(y, sd[p + "3.weight"], sd[p + "3.bias"], 2, 1), x)))
+    x = _lif(_bn_eval(sd, p + "7", _seq(lambda y: F.conv2d(y, sd[p + "6.weight"], sd[p + "6.bias"]), x)))
+    latent_x = _linear_lif_calibrated(sd, "before_latent_layer.0", x.flatten(2), C, seed)
+    z = (torch.rand(T, calib_batch, C, generator=_gen(seed, "svae.calib.z")) < 0.25).float()
+    for name, inp in (("posterior", torch.cat([latent_x, z], -1)), ("prior", z)):
+        sd[name + ".initial_input"] = torch.zeros(1, 1, C)
+        h = _linear_lif_calibrated(sd, name + ".layers.0", inp, 2 * C, seed)
+        h = _linear_lif_calibrated(sd, name + ".layers.2", h, 4 * C, seed)
+        _linear_lif_calibrated(sd, name + ".layers.4", h, k * C, seed)
+    _linear_lif_calibrated(sd, "decoder_input.0", z, 16 * 7 * 7, seed)
+    sd["membrane_output_layer.coef"] = memout_coef(T)
+    return {k_: v.contiguous() for k_, v in sd.items()}
+
+
 def stroke_images(n: int, seed: int = 2024, img: int = 28, channels: int = 1) -> torch.Tensor:
     """``n`` procedurally generated digit-like images [n, channels, img, img] in [0, 1] (the value range of the reference's
     ``ToTensor`` loaders, R/load_dataset_snn.py): two to four pen strokes -- straight segments and quadratic arcs through random
