@@ -630,6 +630,48 @@ int spk_svae_ar_fwd(const uint8_t* x_or_null, const float* z0, const float* w1, 
                     const int* idx, float* sampled_z_out, uint8_t* q_z_out_or_null, int T, int B, int cx, int cz, int h1,
                     int h2, int k, spk_stream_t stream);
 
+/* ---- SNN_VAE baseline: training path (R/snn_model/vae_model.py:198-546 in train() mode) ------------------------------ */
+/* The no-grad prefix passes of one training Bernoulli loop in ONE launch (the kernel of spk_svae_ar_fwd in a prefix mode).
+ * Posterior (x u8 [T,B,cx], idx [T,B,cz] as in spk_svae_ar_fwd): the T-1 passes over the prefixes of [x, z] (:491-513).
+ * Prior (x NULL, cx 0; :365-390 with self.training): sched u8 [T-1] (step t scheduled: t >= 5 and random.random() < p),
+ * noise fp32 [n_sched,B,cz] (the torch.randn_like draws of the scheduled steps, in order), z_teacher fp32 [T,B,cz] (the
+ * posterior's z): a scheduled step runs the MLP over the prefix and sets z_{t+1} = (count_k / k + 0.001f * noise > 0.5), any
+ * other step appends z_teacher[t].  Both write z_t_minus_out fp32 [T,B,cz] (z_0 = z0, the input of the grad pass) and
+ * leave v1..v3 as the reference leaves them.  2 <= T <= 16. */
+int spk_svae_ar_prefix_fwd(const uint8_t* x_or_null, const float* z0, const float* w1, const float* b1, const float* w2,
+                           const float* b2, const float* w3, const float* b3, float* v1_inout, float* v2_inout,
+                           float* v3_inout, const int* idx_or_null, const uint8_t* sched_or_null, const float* noise_or_null,
+                           const float* z_teacher_or_null, float* z_t_minus_out, int T, int B, int cx, int cz, int h1, int h2,
+                           int k, spk_stream_t stream);
+/* Multi-step layer.Linear + the LIFNode's surrogate-gradient training forward.  Input [x | x2] (x2 may be NULL), each fp32
+ * or u8 {0,1} (SPK_LIN_IN_F32 / SPK_LIN_IN_U8) [T,B,n], w [out, x_features + x2_features], bias may be NULL.  lif = 1:
+ * out fp32 spikes [T,B,out], h_seq fp32 [T,B,out] (membrane before reset), v_out [B,out] from v_init (NULL: zeros; may
+ * alias v_out).  lif = 0: out = the Linear's currents, h / v unused.  Same sums as spk_linear_lif_fwd. */
+int spk_linear_lif_train_fwd(const void* x, int x_kind, int x_features, const void* x2_or_null, int x2_kind, int x2_features,
+                             const float* w, const float* bias_or_null, const float* v_init_or_null, float* out,
+                             float* h_seq_or_null, float* v_out_or_null, int lif, int T, int B, int out_features,
+                             spk_stream_t stream);
+/* Backward of spk_linear_lif_train_fwd.  h_seq given: LIF BPTT first (tau 2, v_th 1, v_reset 0, ATan alpha 2,
+ * detach_reset off, no gradient into v_init) into dI_ws [T,B,out]; h_seq NULL: grad_out is dL/dcurrents.  Then
+ * grad_x [T*B, grad_x_cols] = dI W[:, :grad_x_cols] (may be NULL), grad_w [out, in] = dI^T [x | x2], grad_b [out] = sum dI
+ * (may be NULL).  Fixed-order fp32 sums: deterministic. */
+int spk_linear_lif_train_bwd(const float* grad_out, const float* h_seq_or_null, float* dI_ws_or_null, const void* x,
+                             int x_kind, int x_features, const void* x2_or_null, int x2_kind, int x2_features, const float* w,
+                             float* grad_x_or_null, int grad_x_cols, float* grad_w, float* grad_b_or_null, int T, int B,
+                             int out_features, spk_stream_t stream);
+/* Workspace (floats) of spk_svae_latent_loss_fwd's loss reduction. */
+int spk_svae_latent_loss_ws_floats(int B, int cz);
+/* The posterior's gather and the latent MMD loss (:273-285, :531-541).  q_z, p_z fp32 [T,B,cz*k] (layer-3 spikes of the
+ * grad passes), idx int32 [T,B,cz]: sampled_z [T,B,cz] = q_z[.., c*k + idx] (may be NULL); loss [1] =
+ * mean((PSP(mean_k q) - PSP(mean_k p))^2), PSP at tau_s (p_z and loss both given or both NULL).  Fixed-order reduction. */
+int spk_svae_latent_loss_fwd(const float* q_z, const float* p_z_or_null, const int* idx, float* sampled_z_or_null,
+                             float* loss_or_null, float* ws, int T, int B, int cz, int k, float tau_s, spk_stream_t stream);
+/* Its backward: grad_q_z = the MMD term (g_loss, device [1], may be NULL) spread over k plus the scatter of
+ * g_sampled_z [T,B,cz] (may be NULL) at idx; grad_p_z (may be NULL) = minus the MMD term. */
+int spk_svae_latent_loss_bwd(const float* q_z, const float* p_z_or_null, const int* idx, const float* g_loss_or_null,
+                             const float* g_sampled_z_or_null, float* grad_q_z, float* grad_p_z_or_null, int T, int B, int cz,
+                             int k, float tau_s, spk_stream_t stream);
+
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every
  * matrix-core number: devices of one pool differ by ~10 %).  nblocks workgroups of 256 threads issue 4*iters MFMAs per

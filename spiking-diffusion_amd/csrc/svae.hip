@@ -135,7 +135,14 @@ __host__ __device__ inline ArLayout ar_layout(int bt, int T, int cx, int cz, int
 // z_{p+1} = spike[last row][c*k + idx[p][b][c]]; the final pass runs all T rows of [x, z_0..z_{T-1}] and sampled_z[s] takes
 // the spike at idx[s] of row s (R/snn_model/vae_model.py:491-541).  Prior (x == NULL): passes p = 0..T-1 over z_0..z_p, and
 // sampled_z[p] = z_{p+1} (:405-423).  No pass resets a neuron: v runs on through every row of every pass.
-template <int BT>
+// MODE (AR_*): the eval loop above, or only the no-grad prefix passes of one training loop (spk_svae_ar_prefix_fwd).
+// AR_POST_PREFIX: passes p = 0..T-2 of the posterior.  AR_PRIOR_PREFIX: the prior's scheduled sampling
+// (R/snn_model/vae_model.py:365-390): for p = 0..T-2, a scheduled step (sched[p] != 0) runs the MLP over the prefix rows
+// 0..p and sets z_{p+1} = (count_k(last-row spikes) / k + 0.001f * noise > 0.5), any other step copies the teacher row
+// zt[p].  Both write z_0..z_{T-1} to zout ([T,B,cz], the z_t_minus of the grad pass) and leave v1..v3 after the passes.
+enum { AR_EVAL = 0, AR_POST_PREFIX = 1, AR_PRIOR_PREFIX = 2 };
+
+template <int BT, int MODE>
 __global__ __launch_bounds__(SV_THREADS) void svae_ar_kernel(const uint8_t* __restrict__ x, const float* __restrict__ z0,
                                                              const float* __restrict__ w1, const float* __restrict__ b1,
                                                              const float* __restrict__ w2, const float* __restrict__ b2,
@@ -143,7 +150,9 @@ __global__ __launch_bounds__(SV_THREADS) void svae_ar_kernel(const uint8_t* __re
                                                              float* __restrict__ v1g, float* __restrict__ v2g,
                                                              float* __restrict__ v3g, const int* __restrict__ idx,
                                                              float* __restrict__ zout, uint8_t* __restrict__ qz, int T, int B,
-                                                             int cx, int cz, int h1, int h2, int k) {
+                                                             int cx, int cz, int h1, int h2, int k,
+                                                             const uint8_t* __restrict__ sched, const float* __restrict__ noise,
+                                                             const float* __restrict__ zt) {
   extern __shared__ float lds[];
   const int h3 = cz * k;
   const ArLayout L = ar_layout(BT, T, cx, cz, h1, h2, h3);
@@ -179,9 +188,23 @@ __global__ __launch_bounds__(SV_THREADS) void svae_ar_kernel(const uint8_t* __re
 
   const bool post = cx > 0;
   const int nin1 = cx + cz;
-  for (int p = 0; p < T; ++p) {
-    const bool last_pass = post && p == T - 1;
+  const int npass = MODE == AR_EVAL ? T : T - 1;
+  int n_sched = 0;                       // prior prefix: scheduled steps so far (row of noise)
+  for (int p = 0; p < npass; ++p) {
+    const bool last_pass = MODE == AR_EVAL && post && p == T - 1;
     const int len = last_pass ? T : p + 1;
+    if (MODE == AR_PRIOR_PREFIX) {
+      if (!sched[p]) {                   // teacher step: z_{p+1} = z[p], no layer runs
+        for (int e = tid; e < cz * BT; e += SV_THREADS) {
+          const int j = e % BT;
+          zs[(p + 1) * cz * BT + e] = (j < nb) ? zt[((long long)p * B + b0 + j) * cz + e / BT] : 0.0f;
+        }
+        __syncthreads();
+        continue;
+      }
+      for (int e = tid; e < cz * BT; e += SV_THREADS) zs[(p + 1) * cz * BT + e] = 0.0f;   // spike counts of row p
+      __syncthreads();
+    }
     for (int s = 0; s < len; ++s) {
       // layer 1: input row s = [x_s, z_s]
       for (int o = tid; o < h1; o += SV_THREADS) {
@@ -219,19 +242,41 @@ __global__ __launch_bounds__(SV_THREADS) void svae_ar_kernel(const uint8_t* __re
         for (int j = 0; j < BT; ++j) {
           const bool spk = sv_lif(v3[o * BT + j], acc[j] + bo);
           if (j >= nb) continue;
+          if (MODE == AR_PRIOR_PREFIX) {   // count the last row's spikes per channel (integer-valued: exact in any order)
+            if (s == len - 1 && spk) atomicAdd(&zs[((p + 1) * cz + c) * BT + j], 1.0f);
+            continue;
+          }
           const long long b = b0 + j;
-          if (last_pass && qz) qz[((long long)s * B + b) * h3 + o] = spk ? 1 : 0;
+          if (MODE == AR_EVAL && last_pass && qz) qz[((long long)s * B + b) * h3 + o] = spk ? 1 : 0;
           if (!pick_row || idx[((long long)irow * B + b) * cz + c] != r) continue;
           const float zv = spk ? 1.0f : 0.0f;
           if (last_pass) {
             zout[((long long)s * B + b) * cz + c] = zv;
           } else {
             zs[((p + 1) * cz + c) * BT + j] = zv;
-            if (!post) zout[((long long)p * B + b) * cz + c] = zv;
+            if (MODE == AR_EVAL && !post) zout[((long long)p * B + b) * cz + c] = zv;
           }
         }
       }
       __syncthreads();
+    }
+    if (MODE == AR_PRIOR_PREFIX) {       // prob1 = mean_k + 1e-3 * randn (fp32, as the reference), z = prob1 > 0.5
+      for (int e = tid; e < cz * BT; e += SV_THREADS) {
+        const int j = e % BT, c = e / BT;
+        float* zc = &zs[(p + 1) * cz * BT + e];
+        const float nz = (j < nb) ? noise[((long long)n_sched * B + b0 + j) * cz + c] : 0.0f;
+        const float prob = *zc / (float)k + 0.001f * nz;
+        *zc = (j < nb && prob > 0.5f) ? 1.0f : 0.0f;
+      }
+      ++n_sched;
+      __syncthreads();
+    }
+  }
+
+  if (MODE != AR_EVAL) {
+    for (int e = tid; e < T * cz * BT; e += SV_THREADS) {
+      const int j = e % BT, c = (e / BT) % cz, t = e / (BT * cz);
+      if (j < nb) zout[((long long)t * B + b0 + j) * cz + c] = zs[e];
     }
   }
 
@@ -298,11 +343,40 @@ extern "C" int spk_svae_ar_fwd(const uint8_t* x_or_null, const float* z0, const 
   const int bt = ar_tile(B);
   const dim3 grid((B + bt - 1) / bt);
   if (bt == 4)
-    hipLaunchKernelGGL(svae_ar_kernel<4>, grid, dim3(SV_THREADS), (size_t)lds, stream, x_or_null, z0, w1, b1, w2, b2, w3, b3,
-                       v1_inout, v2_inout, v3_inout, idx, sampled_z_out, q_z_out_or_null, T, B, cx, cz, h1, h2, k);
+    hipLaunchKernelGGL((svae_ar_kernel<4, AR_EVAL>), grid, dim3(SV_THREADS), (size_t)lds, stream, x_or_null, z0, w1, b1, w2, b2,
+                       w3, b3, v1_inout, v2_inout, v3_inout, idx, sampled_z_out, q_z_out_or_null, T, B, cx, cz, h1, h2, k,
+                       nullptr, nullptr, nullptr);
   else
-    hipLaunchKernelGGL(svae_ar_kernel<1>, grid, dim3(SV_THREADS), (size_t)lds, stream, x_or_null, z0, w1, b1, w2, b2, w3, b3,
-                       v1_inout, v2_inout, v3_inout, idx, sampled_z_out, q_z_out_or_null, T, B, cx, cz, h1, h2, k);
+    hipLaunchKernelGGL((svae_ar_kernel<1, AR_EVAL>), grid, dim3(SV_THREADS), (size_t)lds, stream, x_or_null, z0, w1, b1, w2, b2,
+                       w3, b3, v1_inout, v2_inout, v3_inout, idx, sampled_z_out, q_z_out_or_null, T, B, cx, cz, h1, h2, k,
+                       nullptr, nullptr, nullptr);
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+
+extern "C" int spk_svae_ar_prefix_fwd(const uint8_t* x_or_null, const float* z0, const float* w1, const float* b1,
+                                      const float* w2, const float* b2, const float* w3, const float* b3, float* v1_inout,
+                                      float* v2_inout, float* v3_inout, const int* idx_or_null, const uint8_t* sched_or_null,
+                                      const float* noise_or_null, const float* z_teacher_or_null, float* z_t_minus_out, int T,
+                                      int B, int cx, int cz, int h1, int h2, int k, hipStream_t stream) {
+  if (!z0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !v1_inout || !v2_inout || !v3_inout || !z_t_minus_out)
+    return SPK_ERR_ARG;
+  if (T < 2 || T > SPK_MAX_T || B <= 0 || cz <= 0 || h1 <= 0 || h2 <= 0 || k <= 0 || cx < 0) return SPK_ERR_ARG;
+  const bool post = x_or_null != nullptr;
+  if (post != (cx > 0)) return SPK_ERR_ARG;
+  if (post && !idx_or_null) return SPK_ERR_ARG;                                                      // posterior: the draws
+  if (!post && (!sched_or_null || !noise_or_null || !z_teacher_or_null)) return SPK_ERR_ARG;         // prior: the schedule
+  const long long lds = ar_lds_bytes(T, B, cx, cz, h1, h2, k);
+  if (lds > SV_LDS_MAX) return SPK_ERR_UNSUPPORTED;
+  const int bt = ar_tile(B);
+  const dim3 grid((B + bt - 1) / bt);
+#define SV_PREFIX(BT, MODE)                                                                                               \
+  hipLaunchKernelGGL((svae_ar_kernel<BT, MODE>), grid, dim3(SV_THREADS), (size_t)lds, stream, x_or_null, z0, w1, b1, w2, b2, \
+                     w3, b3, v1_inout, v2_inout, v3_inout, idx_or_null, z_t_minus_out, nullptr, T, B, cx, cz, h1, h2, k,    \
+                     sched_or_null, noise_or_null, z_teacher_or_null)
+  if (post) { if (bt == 4) SV_PREFIX(4, AR_POST_PREFIX); else SV_PREFIX(1, AR_POST_PREFIX); }
+  else      { if (bt == 4) SV_PREFIX(4, AR_PRIOR_PREFIX); else SV_PREFIX(1, AR_PRIOR_PREFIX); }
+#undef SV_PREFIX
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }

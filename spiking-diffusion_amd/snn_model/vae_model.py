@@ -10,12 +10,16 @@ cover take the framework's operator), native BatchNorm+LIF block tails (``spk_bn
 read-out / code search / losses, the PSP losses and the reconstruction loss as fused operators (``csrc/vq_train.hip``).
 
 ``SNN_VAE`` (R/snn_model/vae_model.py:198-546, the FSVAE-style baseline) runs its eval forward, ``encode``, ``decode`` and
-``sample`` on ``csrc/svae.hip``: Linear + LIF pairs fused, each autoregressive Bernoulli loop one launch; its training branch
-raises ``NotImplementedError``.
+``sample`` on ``csrc/svae.hip``: Linear + LIF pairs fused, each autoregressive Bernoulli loop one launch.  Its training
+branch (MMD + reconstruction losses) runs with autograd on ``csrc/svae_train.hip``: Linear + surrogate LIF forward and
+backward, the no-grad prefix passes of each Bernoulli loop in one launch, the gather and MMD loss fused; the encoder and
+decoder take SNN_VQVAE's training path.
 
 Re-exported names match what ``from snn_model.vae_model import *`` gives R/main.py (``functional`` in particular,
 R/main.py:101-107,317).
 """
+import random
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -268,7 +272,7 @@ class SNN_VQVAE(nn.Module):
         return r['f32'], r['u8']
 
 
-# ---- SNN_VAE: the FSVAE-style baseline (R/snn_model/vae_model.py:198-546), eval path ---------------------------------------
+# ---- SNN_VAE: the FSVAE-style baseline (R/snn_model/vae_model.py:198-546) --------------------------------------------------
 # Every Linear + LIFNode pair runs fused (spk_linear_lif_fwd) and each autoregressive Bernoulli loop is ONE launch
 # (spk_svae_ar_fwd); the modules keep the reference's children, state_dict keys and LIFNode states, so reset_net and
 # load_state_dict behave as there.  The random indices are drawn on the host with the reference's calls in its order.
@@ -295,6 +299,20 @@ def _svae_linear_lif(seq, x, **kw):
     lin, node = seq[0], seq[1]
     B = x.shape[0] if x.dim() == 5 else x.shape[1]
     return ops.linear_lif(x, lin.weight, lin.bias, _svae_node_v(node, B, lin.out_features, x.device), **kw)
+
+
+def _svae_linear_lif_train(seq, x, x2=None):
+    """nn.Sequential(layer.Linear, LIFNode) in training on fp32 [T,B,in] (+ optional concat x2): fp32 spikes with autograd."""
+    lin, node = seq[0], seq[1]
+    v = _svae_node_v(node, x.shape[1], lin.out_features, x.device)
+    return ops.LinearLIFTrainFunction.apply(x, x2, lin.weight, lin.bias, v, True)
+
+
+def _train_guard(what, t):
+    if not torch.is_grad_enabled():
+        _training_oos(f'{what} in train() mode without autograd')
+    if not t.is_cuda:
+        raise NotImplementedError(f"spkdiff: {what} in train() mode needs a ROCm device; there is no CPU path")
 
 
 def _require_device(t, what):
@@ -334,6 +352,17 @@ class _BernoulliSTBP(nn.Module):
         vs = [_svae_node_v(self.layers[i + 1], batch_size, lins[j].out_features, dev) for j, i in enumerate((0, 2, 4))]
         return ops.svae_ar(x, self.initial_input, [(m.weight, m.bias) for m in lins], vs, idx, want_q_z=want_q_z)
 
+    def _state(self, B, dev):
+        lins = [self.layers[i] for i in (0, 2, 4)]
+        vs = [_svae_node_v(self.layers[i + 1], B, lins[j].out_features, dev) for j, i in enumerate((0, 2, 4))]
+        return [(m.weight.detach(), m.bias.detach()) for m in lins], vs
+
+    def _grad_pass(self, x, x2=None):
+        """The one pass with grad of a training loop: the three Linear + LIF layers on [x | x2] -> fp32 spikes [T,B,C*k]."""
+        h = _svae_linear_lif_train(self.layers[0:2], x, x2)
+        h = _svae_linear_lif_train(self.layers[2:4], h)
+        return _svae_linear_lif_train(self.layers[4:6], h)
+
     def _teacher_forced(self, z, want_out=True):
         """The eval pass over [initial_input, z_0 .. z_{T-2}] (one multi-step pass, state carried): u8 [T,B,C*k] or None."""
         _require_device(z, 'z')
@@ -354,9 +383,34 @@ class PriorBernoulliSTBP(_BernoulliSTBP):
         """Eval: p_z (T,B,C,k) of the pass over [initial_input, z_0 .. z_{T-2}] (both branches of the reference compute this
         pass outside training, :338-403).  Advances the layers' LIF state."""
         if self.training:
-            _training_oos('PriorBernoulliSTBP.forward in train() mode (scheduled sampling, :365-390)')
+            p_z, _ = self._train_forward(z, scheduled, p)
+            return p_z.view(self.n_steps, z.shape[1], self.channels, self.k)
         out = self._teacher_forced(z)
         return out.to(torch.float32).view(self.n_steps, z.shape[1], self.channels, self.k)
+
+    def _train_forward(self, z, scheduled=True, p=None):
+        """Training (:338-403): the scheduled-sampling prefix passes without grad (one launch, skipped when no step is
+        scheduled), then one pass with grad over z_t_minus.  Returns (p_z fp32 [T,B,C*k], z_t_minus fp32 [T,B,C]).
+        Host draws as the reference's: random.random() for t = 5..T-2, torch.randn_like([B,C]) per scheduled step."""
+        _train_guard('PriorBernoulliSTBP.forward', z)
+        z = z.detach().to(torch.float32)
+        T, B = z.shape[0], z.shape[1]
+        dev = z.device
+        sched = [False] * (self.n_steps - 1)
+        noise = []
+        if scheduled:
+            for t in range(self.n_steps - 1):
+                if t >= 5 and random.random() < p:
+                    sched[t] = True
+                    noise.append(torch.randn_like(torch.empty((B, self.channels), dtype=torch.float32, device=dev)))
+        z0 = self.initial_input.to(torch.float32)
+        if noise:
+            layers, vs = self._state(B, dev)
+            z_t_minus = ops.svae_ar_prefix(None, z0, layers, vs, sched=torch.tensor(sched, dtype=torch.uint8, device=dev),
+                                           noise=torch.stack(noise), z_teacher=z.contiguous())
+        else:
+            z_t_minus = torch.cat([z0.expand(1, B, self.channels), z[:-1]], 0).contiguous()
+        return self._grad_pass(z_t_minus), z_t_minus
 
     def sample(self, batch_size=64):
         """Autoregressive sampling of z (T,B,C): n_steps passes over the growing prefix, one launch (spk_svae_ar_fwd)."""
@@ -375,7 +429,9 @@ class PosteriorBernoulliSTBP(_BernoulliSTBP):
         """x: (T,B,C) spikes of before_latent_layer (u8 / bool, or fp32 0/1).  Returns (sampled_z (T,B,C) fp32,
         q_z (T,B,C,k) fp32 -- the spikes of the final pass -- or None with want_q_z=False).  One launch."""
         if self.training:
-            _training_oos('PosteriorBernoulliSTBP.forward in train() mode')
+            q, idx = self._train_forward(x)
+            sz, _ = ops.LatentLossFunction.apply(q, None, idx, 2.0)
+            return sz, q.view(x.shape[0], x.shape[1], self.channels, self.k)
         _require_device(x, 'x')
         if x.dtype != torch.uint8 and x.dtype != torch.bool:
             x = x.to(torch.uint8)
@@ -384,6 +440,20 @@ class PosteriorBernoulliSTBP(_BernoulliSTBP):
         if q is not None:
             q = q.to(torch.float32).view(T, B, self.channels, self.k)
         return z, q
+
+
+    def _train_forward(self, x):
+        """Training (:470-546): the T-1 prefix passes without grad in one launch, then one pass with grad over
+        [x, z_t_minus] (gradient into x only).  x fp32 [T,B,C] (with autograd).  Returns (q_z fp32 [T,B,C*k], idx int32
+        [T,B,C]); sampled_z is the gather of q_z at idx (ops.LatentLossFunction)."""
+        _train_guard('PosteriorBernoulliSTBP.forward', x)
+        T, B = x.shape[0], x.shape[1]
+        dev = x.device
+        idx = self._draw_indices(B, dev)
+        layers, vs = self._state(B, dev)
+        z_t_minus = ops.svae_ar_prefix(x.detach().to(torch.uint8), self.initial_input.to(torch.float32), layers, vs, idx=idx)
+        x = x if x.dtype == torch.float32 else x.to(torch.float32)
+        return self._grad_pass(x, z_t_minus), idx
 
 
 class SNN_VAE(nn.Module):
@@ -411,9 +481,33 @@ class SNN_VAE(nn.Module):
         self.membrane_output_layer = MembraneOutputLayer()
         self.psp = PSP()
 
+    def _train_latent(self, x, scheduled=True):
+        """Training encode: encoder (batch-statistics BN, surrogate LIF), before_latent_layer, posterior, prior and the
+        fused gather + MMD loss.  Returns (sampled_z, mmd_loss, q_z flat, p_z flat, prior's z_t_minus, latent_x)."""
+        z = self.encoder(x)                                                           # (T,B,16,7,7) fp32
+        latent_x = _svae_linear_lif_train(self.before_latent_layer, torch.flatten(z, 2).contiguous())
+        return self._latent_from(latent_x, scheduled) + (latent_x,)
+
+    def _latent_from(self, latent_x, scheduled=True):
+        """posterior -> prior -> (sampled_z, mmd_loss, q_z [T,B,C*k], p_z [T,B,C*k], the prior's z_t_minus [T,B,C]) from
+        before_latent_layer's spikes [T,B,C]."""
+        q_z, idx = self.posterior._train_forward(latent_x)
+        sampled_vals, _ = ops.LatentLossFunction.apply(q_z.detach(), None, idx, float(self.psp.tau_s))   # prior input: no grad
+        p_z, z_t_minus = self.prior._train_forward(sampled_vals, scheduled, self.p)
+        sampled_z, mmd = ops.LatentLossFunction.apply(q_z, p_z, idx, float(self.psp.tau_s))
+        return sampled_z, mmd, q_z, p_z, z_t_minus
+
+    def _train_decode(self, z):
+        """decoder_input + view + decoder in training: the decoder's output (T,B,1,28,28) before the read-out."""
+        result = _svae_linear_lif_train(self.decoder_input, z.to(torch.float32).contiguous())
+        return self.decoder(result.view(self.n_steps, result.shape[1], 16, 7, 7))
+
     def _encode(self, x, scheduled=True, full=True):
         if self.training:
-            _training_oos('SNN_VAE.encode in train() mode')
+            _train_guard('SNN_VAE.encode', x)
+            sampled_z, _, q_z, p_z, _, _ = self._train_latent(x, scheduled)
+            T, B = q_z.shape[0], q_z.shape[1]
+            return (sampled_z, q_z.view(T, B, self.latent_dim, self.k), p_z.view(T, B, self.latent_dim, self.k))
         _require_device(x, 'x')
         z_ptc = self.encoder.snn_convs.run(x, IN_SEQ, final='ptc')['ptc']            # u8 [B,7,7,T,16]
         latent_x = _svae_linear_lif(self.before_latent_layer, z_ptc)                 # u8 [T,B,56], flatten(C,H,W) order
@@ -431,6 +525,9 @@ class SNN_VAE(nn.Module):
 
     def decode(self, z):
         """z (T,B,C) -> tanh(membrane read-out) (B,1,28,28): decoder_input writes the PTC spikes the fused decoder reads."""
+        if self.training:
+            _train_guard('SNN_VAE.decode', z)
+            return torch.tanh(self.membrane_output_layer(self._train_decode(z)))
         _require_device(z, 'z')
         ptc = _svae_linear_lif(self.decoder_input, z.to(torch.float32).contiguous(), out_ptc=(16, 7, 7))
         return self.decoder.snn_convs.run(ptc, IN_PTC, final='memout', coef=self.membrane_output_layer.coef.flatten(),
@@ -459,9 +556,13 @@ class SNN_VAE(nn.Module):
         self.p = (last_p - init_p) * epoch / max_epoch + init_p
 
     def forward(self, x, image, scheduled=True):
-        """Eval: (sampled_z (T,B,C), x_recon (B,1,28,28)).  The training branch (MMD + reconstruction loss) is out of scope."""
+        """Eval: (sampled_z (T,B,C), x_recon (B,1,28,28)).  Training: (mmd_loss, recons_loss) with autograd, the
+        reconstruction loss not divided by the data variance (R/snn_model/vae_model.py:299-305)."""
         if self.training:
-            _training_oos('SNN_VAE.forward in train() mode (MMD / reconstruction losses, R/snn_model/vae_model.py:299-305)')
+            _train_guard('SNN_VAE.forward', x)
+            sampled_z, mmd, _, _, _, _ = self._train_latent(x, scheduled)
+            y = self._train_decode(sampled_z)
+            return mmd, ops.ReconLossFunction.apply(y, self.membrane_output_layer.coef, image)      # read-out + tanh + mse
         sampled_z, _, _ = self._encode(x, scheduled, full=False)
         return sampled_z, self.decode(sampled_z)
 

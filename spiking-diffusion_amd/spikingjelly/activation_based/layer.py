@@ -148,8 +148,9 @@ class BatchNorm2d(nn.BatchNorm2d, base.StepModule):
 
 class Linear(nn.Linear, base.StepModule):
     """SJ/activation_based/layer.py:900-922: nn.Linear over the last dimension; 'm' mode folds T into the batch.  The
-    currents come from spk_linear_lif_fwd (fp32 sums in a fixed order, then + bias); the SNN_VAE model runs its
-    Linear + LIFNode pairs fused through the same kernel (snn_model/vae_model.py)."""
+    currents come from spk_linear_lif_fwd (fp32 sums in a fixed order, then + bias), in training (with autograd) from
+    spk_linear_lif_train_fwd / _bwd; the SNN_VAE model runs its Linear + LIFNode pairs fused through the same kernels
+    (snn_model/vae_model.py)."""
 
     def __init__(self, in_features, out_features, bias=True, step_mode='s'):
         super().__init__(in_features, out_features, bias)
@@ -162,11 +163,15 @@ class Linear(nn.Linear, base.StepModule):
         if not x.is_cuda:
             raise RuntimeError(f"spkdiff: input is on '{x.device}'; there is no CPU path (move module and tensors to a ROCm "
                                "device)")
-        if self.training and torch.is_grad_enabled():
-            raise NotImplementedError('spkdiff: layer.Linear training (the SNN_VAE training branch) is outside the '
-                                      'inference path; call .eval() or run under torch.no_grad()')
         if self.step_mode == 'm' and x.dim() < 3:
             raise ValueError(f'expected x with shape [T, N, *, {self.in_features}], but got x with shape {tuple(x.shape)}!')
         lead = x.shape[:-1]
+        if self.training and torch.is_grad_enabled():
+            # training: the plain-currents form of spk_linear_lif_train_fwd / _bwd, with autograd
+            x2 = x.reshape(1, -1, self.in_features)
+            if x2.dtype != torch.float32:
+                x2 = x2.to(torch.float32)
+            y = ops.LinearLIFTrainFunction.apply(x2, None, self.weight, self.bias, None, False)
+            return y.view(tuple(lead) + (self.out_features,))
         y = ops.linear(x.reshape(-1, self.in_features), self.weight, self.bias)
         return y.view(tuple(lead) + (self.out_features,))

@@ -144,6 +144,12 @@ _SIGS = {
     "spk_q_sample": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
     "spk_linear_lif_fwd": (c_int, [P, c_int, P, P, P, P, c_int] + [c_int] * 7 + [P]),
     "spk_svae_ar_fwd": (c_int, [P] * 14 + [c_int] * 7 + [P]),
+    "spk_svae_ar_prefix_fwd": (c_int, [P] * 16 + [c_int] * 7 + [P]),
+    "spk_linear_lif_train_fwd": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P] + [c_int] * 4 + [P]),
+    "spk_linear_lif_train_bwd": (c_int, [P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_int, P, P] + [c_int] * 3 + [P]),
+    "spk_svae_latent_loss_ws_floats": (c_int, [c_int, c_int]),
+    "spk_svae_latent_loss_fwd": (c_int, [P] * 6 + [c_int] * 4 + [c_float, P]),
+    "spk_svae_latent_loss_bwd": (c_int, [P] * 7 + [c_int] * 4 + [c_float, P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -2142,3 +2142,221 @@ def svae_ar(x, z0, layers, vs, idx, want_q_z=False):
     check(lib.spk_svae_ar_fwd(_p(x), _p(z0), _p(w1), _p(bs[0]), _p(w2), _p(bs[1]), _p(w3), _p(bs[2]), _p(v1), _p(v2), _p(v3),
                               _p(idx32), _p(z), _p(q), T, B, cx, cz, h1, h2, k, _stream(idx)), "spk_svae_ar_fwd")
     return z, q
+
+
+# ---------------------------------------------------------------------------------------------- SNN_VAE training path
+def _lin_train_input(x, name, T, B):
+    """fp32 / u8 / bool [T,B,n] -> (contiguous tensor, kind, n)."""
+    x = _dev(x, name)
+    if x.dtype == torch.bool:
+        x = x.view(torch.uint8)
+    if x.dim() != 3 or x.shape[:2] != (T, B) or x.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{name} must be fp32/u8 [{T}, {B}, n], got {x.dtype} {tuple(x.shape)}")
+    return x, (LIN_IN_F32 if x.dtype == torch.float32 else LIN_IN_U8), x.shape[2]
+
+
+def linear_lif_train_fwd(x, weight, bias, v=None, x2=None, lif=True):
+    """Multi-step Linear (+ the LIFNode's training forward), spk_linear_lif_train_fwd.
+
+    x: fp32/u8 [T,B,in1]; x2: optional second input [T,B,in2] read as the concat [x | x2] (weight [out, in1+in2]).
+    lif=True: returns (spikes fp32 [T,B,out], h_seq fp32 [T,B,out]); v fp32 [B,out] (None: zeros) is the state before and,
+    updated in place, after.  lif=False: returns (currents fp32 [T,B,out], None)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError(f"x must be [T, B, in], got {getattr(x, 'shape', None)}")
+    T, B = x.shape[0], x.shape[1]
+    x, k1, n1 = _lin_train_input(x, "x", T, B)
+    if x2 is not None:
+        x2, k2, n2 = _lin_train_input(x2, "x2", T, B)
+    else:
+        k2, n2 = LIN_IN_F32, 0
+    w, b = _linear_params(weight, bias, n1 + n2)
+    n_out = w.shape[0]
+    out = torch.empty((T, B, n_out), dtype=torch.float32, device=x.device)
+    h = None
+    if lif:
+        h = torch.empty_like(out)
+        if v is None:
+            raise ValueError("lif=True needs the neuron state v [B, out]")
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
+                and v.shape == (B, n_out)):
+            raise ValueError(f"v must be a contiguous fp32 [{B}, {n_out}] device tensor")
+    check(lib.spk_linear_lif_train_fwd(_p(x), k1, n1, _p(x2), k2, n2, _p(w), _p(b), _p(v) if lif else None, _p(out), _p(h),
+                                       _p(v) if lif else None, int(bool(lif)), T, B, n_out, _stream(x)),
+          "spk_linear_lif_train_fwd")
+    return out, h
+
+
+def linear_lif_train_bwd(grad_out, h_seq, x, weight, x2=None, grad_x_cols=0, want_bias=True):
+    """Backward of linear_lif_train_fwd (spk_linear_lif_train_bwd): (grad_x fp32 [T,B,grad_x_cols] or None, grad_w, grad_b)."""
+    g = _dev(grad_out, "grad_out", torch.float32)
+    if g.dim() != 3:
+        raise ValueError(f"grad_out must be [T, B, out], got {tuple(g.shape)}")
+    T, B, n_out = g.shape
+    x, k1, n1 = _lin_train_input(x, "x", T, B)
+    if x2 is not None:
+        x2, k2, n2 = _lin_train_input(x2, "x2", T, B)
+    else:
+        k2, n2 = LIN_IN_F32, 0
+    w, _ = _linear_params(weight, None, n1 + n2)
+    if w.shape[0] != n_out:
+        raise ValueError(f"weight has {w.shape[0]} outputs, grad_out {n_out}")
+    ws = None
+    if h_seq is not None:
+        h_seq = _dev(h_seq, "h_seq", torch.float32)
+        if h_seq.shape != g.shape:
+            raise ValueError(f"h_seq {tuple(h_seq.shape)} != grad_out {tuple(g.shape)}")
+        ws = torch.empty_like(g)
+    if not 0 <= grad_x_cols <= n1 + n2:
+        raise ValueError(f"grad_x_cols {grad_x_cols} outside [0, {n1 + n2}]")
+    gx = torch.empty((T, B, grad_x_cols), dtype=torch.float32, device=g.device) if grad_x_cols else None
+    gw = torch.empty_like(w)
+    gb = torch.empty(n_out, dtype=torch.float32, device=g.device) if want_bias else None
+    check(lib.spk_linear_lif_train_bwd(_p(g), _p(h_seq), _p(ws), _p(x), k1, n1, _p(x2), k2, n2, _p(w), _p(gx), grad_x_cols,
+                                       _p(gw), _p(gb), T, B, n_out, _stream(g)), "spk_linear_lif_train_bwd")
+    return gx, gw, gb
+
+
+class LinearLIFTrainFunction(torch.autograd.Function):
+    """layer.Linear + LIFNode (or layer.Linear alone, lif=False) in training, R/snn_model/vae_model.py:212-228,306-546:
+    one launch forward (spk_linear_lif_train_fwd), the BPTT and the three gradient GEMMs backward (spk_linear_lif_train_bwd).
+    apply(x [T,B,in1], x2 [T,B,in2] or None, weight, bias, v [B,out] or None, lif) -> spikes / currents fp32 [T,B,out].
+    v (no gradient: every state a grad pass starts from was made without grad or is the reset value) is updated in place."""
+
+    @staticmethod
+    def forward(ctx, x, x2, weight, bias, v, lif):
+        out, h = linear_lif_train_fwd(x.detach(), weight.detach(), None if bias is None else bias.detach(), v,
+                                      None if x2 is None else x2.detach(), lif)
+        ctx.save_for_backward(x.detach(), None if x2 is None else x2.detach(), weight.detach(), h)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        x, x2, w, h = ctx.saved_tensors
+        n1 = x.shape[2]
+        need_x, need_x2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        cols = n1 + x2.shape[2] if need_x2 else (n1 if need_x else 0)
+        gx, gw, gb = linear_lif_train_bwd(g_out.contiguous(), h, x, w, x2, cols, ctx.has_bias)
+        gx1 = gx[..., :n1] if need_x else None
+        gx2 = gx[..., n1:] if need_x2 else None
+        return gx1, gx2, gw, gb if ctx.needs_input_grad[3] else None, None, None
+
+
+def svae_ar_prefix(x, z0, layers, vs, idx=None, sched=None, noise=None, z_teacher=None):
+    """The no-grad prefix passes of one training Bernoulli loop in one launch (spk_svae_ar_prefix_fwd).
+
+    Posterior: x u8/bool [T,B,cx] and idx [T,B,cz].  Prior: x None, sched bool/u8 [T-1], noise fp32 [n_sched,B,cz] (n_sched =
+    scheduled steps), z_teacher fp32 [T,B,cz].  vs: the three layers' v fp32 [B,h], updated in place.
+    Returns z_t_minus fp32 [T,B,cz]."""
+    (w1, b1), (w2, b2), (w3, b3) = layers
+    if x is not None:
+        x = _dev(x, "x")
+        if x.dtype == torch.bool:
+            x = x.view(torch.uint8)
+        if x.dtype != torch.uint8 or x.dim() != 3:
+            raise ValueError(f"x must be u8 spikes [T, B, cx], got {x.dtype} {tuple(x.shape)}")
+        T, B, cx = x.shape
+        if idx is None:
+            raise ValueError("the posterior's prefix needs idx")
+        idx = _dev(idx, "idx")
+        if idx.dim() != 3 or idx.shape[:2] != (T, B) or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"idx must be an integer [{T}, {B}, cz] tensor, got {idx.dtype} {tuple(idx.shape)}")
+        cz = idx.shape[2]
+        idx = idx if idx.dtype == torch.int32 else idx.to(torch.int32)
+        dev = x.device
+    else:
+        if sched is None or noise is None or z_teacher is None:
+            raise ValueError("the prior's prefix needs sched, noise and z_teacher")
+        z_teacher = _dev(z_teacher, "z_teacher", torch.float32)
+        if z_teacher.dim() != 3:
+            raise ValueError(f"z_teacher must be [T, B, cz], got {tuple(z_teacher.shape)}")
+        T, B, cz = z_teacher.shape
+        cx = 0
+        sched = _dev(sched, "sched")
+        if sched.dtype == torch.bool:
+            sched = sched.view(torch.uint8)
+        if sched.dtype != torch.uint8 or sched.shape != (T - 1,):
+            raise ValueError(f"sched must be bool/u8 [{T - 1}], got {sched.dtype} {tuple(sched.shape)}")
+        n_sched = int(sched.count_nonzero())
+        noise = _dev(noise, "noise", torch.float32)
+        if noise.shape != (n_sched, B, cz):
+            raise ValueError(f"noise must be [{n_sched}, {B}, {cz}], got {tuple(noise.shape)}")
+        dev = z_teacher.device
+    if T < 2:
+        raise ValueError("the prefix passes need T >= 2")
+    z0 = _dev(z0, "initial_input", torch.float32)
+    if z0.numel() != cz:
+        raise ValueError(f"initial_input has {z0.numel()} elements, expected {cz}")
+    w1, b1 = _linear_params(w1, b1, cx + cz)
+    h1 = w1.shape[0]
+    w2, b2 = _linear_params(w2, b2, h1)
+    h2 = w2.shape[0]
+    w3, b3 = _linear_params(w3, b3, h2)
+    if w3.shape[0] % cz:
+        raise ValueError(f"last layer has {w3.shape[0]} outputs, not a multiple of {cz} channels")
+    k = w3.shape[0] // cz
+    bs = [torch.zeros(w.shape[0], dtype=torch.float32, device=w.device) if bb is None else bb
+          for w, bb in ((w1, b1), (w2, b2), (w3, b3))]
+    v1, v2, v3 = vs
+    for v, hh in ((v1, h1), (v2, h2), (v3, w3.shape[0])):
+        if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B, hh)):
+            raise ValueError(f"v must be a contiguous fp32 [{B}, {hh}] device tensor")
+    zm = torch.empty((T, B, cz), dtype=torch.float32, device=dev)
+    check(lib.spk_svae_ar_prefix_fwd(_p(x), _p(z0), _p(w1), _p(bs[0]), _p(w2), _p(bs[1]), _p(w3), _p(bs[2]), _p(v1), _p(v2),
+                                     _p(v3), _p(idx), _p(sched), _p(noise), _p(z_teacher), _p(zm), T, B, cx, cz, h1, h2, k,
+                                     _stream(zm)), "spk_svae_ar_prefix_fwd")
+    return zm
+
+
+def _latent_args(q_z, p_z, idx):
+    q = _dev(q_z.detach(), "q_z", torch.float32)
+    idx = _dev(idx, "idx")
+    if idx.dim() != 3 or idx.dtype != torch.int32:
+        raise ValueError(f"idx must be int32 [T, B, cz], got {idx.dtype} {tuple(idx.shape)}")
+    T, B, cz = idx.shape
+    if q.dim() != 3 or q.shape[:2] != (T, B) or q.shape[2] % cz:
+        raise ValueError(f"q_z must be [{T}, {B}, {cz}*k], got {tuple(q.shape)}")
+    if T > MAX_T:
+        raise NotImplementedError(f"spkdiff: the latent loss keeps at most {MAX_T} steps")
+    p = None
+    if p_z is not None:
+        p = _dev(p_z.detach(), "p_z", torch.float32)
+        if p.shape != q.shape:
+            raise ValueError(f"p_z {tuple(p.shape)} != q_z {tuple(q.shape)}")
+    return q, p, idx, T, B, cz, q.shape[2] // cz
+
+
+class LatentLossFunction(torch.autograd.Function):
+    """The posterior's gather sampled_z[t] = q_z[t].view(-1)[idx_t] (R/snn_model/vae_model.py:531-541) and, with p_z, the MMD
+    loss mean((PSP(mean_k q_z) - PSP(mean_k p_z))^2) (:273-285), fused (spk_svae_latent_loss_fwd / _bwd).
+    apply(q_z [T,B,cz*k], p_z [T,B,cz*k] or None, idx int32 [T,B,cz], tau_s) -> (sampled_z [T,B,cz], loss [] (zero without p_z))."""
+
+    @staticmethod
+    def forward(ctx, q_z, p_z, idx, tau_s):
+        q, p, idx, T, B, cz, k = _latent_args(q_z, p_z, idx)
+        sz = torch.empty((T, B, cz), dtype=torch.float32, device=q.device)
+        loss = torch.zeros((), dtype=torch.float32, device=q.device)
+        ws = None
+        if p is not None:
+            ws = torch.empty(lib.spk_svae_latent_loss_ws_floats(B, cz), dtype=torch.float32, device=q.device)
+        check(lib.spk_svae_latent_loss_fwd(_p(q), _p(p), _p(idx), _p(sz), _p(loss) if p is not None else None, _p(ws), T, B, cz,
+                                           k, float(tau_s), _stream(q)), "spk_svae_latent_loss_fwd")
+        ctx.save_for_backward(q, p, idx)
+        ctx.tau_s = float(tau_s)
+        if p is None:
+            ctx.mark_non_differentiable(loss)
+        return sz, loss
+
+    @staticmethod
+    def backward(ctx, g_sz, g_loss):
+        q, p, idx = ctx.saved_tensors
+        T, B, cz = idx.shape
+        k = q.shape[2] // cz
+        gl = g_loss.reshape(1).contiguous() if (g_loss is not None and p is not None) else None
+        gs = g_sz.contiguous() if g_sz is not None else None
+        gq = torch.empty_like(q)
+        gp = torch.empty_like(p) if (p is not None and ctx.needs_input_grad[1]) else None
+        with timed("train.latent_loss_bwd"):
+            check(lib.spk_svae_latent_loss_bwd(_p(q), _p(p), _p(idx), _p(gl), _p(gs), _p(gq), _p(gp), T, B, cz, k, ctx.tau_s,
+                                               _stream(q)), "spk_svae_latent_loss_bwd")
+        return gq, gp, None, None
