@@ -551,3 +551,92 @@ def sample_images(sd_vae, sd_den, n_samples, mask_id=128, temp=1.0, sample_steps
     """Full BASELINE path: sample tokens, decode (R/main.py:384-401) -> uint8 [B,C,H,W]."""
     tok = absorbing_sample(sd_den, n_samples, mask_id, temp, sample_steps, latent, T, noise)
     return to_uint8(decode_tokens(tok.reshape(n_samples, latent, latent), sd_vae, T)), tok
+
+
+# --------------------------------------------------------------------------- SNN_VAE latent model (DESIGN §4.6)
+# The spiking MLP of PriorBernoulliSTBP / PosteriorBernoulliSTBP (R/snn_model/vae_model.py:306-546): three layer.Linear, each
+# followed by the default LIFNode, driven by four autoregressive loops.  Every neuron keeps its state across the rows of a
+# pass, across the passes of a loop and across calls: the reference never resets inside a loop.  ``layers`` is
+# ((w1, b1), (w2, b2), (w3, b3)) with w3 [cz*k, h2]; ``vs`` is a list of the three layers' v [B, h] (fp32), replaced in place;
+# ``z0`` is initial_input ([cz] or [1,1,cz]); ``idx`` [T,B,cz] holds the draws in [0, k) without the reference's c*k offset.
+def svae_linear_lif(x_seq, w, b, v):
+    """layer.Linear + LIFNode on [n,B,in] -> (fp32 spikes [n,B,out], v).  The sum runs in fp64 and is cast to fp32 (on the
+    dyadic weights of synth.synth_svae_state it is exact, so the reference's fp32 addmm gives the same value in any order),
+    then lif_multi_step: tau 2, v_th 1, hard reset 0.  The train() forward of the LIFNode is the same fp32 update."""
+    cur = x_seq.double() @ w.double().t()
+    if b is not None:
+        cur = cur + b.double()
+    return lif_multi_step(cur.float(), v)
+
+
+def svae_mlp(rows, layers, vs):
+    """One pass of the three Linear + LIF layers over rows [n,B,in] (a multi-step call): the last layer's spikes [n,B,cz*k]."""
+    h = rows.float()
+    for i, (w, b) in enumerate(layers):
+        h, vs[i] = svae_linear_lif(h, w, b, vs[i])
+    return h
+
+
+def svae_pick(spikes, idx):
+    """spikes [n,B,cz*k] -> [n,B,cz]: channel c takes the spike at c*k + idx[..., c] (the reference's view(-1)[random_index])."""
+    n, B, cz = idx.shape
+    return torch.gather(spikes.reshape(n, B, cz, -1), 3, idx.long().unsqueeze(-1)).squeeze(-1)
+
+
+def svae_draw_indices(T, B, cz, k):
+    """The reference's T draws torch.randint(0, k, (B*cz,)) on the default CPU generator, in its order -> int32 [T,B,cz]."""
+    return torch.stack([torch.randint(0, k, (B * cz,)) for _ in range(T)]).view(T, B, cz).to(torch.int32)
+
+
+def _svae_z0(z0, B):
+    z0 = z0.float().reshape(-1)
+    return z0.view(1, 1, -1).expand(1, B, z0.numel())
+
+
+def svae_posterior_prefix(x, z0, layers, vs, idx):
+    """The posterior's T-1 no-grad passes (:491-516): pass t runs rows [x_s, z_s], s <= t, and z_{t+1} is the pick of the last
+    row at idx[t].  x [T,B,cx] spikes.  Returns z_t_minus = z_0 .. z_{T-1} [T,B,cz]."""
+    T, B = x.shape[0], x.shape[1]
+    zs = _svae_z0(z0, B)
+    for t in range(T - 1):
+        out = svae_mlp(torch.cat([x[:t + 1].float(), zs], -1), layers, vs)
+        zs = torch.cat([zs, svae_pick(out[-1:], idx[t:t + 1])], 0)
+    return zs
+
+
+def svae_posterior(x, z0, layers, vs, idx):
+    """PosteriorBernoulliSTBP.forward (:470-546): the prefix passes, then one pass over all T rows [x, z_t_minus] whose
+    spikes are q_z; sampled_z[t] is the pick of row t at idx[t].  Returns (sampled_z [T,B,cz], q_z [T,B,cz*k])."""
+    zs = svae_posterior_prefix(x, z0, layers, vs, idx)
+    q = svae_mlp(torch.cat([x.float(), zs], -1), layers, vs)
+    return svae_pick(q, idx), q
+
+
+def svae_prior_sample(z0, layers, vs, idx):
+    """PriorBernoulliSTBP.sample (:405-423): T passes over the growing prefix z_0 .. z_t, z_{t+1} the pick of the last row at
+    idx[t].  Returns z_1 .. z_T [T,B,cz]."""
+    T, B = idx.shape[0], idx.shape[1]
+    zs = _svae_z0(z0, B)
+    for t in range(T):
+        out = svae_mlp(zs, layers, vs)
+        zs = torch.cat([zs, svae_pick(out[-1:], idx[t:t + 1])], 0)
+    return zs[1:]
+
+
+def svae_prior_prefix(z0, layers, vs, sched, noise, z_teacher):
+    """The prior's scheduled-sampling prefix in training (:365-390).  For t = 0 .. T-2: a scheduled step (sched[t]) runs a
+    pass over z_0 .. z_t and sets z_{t+1} = (mean_k(last row) + 1e-3 * noise[n] > 0.5), fp32, n counting the scheduled steps;
+    any other step copies the teacher row z_teacher[t] and runs no layer.  Returns z_t_minus [T,B,cz]."""
+    T, B, cz = z_teacher.shape
+    zs = _svae_z0(z0, B)
+    n = 0
+    for t in range(T - 1):
+        if bool(sched[t]):
+            out = svae_mlp(zs, layers, vs)[-1]
+            prob = out.reshape(B, cz, -1).mean(-1) + 1e-3 * noise[n].float()
+            n += 1
+            zt = (prob > 0.5).float()
+        else:
+            zt = z_teacher[t].float()
+        zs = torch.cat([zs, zt.unsqueeze(0)], 0)
+    return zs

@@ -2246,7 +2246,8 @@ def svae_ar_prefix(x, z0, layers, vs, idx=None, sched=None, noise=None, z_teache
     """The no-grad prefix passes of one training Bernoulli loop in one launch (spk_svae_ar_prefix_fwd).
 
     Posterior: x u8/bool [T,B,cx] and idx [T,B,cz].  Prior: x None, sched bool/u8 [T-1], noise fp32 [n_sched,B,cz] (n_sched =
-    scheduled steps), z_teacher fp32 [T,B,cz].  vs: the three layers' v fp32 [B,h], updated in place.
+    scheduled steps; with none, [0,B,cz] and the result is [z0, z_teacher[:-1]]), z_teacher fp32 [T,B,cz].  vs: the three
+    layers' v fp32 [B,h], updated in place.
     Returns z_t_minus fp32 [T,B,cz]."""
     (w1, b1), (w2, b2), (w3, b3) = layers
     if x is not None:
@@ -2302,6 +2303,8 @@ def svae_ar_prefix(x, z0, layers, vs, idx=None, sched=None, noise=None, z_teache
         if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.shape == (B, hh)):
             raise ValueError(f"v must be a contiguous fp32 [{B}, {hh}] device tensor")
     zm = torch.empty((T, B, cz), dtype=torch.float32, device=dev)
+    if x is None and noise.numel() == 0:
+        noise = z_teacher     # no scheduled step: the kernel never reads noise, but the entry point wants a non-null pointer
     check(lib.spk_svae_ar_prefix_fwd(_p(x), _p(z0), _p(w1), _p(bs[0]), _p(w2), _p(bs[1]), _p(w3), _p(bs[2]), _p(v1), _p(v2),
                                      _p(v3), _p(idx), _p(sched), _p(noise), _p(z_teacher), _p(zm), T, B, cx, cz, h1, h2, k,
                                      _stream(zm)), "spk_svae_ar_prefix_fwd")
