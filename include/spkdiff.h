@@ -672,6 +672,19 @@ int spk_svae_latent_loss_bwd(const float* q_z, const float* p_z_or_null, const i
                              const float* g_sampled_z_or_null, float* grad_q_z, float* grad_p_z_or_null, int T, int B, int cz,
                              int k, float tau_s, spk_stream_t stream);
 
+/* ---- SNN_VQVAE_uni: codebook-usage statistic (csrc/vq_usage.hip) ---------------------------------------------------- */
+/* The statistic VectorQuantizer_uni.forward computes on every call, R/snn_model/vae_model.py:705-718 (unique, bincount, argmax,
+ * masked_select, mse_loss), in one launch.  idx int64 [N] (entries outside [0, K) are not counted) ->
+ *   hist_out int64 [K] = bincount(idx, minlength=K);
+ *   stats_out int64 [3] = {number of used codes, max_index (first maximum of hist), FID_loss};
+ * FID_loss is fp32, stored as its bit pattern in the low 32 bits of stats_out[2]: 0.001f * sum_{k != max_index}
+ * ((float)hist[k] - (float)N / K)^2 / (K - 1), fp32 arithmetic, fixed summation order (K = 1: NaN, as mse_loss of empty
+ * tensors).  Integer results are exact; the whole result is deterministic.  ws: at least 8 * (K + 1) bytes, zeroed by the call
+ * (one hipMemsetAsync ahead of the launch); capturable in a hipGraph.  SPK_ERR_UNSUPPORTED for K > 4096 (the LDS histogram) or
+ * N > 2^31 - 1. */
+int spk_vq_code_usage(const long long* idx, long long N, int K, long long* hist_out, long long* stats_out, void* ws,
+                      spk_stream_t stream);
+
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every
  * matrix-core number: devices of one pool differ by ~10 %).  nblocks workgroups of 256 threads issue 4*iters MFMAs per

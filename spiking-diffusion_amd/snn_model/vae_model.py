@@ -15,6 +15,9 @@ branch (MMD + reconstruction losses) runs with autograd on ``csrc/svae_train.hip
 backward, the no-grad prefix passes of each Bernoulli loop in one launch, the gather and MMD loss fused; the encoder and
 decoder take SNN_VQVAE's training path.
 
+``SNN_VQVAE_uni`` (R/snn_model/vae_model.py:674-801) is SNN_VQVAE with ``VectorQuantizer_uni``: the same kernels, plus the
+codebook-usage statistic the quantizer computes and prints on every call, one launch of ``csrc/vq_usage.hip``.
+
 Re-exported names match what ``from snn_model.vae_model import *`` gives R/main.py (``functional`` in particular,
 R/main.py:101-107,317).
 """
@@ -85,6 +88,11 @@ class VectorQuantizer(nn.Module):
         commitment losses, straight-through estimator, spike generator, PSP losses.  Native pieces: the membrane read-out
         (spk_memout_fwd), the code search (spk_vq_argmin), the spike generator's BatchNorm+LIF (spk_bn_lif_train_*) and
         the PSP filter (spk_psp); the remaining element-wise algebra and the embedding gradient are torch plumbing."""
+        quantized, loss, _ = self._train_forward_idx(x)
+        return quantized, loss
+
+    def _train_forward_idx(self, x):
+        """_train_forward, also returning the code indices int64 [B*h*w]."""
         if not torch.is_grad_enabled():
             _training_oos('VectorQuantizer.forward in train() mode without autograd')
         T = x.shape[0]
@@ -94,6 +102,7 @@ class VectorQuantizer(nn.Module):
             # (ops.VQTrainFunction; the module-by-module algebra below is the same arithmetic through autograd)
             quantized, loss_1 = ops.VQTrainFunction.apply(x, self.memout.coef, self.alpha, self.embeddings.weight,
                                                           self.commitment_cost)
+            encoding_indices = getattr(quantized.grad_fn, "indices", None)     # (the code search's result, kept on the autograd node)
         else:
             x_memout = (1 - self.alpha) * self.memout(x) + self.alpha * torch.sum(x, dim=0) / self.num_step
             x_memout = x_memout.permute(0, 2, 3, 1).contiguous()
@@ -116,7 +125,7 @@ class VectorQuantizer(nn.Module):
             q_latent_loss_2 = torch.mean((pq - px.detach()) ** 2)
             e_latent_loss_2 = torch.mean((pq.detach() - px) ** 2)
             loss_2 = q_latent_loss_2 + self.commitment_cost * e_latent_loss_2
-        return quantized, loss_1 + loss_2
+        return quantized, loss_1 + loss_2, encoding_indices
 
     def get_code_indices(self, flat_x):
         """argmin_k ||x - e_k||^2 for rows of flat_x [N, D] (R/snn_model/vae_model.py:87-95)."""
@@ -207,12 +216,7 @@ class SNN_VQVAE(nn.Module):
                 _training_oos('SNN_VQVAE.forward in train() mode without autograd')
             z = self.encoder(x)
             e, e_q_loss = self.vq_layer(z)
-            y = self.decoder(e)
-            if self.vq_layer.fused_train and y.is_cuda and y.shape[1:] == image.shape and image.dtype == torch.float32:
-                real_recon_loss = ops.ReconLossFunction.apply(y, self.memout.coef, image)      # read-out + tanh + mse: one launch
-            else:
-                x_recon = torch.tanh(self.memout(y))
-                real_recon_loss = F.mse_loss(x_recon, image)
+            real_recon_loss = self._train_recon_loss(self.decoder(e), image)
             return e_q_loss, real_recon_loss / self.data_variance, real_recon_loss
         T = x.shape[0]
         enc = self.encoder.snn_convs
@@ -230,6 +234,13 @@ class SNN_VQVAE(nn.Module):
         x_recon = self.decoder(e)
         x_recon = torch.tanh(self.memout(x_recon))
         return e, x_recon, enco
+
+    def _train_recon_loss(self, y, image):
+        """mse_loss(tanh(memout(decoder output y)), image) of the training branch (R/snn_model/vae_model.py:192-194)."""
+        if self.vq_layer.fused_train and y.is_cuda and y.shape[1:] == image.shape and image.dtype == torch.float32:
+            return ops.ReconLossFunction.apply(y, self.memout.coef, image)      # read-out + tanh + mse: one launch
+        x_recon = torch.tanh(self.memout(y))
+        return F.mse_loss(x_recon, image)
 
     # ---- convenience entry points of the MI355X build (not in the reference) -----------------------------------
     @torch.no_grad()
@@ -567,14 +578,98 @@ class SNN_VAE(nn.Module):
         return sampled_z, self.decode(sampled_z)
 
 
+# ---- SNN_VQVAE_uni: SNN_VQVAE with a codebook-usage statistic (R/snn_model/vae_model.py:674-801) ----------------------------
+# The modules, state_dict keys and the arithmetic of e, x_recon, the indices and the training losses are SNN_VQVAE's; the
+# quantizer also computes, on every call, the histogram of the codes, the number of codes used, the most used code and the
+# "FID_loss" (:705-718, one launch: spk_vq_code_usage) and prints them.  In train() mode the printed FID_loss is replaced by a
+# CPU int64 zero (:752), so the gradients are SNN_VQVAE's.  (The reference file defines SNN_VQVAE_uni's __init__ and forward a
+# second time at :806-879, after the class's forward; those definitions shadow the ones at :772-801, and with them
+# R/main.py:101 fails at construction.  This class is the :674-801 model that R/main.py's snn-vq-vae-uni branches call.)
+
+def _device_repr(t, device):
+    """repr of the host tensor t as torch prints the same values on ``device`` (the device suffix, torch's line rule)."""
+    s, suffix = repr(t)[:-1], f"device='{device}'"
+    last_line_len = len(s) - s.rfind('\n') + 1
+    if last_line_len + len(suffix) + 2 > torch._tensor_str.PRINT_OPTS.linewidth:
+        return s + ',\n       ' + suffix + ')'
+    return s + ', ' + suffix + ')'
+
+
+def print_code_usage(usage, n, device):
+    """The four lines R/snn_model/vae_model.py:714-718 prints, from ONE device-to-host copy of the statistic (the reference
+    synchronises at the same place: its prints read device tensors)."""
+    hist, used, m, fid = ops.unpack_code_usage(usage.packed.cpu())
+    K = hist.numel()
+    keep = torch.ne(torch.arange(K), m)
+    print(n)
+    print(_device_repr(torch.masked_select(hist, keep), device))
+    print(_device_repr(torch.masked_select(torch.ones(K) * n / K, keep), device))
+    print(torch.Size([used]), fid)
+
+
+class VectorQuantizer_uni(VectorQuantizer):
+    """VectorQuantizer plus the codebook-usage statistic (R/snn_model/vae_model.py:674-766).  ``print_usage`` (not in the
+    reference; default True) prints it as the reference does, one synchronising copy per call; False skips the prints and
+    the copy, so the call stays asynchronous and capturable.  ``usage`` holds the last statistic (ops.CodeUsage, device
+    tensors) either way."""
+
+    def __init__(self, embedding_dim, num_embeddings, commitment_cost):
+        super().__init__(embedding_dim, num_embeddings, commitment_cost)
+        self.print_usage = True
+        self.usage = None
+
+    def code_usage(self, encoding_indices):
+        """The statistic of :705-718 on encoding_indices (device) -> ops.CodeUsage; printed when print_usage is set."""
+        self.usage = ops.vq_code_usage(encoding_indices, self.num_embeddings)
+        if self.print_usage:
+            print_code_usage(self.usage, encoding_indices.numel(), encoding_indices.device)
+        return self.usage
+
+    def forward(self, x):
+        # x: (T,N,C,H,W) spikes of the encoder
+        if self.training:
+            quantized, loss, encoding_indices = self._train_forward_idx(x)
+            if encoding_indices is None:
+                raise NotImplementedError('spkdiff: VectorQuantizer_uni in train() mode needs the codebook or alpha to '
+                                          'require grad (the code indices come from the autograd node)')
+            self.code_usage(encoding_indices)
+            return quantized, loss, torch.tensor(0)          # the reference's FID_loss in train() mode (:752)
+        quantized, encoding_indices = super().forward(x)
+        self.code_usage(encoding_indices)
+        return quantized, encoding_indices
+
+
+class SNN_VQVAE_uni(SNN_VQVAE):
+    """VQ-VAE (R/snn_model/vae_model.py:768-801): SNN_VQVAE with VectorQuantizer_uni."""
+
+    def __init__(self, in_dim, embedding_dim, num_embeddings, data_variance, commitment_cost=0.25):
+        super().__init__(in_dim, embedding_dim, num_embeddings, data_variance, commitment_cost)
+        self.vq_layer = VectorQuantizer_uni(embedding_dim, num_embeddings, commitment_cost)
+
+    def forward(self, x, image):
+        # x: [t, B, C, H, W]
+        if self.training:
+            if not torch.is_grad_enabled():
+                _training_oos('SNN_VQVAE_uni.forward in train() mode without autograd')
+            z = self.encoder(x)
+            e, e_q_loss, FID_loss = self.vq_layer(z)
+            real_recon_loss = self._train_recon_loss(self.decoder(e), image)
+            return e_q_loss + FID_loss, real_recon_loss / self.data_variance, real_recon_loss
+        vq = self.vq_layer
+        vq.usage = None
+        e, x_recon, encoding_indices = super().forward(x, image)
+        if vq.usage is None:            # the fused end-to-end path runs the quantizer's pieces, not its forward
+            vq.code_usage(encoding_indices)
+        return e, x_recon, encoding_indices
+
+
 def _not_in_scope(name):
     class _Stub(nn.Module):
         def __init__(self, *a, **k):
             raise NotImplementedError(f'spkdiff: {name} is a baseline model outside the named hot path '
-                                      '(SURVEY.md §2.1 #3); only SNN_VQVAE and SNN_VAE are implemented')
+                                      '(SURVEY.md §2.1 #3); only SNN_VQVAE, SNN_VQVAE_uni and SNN_VAE are implemented')
     _Stub.__name__ = name
     return _Stub
 
 
 VQVAE = _not_in_scope('VQVAE')
-SNN_VQVAE_uni = _not_in_scope('SNN_VQVAE_uni')

@@ -150,6 +150,7 @@ _SIGS = {
     "spk_svae_latent_loss_ws_floats": (c_int, [c_int, c_int]),
     "spk_svae_latent_loss_fwd": (c_int, [P] * 6 + [c_int] * 4 + [c_float, P]),
     "spk_svae_latent_loss_bwd": (c_int, [P] * 7 + [c_int] * 4 + [c_float, P]),
+    "spk_vq_code_usage": (c_int, [P, c_longlong, c_int, P, P, P, P]),
 }
 
 EXPORTS = tuple(_SIGS)

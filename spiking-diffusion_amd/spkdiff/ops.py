@@ -5,7 +5,10 @@ All tensors must live on a ROCm device ("cuda"); CPU tensors are rejected -- the
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, lib
@@ -1622,6 +1625,64 @@ def vq_argmin(flat_x, codebook):
     check(lib.spk_vq_argmin(_p(flat_x), _p(codebook), _p(idx), N, D, codebook.shape[0], _stream(flat_x)),
           "spk_vq_argmin")
     return idx
+
+
+VQ_USAGE_MAX_K = 4096        # spk_vq_code_usage keeps the histogram in LDS: larger codebooks take the torch ops below
+
+
+class CodeUsage(NamedTuple):
+    """Codebook-usage statistic of VectorQuantizer_uni (R/snn_model/vae_model.py:705-718), device tensors.  hist, used,
+    max_index and fid_loss are views of ``packed`` (int64 [K + 3] = hist, used, max_index, fp32 bits of fid_loss), so one
+    device-to-host copy of ``packed`` carries all of it."""
+    hist: torch.Tensor           # int64 [K]   bincount(idx, minlength=K)
+    used: torch.Tensor           # int64 []    len(unique(idx))
+    max_index: torch.Tensor      # int64 []    argmax(hist), first maximum
+    fid_loss: torch.Tensor       # fp32 []     0.001 * mse_loss(hist without max_index, N / K)
+    packed: torch.Tensor
+
+
+def _code_usage_views(packed, K):
+    return CodeUsage(packed[:K], packed[K], packed[K + 1], packed[K + 2:K + 3].view(torch.float32)[0], packed)
+
+
+def unpack_code_usage(packed_host):
+    """Host copy of CodeUsage.packed -> (hist int64 [K], used, max_index, fid_loss as a Python float)."""
+    K = packed_host.numel() - 3
+    return (packed_host[:K], int(packed_host[K]), int(packed_host[K + 1]),
+            float(packed_host[K + 2:K + 3].view(torch.float32)[0]))
+
+
+def vq_code_usage_torch(idx, K):
+    """The statistic with the framework's operators, as the reference spells it (the fallback for K > VQ_USAGE_MAX_K)."""
+    N = idx.numel()
+    packed = torch.zeros(K + 3, dtype=torch.int64, device=idx.device)
+    hist = torch.bincount(idx.reshape(-1), minlength=K)
+    packed[:K] = hist
+    packed[K] = (hist > 0).sum()
+    m = torch.argmax(hist)
+    packed[K + 1] = m
+    mask = torch.ne(torch.arange(K, device=idx.device), m)
+    targets = (torch.ones(K) * N / K).to(idx.device)
+    fid = 0.001 * F.mse_loss(torch.masked_select(hist, mask), torch.masked_select(targets, mask))
+    packed[K + 2:K + 3].view(torch.float32)[0] = fid
+    return _code_usage_views(packed, K)
+
+
+def vq_code_usage(idx, K):
+    """idx int64 [N] (device) -> CodeUsage: the histogram, the number of used codes, the first maximum and FID_loss of
+    R/snn_model/vae_model.py:705-718, one launch (spk_vq_code_usage) and no host synchronisation.  Integer results are
+    exact, the whole result deterministic.  K > VQ_USAGE_MAX_K takes vq_code_usage_torch."""
+    idx = _dev(idx.reshape(-1), "idx", torch.int64)
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"vq_code_usage: K must be positive, got {K}")
+    packed = torch.empty(K + 3, dtype=torch.int64, device=idx.device)
+    ws = torch.empty(K + 1, dtype=torch.int64, device=idx.device)
+    rc = lib.spk_vq_code_usage(_p(idx), idx.numel(), K, _p(packed), _p(packed[K:]), _p(ws), _stream(idx))
+    if rc == -2 and K > VQ_USAGE_MAX_K:
+        return vq_code_usage_torch(idx, K)
+    check(rc, "spk_vq_code_usage")
+    return _code_usage_views(packed, K)
 
 
 _VQ_TRAIN_WS = {}
