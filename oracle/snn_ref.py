@@ -492,6 +492,98 @@ def snn_vqvae_train_forward(x_seq, image, sd, data_variance, commitment_cost=0.2
     return (e_q_loss, real_recon_loss / data_variance, real_recon_loss), idx
 
 
+# --------------------------------------------------------------------------- VQ kernels (csrc/vq.hip, csrc/vq_train.hip)
+# Host restatements the VQ kernels are held to at every shape: the code search in fp64 in the kernels' order (every index
+# bit for bit, ties and NaN included), the read-outs in fp32 in the reference's order, the training algebra and the two
+# loss kernels in fp64.
+def vq_distances_f64(flat_x, codebook):
+    """||x||^2 + ||e_k||^2 - 2 x.e_k of R/snn_model/vae_model.py:87-93 in fp64: every product of two fp32 values is exact in
+    fp64, the three sums run over d ascending, then (x2 + e2) - 2 dot.  [N, D], [K, D] -> [N, K] float64."""
+    x, e = flat_x.double(), codebook.double()
+    N, D = x.shape
+    x2 = torch.zeros(N, dtype=torch.float64)
+    e2 = torch.zeros(e.shape[0], dtype=torch.float64)
+    dot = torch.zeros(N, e.shape[0], dtype=torch.float64)
+    for d in range(D):
+        x2 = x2 + x[:, d] * x[:, d]
+        e2 = e2 + e[:, d] * e[:, d]
+        dot.addcmul_(x[:, d:d + 1], e[None, :, d])      # (an exact product: fused or not, the same sum)
+    return x2[:, None] + e2[None, :] - 2.0 * dot
+
+
+def vq_argmin_f64(flat_x, codebook, chunk=8192):
+    """torch.argmin over vq_distances_f64, ``chunk`` rows at a time: the first NaN, else the first minimum; always in [0, K)."""
+    out = [torch.argmin(vq_distances_f64(flat_x[i:i + chunk], codebook), dim=1) for i in range(0, flat_x.shape[0], chunk)]
+    return torch.cat(out) if out else torch.zeros(0, dtype=torch.int64)
+
+
+def vq_readout_f32(z_ptc, coef, alpha):
+    """x_memout of R/snn_model/vae_model.py:42 in fp32 with an explicit t-ascending loop: (1 - alpha) * m + (alpha * s) / T,
+    m = sum_t z[t] * coef[t], s = sum_t z[t].  z_ptc u8/fp32 [B, h, w, T, D] -> [B*h*w, D] float32."""
+    B, h, w, T, D = z_ptc.shape
+    z = z_ptc.float()
+    coef, alpha = coef.float().flatten(), alpha.float().reshape(())
+    m = torch.zeros(B, h, w, D)
+    s = torch.zeros(B, h, w, D)
+    for t in range(T):
+        m = m + z[:, :, :, t] * coef[t]
+        s = s + z[:, :, :, t]
+    return ((1 - alpha) * m + (alpha * s) / T).reshape(-1, D)
+
+
+def vq_train_f64(x_seq, coef, alpha, codebook, beta, g_out, g_loss):
+    """The training branch of VectorQuantizer.forward up to the spike generator (R/snn_model/vae_model.py:61-78) and its
+    backward for the upstream gradients (g_out [B, D, h, w] of the straight-through value, g_loss of loss_1).  The read-out
+    sums m and s are fp32 in the reference's order (what the code search sees); everything after them is fp64.
+    x_seq [T, B, D, h, w] -> dict idx, q (the straight-through value [B, D, h, w]), loss, g_x, g_alpha, g_E (float64)."""
+    T, B, D, h, w = x_seq.shape
+    cf = coef.float().flatten()
+    m = torch.zeros(B, D, h, w)
+    s = torch.zeros(B, D, h, w)
+    for t in range(T):
+        m = m + x_seq[t].float() * cf[t]
+        s = s + x_seq[t].float()
+    a32 = alpha.float().reshape(())
+    xm32 = ((1 - a32) * m + (a32 * s) / T).permute(0, 2, 3, 1).reshape(-1, D)
+    idx = vq_argmin_f64(xm32, codebook)
+    N = xm32.shape[0]
+    xm, E, a = xm32.double(), codebook.double(), alpha.double().reshape(())
+    q = E[idx]
+    diff = q - xm
+    mse = (diff * diff).sum() / (N * D)
+    loss = mse + beta * mse
+    gl = float(g_loss)
+    g = g_out.double().permute(0, 2, 3, 1).reshape(-1, D) + gl * beta * 2.0 / (N * D) * (xm - q)       # d/d x_m
+    g_nchw = g.reshape(B, h, w, D).permute(0, 3, 1, 2)
+    cf64 = cf.double()
+    g_x = torch.stack([g_nchw * ((1 - a) * cf64[t]) + g_nchw * a / T for t in range(T)])
+    dxa = (s.double() / T - m.double()).permute(0, 2, 3, 1).reshape(-1, D)
+    g_alpha = (g * dxa).sum()
+    g_E = torch.zeros_like(E).index_add_(0, idx, gl * 2.0 / (N * D) * (q - xm))
+    return {"idx": idx, "q": (xm + (q - xm)).reshape(B, h, w, D).permute(0, 3, 1, 2), "loss": loss, "g_x": g_x,
+            "g_alpha": g_alpha, "g_E": g_E, "xm": xm32}
+
+
+def psp_loss_f64(q_seq, x_seq, beta, tau_s, g_loss):
+    """loss_2 of R/snn_model/vae_model.py:79-84 and its gradients in fp64: mean((psp(q) - sg(psp(x)))^2) +
+    beta * mean((sg(psp(q)) - psp(x))^2) -> (loss, g_q, g_x) for the upstream gradient g_loss."""
+    q = q_seq.double().requires_grad_(True)
+    x = x_seq.double().requires_grad_(True)
+    pq, px = psp_filter(q, tau_s), psp_filter(x, tau_s)
+    loss = torch.mean((pq - px.detach()) ** 2) + beta * torch.mean((pq.detach() - px) ** 2)
+    g_q, g_x = torch.autograd.grad(loss, (q, x), torch.tensor(float(g_loss), dtype=torch.float64))
+    return loss.detach(), g_q, g_x
+
+
+def recon_loss_f64(y_seq, coef, image, g_loss):
+    """mse_loss(tanh(memout(y)), image) of R/snn_model/vae_model.py:189-196 in fp64 -> (loss, g_y)."""
+    y = y_seq.double().requires_grad_(True)
+    T = y.shape[0]
+    loss = F.mse_loss(torch.tanh(torch.sum(y * coef.double().reshape((T,) + (1,) * (y.dim() - 1)), dim=0)), image.double())
+    (g_y,) = torch.autograd.grad(loss, (y,), torch.tensor(float(g_loss), dtype=torch.float64))
+    return loss.detach(), g_y
+
+
 # --------------------------------------------------------------------------- a9
 def categorical_sample(logits, q=None):
     """``dists.Categorical(logits=l).sample()`` as torch evaluates it on CPU:

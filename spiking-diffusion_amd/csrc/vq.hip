@@ -5,13 +5,27 @@
 //
 // Read-out arithmetic follows the reference in fp32:  x = (1-alpha)*sum_t z[t]*coef[t] + (alpha*sum_t z[t])/T.
 // The distance  |x|^2 + |e_k|^2 - 2 x.e_k  is evaluated in fp64 (exact products, order-independent), and the
-// argmin takes the FIRST minimal index like torch.argmin.  Code indices are int64 like the reference's.
+// argmin is torch.argmin's over those distances: a NaN is below every number (the first NaN wins), ties go to the
+// lowest index, and the index is always in [0, K) -- also for rows of NaN or inf.  Code indices are int64 like the
+// reference's.
 #include "spk_common.h"
 #include "../../include/spkdiff.h"
 
 namespace {
 
 constexpr int VQ_MAX_D = 64;
+constexpr int VQ_NONE = 0x7fffffff;                                // "no candidate yet": loses to every real code
+
+// The argmin in three parts.  A lane sees its codes in ascending order and starts from (+inf, VQ_NONE): it keeps a candidate
+// while its best is not NaN and the candidate is NaN or strictly smaller (vq_lane_takes), so it holds its first NaN, else its
+// first minimum, else -- every distance +inf -- nothing.  The lanes are combined in torch.argmin's order (vq_better: NaN first,
+// then ascending distance, then ascending index), and a row left with VQ_NONE had only +inf distances: code 0 (vq_index).
+__device__ __forceinline__ bool vq_lane_takes(double d, double b) { return b == b && !(d >= b); }
+__device__ __forceinline__ bool vq_better(double d, int k, double b, int i) {
+  if (b != b) return d != d && k < i;
+  return d != d || d < b || (d == b && k < i);
+}
+__device__ __forceinline__ int vq_index(int besti) { return besti == VQ_NONE ? 0 : besti; }
 
 // block = 256 threads = 4 waves; one wave per latent position; the codebook and its squared norms are staged in LDS once
 // per block; a position's read-out vector lives in registers (16 lane broadcasts), so the position loop has no barrier.
@@ -64,8 +78,8 @@ __global__ __launch_bounds__(256) void vq_kernel(const uint8_t* __restrict__ z, 
       xl = one_m_alpha * m + (alpha * cnt) / (float)T;
       if (xm_out) xm_out[p * D + lane] = xl;
     }
-    double best = 1.0e300;
-    int besti = 0x7fffffff;
+    double best = __builtin_inf();
+    int besti = VQ_NONE;
     double x2 = 0.0;
     if constexpr (DC > 0) {
       double xr[DC];
@@ -78,7 +92,7 @@ __global__ __launch_bounds__(256) void vq_kernel(const uint8_t* __restrict__ z, 
 #pragma unroll
         for (int d = 0; d < DC; ++d) dot += xr[d] * (double)s_cb[kc * (DC + 1) + d];
         const double dist = x2 + s_e2[kc] - 2.0 * dot;
-        if (k < K && dist < best) { best = dist; besti = k; }      // k increasing per lane: first minimum kept
+        if (k < K && vq_lane_takes(dist, best)) { best = dist; besti = k; }
       }
     } else {
       for (int d = 0; d < D; ++d) { const double xv = (double)__shfl(xl, d); x2 += xv * xv; }
@@ -88,15 +102,16 @@ __global__ __launch_bounds__(256) void vq_kernel(const uint8_t* __restrict__ z, 
         double dot = 0.0;
         for (int d = 0; d < D; ++d) dot += (double)__shfl(xl, d) * (double)s_cb[kc * (D + 1) + d];
         const double dist = x2 + s_e2[kc] - 2.0 * dot;
-        if (k < K && dist < best) { best = dist; besti = k; }      // k increasing per lane: first minimum kept
+        if (k < K && vq_lane_takes(dist, best)) { best = dist; besti = k; }
       }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
       double ob = __shfl_xor(best, off);
       int oi = __shfl_xor(besti, off);
-      if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+      if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
     }
+    besti = vq_index(besti);
     if (lane == 0) idx_out[p] = (long long)besti;
     if (zq_out && lane < D) {
       const int b = (int)(p / HW), hw = (int)(p % HW);
@@ -153,8 +168,8 @@ __global__ __launch_bounds__(256) void vq16_kernel(const uint8_t* __restrict__ z
 #pragma unroll
       // (products of two fp32 values are exact in fp64: fma(a, b, s) == s + a * b bit for bit, in half the instructions)
       for (int d = 0; d < D; ++d) { xr[d] = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(xl), 16 * j + d)); x2 = fma(xr[d], xr[d], x2); }
-      double best = 1.0e300;
-      int besti = 0x7fffffff;
+      double best = __builtin_inf();
+      int besti = VQ_NONE;
       for (int k0 = 0; k0 < K; k0 += 64) {
         const int k = k0 + lane;
         const int kc = k < K ? k : K - 1;
@@ -162,14 +177,15 @@ __global__ __launch_bounds__(256) void vq16_kernel(const uint8_t* __restrict__ z
 #pragma unroll
         for (int d = 0; d < D; ++d) dot = fma(xr[d], s_cbd[kc * (D + 1) + d], dot);
         const double dist = x2 + s_e2[kc] - 2.0 * dot;
-        if (k < K && dist < best) { best = dist; besti = k; }      // k increasing per lane: first minimum kept
+        if (k < K && vq_lane_takes(dist, best)) { best = dist; besti = k; }
       }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) {
         const double ob = __shfl_xor(best, off);
         const int oi = __shfl_xor(besti, off);
-        if (ob < best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+        if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
       }
+      besti = vq_index(besti);
       if (lane == 0) idx_out[p] = (long long)besti;
       if (zq_out && lane < D) {
         const int b = (int)(p / HW), hw = (int)(p % HW);

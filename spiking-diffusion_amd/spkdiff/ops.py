@@ -1685,14 +1685,11 @@ def vq_code_usage(idx, K):
     return _code_usage_views(packed, K)
 
 
-_VQ_TRAIN_WS = {}
-
-
 def _vq_train_ws(device):
-    ws = _VQ_TRAIN_WS.get(device)
-    if ws is None:
-        ws = _VQ_TRAIN_WS[device] = torch.zeros(int(lib.spk_vq_train_ws_bytes()), dtype=torch.uint8, device=device)
-    return ws
+    """Block partials and the last-block ticket of spk_vq_train_quant / _bwd, spk_psp_loss_fwd and spk_recon_loss_fwd.  The
+    ticket protocol needs the buffer to itself while a launch is in flight, so it is one buffer per (device, stream) -- or per
+    ops.flag_scope store under capture -- with _flag_ws's rule against a first use during capture."""
+    return _flag_ws("vq_train", device, (int(lib.spk_vq_train_ws_bytes()) + 3) // 4)
 
 
 class VQTrainFunction(torch.autograd.Function):
@@ -1716,9 +1713,13 @@ class VQTrainFunction(torch.autograd.Function):
         idx = vq_argmin(xm, E)
         out = torch.empty((B, D, h, w), dtype=torch.float32, device=x.device)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
-        check(lib.spk_vq_train_quant(_p(xm), _p(idx), _p(E), _p(out), _p(loss), float(beta), _p(_vq_train_ws(x.device)), N, D, HW,
-                                     _stream(x)), "spk_vq_train_quant")
+        ws = _vq_train_ws(x.device)
+        check(lib.spk_vq_train_quant(_p(xm), _p(idx), _p(E), _p(out), _p(loss), float(beta), _p(ws), N, D, HW, _stream(x)),
+              "spk_vq_train_quant")
         ctx.save_for_backward(xm, idx, E, dxa, cf, al)
+        # (the backward runs on this stream, but in autograd's own thread, which sees neither this thread's flag_scope nor,
+        #  under capture, a workspace of its own: it takes the forward's)
+        ctx.ws = ws
         ctx.cfg = (T, B, D, h, w, float(beta), tuple(alpha.shape))
         ctx.mark_non_differentiable(idx)
         ctx.indices = idx
@@ -1736,7 +1737,7 @@ class VQTrainFunction(torch.autograd.Function):
         gE = torch.empty_like(E)
         with timed("train.vq_bwd"):
             check(lib.spk_vq_train_bwd(_p(go), _p(gl), _p(xm), _p(idx), _p(E), _p(dxa), _p(cf), _p(al), beta, _p(gx), _p(ga), _p(gE),
-                                       _p(_vq_train_ws(xm.device)), T, N, D, h * w, K, _stream(xm)), "spk_vq_train_bwd")
+                                       _p(ctx.ws), T, N, D, h * w, K, _stream(xm)), "spk_vq_train_bwd")
         return gx, None, ga.reshape(ashape), gE, None
 
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 
 from .fused import invalidate_derived
+from .ops import flag_scope
 
 
 class GraphedTrainStep:
@@ -89,16 +90,19 @@ class GraphedVQVAETrainStep:
             functional.reset_net(model)
             return loss_eq, loss_rec, real
 
+        # the loss kernels' workspaces (ops._vq_train_ws) come from a store of this graph's own: the capture stream is not the
+        # warm-up stream, and a workspace first created inside a capture outside a scope is refused
+        self.ws_store = {}
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+        with torch.cuda.stream(side), flag_scope(self.ws_store):
             for _ in range(max(1, warmup)):
                 optimizer.zero_grad(set_to_none=True)
                 step()
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)
-        with torch.cuda.graph(self.graph):
+        with torch.cuda.graph(self.graph), flag_scope(self.ws_store):
             self.losses = step()
 
     def __call__(self, images: torch.Tensor):
