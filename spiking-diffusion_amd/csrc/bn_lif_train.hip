@@ -124,13 +124,7 @@ __global__ __launch_bounds__(TPB) void bn_lif_apply_kernel(const float* __restri
     for (int t = 0; t < SPK_MAX_T; ++t) yv[t] = t < g.T ? y[n + t * ts] : 0.0f;
 #pragma unroll
     for (int t = 0; t < SPK_MAX_T; ++t) {
-      if (t < g.T) {
-        const float z = fmaf(yv[t], a, b);
-        const float h = v + (z - (v - v_reset)) / tau;
-        const float s = (h - v_th >= 0.0f) ? 1.0f : 0.0f;
-        v = (1.0f - s) * h + s * v_reset;
-        spikes[n + t * ts] = s;
-      }
+      if (t < g.T) spikes[n + t * ts] = spk_lif_train_step(v, fmaf(yv[t], a, b), tau, v_th, v_reset).s;
     }
     if (v_out) v_out[n] = v;
   }
@@ -165,27 +159,13 @@ __global__ __launch_bounds__(TPB) void bn_lif_bwd1_kernel(const float* __restric
       }
 #pragma unroll
       for (int t = 0; t < SPK_MAX_T; ++t) {
-        if (t < g.T) {
-          const float z = fmaf(yv[t], a, b);
-          const float h = v + (z - (v - v_reset)) / tau;
-          const float s = (h - v_th >= 0.0f) ? 1.0f : 0.0f;
-          v = (1.0f - s) * h + s * v_reset;
-          hv[t] = h;
-        }
+        if (t < g.T) hv[t] = spk_lif_train_step(v, fmaf(yv[t], a, b), tau, v_th, v_reset).h;
       }
       float G = grad_v_last ? grad_v_last[n] : 0.0f;
 #pragma unroll
       for (int t = SPK_MAX_T - 1; t >= 0; --t) {
         if (t < g.T) {
-          const float over = hv[t] - v_th;
-          const float s = over >= 0.0f ? 1.0f : 0.0f;
-          const float ax = 1.57079632679489661923f * alpha * over;
-          const float g_s = alpha / 2.0f / (1.0f + ax * ax);
-          float dv_dh = 1.0f - s;
-          if (!DETACH) dv_dh = (v_reset - hv[t]) * g_s + dv_dh;
-          const float gh = G * dv_dh + gsv[t] * g_s;
-          const float gz = gh * inv_tau;
-          G = gh * carry;
+          const float gz = spk_atan_bptt_step<DETACH>(G, gsv[t], hv[t], v_th, v_reset, alpha, inv_tau, carry);
           grad_y[n + t * ts] = gz;
           s1 += (double)gz;
           s2 += (double)gz * (double)((yv[t] - mean) * invstd);
@@ -327,11 +307,9 @@ __global__ __launch_bounds__(TPB) void bn_lif_apply_v_kernel(const float* __rest
         vf o;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-          const float z = fmaf(in[t][i], a[i], b[i]);
-          const float h = v[i] + (z - (v[i] - v_reset)) / tau;
-          const float sp = (h - v_th >= 0.0f) ? 1.0f : 0.0f;
-          v[i] = (1.0f - sp) * h + sp * v_reset;
-          o[i] = sp;
+          float vi = v[i];                          // (an element of a vector type does not bind to a reference)
+          o[i] = spk_lif_train_step(vi, fmaf(in[t][i], a[i], b[i]), tau, v_th, v_reset).s;
+          v[i] = vi;
         }
         sv[n + t * ts] = o;
         if constexpr (VEC == 4) {
@@ -339,8 +317,7 @@ __global__ __launch_bounds__(TPB) void bn_lif_apply_v_kernel(const float* __rest
           // MFMA forward reads (spk_spikes_nhwc_to_fp4 made them from the fp32 tensor: a launch per layer and iteration)
           if (c4) {
             const int bb = r / HW, hw = r - bb * HW, c = q * 4;
-            const unsigned w = (o[0] != 0.f ? 0x2u : 0u) | (o[1] != 0.f ? 0x20u : 0u) | (o[2] != 0.f ? 0x200u : 0u) |
-                               (o[3] != 0.f ? 0x2000u : 0u);
+            const unsigned w = spk_e2m1_nibbles4(o[0], o[1], o[2], o[3]);
             *reinterpret_cast<uint16_t*>(c4 + ((((long long)bb * (g.C >> 6) + (c >> 6)) * HW + hw) * g.T + t) * 32 +
                                          ((c & 63) >> 1)) = (uint16_t)w;
           }
@@ -394,11 +371,9 @@ __global__ __launch_bounds__(TPB) void bn_lif_bwd1_v_kernel(const float* __restr
       if (t < g.T) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-          const float z = fmaf(yy[t][i], a[i], b[i]);
-          const float h = v[i] + (z - (v[i] - v_reset)) / tau;
-          const float sp = (h - v_th >= 0.0f) ? 1.0f : 0.0f;
-          v[i] = (1.0f - sp) * h + sp * v_reset;
-          hh[t][i] = h;
+          float vi = v[i];
+          hh[t][i] = spk_lif_train_step(vi, fmaf(yy[t][i], a[i], b[i]), tau, v_th, v_reset).h;
+          v[i] = vi;
         }
       }
     }
@@ -414,15 +389,9 @@ __global__ __launch_bounds__(TPB) void bn_lif_bwd1_v_kernel(const float* __restr
         vf o;
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
-          const float over = hh[t][i] - v_th;
-          const float sp = over >= 0.0f ? 1.0f : 0.0f;
-          const float ax = 1.57079632679489661923f * alpha * over;
-          const float g_s = alpha / 2.0f / (1.0f + ax * ax);
-          float dv_dh = 1.0f - sp;
-          if (!DETACH) dv_dh = (v_reset - hh[t][i]) * g_s + dv_dh;
-          const float gh = G[i] * dv_dh + gs[t][i] * g_s;
-          const float gz = gh * inv_tau;
-          G[i] = gh * carry;
+          float Gi = G[i];
+          const float gz = spk_atan_bptt_step<DETACH>(Gi, gs[t][i], hh[t][i], v_th, v_reset, alpha, inv_tau, carry);
+          G[i] = Gi;
           o[i] = gz;
           s1[i] += (double)gz;
           s2[i] += (double)gz * (double)((yy[t][i] - mean[i]) * invstd[i]);

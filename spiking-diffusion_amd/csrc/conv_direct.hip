@@ -237,15 +237,7 @@ __global__ __launch_bounds__(256) void conv_fused_kernel(FusedArgs a) {
         const unsigned bitsv = spk_transpose16_rows(mybits, (int)(threadIdx.x & 63));
         const int tl = (int)(threadIdx.x & 15), co16 = co & ~15;
         if (tl < T) {
-          auto spread8 = [](unsigned x) -> unsigned {        // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-            x = (x | (x << 12)) & 0x000f000fu;
-            x = (x | (x << 6)) & 0x03030303u;
-            x = (x | (x << 3)) & 0x11111111u;
-            return x << 1;
-          };
-          uint2 o;
-          o.x = spread8(bitsv & 0xffu);
-          o.y = spread8((bitsv >> 8) & 0xffu);
+          const uint2 o = spk_e2m1_record(bitsv);
           uint8_t* dst = a.out_ptc + ((((long long)b * (a.Cout / a.out_c4) + (co16 / a.out_c4)) * plane + oy * a.Wo + ox) * T + tl) *
                                          (a.out_c4 >> 1) + ((co16 % a.out_c4) >> 1);
           *reinterpret_cast<uint2*>(dst) = o;
@@ -302,15 +294,7 @@ __device__ __forceinline__ void tinv_store(const TinvArgs& a, unsigned mybits, i
   const int tl = lane & 15, co16 = co & ~15;
   if (!ok) return;
   if (a.out_c4) {
-    auto spread8 = [](unsigned x) -> unsigned {        // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-      x = (x | (x << 12)) & 0x000f000fu;
-      x = (x | (x << 6)) & 0x03030303u;
-      x = (x | (x << 3)) & 0x11111111u;
-      return x << 1;
-    };
-    uint2 o;
-    o.x = spread8(bitsv & 0xffu);
-    o.y = spread8((bitsv >> 8) & 0xffu);
+    const uint2 o = spk_e2m1_record(bitsv);
     uint8_t* dst = a.out + ((((long long)b * (a.Cout / a.out_c4) + (co16 / a.out_c4)) * plane + op) * 16 + tl) * (a.out_c4 >> 1) +
                    ((co16 % a.out_c4) >> 1);
     *reinterpret_cast<uint2*>(dst) = o;
@@ -534,12 +518,6 @@ __global__ __launch_bounds__(256) void spikegen_table_kernel(const float* __rest
 template <int COUT>
 __global__ __launch_bounds__(256) void spikegen_expand_kernel(const long long* __restrict__ tok, const unsigned short* __restrict__ table,
                                                               uint8_t* __restrict__ out, long long npos, int K) {
-  auto spread8 = [](unsigned x) -> unsigned {          // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-    x = (x | (x << 12)) & 0x000f000fu;
-    x = (x | (x << 6)) & 0x03030303u;
-    x = (x | (x << 3)) & 0x11111111u;
-    return x << 1;
-  };
   const long long total = npos * 16;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long p = i >> 4;
@@ -559,10 +537,10 @@ __global__ __launch_bounds__(256) void spikegen_expand_kernel(const long long* _
       }
     }
     uint4 o;
-    o.x = spread8(mask & 0xffu);
-    o.y = spread8((mask >> 8) & 0xffu);
-    o.z = COUT > 16 ? spread8((mask >> 16) & 0xffu) : 0u;
-    o.w = COUT > 16 ? spread8((mask >> 24) & 0xffu) : 0u;
+    o.x = spk_spread8(mask & 0xffu);
+    o.y = spk_spread8((mask >> 8) & 0xffu);
+    o.z = COUT > 16 ? spk_spread8((mask >> 16) & 0xffu) : 0u;
+    o.w = COUT > 16 ? spk_spread8((mask >> 24) & 0xffu) : 0u;
     *reinterpret_cast<uint4*>(out + i * 16) = o;                                          // [position][t][16 B]
   }
 }

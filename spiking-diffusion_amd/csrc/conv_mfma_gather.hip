@@ -23,40 +23,6 @@ typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 constexpr int T16 = 16;
 
-// (the 16x16 bit transpose of den_common.h; this file keeps to spk_common.h, so it carries the same few lines)
-__device__ __forceinline__ unsigned transpose16_rows_g(unsigned x, int lane) {
-  unsigned y;
-  // (opaque copy of the lane id: the three per-lane constants of a round are recomputed here -- three vector instructions --
-  //  instead of being hoisted out of the caller's loops, where eight of them stayed live across the K loop: 256 registers + spills)
-  int ln = lane;
-  asm volatile("" : "+v"(ln));
-#define SPK_TR16_ROUND_G(S, LOW)                                                                     \
-  do {                                                                                               \
-    const unsigned sh = (unsigned)ln & (unsigned)(S);            /* 0 or S */                         \
-    const unsigned keep = (unsigned)(LOW) << sh;                                                     \
-    const unsigned amt = (32u - (unsigned)(S)) + 2u * sh;        /* 32 - S, or 32 + S = S (mod 32) */ \
-    const unsigned yr = __builtin_amdgcn_alignbit(y, y, amt);                                        \
-    x = (x & keep) | (yr & ~keep);                                                                   \
-  } while (0)
-  y = __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(x, 0x140, 0xF, 0xF, true), 0x141, 0xF, 0xF, true);
-  SPK_TR16_ROUND_G(8, 0x00FFu);
-  y = __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(x, 0x141, 0xF, 0xF, true), 0x1B, 0xF, 0xF, true);
-  SPK_TR16_ROUND_G(4, 0x0F0Fu);
-  y = __builtin_amdgcn_mov_dpp(x, 0x4E, 0xF, 0xF, true);
-  SPK_TR16_ROUND_G(2, 0x3333u);
-  y = __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true);
-  SPK_TR16_ROUND_G(1, 0x5555u);
-#undef SPK_TR16_ROUND_G
-  return x;
-}
-
-__device__ __forceinline__ unsigned spread8_g(unsigned x) {        // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-  x = (x | (x << 12)) & 0x000f000fu;
-  x = (x | (x << 6)) & 0x03030303u;
-  x = (x | (x << 3)) & 0x11111111u;
-  return x << 1;
-}
-
 struct GArgs {
   uint8_t* out_s32;       // MODE_LIF, optional: nibble-packed "S32" spikes [B][Cout/32][Ho*Wo][16][16 B] (den_mfma_fp6v2.hip)
   const uint8_t* in;      // PTC [B][H*W][16][Cin]
@@ -211,13 +177,10 @@ __global__ __launch_bounds__(256) void conv_mfma_gather_kernel(GArgs a) {
       for (int r = 0; r < 16; ++r) m = m + ((mybits >> r) & 1u ? a.coef[r] : 0.f);
       a.out_f32[((long long)b * HWo + opos) * a.Cout + co] = m;
     }
-    const unsigned bitsv = transpose16_rows_g(mybits, lane);      // lane t of each 16-lane row: 16 channel bits of step t
+    const unsigned bitsv = spk_transpose16_rows(mybits, lane);      // lane t of each 16-lane row: 16 channel bits of step t
     if (pos_ok && a.out_s32) {                                     // this task's 16 channels = half of a 32-channel record
-      uint2 o2;
-      o2.x = spread8_g(bitsv & 0xffu);
-      o2.y = spread8_g((bitsv >> 8) & 0xffu);
       *reinterpret_cast<uint2*>(a.out_s32 + ((((long long)b * (a.Cout >> 5) + (g >> 1)) * HWo + opos) * T16 + (lane & 15)) * 16 +
-                                8 * (g & 1)) = o2;
+                                8 * (g & 1)) = spk_e2m1_record(bitsv);
     }
     if (pos_ok && a.out_ptc) {
       uint4 o;
@@ -384,13 +347,10 @@ __device__ __forceinline__ void gather2_body(const GArgs& a, int b, int g, int p
       for (int r = 0; r < 16; ++r) m = m + ((mybits >> r) & 1u ? a.coef[r] : 0.f);
       a.out_f32[((long long)b * HWo + opos) * a.Cout + co] = m;
     }
-    const unsigned bitsv = transpose16_rows_g(mybits, lane);
+    const unsigned bitsv = spk_transpose16_rows(mybits, lane);
     if (pos_ok && a.out_s32) {                                     // this task's 16 channels = half of a 32-channel record
-      uint2 o2;
-      o2.x = spread8_g(bitsv & 0xffu);
-      o2.y = spread8_g((bitsv >> 8) & 0xffu);
       *reinterpret_cast<uint2*>(a.out_s32 + ((((long long)b * (a.Cout >> 5) + (g >> 1)) * HWo + opos) * T16 + (lane & 15)) * 16 +
-                                8 * (g & 1)) = o2;
+                                8 * (g & 1)) = spk_e2m1_record(bitsv);
     }
     if (pos_ok && a.out_ptc) {
       uint4 o;
@@ -727,28 +687,13 @@ __global__ __launch_bounds__(256) void pack_i8_generic_kernel(const float* __res
   float m = 0.f;
   if (real)
     for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(wat(i / KK, i % KK)));
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  m = smax[0];
-  int e = 0;
-  if (m > 0.f) frexpf(m, &e);
-  const int sh = 30 - e;
+  const int sh = 30 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^30
   if (threadIdx.x == 0) { scale[co] = ldexp(1.0, -sh); bias_d[co] = (real && bias) ? (double)bias[co] : 0.0; }
   const int npad = nchunks * 32 * KK;
   for (int i = threadIdx.x; i < npad; i += 256) {
     const int ci = i / KK, tap = i % KK;
-    long long q = (real && ci < Cin) ? (long long)rint(ldexp((double)wat(ci, tap), sh)) : 0;
     int dg[4];
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-      int r = (int)(((q + 128) & 255) - 128);
-      dg[d] = r;
-      q = (q - r) >> 8;
-    }
+    spk_balanced_digits<8>((real && ci < Cin) ? (long long)rint(ldexp((double)wat(ci, tap), sh)) : 0, dg);
     const int c = ci >> 5, kk = ci & 31;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {

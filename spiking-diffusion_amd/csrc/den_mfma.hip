@@ -536,28 +536,13 @@ __global__ __launch_bounds__(256) void pack_i8_kernel(const float* __restrict__ 
   const float* wc = w + (long long)co * n;
   float m = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(wc[i]));
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  m = smax[0];
-  int e = 0;
-  if (m > 0.f) frexpf(m, &e);                 // m = f * 2^e, f in [0.5, 1)  ->  m < 2^e
-  const int sh = 30 - e;                      // |w| * 2^sh < 2^30
+  const int sh = 30 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^30
   if (threadIdx.x == 0) { scale[co] = ldexp(1.0, -sh); bias_d[co] = bias ? (double)bias[co] : 0.0; }
   const int nchunks = Cin / CK, g = co >> 4, ch = co & 15;
   for (int i = threadIdx.x; i < n; i += 256) {
     const int ci = i / 9, tap = i % 9;
-    long long q = (long long)rint(ldexp((double)wc[i], sh));
     int dg[4];
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-      int r = (int)(((q + 128) & 255) - 128);
-      dg[d] = r;
-      q = (q - r) >> 8;
-    }
+    spk_balanced_digits<8>((long long)rint(ldexp((double)wc[i], sh)), dg);
     const int c = ci / CK, k = ci % CK;
 #pragma unroll
     for (int d = 0; d < 4; ++d) {

@@ -371,15 +371,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_fp6_kernel(Fp6Args a) {
         a.out_cnt[(((long long)b * (a.Cout >> 5) + (co >> 5)) * HW + p) * 32 + (co & 31)] = (uint8_t)cnt;
       // every lane stores one (position, time step): 16 channels = 16 e2m1 nibbles = 8 bytes
       if (pos_ok) {
-        auto spread8 = [](unsigned x) -> unsigned {          // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-          x = (x | (x << 12)) & 0x000f000fu;
-          x = (x | (x << 6)) & 0x03030303u;
-          x = (x | (x << 3)) & 0x11111111u;
-          return x << 1;
-        };
-        uint2 o;
-        o.x = spread8(bitsv & 0xffu);
-        o.y = spread8((bitsv >> 8) & 0xffu);
+        const uint2 o = spk_e2m1_record(bitsv);
         const int co0 = g * 16;
         uint8_t* dst = a.out + ((((long long)b * (a.Cout >> 6) + (co0 >> 6)) * HW + p) * T16 + (lane & 15)) * 32 +
                        ((co0 & 63) >> 1);
@@ -495,15 +487,7 @@ __global__ __launch_bounds__(256) void conv3x3_fp6_lastpos_kernel(Fp6Args a) {
     if (a.v_io && ok) a.v_io[vidx] = v;
     if (a.out_cnt && ok) a.out_cnt[(((long long)b * (a.Cout >> 5) + (co >> 5)) * HW + p) * 32 + (co & 31)] = (uint8_t)cnt;
     if (ok) {
-      auto spread8 = [](unsigned q) -> unsigned {
-        q = (q | (q << 12)) & 0x000f000fu;
-        q = (q | (q << 6)) & 0x03030303u;
-        q = (q | (q << 3)) & 0x11111111u;
-        return q << 1;
-      };
-      uint2 o;
-      o.x = spread8(bitsv & 0xffu);
-      o.y = spread8((bitsv >> 8) & 0xffu);
+      const uint2 o = spk_e2m1_record(bitsv);
       const int co0 = g * 16;
       uint8_t* dst = a.out + ((((long long)b * (a.Cout >> 6) + (co0 >> 6)) * HW + p) * T16 + (lane & 15)) * 32 + ((co0 & 63) >> 1);
       *reinterpret_cast<uint2*>(dst) = o;
@@ -524,16 +508,7 @@ __device__ __forceinline__ void pack_fp6_channel(const float* __restrict__ w, co
   const float* wc = w + (long long)co * n;     // w_cl: the channel's weights are stored [3][3][Cin] (channels-last memory format)
   float m = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(wc[i]));
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  m = smax[0];
-  int e = 0;
-  if (m > 0.f) frexpf(m, &e);                 // m = f * 2^e, f in [0.5, 1)  ->  m < 2^e
-  const int sh = 29 - e;                      // |w| * 2^sh < 2^29 <= 16.5 * 32^5
+  const int sh = 29 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^29 <= 16.5 * 32^5
   if (threadIdx.x == 0) { scale[co] = ldexp(1.0, -sh); bias_d[co] = bias ? (double)bias[co] : 0.0; }
   const int nchunks = Cin / CK, g = co >> 4, ch = co & 15;
   // Every thread converts elements to their six digit codes (bytes in LDS, [plane][ci * 9 + tap]); then one thread packs the 16
@@ -765,8 +740,7 @@ __global__ void spikes_nhwc_to_fp4_kernel(const float* __restrict__ s, uint8_t* 
     const long long tb = row / HW;
     const int b = (int)(tb % B), t = (int)(tb / B);
     const float4 v = reinterpret_cast<const float4*>(s)[i];
-    const unsigned w = (v.x != 0.f ? 0x2u : 0u) | (v.y != 0.f ? 0x20u : 0u) | (v.z != 0.f ? 0x200u : 0u) |
-                       (v.w != 0.f ? 0x2000u : 0u);
+    const unsigned w = spk_e2m1_nibbles4(v.x, v.y, v.z, v.w);
     const int c = q * 4;
     uint8_t* dst = o + ((((long long)b * (C >> 6) + (c >> 6)) * HW + hw) * T + t) * 32 + ((c & 63) >> 1);
     *reinterpret_cast<uint16_t*>(dst) = (uint16_t)w;
@@ -791,8 +765,7 @@ __global__ void spikes_nhwc_to_fp4_counts_kernel(const float* __restrict__ s, ui
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int t = 0; t < T; ++t) {
       const float4 v = reinterpret_cast<const float4*>(s)[t * plane + i];
-      const unsigned w = (v.x != 0.f ? 0x2u : 0u) | (v.y != 0.f ? 0x20u : 0u) | (v.z != 0.f ? 0x200u : 0u) |
-                         (v.w != 0.f ? 0x2000u : 0u);
+      const unsigned w = spk_e2m1_nibbles4(v.x, v.y, v.z, v.w);
       acc.x += v.x != 0.f ? 1.f : 0.f; acc.y += v.y != 0.f ? 1.f : 0.f;
       acc.z += v.z != 0.f ? 1.f : 0.f; acc.w += v.w != 0.f ? 1.f : 0.f;
       *reinterpret_cast<uint16_t*>(dst + t * 32) = (uint16_t)w;

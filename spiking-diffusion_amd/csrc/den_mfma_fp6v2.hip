@@ -134,25 +134,6 @@ constexpr int SPK_V2_PF = 6;            // four-wave items: A fragments requeste
 // unflagged neuron provably emits the exact path's spikes; flagged ones are recomputed exactly.
 constexpr float CERT_4EPS = 4.0f * 2.38418579e-07f;
 
-// compile-time loop: f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>).  The K loop must be straight-line
-// code with constant accumulator indices (a runtime index would send the accumulators through scratch); this does not
-// depend on the unroller's size heuristics.
-template <typename F, int... S>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
-  (f(std::integral_constant<int, S>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ unsigned spread8(unsigned x) {          // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-  x = (x | (x << 12)) & 0x000f000fu;
-  x = (x | (x << 6)) & 0x03030303u;
-  x = (x | (x << 3)) & 0x11111111u;
-  return x << 1;
-}
-
 // Store the spikes of one 32-row tile: every lane holds the 16 step bits of its neuron (channel = lane & 31 of the group,
 // position = its lane half); a 16x16 bit transpose per 16-lane row gives lane t the 16 channel bits of step t = 8 bytes of
 // the (position, t) record.
@@ -160,12 +141,7 @@ __device__ __forceinline__ void store_tile_spikes(uint8_t* out, uint8_t* out_cnt
                                                   long long cnt_base, bool ok) {
   const unsigned bitsv = spk_transpose16_rows(mybits, lane);
   if (out_cnt && ok) out_cnt[cnt_base + (lane & 31)] = (uint8_t)__popc(mybits);
-  if (ok) {
-    uint2 o;
-    o.x = spread8(bitsv & 0xffu);
-    o.y = spread8((bitsv >> 8) & 0xffu);
-    *reinterpret_cast<uint2*>(out + rec_base + (lane & 15) * 16 + 8 * ((lane >> 4) & 1)) = o;
-  }
+  if (ok) *reinterpret_cast<uint2*>(out + rec_base + (lane & 15) * 16 + 8 * ((lane >> 4) & 1)) = spk_e2m1_record(bitsv);
 }
 
 // NWV = waves per workgroup: 8 (two per SIMD, 3 row tiles each, 256 registers: the partner wave's MFMAs run under this wave's copy
@@ -1128,16 +1104,7 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
   const float* wc = w + (long long)co * n;
   float m = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(wc[i]));
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  m = smax[0];
-  int e = 0;
-  if (m > 0.f) frexpf(m, &e);                 // m = f * 2^e, f in [0.5, 1)  ->  m < 2^e
-  const int sh = 29 - e;                      // |w| * 2^sh < 2^29 <= 16.5 * 32^5
+  const int sh = 29 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^29 <= 16.5 * 32^5
   double l1 = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
     const double q = rint(ldexp((double)wc[i], sh));
@@ -1169,19 +1136,12 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
     if (valid) {
       for (int j = 0; j < 32; ++j) {
         const int ci = c * CK + j;
-        long long q = (long long)rint(ldexp((double)wc[ci * 9 + tap], sh));
         int dg[6];
-#pragma unroll
-        for (int p = 5; p >= 1; --p) {
-          const int r = (int)(((q + 16) & 31) - 16);
-          dg[p] = r;
-          q = (q - r) >> 5;
-        }
-        dg[0] = (int)q;                          // in [-16, 16]
+        spk_balanced_digits<5>((long long)rint(ldexp((double)wc[ci * 9 + tap], sh)), dg);
         int d = 0;
 #pragma unroll
         for (int p = 0; p < 6; ++p) d = (p == digit) ? dg[p] : d;
-        const unsigned code = (d < 0 ? 0x20u : 0u) | (unsigned)(d < 0 ? -d : d);
+        const unsigned code = spk_e2m3_code(d);
         const int bit = 6 * j, wd = bit >> 5, sft = bit & 31;
 #pragma unroll
         for (int q2 = 0; q2 < 6; ++q2) {         // static register indexing

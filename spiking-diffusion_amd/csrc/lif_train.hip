@@ -49,10 +49,8 @@ __global__ __launch_bounds__(256) void lif_train_fwd_kernel(const float* __restr
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        const float h = v[k] + (xv[k] - (v[k] - v_reset)) / tau;
-        const float s = (h - v_th >= 0.0f) ? 1.0f : 0.0f;
-        v[k] = (1.0f - s) * h + s * v_reset;
-        hv[k] = h; sv[k] = s;
+        const SpkLifHS r = spk_lif_train_step(v[k], xv[k], tau, v_th, v_reset);
+        hv[k] = r.h; sv[k] = r.s;
       }
       float* ph = h_seq + (long long)t * N + n0;
       float* ps = s_seq + (long long)t * N + n0;
@@ -93,17 +91,7 @@ __global__ __launch_bounds__(256) void lif_train_bwd_kernel(const float* __restr
         gs[0] = *pg; hv[0] = *ph;
       }
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float over = hv[k] - v_th;
-        const float s = over >= 0.0f ? 1.0f : 0.0f;
-        const float ax = 1.57079632679489661923f * alpha * over;
-        const float g_s = alpha / 2.0f / (1.0f + ax * ax);
-        float dv_dh = 1.0f - s;
-        if (!DETACH) dv_dh = (v_reset - hv[k]) * g_s + dv_dh;
-        const float gh = G[k] * dv_dh + gs[k] * g_s;
-        gx[k] = gh * inv_tau;
-        G[k] = gh * carry;
-      }
+      for (int k = 0; k < VEC; ++k) gx[k] = spk_atan_bptt_step<DETACH>(G[k], gs[k], hv[k], v_th, v_reset, alpha, inv_tau, carry);
       float* px = grad_x + (long long)t * N + n0;
       if constexpr (VEC == 4) *reinterpret_cast<float4*>(px) = make_float4(gx[0], gx[1], gx[2], gx[3]);
       else *px = gx[0];

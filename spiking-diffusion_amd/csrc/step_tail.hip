@@ -304,16 +304,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
       const unsigned bitsv = spk_transpose16_rows(mybits, lane);
       const int tl = lane & 15, co16 = co & ~15;
       if (!ok) continue;
-      unsigned lo8 = bitsv & 0xffu, hi8 = (bitsv >> 8) & 0xffu;
-      auto spread8 = [](unsigned x) -> unsigned {                       // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-        x = (x | (x << 12)) & 0x000f000fu;
-        x = (x | (x << 6)) & 0x03030303u;
-        x = (x | (x << 3)) & 0x11111111u;
-        return x << 1;
-      };
-      uint2 o;
-      o.x = spread8(lo8);
-      o.y = spread8(hi8);
+      const uint2 o = spk_e2m1_record(bitsv);
       uint8_t* dst = a.x1_out + ((((long long)b * 2 + (co16 >> 5)) * HW + op) * 16 + tl) * 16 + ((co16 & 31) >> 1);
       *reinterpret_cast<uint2*>(dst) = o;
     }

@@ -58,15 +58,6 @@ struct TArgs {
   int B, Cout, Cin;
 };
 
-template <typename F, int... S>
-__device__ __forceinline__ void tfor_impl(F&& f, std::integer_sequence<int, S...>) {
-  (f(std::integral_constant<int, S>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void tfor(F&& f) {
-  tfor_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
 constexpr float CERT_4EPS = 4.0f * 2.38418579e-07f;
 constexpr int SPK_VT_NWV = 16;          // waves per workgroup.  Round 4: SIXTEEN (four per SIMD) with one tile per pass: the four-digit form needs ~100
                                         // registers at one tile per pass, four waves issue vector instructions at 2.0 instead of 3.1 cycles each
@@ -85,13 +76,6 @@ constexpr int SPK_VT_TPP = 1;           // row tiles per pass (a weight tile rea
 //  waves 4..7, 270-275 against 266-267 us on convT2.)
 constexpr int SPK_VT_NHOLD = 1;         // held taps per class.  All four taps of the four-tap class need 96 registers with two chunks: twelve waves
                                         // (168 registers each) hold three, sixteen (128) hold one
-
-__device__ __forceinline__ unsigned spread8_v(unsigned x) {        // bit k -> nibble k, as the e2m1 code of 1.0 (0x2)
-  x = (x | (x << 12)) & 0x000f000fu;
-  x = (x | (x << 6)) & 0x03030303u;
-  x = (x | (x << 3)) & 0x11111111u;
-  return x << 1;
-}
 
 template <int GEO, int H, int W>
 struct Geo {
@@ -310,7 +294,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         const v8i b8 = {bv[0], bv[1], bv[2], bv[3], bv[4], bv[5], 0, 0};
         d = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, d, 4, 2, 0, sc_a, 0, sb);
       };
-      tfor<9>([&](auto tap_tag) {
+      static_for<9>([&](auto tap_tag) {
         constexpr int TAP = decltype(tap_tag)::value, KY = TAP / 3, KX = TAP % 3;
         // GEO 0: oy = 2 iy - 1 + ky: class parity PY takes ky = 1 (iy = qy) when even, ky = 0 (iy = qy + 1) and ky = 2 (iy = qy) when odd
         constexpr bool ON = GEO == 1 || ((PY == 0 ? KY == 1 : KY != 1) && (PX == 0 ? KX == 1 : KX != 1));
@@ -412,9 +396,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
           const unsigned bitsv = spk_transpose16_rows(mybits, lane);
           const int t = lane & 15, hi = (lane >> 4) & 1;
           if (ok && OUT == OUT_S32) {
-            uint2 o;
-            o.x = spread8_v(bitsv & 0xffu);
-            o.y = spread8_v((bitsv >> 8) & 0xffu);
+            const uint2 o = spk_e2m1_record(bitsv);
             uint8_t* rec = reinterpret_cast<uint8_t*>(a.out) + ((((long long)b * G + g) * Ho * Wo + oy * Wo + ox) * T16 + t) * 16;
             *reinterpret_cast<uint2*>(rec + 8 * hi) = o;
           }
@@ -433,7 +415,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
     // the item's passes, class-major, dealt round-robin over the waves (every wave gets a mix of cheap and expensive classes); a
     // wave's passes of one class follow one another, so the class's first-tap weight fragments are read once for all of them
     [[maybe_unused]] int Pdyn = wave;                          // (DYN) the wave's pass: the first NWV are dealt, the rest handed out
-    tfor<NCLS>([&](auto cls_tag) {
+    static_for<NCLS>([&](auto cls_tag) {
       constexpr int CLS = decltype(cls_tag)::value;
       constexpr int NHELD = n_on_taps<GEO, CLS>() < SPK_VT_NHOLD ? n_on_taps<GEO, CLS>() : SPK_VT_NHOLD;
       int P = DYN ? Pdyn : CLS * NPASS + ((wave - CLS * NPASS) % SPK_VT_NWV + SPK_VT_NWV) % SPK_VT_NWV;   // static: first P >= CLS * NPASS with P = wave (mod NWV)
@@ -443,7 +425,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         for (int h = 0; h < SPK_VT_NHOLD; ++h)
 #pragma unroll
           for (int j = 0; j < NCH * 2; ++j) hb[h][j] = v6i{0, 0, 0, 0, 0, 0};
-        tfor<NHELD>([&](auto h_tag) {
+        static_for<NHELD>([&](auto h_tag) {
           constexpr int h = decltype(h_tag)::value, TAPH = on_tap<GEO, CLS>(h);
 #pragma unroll
           for (int j = 0; j < NCH * 2; ++j) {
@@ -615,16 +597,7 @@ __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restri
   };
   float m = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(wat(i / 9, i % 9)));
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  m = smax[0];
-  int e = 0;
-  if (m > 0.f) frexpf(m, &e);
-  const int sh = 29 - e;                      // |w| * 2^sh < 2^29 <= 16.5 * 32^5
+  const int sh = 29 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^29 <= 16.5 * 32^5
   for (int i = threadIdx.x; i < n; i += 256) {
     const int ci = i / 9, tap = i - 9 * ci;
     qtab[((long long)co * 9 + tap) * Cin + ci] = (int)rint(ldexp((double)wat(ci, tap), sh));
@@ -640,19 +613,12 @@ __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restri
     unsigned bits[6] = {0, 0, 0, 0, 0, 0};
     for (int k = 0; k < 32 && live; ++k) {
       const int ci = chunk * 32 + k;
-      long long q = ci < Cin ? (long long)rint(ldexp((double)wat(ci, tap), sh)) : 0ll;
       int dg[6];
-#pragma unroll
-      for (int p = 5; p >= 1; --p) {
-        const int r = (int)(((q + 16) & 31) - 16);
-        dg[p] = r;
-        q = (q - r) >> 5;
-      }
-      dg[0] = (int)q;
+      spk_balanced_digits<5>(ci < Cin ? (long long)rint(ldexp((double)wat(ci, tap), sh)) : 0ll, dg);
       int d = 0;
 #pragma unroll
       for (int p = 0; p < 6; ++p) d = (p == digit) ? dg[p] : d;
-      const unsigned code = (d < 0 ? 0x20u : 0u) | (unsigned)(d < 0 ? -d : d);
+      const unsigned code = spk_e2m3_code(d);
       const int bit = 6 * k, wd = bit >> 5, sft = bit & 31;
 #pragma unroll
       for (int q2 = 0; q2 < 6; ++q2) {

@@ -531,10 +531,8 @@ class DummyModel(nn.Module):
 
     def _conv6_params(self):
         conv = self.conv6[0]
-        if not hasattr(conv, '_spk_params'):
-            from spkdiff.fused import ConvParams
-            object.__setattr__(conv, '_spk_params', ConvParams())
-        return conv, conv._spk_params.get_i8(conv, pad_cout=True)
+        from spkdiff.fused import conv_params
+        return conv, conv_params(conv).get_i8(conv, pad_cout=True)
 
     def _run(self, inp_b2hw, stateful, record=None):
         T = self.n_steps

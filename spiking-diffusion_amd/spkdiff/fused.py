@@ -22,68 +22,62 @@ def _ver(t):
 
 
 class ConvParams:
-    """Prepared weights of one conv layer, rebuilt when the parameters change:
+    """Prepared weights of one conv layer, one cached entry per form, each rebuilt on first use after the parameters change:
     ``get``  -> fp32 packed [k*k][Cin][Cout] for the direct kernels;
-    ``get_i8`` -> int8 digit planes + fp64 scale / bias for the MFMA kernel (built on first use)."""
+    ``get_i8`` -> int8 digit planes + fp64 scale / bias for the MFMA kernel; the other getters: the digit tiles of the
+    other matrix-core kernels."""
 
     def __init__(self):
-        self.key = None
-        self.w_packed = None
-        self.key_i8 = None
-        self.i8 = None
+        self.forms = {}                 # form -> (parameter versions it was built from, the derived tensor(s))
+
+    @staticmethod
+    def version(conv):
+        return (_ver(conv.weight), _ver(conv.bias))
 
     def invalidate(self):
         """Forget every derived form (call after writing weights through ``.data``: that does not bump ``_version``)."""
-        self.key = self.key_i8 = None
-        self.key_fp6 = self.key_i8g = self.key_fp6v2 = self.key_convT_fp6 = None
+        self.forms.clear()
+
+    def _form(self, name, conv, build, *extra):
+        key = self.version(conv) + extra
+        ent = self.forms.get(name)
+        if ent is None or ent[0] != key:
+            ent = self.forms[name] = (key, build())
+        return ent[1]
 
     def get(self, conv):
-        key = (_ver(conv.weight), _ver(conv.bias))
-        if key != self.key:
-            transposed = isinstance(conv, nn.ConvTranspose2d)
-            self.w_packed = ops.pack_conv_weight(conv.weight, transposed)
-            self.key = key
-        return self.w_packed
+        return self._form('fp32', conv, lambda: ops.pack_conv_weight(conv.weight, isinstance(conv, nn.ConvTranspose2d)))
 
     def get_i8(self, conv, pad_cout=False):
         """int8 digit planes of the denoiser family; pad_cout: output channels zero-padded to a multiple of 16 (logits layer)."""
-        key = (_ver(conv.weight), _ver(conv.bias), bool(pad_cout))
-        if key != self.key_i8:
-            self.i8 = ops.den_pack_weight_i8(conv.weight, conv.bias, pad_cout=pad_cout)
-            self.key_i8 = key
-        return self.i8
+        return self._form('i8', conv, lambda: ops.den_pack_weight_i8(conv.weight, conv.bias, pad_cout=pad_cout), bool(pad_cout))
 
     def get_fp6(self, conv):
-        """six fp6 digit planes + fp64 scale / bias for the block-scaled MFMA kernel (built on first use)."""
-        key = (_ver(conv.weight), _ver(conv.bias))
-        if key != getattr(self, 'key_fp6', None):
-            self.fp6 = ops.den_pack_weight_fp6(conv.weight, conv.bias)
-            self.key_fp6 = key
-        return self.fp6
+        """six fp6 digit planes + fp64 scale / bias for the block-scaled MFMA kernel."""
+        return self._form('fp6', conv, lambda: ops.den_pack_weight_fp6(conv.weight, conv.bias))
 
     def get_vae_fp6(self, conv):
-        """digit tiles of the fp6 kernel of the VQ-VAE's stride-2 layers (csrc/vae_fp6.hip), built on first use."""
-        key = (_ver(conv.weight), _ver(conv.bias))
-        if key != getattr(self, 'key_convT_fp6', None):
-            self.convT_fp6 = ops.vae_fp6_pack(conv.weight, conv.bias, isinstance(conv, nn.ConvTranspose2d))
-            self.key_convT_fp6 = key
-        return self.convT_fp6
+        """digit tiles of the fp6 kernel of the VQ-VAE's stride-2 layers (csrc/vae_fp6.hip)."""
+        return self._form('vae_fp6', conv,
+                          lambda: ops.vae_fp6_pack(conv.weight, conv.bias, isinstance(conv, nn.ConvTranspose2d)))
 
     def get_fp6v2(self, conv):
-        """digit tiles of the second-generation fp6 kernel (+ scale / bias / L1 norms / an fp32 copy), built on first use."""
-        key = (_ver(conv.weight), _ver(conv.bias))
-        if key != getattr(self, 'key_fp6v2', None):
-            self.fp6v2 = ops.den_pack_weight_fp6v2(conv.weight, conv.bias)
-            self.key_fp6v2 = key
-        return self.fp6v2
+        """digit tiles of the second-generation fp6 kernel (+ scale / bias / L1 norms / an fp32 copy)."""
+        return self._form('fp6v2', conv, lambda: ops.den_pack_weight_fp6v2(conv.weight, conv.bias))
 
     def get_i8_generic(self, conv):
         """int8 digit planes in the layout of the gather-MFMA kernel (any k, Conv2d or ConvTranspose2d)."""
-        key = (_ver(conv.weight), _ver(conv.bias))
-        if key != getattr(self, 'key_i8g', None):
-            self.i8g = ops.pack_conv_weight_i8(conv.weight, conv.bias, isinstance(conv, nn.ConvTranspose2d))
-            self.key_i8g = key
-        return self.i8g
+        return self._form('i8g', conv,
+                          lambda: ops.pack_conv_weight_i8(conv.weight, conv.bias, isinstance(conv, nn.ConvTranspose2d)))
+
+
+def conv_params(conv):
+    """The ``ConvParams`` of ``conv`` (attached on first use)."""
+    pr = getattr(conv, '_spk_params', None)
+    if pr is None:
+        pr = ConvParams()
+        object.__setattr__(conv, '_spk_params', pr)
+    return pr
 
 
 def conv_geometry(conv):
@@ -143,7 +137,7 @@ def derived_refs(module):
     for m in module.modules():
         pr = getattr(m, '_spk_params', None)
         if pr is not None:
-            refs.append(tuple(v for v in vars(pr).values() if v is not None))
+            refs.append(tuple(v for _, v in pr.forms.values()))
         if isinstance(m, layer.BatchNorm2d) and m._affine_cache is not None:
             refs.append(m._affine_cache)
     return refs
@@ -342,14 +336,12 @@ class FusedSequential(nn.Sequential):
         if (geo['k'] != 1 or geo['stride'] != 1 or geo['pad'] != 0 or conv.out_channels not in (16, 32) or
                 conv.in_channels != codebook.shape[1]):
             return None
-        if not hasattr(conv, '_spk_params'):
-            object.__setattr__(conv, '_spk_params', ConvParams())
         a, b = bn.affine_terms()
         bias = None if conv.bias is None else conv.bias.detach()
-        packed = conv._spk_params.get(conv)
+        packed = conv_params(conv).get(conv)
         # the table is kept while the parameter versions that went into it AND the invalidation epochs are unchanged; the buffer
         # belongs to this container (no table is shared between models)
-        key = (conv._spk_params.key, bn._affine_cache[0], _ver(codebook), derived_epoch(self), tuple(epoch))
+        key = (ConvParams.version(conv), bn._affine_cache[0], _ver(codebook), derived_epoch(self), tuple(epoch))
         if not isinstance(getattr(self, '_spikegen_tab', None), dict):
             object.__setattr__(self, '_spikegen_tab', {})
         return ops.spikegen_tokens_s32(tokens, codebook, packed, bias, a, b, T=T, table_key=key, table_slot=self._spikegen_tab)
@@ -382,8 +374,7 @@ class FusedSequential(nn.Sequential):
         for bi, (conv, bn, lif) in enumerate(blocks):
             with ops.timed(getattr(conv, '_spk_tag', None)):          # bench.py tags layers it wants timed in situ
                 last = bi == len(blocks) - 1
-                if not hasattr(conv, '_spk_params'):
-                    object.__setattr__(conv, '_spk_params', ConvParams())
+                pr = conv_params(conv)
                 geo = conv_geometry(conv)
                 bias = None if conv.bias is None else conv.bias.detach()
                 src1 = in1 if (last and in1 is not None) else None
@@ -395,7 +386,7 @@ class FusedSequential(nn.Sequential):
                     if vk == ops.VAE_OUT_COLLAPSED and bi == len(blocks) - 2 and tail_ok:
                         # decoder convT2, handing the read-out layer its time-collapsed spikes
                         a, b = bn.affine_terms()
-                        cur = ops.vae_fp6_fwd(cur, conv._spk_params.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
+                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
                                               transposed=True, out_kind=vk, coef=coef)
                         kind = 'collapsed'
                         continue
@@ -403,13 +394,13 @@ class FusedSequential(nn.Sequential):
                             self._next_convT_fp6_hw(blocks[bi + 1], cur.shape[2], cur.shape[3], geo, T)):
                         # decoder convT1 fed nibble-packed spikes directly (the token-table spike generator)
                         a, b = bn.affine_terms()
-                        cur = ops.vae_fp6_fwd(cur, conv._spk_params.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
+                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
                                               transposed=True, out_kind=ops.VAE_OUT_S32)
                         kind = IN_PTC
                         continue
                     if vk == ops.VAE_OUT_PTC and not last:
                         a, b = bn.affine_terms()                  # encoder conv2: plain u8 PTC out for the 1x1 layer
-                        cur = ops.vae_fp6_fwd(cur, conv._spk_params.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
+                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
                                               transposed=False, out_kind=vk)
                         kind = IN_PTC
                         continue
@@ -423,7 +414,7 @@ class FusedSequential(nn.Sequential):
                         raise NotImplementedError('spkdiff: S32 spikes are only consumed by the fp6v2 MFMA conv (3x3/s1/p1 + BN + '
                                                   'LIF, T=16, 7x7, fresh LIF state, S32 output)')
                     a, b = bn.affine_terms()
-                    o = ops.den_conv3x3_mfma_fp6v2(cur, conv._spk_params.get_fp6v2(conv), conv.out_channels, bn_a=a, bn_b=b,
+                    o = ops.den_conv3x3_mfma_fp6v2(cur, pr.get_fp6v2(conv), conv.out_channels, bn_a=a, bn_b=b,
                                                    want_counts=last and want_counts, need_radius=need_radius)
                     if last and want_counts:
                         out['ptc'], out['cnt'] = o
@@ -450,7 +441,7 @@ class FusedSequential(nn.Sequential):
                             raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
                                                f'{shape}; call functional.reset_net first')
                         v = lif.v
-                    o = ops.den_conv3x3_mfma_fp6(cur, conv._spk_params.get_fp6(conv), conv.out_channels, bn_a=a, bn_b=b, v=v,
+                    o = ops.den_conv3x3_mfma_fp6(cur, pr.get_fp6(conv), conv.out_channels, bn_a=a, bn_b=b, v=v,
                                                  want_counts=last and want_counts)
                     if last and want_counts:
                         out['ptc'], out['cnt'] = o
@@ -466,7 +457,7 @@ class FusedSequential(nn.Sequential):
                                                    T, cur.shape[2], cur.shape[3]) and
                             (lif is None or not last or (final == 'ptc' and chunk_out == 32)))
                 if use_mfma:
-                    packed = conv._spk_params.get_i8(conv)
+                    packed = pr.get_i8(conv)
                     if lif is not None:
                         a, b = bn.affine_terms()
                         v = None
@@ -501,7 +492,7 @@ class FusedSequential(nn.Sequential):
                               not (last and chunk_out) and
                               ops.conv_mfma_supported(conv.in_channels, conv.out_channels, T, g_mode))
                 if use_gather:
-                    packed = conv._spk_params.get_i8_generic(conv)
+                    packed = pr.get_i8_generic(conv)
                     if lif is not None:
                         a, b = bn.affine_terms()
                         v = None
@@ -521,7 +512,7 @@ class FusedSequential(nn.Sequential):
                                 conv.out_channels % 32 == 0 and self._collapsible(blocks[-1], coef, T) and
                                 self._next_convT_fp6(blocks[bi + 1], cur, geo, T)):
                             if self._vae_kind(conv, geo, T, cur.shape[1], cur.shape[2]) == ops.VAE_OUT_S32:
-                                cur = ops.vae_fp6_fwd(ops.ptc_to_s32(cur), conv._spk_params.get_vae_fp6(conv), conv.out_channels,
+                                cur = ops.vae_fp6_fwd(ops.ptc_to_s32(cur), pr.get_vae_fp6(conv), conv.out_channels,
                                                       bn_a=a, bn_b=b, transposed=True, out_kind=ops.VAE_OUT_S32)
                             else:
                                 cur = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=None,
@@ -548,7 +539,7 @@ class FusedSequential(nn.Sequential):
                                                 apply_tanh=apply_tanh, want_u8=want_u8, **geo)
                         out['f32'], out['u8'] = r['f32'], r['u8']
                     continue
-                w_packed = conv._spk_params.get(conv)
+                w_packed = pr.get(conv)
                 if lif is not None:
                     a, b = bn.affine_terms()
                     v = None

@@ -292,6 +292,9 @@ def test_shipped_library_has_no_settable_state_and_no_variant_sources():
         for m in re.finditer(r"^\s*#\s*ifndef\s+((?:SPK|CT)_\w+)", txt, re.M):
             nxt = txt[m.end():].lstrip().splitlines()[0] if txt[m.end():].strip() else ""
             assert re.match(r"#\s*define\s+" + m.group(1) + r"\s*$", nxt) and m.group(1).endswith("_H"), (path, m.group(1))
+    # the shared spike-record / neuron helpers have one definition, in spk_common.h (nibble spread, bit transpose, ATan surrogate)
+    for body in ("0x000f000fu", "0x140, 0xF", "1.57079632679489661923f"):
+        assert [os.path.basename(p) for p in srcs if body in open(p).read()] == ["spk_common.h"], body
     assert len(open(os.path.join(csrc, "den_mfma_fp6v2.hip")).read().splitlines()) < 2000
 
 
