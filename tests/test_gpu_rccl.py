@@ -58,7 +58,7 @@ def test_two_rank_bench_on_one_device_gives_the_one_rank_job():
     two ranks on one device; the RCCL transport itself is test_rccl_one_rank_collectives_on_the_device).  The same job -- seed,
     steps, warm-up, GLOBAL batch -- as ONE rank must give the same global_token_checksum: the sample does not depend on the split
     (R/snn_model/vq_diffusion.py:103-142 per image)."""
-    common = ["--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--dense-only"]
+    common = ["--full", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--dense-only"]
     p2, d2 = _bench_child(["--gpus", "2", "--batch", "48"] + common, {"SPKDIFF_BENCH_SHARE_GPU": "1"})
     assert p2.returncode == 0 and d2 is not None, (p2.stdout[-1500:], p2.stderr[-3000:])
     assert len([ln for ln in p2.stdout.splitlines() if ln.strip()]) == 1, "exactly one line on stdout"

@@ -8,7 +8,7 @@ O=gpurun_out/${TAG}_final; rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests -m gpu -q -x > $O/gputest.log 2>&1
 grep -v PARITY_REPORT $O/gputest.log | tail -4 | cut -c1-300
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
 cut -c1-400 $O/bench_default.json
 python bench.py --workload train --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_train.json
 cut -c1-250 $O/bench_train.json

@@ -9,7 +9,7 @@ TAG=${1:-r6}
 O=$R/gpurun_out/${TAG}prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_prof.json 2> $O/bench_under_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_under_prof.json 2> $O/bench_under_prof.err
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $O/v2_$c -- python $R/tools/fp6v2_one.py 512 256 13 > $O/v2_$c.log 2>&1
   rocprofv3 --pmc $c --output-format csv -d $O/v2c5_$c -- python $R/tools/fp6v2_one.py 256 512 13 > $O/v2c5_$c.log 2>&1
@@ -23,7 +23,7 @@ ls -R $O | grep -c csv
 head -c 300 $O/bench_under_prof.json
 # a second trace of the headline measurement alone (per-layer table of profiles/README.md)
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_headline -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --dense-only > $O/bench_headline_under_prof.json 2> $O/bench_headline_under_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_headline -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --dense-only > $O/bench_headline_under_prof.json 2> $O/bench_headline_under_prof.err
 # trace of the encode->decode workload (configs[2]) and of the reverse process with elimination + position lists
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_encdec -- python $R/bench.py --workload encdec --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_encdec_under_prof.json 2> $O/bench_encdec_under_prof.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_lists -- python $R/tools/listed_time.py 256 2 > $O/listed_time.log 2>&1
