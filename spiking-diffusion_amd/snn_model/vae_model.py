@@ -31,7 +31,7 @@ from spikingjelly.activation_based import neuron, functional, layer, surrogate, 
 from spikingjelly import visualizing  # noqa: F401
 
 from spkdiff import ops
-from spkdiff.fused import FusedSequential, has_hooks, derived_epoch
+from spkdiff.fused import FusedSequential, conv_geometry, has_hooks, derived_epoch
 from spkdiff.ops import IN_PTC, IN_SEQ, IN_TINV
 
 from .snn_layers import *  # noqa: F401,F403
@@ -255,15 +255,10 @@ class SNN_VQVAE(nn.Module):
     def _decoder_takes_s32(self, T, h, w):
         """Will the decoder's first layer take nibble-packed spikes (the fp6 transposed-convolution kernel, csrc/vae_fp6.hip)?"""
         blocks = self.decoder.snn_convs._blocks()
-        if blocks is None or len(blocks) < 3 or T != 16:
+        if blocks is None or len(blocks) != 3 or T != 16:
             return False
-        conv = blocks[-3][0]
-        from spkdiff.fused import conv_geometry, has_hooks
-        if has_hooks(conv) or len(blocks) != 3:
-            return False
-        geo = conv_geometry(conv)
-        return ops.vae_fp6_kind(conv.in_channels, conv.out_channels, geo['k'], geo['stride'], geo['pad'], geo['out_pad'],
-                                geo['transposed'], T, h, w) == ops.VAE_OUT_S32
+        conv = blocks[0][0]
+        return FusedSequential._vae_kind(conv, conv_geometry(conv), T, h, w) == ops.VAE_OUT_S32
 
     @torch.no_grad()
     def decode_tokens(self, tokens, T=16, want_u8=True):

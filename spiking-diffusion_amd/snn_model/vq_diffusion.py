@@ -18,7 +18,8 @@ from spikingjelly.activation_based import neuron, functional, layer, surrogate, 
 from spikingjelly import visualizing  # noqa: F401
 
 from spkdiff import ops
-from spkdiff.fused import FusedSequential, invalidate_derived, has_hooks, derived_epoch, derived_refs
+from spkdiff.fused import (FusedSequential, invalidate_derived, has_hooks, derived_epoch, derived_refs, exact_spike_conv,
+                           keep_channels_last)
 from spkdiff.ops import IN_PTC, IN_TINV
 
 from .vae_model import *  # noqa: F401,F403  (R/snn_model/vq_diffusion.py:21)
@@ -452,9 +453,6 @@ class DummyModel(nn.Module):
     # conv6 + mean over T evaluated as ONE convolution of the per-neuron spike counts (exact linearity; the sum over T
     # is rounded once instead of T times: logits agree with the per-step form to ~1 ulp).  False = per-step form.
     collapse_conv6 = True
-    # training: conv6 + mean over T as ONE autograd operator (ops.SpikeConvMeanTrainFunction): same forward operations, the
-    # backward convolves the output gradient once with the spike counts / once for all steps.  False: two operators.
-    collapse_conv6_backward = True
 
     _latent_hw = (7, 7)        # latent size of the last call (7x7 MNIST-shaped, 8x8 CIFAR-shaped)
 
@@ -611,8 +609,9 @@ class DummyModel(nn.Module):
         cat = ops.CatChannelsFunction.apply(x5, x1)
         c6 = self.conv6
         blocks6 = c6._blocks()
-        if self.collapse_conv6_backward and c6._trainable_fused(blocks6, cat) and c6.exact_conv_fits(blocks6, cat):
-            # conv6 + the time mean as one operator whose backward runs on the spike counts (1/T of the per-step backward)
+        if c6._trainable_fused(blocks6, cat) and c6.exact_conv_fits(blocks6, cat):
+            # conv6 + the time mean as ONE autograd operator: same forward operations, the backward convolves the output
+            # gradient once with the spike counts (1/T of the per-step backward)
             conv = blocks6[0][0]
             return ops.SpikeConvMeanTrainFunction.apply(cat, conv.weight, conv.bias, None if preps is None else preps[4])
         x6 = c6.train_forward(cat, binary_input=True) if c6._trainable_fused(blocks6, cat) else c6(cat)
@@ -631,19 +630,14 @@ class DummyModel(nn.Module):
         layers = []
         for i, blk in enumerate((self.conv2, self.conv3, self.conv4, self.conv5, self.conv6)):
             blocks = blk._blocks()
-            if blocks is None or len(blocks) != 1 or not blk.exact_train_forward:
+            if blocks is None or len(blocks) != 1:
                 return None
             conv = blocks[0][0]
             w = conv.weight
-            if w.dim() == 4 and not w.is_contiguous(memory_format=torch.channels_last):
-                w.data = w.data.contiguous(memory_format=torch.channels_last)
-            if not (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.groups == 1
-                    and tuple(conv.dilation) == (1, 1) and conv.padding_mode == 'zeros' and w.requires_grad and conv.training
-                    and ops.den_fp6_supported(conv.out_channels, conv.in_channels, 3, 1, 1, T, H, W)):
+            keep_channels_last(w)
+            if not (w.requires_grad and conv.training and exact_spike_conv(conv, T, H, W)):
                 return None
             last = i == 4
-            if last and not self.collapse_conv6_backward:
-                return None
             n_dg = B if last else (T * B if ops.conv3x3_dgrad_supported(conv.out_channels, conv.in_channels, H, W, T * B) else 0)
             if last and not (conv.out_channels % 16 == 0 and conv.in_channels % 32 == 0 and (H, W) in ((7, 7), (8, 8))):
                 n_dg = 0

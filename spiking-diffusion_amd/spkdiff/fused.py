@@ -8,6 +8,8 @@ R/snn_model/vq_diffusion.py:161-187).
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 
@@ -86,6 +88,47 @@ def conv_geometry(conv):
     return dict(k=layer._one(conv.kernel_size, 'kernel_size'), stride=layer._one(conv.stride, 'stride'),
                 pad=layer._one(conv.padding, 'padding'), transposed=transposed,
                 out_pad=layer._one(conv.output_padding, 'output_padding') if transposed else 0)
+
+
+def keep_channels_last(w):
+    """Keep a 4-D conv weight channels-last while training: the library's NHWC kernels then read it (and write its gradient)
+    without a per-call layout copy, and the fp6 packing reads it as stored; values, shape and state_dict keys are unchanged."""
+    if w.dim() == 4 and not w.is_contiguous(memory_format=torch.channels_last):
+        w.data = w.data.contiguous(memory_format=torch.channels_last)
+
+
+def exact_spike_conv(conv, T, H, W):
+    """Does ``conv`` take the exact fp6 MFMA training forward (ops.SpikeConvTrainFunction) on spikes [T,B,Cin,H,W]?"""
+    return (isinstance(conv, layer.Conv2d) and conv.groups == 1 and tuple(conv.dilation) == (1, 1)
+            and conv.padding_mode == 'zeros' and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
+            and conv.padding == (1, 1) and ops.den_fp6_supported(conv.out_channels, conv.in_channels, 3, 1, 1, T, H, W))
+
+
+def _in_hw(x, kind):
+    """H x W of the map an input of layout ``kind`` holds (PTC [B,H,W,T,C]; chunked records [B,C/c,H,W,T,c]; fp32 [...,H,W])."""
+    if kind == IN_PTC:
+        return (x.shape[2], x.shape[3]) if x.dim() == 6 else (x.shape[1], x.shape[2])
+    return x.shape[-2], x.shape[-1]
+
+
+def _out_hw(geo, H, W):
+    """H x W of the output of a layer of geometry ``geo`` (conv_geometry) on an H x W map."""
+    args = (geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
+    return ops.conv_out_size(H, *args), ops.conv_out_size(W, *args)
+
+
+def _lif_state(lif, B, Cout, Ho, Wo, device, stateful):
+    """The membrane state a fused launch reads and updates: the LIFNode's ``v`` (materialised from its float reset value on
+    first use), or None for a stateless call (fresh state, nothing written)."""
+    if not stateful:
+        return None
+    shape = (B, Cout, Ho, Wo)
+    if isinstance(lif.v, float):
+        lif.v = torch.full(shape, lif.v, dtype=torch.float32, device=device)
+    elif tuple(lif.v.shape) != shape:
+        raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
+                           f'{shape}; call functional.reset_net first')
+    return lif.v
 
 
 def _is_conv(m):
@@ -202,22 +245,13 @@ class FusedSequential(nn.Sequential):
                     return False
         return True
 
-    # exact MFMA forward for spike-input 3x3 convolutions in training (ops.SpikeConvTrainFunction); False = library forward
-    exact_train_forward = True
-
     def exact_conv_fits(self, blocks, x):
         """True for a single conv-only block whose convolution the exact MFMA training forward takes on spikes x."""
-        if blocks is None or len(blocks) != 1 or blocks[0][2] is not None or blocks[0][1] is not None or not self.exact_train_forward:
+        if blocks is None or len(blocks) != 1 or blocks[0][2] is not None or blocks[0][1] is not None:
             return False
         conv = blocks[0][0]
-        w = conv.weight
-        if w.dim() == 4 and not w.is_contiguous(memory_format=torch.channels_last):
-            w.data = w.data.contiguous(memory_format=torch.channels_last)
-        return (isinstance(conv, layer.Conv2d) and conv.groups == 1 and tuple(conv.dilation) == (1, 1)
-                and conv.padding_mode == 'zeros' and conv.kernel_size[0] == conv.kernel_size[1]
-                and ops.den_fp6_supported(conv.out_channels, conv.in_channels, conv.kernel_size[0], conv.stride[0],
-                                          conv.padding[0] if not isinstance(conv.padding, str) else -1, x.shape[0],
-                                          x.shape[3], x.shape[4]))
+        keep_channels_last(conv.weight)
+        return exact_spike_conv(conv, x.shape[0], x.shape[3], x.shape[4])
 
     def train_forward(self, x, binary_input=False, prep=None, want_c4=False):
         """[T,B,C,H,W] -> spikes [T,B,C',H',W'] (or the raw conv output of a conv-only last block), differentiable.
@@ -231,16 +265,8 @@ class FusedSequential(nn.Sequential):
         if c4_in is not None:                          # (packed spikes, version of x they were made from): stale after an in-place write
             c4_in = c4_in[0] if c4_in[1] == x._version else None
         for bi, (conv, bn, lif) in enumerate(blocks):
-            w = conv.weight
-            if w.dim() == 4 and not w.is_contiguous(memory_format=torch.channels_last):
-                # keep the parameter itself channels-last while training: the library's NHWC kernels then read it (and
-                # write its gradient) without a per-call layout copy; values, shape and state_dict keys are unchanged
-                w.data = w.data.contiguous(memory_format=torch.channels_last)
-            if (binary_input and self.exact_train_forward and isinstance(conv, layer.Conv2d) and conv.groups == 1
-                    and tuple(conv.dilation) == (1, 1) and conv.padding_mode == 'zeros'
-                    and ops.den_fp6_supported(conv.out_channels, conv.in_channels, conv.kernel_size[0], conv.stride[0],
-                                              conv.padding[0] if not isinstance(conv.padding, str) else -1, x.shape[0],
-                                              x.shape[3], x.shape[4]) and conv.kernel_size[0] == conv.kernel_size[1]):
+            keep_channels_last(conv.weight)
+            if binary_input and exact_spike_conv(conv, x.shape[0], x.shape[3], x.shape[4]):
                 x = ops.SpikeConvTrainFunction.apply(x, conv.weight, conv.bias, prep if len(blocks) == 1 else None,
                                                      c4_in if bi == 0 else None)
             else:
@@ -284,29 +310,15 @@ class FusedSequential(nn.Sequential):
                                 geo['transposed'], T, H, W)
 
     @staticmethod
-    def _next_convT_fp6(block, cur, geo, T):
-        """Will ``block`` (the one after the layer with geometry ``geo`` applied to the PTC tensor ``cur``) take the fp6
-        transposed-convolution kernel?"""
+    def _next_convT_fp6(block, geo, H, W, T):
+        """Will ``block`` (the one after a layer of geometry ``geo`` on an H x W map) take the fp6 transposed-convolution
+        kernel?"""
         conv, bn, lif = block
         if bn is None or lif is None or has_hooks(conv) or has_hooks(bn) or has_hooks(lif):
             return False
         g2 = conv_geometry(conv)
-        Ho = ops.conv_out_size(cur.shape[1], geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-        Wo = ops.conv_out_size(cur.shape[2], geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
         return ops.convT_fp6_supported(conv.in_channels, conv.out_channels, g2['k'], g2['stride'], g2['pad'], g2['out_pad'],
-                                       g2['transposed'], T, Ho, Wo)
-
-    @staticmethod
-    def _next_convT_fp6_hw(block, H, W, geo, T):
-        """_next_convT_fp6 for a layer whose input map is H x W (S32 input: the map sits in dims 2, 3)."""
-        conv, bn, lif = block
-        if bn is None or lif is None or has_hooks(conv) or has_hooks(bn) or has_hooks(lif):
-            return False
-        g2 = conv_geometry(conv)
-        Ho = ops.conv_out_size(H, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-        Wo = ops.conv_out_size(W, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-        return ops.convT_fp6_supported(conv.in_channels, conv.out_channels, g2['k'], g2['stride'], g2['pad'], g2['out_pad'],
-                                       g2['transposed'], T, Ho, Wo)
+                                       g2['transposed'], T, *_out_hw(geo, H, W))
 
     @staticmethod
     def _collapsible(block, coef, T):
@@ -369,225 +381,212 @@ class FusedSequential(nn.Sequential):
             T = x.shape[-2]
         elif T is None:
             raise ValueError('T is required for a time-invariant input')
+        ctx = SimpleNamespace(blocks=blocks, T=T, final=final, in1=in1, coef=coef, apply_tanh=apply_tanh, want_u8=want_u8,
+                              stateful=stateful, want_pre=want_pre, chunk_out=chunk_out, impl=impl, want_counts=want_counts,
+                              need_radius=need_radius,
+                              out={'ptc': None, 'f32': None, 'u8': None, 'pre': [], 'cnt': None})
         cur, kind = x, in_kind
-        out = {'ptc': None, 'f32': None, 'u8': None, 'pre': [], 'cnt': None}
-        for bi, (conv, bn, lif) in enumerate(blocks):
+        for bi, (conv, _, _) in enumerate(blocks):
             with ops.timed(getattr(conv, '_spk_tag', None)):          # bench.py tags layers it wants timed in situ
-                last = bi == len(blocks) - 1
-                pr = conv_params(conv)
                 geo = conv_geometry(conv)
-                bias = None if conv.bias is None else conv.bias.detach()
-                src1 = in1 if (last and in1 is not None) else None
-                c4 = kind == IN_PTC and cur.dim() == 6 and cur.dtype == ops.C4_DTYPE
-                if c4 and cur.shape[-1] == 16 and lif is not None and not stateful and impl != 'direct' and not want_pre and src1 is None:
-                    # the VQ-VAE's stride-2 layers on the fp6 MFMA (stateless calls; csrc/vae_fp6.hip)
-                    vk = self._vae_kind(conv, geo, T, cur.shape[2], cur.shape[3])
-                    tail_ok = final == 'memout' and self._collapsible(blocks[-1], coef, T)
-                    if vk == ops.VAE_OUT_COLLAPSED and bi == len(blocks) - 2 and tail_ok:
-                        # decoder convT2, handing the read-out layer its time-collapsed spikes
-                        a, b = bn.affine_terms()
-                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
-                                              transposed=True, out_kind=vk, coef=coef)
-                        kind = 'collapsed'
-                        continue
-                    if (vk == ops.VAE_OUT_S32 and bi == len(blocks) - 3 and tail_ok and conv.out_channels % 32 == 0 and
-                            self._next_convT_fp6_hw(blocks[bi + 1], cur.shape[2], cur.shape[3], geo, T)):
-                        # decoder convT1 fed nibble-packed spikes directly (the token-table spike generator)
-                        a, b = bn.affine_terms()
-                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
-                                              transposed=True, out_kind=ops.VAE_OUT_S32)
-                        kind = IN_PTC
-                        continue
-                    if vk == ops.VAE_OUT_PTC and not last:
-                        a, b = bn.affine_terms()                  # encoder conv2: plain u8 PTC out for the 1x1 layer
-                        cur = ops.vae_fp6_fwd(cur, pr.get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
-                                              transposed=False, out_kind=vk)
-                        kind = IN_PTC
-                        continue
-                if c4 and cur.shape[-1] == 16:               # S32 records: the sampler's second-generation fp6 kernel
-                    ok = (impl != 'direct' and lif is not None and not want_pre and src1 is None and not geo['transposed'] and
-                          not stateful and
-                          ops.den_fp6v2_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], T,
-                                                  cur.shape[2], cur.shape[3]) and
-                          (not last or (final == 'ptc' and chunk_out == ops.CHUNK_S32)))
-                    if not ok:
-                        raise NotImplementedError('spkdiff: S32 spikes are only consumed by the fp6v2 MFMA conv (3x3/s1/p1 + BN + '
-                                                  'LIF, T=16, 7x7, fresh LIF state, S32 output)')
-                    a, b = bn.affine_terms()
-                    o = ops.den_conv3x3_mfma_fp6v2(cur, pr.get_fp6v2(conv), conv.out_channels, bn_a=a, bn_b=b,
-                                                   want_counts=last and want_counts, need_radius=need_radius)
-                    if last and want_counts:
-                        out['ptc'], out['cnt'] = o
-                    elif last:
-                        out['ptc'] = o
+                if kind == IN_PTC and cur.dim() == 6 and cur.dtype == ops.C4_DTYPE:
+                    if cur.shape[-1] == 16:
+                        nxt = self._vae_fp6(ctx, bi, geo, cur) or self._fp6v2(ctx, bi, geo, cur)
                     else:
-                        cur, kind = o, IN_PTC
-                    continue
-                if c4:
-                    ok = (impl != 'direct' and lif is not None and not want_pre and src1 is None and not geo['transposed'] and
-                          ops.den_fp6_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], T,
-                                                cur.shape[2], cur.shape[3]) and
-                          (not last or (final == 'ptc' and chunk_out == ops.CHUNK_C4)))
-                    if not ok:
-                        raise NotImplementedError('spkdiff: fp4-packed (C4) spikes are only consumed by the fp6 MFMA conv '
-                                                  '(3x3/s1/p1 + BN + LIF, T=16, C4 output)')
-                    a, b = bn.affine_terms()
-                    v = None
-                    if stateful:
-                        shape = (cur.shape[0], conv.out_channels, cur.shape[2], cur.shape[3])
-                        if isinstance(lif.v, float):
-                            lif.v = torch.full(shape, lif.v, dtype=torch.float32, device=cur.device)
-                        elif tuple(lif.v.shape) != shape:
-                            raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
-                                               f'{shape}; call functional.reset_net first')
-                        v = lif.v
-                    o = ops.den_conv3x3_mfma_fp6(cur, pr.get_fp6(conv), conv.out_channels, bn_a=a, bn_b=b, v=v,
-                                                 want_counts=last and want_counts)
-                    if last and want_counts:
-                        out['ptc'], out['cnt'] = o
-                    elif last:
-                        out['ptc'] = o
-                    else:
-                        cur, kind = o, IN_PTC
-                    continue
-                cptc = kind == IN_PTC and cur.dim() == 6 and cur.shape[-1] == 32 and (src1 is None or src1.dim() == 6)
-                use_mfma = (impl != 'direct' and cptc and not geo['transposed'] and not want_pre and
-                            (lif is not None or final == 'mean') and
-                            ops.den_mfma_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'],
-                                                   T, cur.shape[2], cur.shape[3]) and
-                            (lif is None or not last or (final == 'ptc' and chunk_out == 32)))
-                if use_mfma:
-                    packed = pr.get_i8(conv)
-                    if lif is not None:
-                        a, b = bn.affine_terms()
-                        v = None
-                        if stateful:
-                            shape = (cur.shape[0], conv.out_channels, cur.shape[2], cur.shape[3])
-                            if isinstance(lif.v, float):
-                                lif.v = torch.full(shape, lif.v, dtype=torch.float32, device=cur.device)
-                            elif tuple(lif.v.shape) != shape:
-                                raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
-                                                   f'{shape}; call functional.reset_net first')
-                            v = lif.v
-                        o = ops.den_conv3x3_mfma(cur, packed, conv.out_channels, mode=MODE_LIF, in1=src1, bn_a=a, bn_b=b, v=v,
-                                                 want_counts=last and want_counts)
-                        if last and want_counts:
-                            out['ptc'], out['cnt'] = o
-                        elif last:
-                            out['ptc'] = o
-                        else:
-                            cur, kind = o, IN_PTC
-                    else:
-                        out['f32'] = ops.den_conv3x3_mfma(cur, packed, conv.out_channels, mode=MODE_MEAN, in1=src1)
-                    continue
-                if kind == 'collapsed':                      # (see the producing block below)
-                    r = ops.readout_collapsed(cur, conv.weight.detach(), bias, coef, apply_tanh=apply_tanh, want_u8=want_u8,
-                                              k=geo['k'], pad=geo['pad'], transposed=geo['transposed'])
-                    out['f32'], out['u8'] = r['f32'], r['u8']
-                    continue
-                # spiking VQ-VAE layers: gather-MFMA kernel (plain PTC input, T = 16)
-                plain_ptc = kind == IN_PTC and cur.dim() == 5 and src1 is None
-                g_mode = MODE_LIF if lif is not None else (MODE_MEMOUT if final == 'memout' else None)
-                use_gather = (impl != 'direct' and plain_ptc and g_mode is not None and not want_pre and not want_counts and
-                              not (last and chunk_out) and
-                              ops.conv_mfma_supported(conv.in_channels, conv.out_channels, T, g_mode))
-                if use_gather:
-                    packed = pr.get_i8_generic(conv)
-                    if lif is not None:
-                        a, b = bn.affine_terms()
-                        v = None
-                        if stateful:
-                            Ho = ops.conv_out_size(cur.shape[1], geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                            Wo = ops.conv_out_size(cur.shape[2], geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                            shape = (cur.shape[0], conv.out_channels, Ho, Wo)
-                            if isinstance(lif.v, float):
-                                lif.v = torch.full(shape, lif.v, dtype=torch.float32, device=cur.device)
-                            elif tuple(lif.v.shape) != shape:
-                                raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
-                                                   f'{shape}; call functional.reset_net first')
-                            v = lif.v
-                        # the next block runs on the fp6 MFMA (decoder convT2, stateless call): it reads nibble-packed spikes;
-                        # this one (decoder convT1) does too where its shape has an instance
-                        if (not last and not stateful and impl != 'direct' and bi == len(blocks) - 3 and final == 'memout' and
-                                conv.out_channels % 32 == 0 and self._collapsible(blocks[-1], coef, T) and
-                                self._next_convT_fp6(blocks[bi + 1], cur, geo, T)):
-                            if self._vae_kind(conv, geo, T, cur.shape[1], cur.shape[2]) == ops.VAE_OUT_S32:
-                                cur = ops.vae_fp6_fwd(ops.ptc_to_s32(cur), pr.get_vae_fp6(conv), conv.out_channels,
-                                                      bn_a=a, bn_b=b, transposed=True, out_kind=ops.VAE_OUT_S32)
-                            else:
-                                cur = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=None,
-                                                          out_s32=True, **geo)
-                            kind = IN_PTC
-                            continue
-                        # a linear read-out layer next (conv-only last block + 'memout'): hand it sum_t coef[t] * spikes[t]
-                        # instead of the spike frames -- one convolution instead of T, no spike tensor in between
-                        if (not last and bi == len(blocks) - 2 and final == 'memout' and impl != 'direct' and
-                                self._collapsible(blocks[-1], coef, T)):
-                            cur = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=v,
-                                                      collapse_coef=coef, **geo)
-                            kind = 'collapsed'
-                            continue
-                        o = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=v, **geo)
-                        if last:
-                            out['ptc'] = o
-                            if final in ('f32', 'both'):
-                                out['f32'] = ops.ptc_to_spikes(o)
-                        else:
-                            cur, kind = o, IN_PTC
-                    else:
-                        r = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_MEMOUT, coef=coef,
-                                                apply_tanh=apply_tanh, want_u8=want_u8, **geo)
-                        out['f32'], out['u8'] = r['f32'], r['u8']
-                    continue
-                w_packed = pr.get(conv)
-                if lif is not None:
-                    a, b = bn.affine_terms()
-                    v = None
-                    if stateful:
-                        B = cur.shape[0] if kind != IN_SEQ else cur.shape[1]
-                        if kind == IN_PTC:
-                            H, W = (cur.shape[2], cur.shape[3]) if cur.dim() == 6 else (cur.shape[1], cur.shape[2])
-                        else:
-                            H, W = cur.shape[-2], cur.shape[-1]
-                        Ho = ops.conv_out_size(H, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                        Wo = ops.conv_out_size(W, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                        if isinstance(lif.v, float):
-                            lif.v = torch.full((B, conv.out_channels, Ho, Wo), lif.v, dtype=torch.float32,
-                                               device=cur.device)
-                        elif tuple(lif.v.shape) != (B, conv.out_channels, Ho, Wo):
-                            raise RuntimeError(f'LIFNode state has shape {tuple(lif.v.shape)} but the input implies '
-                                               f'{(B, conv.out_channels, Ho, Wo)}; call functional.reset_net first')
-                        v = lif.v
-                    co_chunk = chunk_out if last else None
-                    if (not last and not stateful and impl != 'direct' and not want_pre and conv.out_channels % 32 == 0 and
-                            blocks[bi + 1][2] is not None):
-                        # the next block runs on the fp6 MFMA (encoder conv2, stateless call): it reads nibble-packed spikes
-                        if kind == IN_PTC:
-                            Hi, Wi = (cur.shape[2], cur.shape[3]) if cur.dim() == 6 else (cur.shape[1], cur.shape[2])
-                        else:
-                            Hi, Wi = cur.shape[-2], cur.shape[-1]
-                        Hn = ops.conv_out_size(Hi, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                        Wn = ops.conv_out_size(Wi, geo['k'], geo['stride'], geo['pad'], geo['transposed'], geo['out_pad'])
-                        nconv = blocks[bi + 1][0]
-                        if self._vae_kind(nconv, conv_geometry(nconv), T, Hn, Wn) == ops.VAE_OUT_PTC and bi + 1 < len(blocks) - 1:
-                            co_chunk = ops.CHUNK_S32
-                    r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=T, mode=MODE_LIF, in1=src1, bn_a=a, bn_b=b,
-                                       v=v, want_ptc=(not last) or final in ('ptc', 'both'),
-                                       want_f32=last and final in ('f32', 'both'), want_pre=want_pre,
-                                       chunk_out=co_chunk, want_counts=last and want_counts, **geo)
-                    if want_pre:
-                        out['pre'].append(r['pre'])
-                    if last:
-                        out['ptc'], out['f32'], out['cnt'] = r['ptc'], r['f32'], r['cnt']
-                    else:
-                        cur, kind = r['ptc'], IN_PTC
+                        nxt = self._fp6(ctx, bi, geo, cur)
+                elif self._i8_fits(ctx, bi, geo, cur, kind):
+                    nxt = self._i8(ctx, bi, cur)
+                elif kind == 'collapsed':
+                    nxt = self._readout(ctx, bi, geo, cur)
+                elif self._gather_fits(ctx, bi, cur, kind):
+                    nxt = self._gather(ctx, bi, geo, cur)
                 else:
-                    if final == 'memout':
-                        r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=T, mode=MODE_MEMOUT, in1=src1, coef=coef,
-                                           apply_tanh=apply_tanh, want_u8=want_u8, **geo)
-                    elif final == 'mean':
-                        r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=T, mode=MODE_MEAN, in1=src1, **geo)
-                    else:
-                        r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=T, mode=MODE_RAW, in1=src1, **geo)
-                    out['f32'], out['u8'] = r['f32'], r['u8']
-        return out
+                    nxt = self._direct(ctx, bi, geo, cur, kind)
+                if nxt is not None:
+                    cur, kind = nxt
+        return ctx.out
+
+    # One method per input layout.  Each returns the next block's input (tensor, kind) or, for the last block, fills ctx.out.
+
+    @staticmethod
+    def _spikes_out(ctx, bi, o):
+        """Spikes ``o`` of block bi: the next block's input, or the last block's result (with its counts when asked for)."""
+        if bi < len(ctx.blocks) - 1:
+            return o, IN_PTC
+        ctx.out['ptc'], ctx.out['cnt'] = o if ctx.want_counts else (o, None)
+        return None
+
+    def _vae_fp6(self, ctx, bi, geo, cur):
+        """The VQ-VAE's stride-2 layers on the fp6 MFMA (S32 input, stateless calls; csrc/vae_fp6.hip); None where no such
+        form exists."""
+        conv, bn, lif = ctx.blocks[bi]
+        n = len(ctx.blocks)
+        if lif is None or ctx.stateful or ctx.impl == 'direct' or ctx.want_pre or (bi == n - 1 and ctx.in1 is not None):
+            return None
+        H, W = cur.shape[2], cur.shape[3]
+        vk = self._vae_kind(conv, geo, ctx.T, H, W)
+        tail_ok = ctx.final == 'memout' and self._collapsible(ctx.blocks[-1], ctx.coef, ctx.T)
+        if vk == ops.VAE_OUT_COLLAPSED and bi == n - 2 and tail_ok:
+            kind = 'collapsed'          # decoder convT2, handing the read-out layer its time-collapsed spikes
+        elif (vk == ops.VAE_OUT_S32 and bi == n - 3 and tail_ok and conv.out_channels % 32 == 0 and
+              self._next_convT_fp6(ctx.blocks[bi + 1], geo, H, W, ctx.T)):
+            kind = IN_PTC               # decoder convT1 fed nibble-packed spikes directly (the token-table spike generator)
+        elif vk == ops.VAE_OUT_PTC and bi < n - 1:
+            kind = IN_PTC               # encoder conv2: plain u8 PTC out for the 1x1 layer
+        else:
+            return None
+        a, b = bn.affine_terms()
+        return ops.vae_fp6_fwd(cur, conv_params(conv).get_vae_fp6(conv), conv.out_channels, bn_a=a, bn_b=b,
+                               transposed=geo['transposed'], out_kind=vk,
+                               coef=ctx.coef if vk == ops.VAE_OUT_COLLAPSED else None), kind
+
+    def _fp6v2(self, ctx, bi, geo, cur):
+        """S32 records: the sampler's second-generation fp6 kernel."""
+        conv, bn, lif = ctx.blocks[bi]
+        last = bi == len(ctx.blocks) - 1
+        ok = (ctx.impl != 'direct' and lif is not None and not ctx.want_pre and not (last and ctx.in1 is not None) and
+              not geo['transposed'] and not ctx.stateful and
+              ops.den_fp6v2_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], ctx.T,
+                                      cur.shape[2], cur.shape[3]) and
+              (not last or (ctx.final == 'ptc' and ctx.chunk_out == ops.CHUNK_S32)))
+        if not ok:
+            raise NotImplementedError('spkdiff: S32 spikes are only consumed by the fp6v2 MFMA conv (3x3/s1/p1 + BN + '
+                                      'LIF, T=16, 7x7, fresh LIF state, S32 output)')
+        a, b = bn.affine_terms()
+        o = ops.den_conv3x3_mfma_fp6v2(cur, conv_params(conv).get_fp6v2(conv), conv.out_channels, bn_a=a, bn_b=b,
+                                       want_counts=last and ctx.want_counts, need_radius=ctx.need_radius)
+        return self._spikes_out(ctx, bi, o)
+
+    def _fp6(self, ctx, bi, geo, cur):
+        """C4 records: the block-scaled fp6 kernel."""
+        conv, bn, lif = ctx.blocks[bi]
+        last = bi == len(ctx.blocks) - 1
+        ok = (ctx.impl != 'direct' and lif is not None and not ctx.want_pre and not (last and ctx.in1 is not None) and
+              not geo['transposed'] and
+              ops.den_fp6_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], ctx.T,
+                                    cur.shape[2], cur.shape[3]) and
+              (not last or (ctx.final == 'ptc' and ctx.chunk_out == ops.CHUNK_C4)))
+        if not ok:
+            raise NotImplementedError('spkdiff: fp4-packed (C4) spikes are only consumed by the fp6 MFMA conv '
+                                      '(3x3/s1/p1 + BN + LIF, T=16, C4 output)')
+        a, b = bn.affine_terms()
+        v = _lif_state(lif, cur.shape[0], conv.out_channels, cur.shape[2], cur.shape[3], cur.device, ctx.stateful)
+        o = ops.den_conv3x3_mfma_fp6(cur, conv_params(conv).get_fp6(conv), conv.out_channels, bn_a=a, bn_b=b, v=v,
+                                     want_counts=last and ctx.want_counts)
+        return self._spikes_out(ctx, bi, o)
+
+    @staticmethod
+    def _i8_fits(ctx, bi, geo, cur, kind):
+        conv, _, lif = ctx.blocks[bi]
+        last = bi == len(ctx.blocks) - 1
+        src1 = ctx.in1 if last else None
+        return (ctx.impl != 'direct' and kind == IN_PTC and cur.dim() == 6 and cur.shape[-1] == 32 and
+                (src1 is None or src1.dim() == 6) and not geo['transposed'] and not ctx.want_pre and
+                (lif is not None or ctx.final == 'mean') and
+                ops.den_mfma_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], ctx.T,
+                                       cur.shape[2], cur.shape[3]) and
+                (lif is None or not last or (ctx.final == 'ptc' and ctx.chunk_out == 32)))
+
+    def _i8(self, ctx, bi, cur):
+        """CPTC u8 records: the int8 MFMA kernel of the denoiser."""
+        conv, bn, lif = ctx.blocks[bi]
+        last = bi == len(ctx.blocks) - 1
+        src1 = ctx.in1 if last else None
+        packed = conv_params(conv).get_i8(conv)
+        if lif is None:
+            ctx.out['f32'] = ops.den_conv3x3_mfma(cur, packed, conv.out_channels, mode=MODE_MEAN, in1=src1)
+            return None
+        a, b = bn.affine_terms()
+        v = _lif_state(lif, cur.shape[0], conv.out_channels, cur.shape[2], cur.shape[3], cur.device, ctx.stateful)
+        o = ops.den_conv3x3_mfma(cur, packed, conv.out_channels, mode=MODE_LIF, in1=src1, bn_a=a, bn_b=b, v=v,
+                                 want_counts=last and ctx.want_counts)
+        return self._spikes_out(ctx, bi, o)
+
+    @staticmethod
+    def _readout(ctx, bi, geo, cur):
+        """Time-collapsed spikes (see the producing blocks): the linear read-out layer as one convolution."""
+        conv = ctx.blocks[bi][0]
+        r = ops.readout_collapsed(cur, conv.weight.detach(), None if conv.bias is None else conv.bias.detach(), ctx.coef,
+                                  apply_tanh=ctx.apply_tanh, want_u8=ctx.want_u8, k=geo['k'], pad=geo['pad'],
+                                  transposed=geo['transposed'])
+        ctx.out['f32'], ctx.out['u8'] = r['f32'], r['u8']
+
+    @staticmethod
+    def _gather_fits(ctx, bi, cur, kind):
+        conv, _, lif = ctx.blocks[bi]
+        last = bi == len(ctx.blocks) - 1
+        mode = MODE_LIF if lif is not None else (MODE_MEMOUT if ctx.final == 'memout' else None)
+        return (ctx.impl != 'direct' and kind == IN_PTC and cur.dim() == 5 and not (last and ctx.in1 is not None) and
+                mode is not None and not ctx.want_pre and not ctx.want_counts and not (last and ctx.chunk_out) and
+                ops.conv_mfma_supported(conv.in_channels, conv.out_channels, ctx.T, mode))
+
+    def _gather(self, ctx, bi, geo, cur):
+        """Plain PTC spikes (the spiking VQ-VAE's layers, T = 16): the gather-MFMA kernel."""
+        conv, bn, lif = ctx.blocks[bi]
+        n = len(ctx.blocks)
+        packed = conv_params(conv).get_i8_generic(conv)
+        if lif is None:
+            r = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_MEMOUT, coef=ctx.coef,
+                                    apply_tanh=ctx.apply_tanh, want_u8=ctx.want_u8, **geo)
+            ctx.out['f32'], ctx.out['u8'] = r['f32'], r['u8']
+            return None
+        a, b = bn.affine_terms()
+        H, W = cur.shape[1], cur.shape[2]
+        v = _lif_state(lif, cur.shape[0], conv.out_channels, *_out_hw(geo, H, W), cur.device, ctx.stateful)
+        # the next block runs on the fp6 MFMA (decoder convT2, stateless call): it reads nibble-packed spikes;
+        # this one (decoder convT1) does too where its shape has an instance
+        if (bi == n - 3 and not ctx.stateful and ctx.final == 'memout' and conv.out_channels % 32 == 0 and
+                self._collapsible(ctx.blocks[-1], ctx.coef, ctx.T) and
+                self._next_convT_fp6(ctx.blocks[bi + 1], geo, H, W, ctx.T)):
+            if self._vae_kind(conv, geo, ctx.T, H, W) == ops.VAE_OUT_S32:
+                return ops.vae_fp6_fwd(ops.ptc_to_s32(cur), conv_params(conv).get_vae_fp6(conv), conv.out_channels,
+                                       bn_a=a, bn_b=b, transposed=True, out_kind=ops.VAE_OUT_S32), IN_PTC
+            return ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=None,
+                                       out_s32=True, **geo), IN_PTC
+        # a linear read-out layer next (conv-only last block + 'memout'): hand it sum_t coef[t] * spikes[t]
+        # instead of the spike frames -- one convolution instead of T, no spike tensor in between
+        if bi == n - 2 and ctx.final == 'memout' and self._collapsible(ctx.blocks[-1], ctx.coef, ctx.T):
+            return ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=v,
+                                       collapse_coef=ctx.coef, **geo), 'collapsed'
+        o = ops.conv_mfma_fused(cur, packed, conv.out_channels, mode=MODE_LIF, bn_a=a, bn_b=b, v=v, **geo)
+        if bi == n - 1 and ctx.final in ('f32', 'both'):
+            ctx.out['f32'] = ops.ptc_to_spikes(o)
+        return self._spikes_out(ctx, bi, o)
+
+    def _direct(self, ctx, bi, geo, cur, kind):
+        """Any other input (fp32 sequence, time-invariant fp32, PTC u8 the MFMA kernels do not take): the direct kernels."""
+        conv, bn, lif = ctx.blocks[bi]
+        n = len(ctx.blocks)
+        last = bi == n - 1
+        src1 = ctx.in1 if last else None
+        bias = None if conv.bias is None else conv.bias.detach()
+        w_packed = conv_params(conv).get(conv)
+        if lif is None:
+            if ctx.final == 'memout':
+                r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=ctx.T, mode=MODE_MEMOUT, in1=src1, coef=ctx.coef,
+                                   apply_tanh=ctx.apply_tanh, want_u8=ctx.want_u8, **geo)
+            else:
+                r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=ctx.T, in1=src1,
+                                   mode=MODE_MEAN if ctx.final == 'mean' else MODE_RAW, **geo)
+            ctx.out['f32'], ctx.out['u8'] = r['f32'], r['u8']
+            return None
+        a, b = bn.affine_terms()
+        Ho, Wo = _out_hw(geo, *_in_hw(cur, kind))
+        v = _lif_state(lif, cur.shape[1] if kind == IN_SEQ else cur.shape[0], conv.out_channels, Ho, Wo, cur.device,
+                       ctx.stateful)
+        co_chunk = ctx.chunk_out if last else None
+        if (bi < n - 2 and not ctx.stateful and ctx.impl != 'direct' and not ctx.want_pre and conv.out_channels % 32 == 0 and
+                ctx.blocks[bi + 1][2] is not None):
+            # the next block runs on the fp6 MFMA (encoder conv2, stateless call): it reads nibble-packed spikes
+            nconv = ctx.blocks[bi + 1][0]
+            if self._vae_kind(nconv, conv_geometry(nconv), ctx.T, Ho, Wo) == ops.VAE_OUT_PTC:
+                co_chunk = ops.CHUNK_S32
+        r = ops.conv_fused(cur, w_packed, bias, in_kind=kind, T=ctx.T, mode=MODE_LIF, in1=src1, bn_a=a, bn_b=b, v=v,
+                           want_ptc=not last or ctx.final in ('ptc', 'both'), want_f32=last and ctx.final in ('f32', 'both'),
+                           want_pre=ctx.want_pre, chunk_out=co_chunk, want_counts=last and ctx.want_counts, **geo)
+        if ctx.want_pre:
+            ctx.out['pre'].append(r['pre'])
+        if not last:
+            return r['ptc'], IN_PTC
+        ctx.out['ptc'], ctx.out['f32'], ctx.out['cnt'] = r['ptc'], r['f32'], r['cnt']
+        return None

@@ -2,7 +2,7 @@
 
 usage: python tools/train_step_time.py [B] [steps] [--modular]
 --modular runs the blocks module by module (library convolution and BatchNorm + the LIF-only HIP pair) instead of the fused
-graph; --library-forward keeps the fused block tails but uses the library's forward convolutions."""
+graph."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "spiking-diffusion_amd"), ROOT]
@@ -19,8 +19,6 @@ if "--modular" in sys.argv:
             x = m(x)
         return x
     fused.FusedSequential.train_forward = _module_by_module
-if "--library-forward" in sys.argv:
-    fused.FusedSequential.exact_train_forward = False
 dev = torch.device("cuda")
 den = DummyModel(1, 128).cuda(0)
 functional.set_step_mode(net=den, step_mode='m')
