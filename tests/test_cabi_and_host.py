@@ -383,6 +383,29 @@ def test_round4_training_entry_points_check_their_arguments_on_the_host():
     assert lib.spk_conv3x3_wgrad_small(None, None, None, 0, None, None, 8, 7, 7, 64, 2, 1, None) == -1
 
 
+def test_conv_train_boundary_cases_land_on_the_side_they_claim():
+    """tests/_conv_train_cases.py: the shapes the GPU suite runs on either side of CT_BIG_ITEMS, CT_C1_ROWS_CAP, CT_C1W_CAP and the
+    weight gradient's workgroup cap still sit there (the thresholds are read from csrc/conv_train.hip), the register-form cases
+    stay off the LDS form, and the host mirror's workgroup counts are the library's (its workspace size is nwg partials)."""
+    import _conv_train_cases as cases
+    from spkdiff import _lib
+    lib = _lib.lib
+    all_cases = cases.BOUNDARY_CASES + cases.REGISTER_WGRAD_CASES
+    assert cases.check_claims(all_cases) == []
+    assert len({c["id"] for c in all_cases}) == len(all_cases)
+    assert sorted(cases.launch(c)["ntw"] for c in cases.REGISTER_WGRAD_CASES) == [1, 2, 3, 3, 4, 5]
+    assert {(cases.wgrad_args(c["layer"], c["N"])[-1], cases.launch(c)["bias_vec4"]) for c in cases.REGISTER_WGRAD_CASES} == \
+        {(1, False), (1, True), (2, False), (2, True)}
+    for c in all_cases:
+        L = cases.launch(c)
+        if c["op"] == "wgrad":
+            n, hu, wu, cu, hv, wv, cv, k, s, p, bf = cases.wgrad_args(c["layer"], c["N"])
+            assert lib.spk_conv_train_wgrad_ws_bytes(n, hv, wv, cu, cv, k) == L["ws_bytes"], c["id"]
+        else:
+            n, hi, wi, cred, ho, wo, cout, k, s, p, form = cases.gather_args(c["layer"], c["N"], c["op"])
+            assert lib.spk_conv_train_gather_supported(cred, cout, k, s, form) == 1, c["id"]
+
+
 def test_training_convolution_entry_points_reject_and_accept_on_the_host():
     """csrc/conv_train.hip: the support queries and the argument checks run on the host (no launch): the six layers of the MNIST
     model and the first / read-out layers of the RGB model are taken in every direction they are used, shapes outside the limits
