@@ -685,6 +685,25 @@ int spk_svae_latent_loss_bwd(const float* q_z, const float* p_z_or_null, const i
 int spk_vq_code_usage(const long long* idx, long long N, int K, long long* hist_out, long long* stats_out, void* ws,
                       spk_stream_t stream);
 
+/* ---- reconstruction metrics of main.py: SSIM and MSE (csrc/ssim.hip) ------------------------------------------------ */
+/* Workspace of spk_ssim_mse in bytes (two fp64 partials per 32x32 tile of every output plane), or the SPK_ERR_* code
+ * spk_ssim_mse would return for these sizes. */
+long long spk_ssim_mse_ws_bytes(int N, int C, int H, int W, int window_size);
+/* The per-batch metrics of R/main.py:318-320 in one launch (two when an image has several channels or tiles): _ssim of R/metric/pytorch_ssim/__init__.py:17-39 (five depthwise
+ * window convolutions with zero padding window_size / 2, the SSIM map, its mean) and the squared error of F.mse_loss.  img1,
+ * img2 fp32 [N,C,H,W] contiguous; window2d fp32 [window_size, window_size], the values of create_window (:11-15).  Inputs and
+ * window are widened to fp64 and every product, window sum (direct 2-D form), map value and reduction is fp64:
+ *   ssim_sum_out fp64 [N] = sum of the SSIM map of image n over (C, H', W'), H' = H + 2 (window_size / 2) - window_size + 1
+ *                           (H for an odd window, H + 1 for an even one; a window larger than the image is legal);
+ *   sq_sum_out   fp64 [N] = sum of (img1 - img2)^2 of image n over (C, H, W).
+ * SSIM(size_average=True) = sum(ssim_sum) / (N C H' W'), size_average=False = ssim_sum / (C H' W'), mse = sum(sq_sum) / (N C H W).
+ * A NaN in an image makes that image's two sums NaN and no other's.  Fixed-order reductions, no floating-point atomics: two
+ * calls give bit-equal results.  ws_buf: spk_ssim_mse_ws_bytes bytes, 8-byte aligned, this call's alone while it is in flight;
+ * nothing is expected of its contents (the per-tile partials are written before the second launch reads them); capturable in a
+ * hipGraph.  SPK_ERR_UNSUPPORTED for window_size > 31 or 2^31 tiles and more. */
+int spk_ssim_mse(const float* img1, const float* img2, const float* window2d, double* ssim_sum_out, double* sq_sum_out,
+                 void* ws_buf, int N, int C, int H, int W, int window_size, spk_stream_t stream);
+
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every
  * matrix-core number: devices of one pool differ by ~10 %).  nblocks workgroups of 256 threads issue 4*iters MFMAs per

@@ -151,6 +151,8 @@ _SIGS = {
     "spk_svae_latent_loss_fwd": (c_int, [P] * 6 + [c_int] * 4 + [c_float, P]),
     "spk_svae_latent_loss_bwd": (c_int, [P] * 7 + [c_int] * 4 + [c_float, P]),
     "spk_vq_code_usage": (c_int, [P, c_longlong, c_int, P, P, P, P]),
+    "spk_ssim_mse_ws_bytes": (c_longlong, [c_int] * 5),
+    "spk_ssim_mse": (c_int, [P] * 6 + [c_int] * 5 + [P]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -1685,6 +1685,57 @@ def vq_code_usage(idx, K):
     return _code_usage_views(packed, K)
 
 
+SSIM_MAX_WINDOW = 31         # spk_ssim_mse stages a 32x32 tile plus the window's halo in LDS
+
+
+def ssim_mse_out_size(n, window_size):
+    """H' of the SSIM map: F.conv2d(padding=window_size // 2) of an n-pixel side (n for an odd window, n + 1 for an even one)."""
+    return n + 2 * (window_size // 2) - window_size + 1
+
+
+def ssim_mse(img1, img2, window2d, ws=None, out=None):
+    """img1, img2 fp32 [N,C,H,W] and the 2-D window fp32 [ws,ws] of metric.pytorch_ssim.create_window (device) ->
+    (ssim_sum fp64 [N], sq_sum fp64 [N]): per image the sum of the SSIM map over (C, H', W') and the sum of (img1 - img2)^2
+    over (C, H, W), fp64 arithmetic, one launch (spk_ssim_mse), deterministic, no host synchronisation.  ``ws``: a workspace
+    of ``ssim_mse_ws(...)`` to reuse (this call's alone while it is in flight); ``out``: fp64 [2, N] to write (rows ssim_sum,
+    sq_sum)."""
+    img1 = _dev(img1, "img1", torch.float32)
+    img2 = _dev(img2, "img2", torch.float32)
+    window2d = _dev(window2d, "window2d", torch.float32)
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError(f"ssim_mse: img1 {tuple(img1.shape)} and img2 {tuple(img2.shape)} must be equal [N,C,H,W] shapes")
+    if img2.device != img1.device or window2d.device != img1.device:
+        raise ValueError("ssim_mse: img1, img2 and window2d must be on one device")
+    if window2d.dim() != 2 or window2d.shape[0] != window2d.shape[1]:
+        raise ValueError(f"ssim_mse: window2d must be [ws, ws], got {tuple(window2d.shape)}")
+    N, C, H, W = img1.shape
+    wsz = int(window2d.shape[0])
+    nbytes = int(lib.spk_ssim_mse_ws_bytes(N, C, H, W, wsz))
+    if nbytes < 0:
+        check(nbytes, "spk_ssim_mse_ws_bytes")
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=img1.device)
+    elif not (ws.is_cuda and ws.device == img1.device and ws.is_contiguous() and ws.data_ptr() % 8 == 0
+              and ws.numel() * ws.element_size() >= nbytes):
+        raise ValueError(f"ssim_mse: ws must be a contiguous 8-byte aligned device buffer of at least {nbytes} bytes")
+    if out is None:
+        out = torch.empty((2, N), dtype=torch.float64, device=img1.device)
+    elif not (out.is_cuda and out.device == img1.device and out.dtype == torch.float64 and out.is_contiguous()
+              and out.shape == (2, N)):
+        raise ValueError(f"ssim_mse: out must be a contiguous fp64 [2, {N}] device tensor")
+    check(lib.spk_ssim_mse(_p(img1), _p(img2), _p(window2d), _p(out[0]), _p(out[1]), _p(ws), N, C, H, W, wsz, _stream(img1)),
+          "spk_ssim_mse")
+    return out[0], out[1]
+
+
+def ssim_mse_ws(N, C, H, W, window_size, device):
+    """A workspace for ssim_mse calls of this shape."""
+    nbytes = int(lib.spk_ssim_mse_ws_bytes(N, C, H, W, window_size))
+    if nbytes < 0:
+        check(nbytes, "spk_ssim_mse_ws_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
 def _vq_train_ws(device):
     """Block partials and the last-block ticket of spk_vq_train_quant / _bwd, spk_psp_loss_fwd and spk_recon_loss_fwd.  The
     ticket protocol needs the buffer to itself while a launch is in flight, so it is one buffer per (device, stream) -- or per
