@@ -11,7 +11,8 @@
 //    fifth digit) sit in ONE lane: no cross-lane exchange in the epilogue, and all 64 lanes scan their own neuron.
 // 2. FOUR DIGITS ON THE MATRIX CORES, THE LAST TWO ONLY WHERE THEY MATTER.  The fifth and sixth digit move a pre-activation by
 //    at most 528 units of 2^-s per ACTIVE input.  The main kernel multiplies the four leading digits (18 instead of 27 MFMAs
-//    per row tile and 32-channel chunk: two digit pairs per tap), counts the active inputs of every row while their fragments
+//    per row tile and 32-channel chunk: two digit pairs per tap; 15.25 on average on full 7x7 items, whose border tiles leave
+//    out the taps that read only the zero border: "BORDER SKIP" below), counts the active inputs of every row while their fragments
 //    pass through its registers (four v_bcnt per fragment), recombines in fp32, and CERTIFIES every spike decision: every
 //    neuron carries a running bound D_t on |h_approx - h_exact| (the dropped digits for the counted inputs of each step, the
 //    fp32 recombination and every rounding of BN / LIF on either path, see "Certification" below) and is flagged when its
@@ -165,7 +166,83 @@ __device__ const uint8_t V2_HALF_REC[2][64] = {
     {24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47,
      47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 47, 24}};
 
-template <int H, int W, int NWV, bool SPLIT, int NTP, bool HALF = false>
+// BORDER SKIP (full 7x7 items).  A tap that reads only the zero border of the LDS image multiplies nothing: its MFMAs add exactly +0 to
+// an exact integer accumulation.  24 of the 49 positions lie on the border and miss 3 of their 9 taps (5 at a corner).  Position 48 is the
+// tail launch's; the other 23 are gathered by SIDE, one wave per side, so that both positions of a tile miss the same three taps and the
+// whole tap BLOCK -- its MFMAs, its two weight tiles, its fragment reads -- drops out of that wave's K loop:
+//   top    0 1 | 2 3 | 4 5            6 blocks x 3 tiles   (no taps 0 1 2)
+//   right  6 13 | 20 27 | 34 41       6 blocks x 3 tiles   (no taps 2 5 8)
+//   left   7 14 | 21 28 | 35 42       6 blocks x 3 tiles   (no taps 0 3 6)
+//   bottom 43 44 | 45 46 | 47 40      6 blocks x 3 tiles + taps 6 7 8 on the third tile alone (40 is interior)
+//   four interior waves               9 blocks x 3 tiles
+// i.e. 11 x 6 + 13 x 9 = 183 (tile, tap) steps per chunk instead of 216: 15.25 MFMAs per row tile and chunk on average instead of 18.
+// A K loop follows its class's block list: blocks in issue order, each one tap on the LAST nt tiles of the wave.  The bottom wave's
+// one-tile blocks come second, not last: behind the chunk barrier (four steps before the end) nothing may read the current buffers,
+// and a block's weight tiles are requested at the first step of the block before it.
+enum : int { V2_INT = 0, V2_TOP, V2_RIGHT, V2_LEFT, V2_BOTTOM, V2_NCLS };
+struct V2Plan { int nblk; int tap[9]; int nt[9]; };
+constexpr int V2_FT = 3;                                 // row tiles per wave of a full item
+constexpr V2Plan V2_PLAN[V2_NCLS] = {
+    {9, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {3, 3, 3, 3, 3, 3, 3, 3, 3}},
+    {6, {3, 4, 5, 6, 7, 8}, {3, 3, 3, 3, 3, 3}},
+    {6, {0, 1, 3, 4, 6, 7}, {3, 3, 3, 3, 3, 3}},
+    {6, {1, 2, 4, 5, 7, 8}, {3, 3, 3, 3, 3, 3}},
+    {9, {0, 6, 7, 8, 1, 2, 3, 4, 5}, {3, 1, 1, 1, 3, 3, 3, 3, 3}}};
+constexpr V2Plan v2_uniform_plan(int nt) {               // every other form: all nine taps on all tiles
+  V2Plan p = {9, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {}};
+  for (int b = 0; b < 9; ++b) p.nt[b] = nt;
+  return p;
+}
+constexpr int v2_plan_start(const V2Plan& p, int blk) {  // first step of a block (blk == nblk: the number of steps)
+  int n = 0;
+  for (int b = 0; b < blk; ++b) n += p.nt[b];
+  return n;
+}
+constexpr int v2_plan_blk(const V2Plan& p, int s) {      // block of a step
+  int b = 0;
+  while (s >= p.nt[b]) s -= p.nt[b++];
+  return b;
+}
+// [wave][tile][half] -> position; waves w and w + 4 share a SIMD: one border wave beside one interior wave, i.e. 45 / 45 / 45 / 48
+// steps per SIMD and chunk instead of 54.  Same box, three alternating passes, B = 256 (profiles/border_skip_ab.txt): den.conv4 /
+// conv5 launches 359-373 / 344-351 -> 334 / 312-314 us, dense reverse process 85.4-86.2 -> 77.5-77.8 ms.  Border waves 0 2 4 6
+// (two border waves on one SIMD, two interior waves on the next: the chunk again lasts 54 steps, only its LDS traffic falls):
+// 351-359 / 319-321 us, 79.4-79.7 ms.
+__device__ constexpr uint8_t V2_FULL_POS[8][V2_FT][2] = {
+    {{0, 1}, {2, 3}, {4, 5}},       {{6, 13}, {20, 27}, {34, 41}},  {{7, 14}, {21, 28}, {35, 42}},  {{43, 44}, {45, 46}, {47, 40}},
+    {{8, 9}, {10, 11}, {12, 15}},   {{16, 17}, {18, 19}, {22, 23}}, {{24, 25}, {26, 29}, {30, 31}}, {{32, 33}, {36, 37}, {38, 39}}};
+__device__ constexpr uint8_t V2_WAVE_CLS[8] = {V2_TOP, V2_RIGHT, V2_LEFT, V2_BOTTOM, V2_INT, V2_INT, V2_INT, V2_INT};
+// the table is a permutation of 0 .. 47, no (tile, tap) step is issued twice, and every step a wave omits lies outside the image for
+// BOTH positions of its tile
+constexpr bool v2_full_map_ok() {
+  bool seen[48] = {};
+  for (int w = 0; w < 8; ++w)
+    for (int i = 0; i < V2_FT; ++i)
+      for (int h = 0; h < 2; ++h) {
+        const int p = V2_FULL_POS[w][i][h];
+        if (p >= 48 || seen[p]) return false;
+        seen[p] = true;
+      }
+  for (int w = 0; w < 8; ++w) {
+    const V2Plan& pl = V2_PLAN[V2_WAVE_CLS[w]];
+    for (int i = 0; i < V2_FT; ++i)
+      for (int tap = 0; tap < 9; ++tap) {
+        int n = 0;
+        for (int b = 0; b < pl.nblk; ++b) n += pl.tap[b] == tap && i >= V2_FT - pl.nt[b];
+        if (n > 1) return false;
+        for (int h = 0; h < 2 && n == 0; ++h) {
+          const int y = V2_FULL_POS[w][i][h] / 7 + tap / 3 - 1, x = V2_FULL_POS[w][i][h] % 7 + tap % 3 - 1;
+          if (y >= 0 && y < 7 && x >= 0 && x < 7) return false;
+        }
+      }
+  }
+  return true;
+}
+static_assert(v2_full_map_ok(), "full 7x7 items: position table and block lists");
+
+// CLS (full 7x7 items): the wave class this instance serves; the kernel branches once per wave, so that a class's K loop, scan and
+// register allocation are its own (one body whose chunk loops alone were per class spilled 109 registers at the joins).
+template <int H, int W, int NWV, bool SPLIT, int NTP, bool HALF = false, int CLS = V2_INT>
 __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const int il, const int lanes, const int n_images,
                                            const int* __restrict__ slots) {
   constexpr bool PRUNE = NTP > 0;
@@ -176,9 +253,9 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   constexpr bool REC = !PRUNE;
   // AH (round 5): the chunk barrier sits four steps BEFORE the end of the chunk instead of at its start.  Every read of the
   // current buffers has been issued by then (the last spike fragment at step NSTEP - 5, the last weight tile at the first step of
-  // tap 7), so that barrier both publishes the next chunk's copies and releases the current buffers -- and the four steps behind
-  // it read the next chunk's first fragments: no LDS round trip in front of a chunk's first MFMA any more.  The first chunk of an
-  // item still starts with its reads (the fragment registers must not live through the epilogue).
+  // the last block but one), so that barrier both publishes the next chunk's copies and releases the current buffers -- and the
+  // four steps behind it read the next chunk's first fragments: no LDS round trip in front of a chunk's first MFMA any more.  The
+  // first chunk of an item still starts with its reads (the fragment registers must not live through the epilogue).
   // (Three slab buffers, the copies issued two chunks ahead, measured 1 % slower: conv4 376 against 373 us,
   //  profiles/r5_ab_kernel_variants.txt (4), (5).)
   constexpr int HW = H * W, PW = W + 1;
@@ -196,7 +273,9 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   constexpr int NA = Hin * PPR;
   constexpr int NPA = (NA + NWV - 1) / NWV;            // A pieces per wave
   constexpr int NPW = (W_PIECES + NWV - 1) / NWV;      // W pieces per wave
-  constexpr int NSTEP = 9 * NT;
+  constexpr bool BSKIP = NWV == 8 && !PRUNE && !SPLIT;  // full 7x7 items: per-wave block lists without the pure-border taps (V2_PLAN)
+  static_assert(!BSKIP || (H == 7 && W == 7 && NT == V2_FT), "border skip: the position table is for 7x7 items of three tiles per wave");
+  static_assert(BSKIP || CLS == V2_INT, "wave classes: full 7x7 items only");
   static_assert(NWV >= 8 || NACC * NT <= 16 || (NT - 1) * NACC <= N_AGPR + 2, "only the last tile may straddle the register files");
   constexpr bool AH = NWV == 8 && !PRUNE;                // (two waves per SIMD on full items)
   constexpr int NBUF = 2;                              // slab buffers: the copies of chunk c + 1 are issued during chunk c
@@ -217,17 +296,17 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
     for (int i = tid; i < NPP * 16; i += NWV * 64) s_cin[i] = 0;
   __syncthreads();         // no wave's first DMA piece may land in a cell another wave has yet to zero
 
-  // per-lane LDS byte offsets of this wave's A fragments (tile ti = wave + NWV * i), relative to tap (0, 0): the same cell for
-  // both K halves (digit-pair instructions)
+  // per-lane LDS byte offsets of this wave's A fragments (tile ti = wave + NWV * i; full 7x7 items: the positions of V2_FULL_POS),
+  // relative to tap (0, 0): the same cell for both K halves (digit-pair instructions)
   const int row = lane & 31, half = lane >> 5;
   const int hsel = (row >> 2) & 1, tt = (row & 3) + 4 * (row >> 3);
   int a_off[NT];
   int p_out[NT];                                          // output position of this lane's accumulator rows
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
-    const int p = 2 * (wave + NWV * i) + hsel;
+    const int p = BSKIP ? (int)V2_FULL_POS[wave & 7][i % V2_FT][hsel] : 2 * (wave + NWV * i) + hsel;
     a_off[i] = ((p / W) * PW + (p % W)) * POSB + tt * 16;
-    p_out[i] = 2 * (wave + NWV * i) + half;
+    p_out[i] = BSKIP ? (int)V2_FULL_POS[wave & 7][i % V2_FT][half] : 2 * (wave + NWV * i) + half;
   }
 
   // DMA piece table (wave-uniform): bits 0..13 source byte offset in the slab, 14..28 LDS byte offset in the image,
@@ -324,7 +403,7 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
       rec_off[k] = rec_ok[k] ? (((cl / W) + 1) * PW + 1 + (cl % W)) * POSB + t * 16 : 0;
     }
     constexpr int PFX = NWV == 4 ? SPK_V2_PF : 4;
-    v6i bp[2][2];                                         // digit-pair tiles of tap parity [tap & 1][pair]   (AH: carried over the
+    v6i bp[2][2];                                         // digit-pair tiles of block parity [blk & 1][pair]  (AH: carried over the
     v4i af[PFX];                                          //  chunks of an item: a chunk's last steps fill them for the next one)
     for (int c = 0; c < nch; ++c, ++it) {
       const int buf = it & 1, buf1 = buf ^ 1;             // this chunk's buffers, the next chunk's (where this chunk's copies go)
@@ -349,13 +428,28 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
         const uint8_t* A = sA + buf * A_BYTES + band_off;
         const uint8_t* Wb = sW + buf * W_LDS;
         auto toff = [](int tap) constexpr -> int { return ((tap / 3) * PW + (tap % 3)) * POSB; };
-        // Step order: blocks of NT steps (one per row tile), one block per tap; a step issues the two digit-pair MFMAs
-        constexpr int NBLK = 9;
-        auto lda = [&](auto s_tag) -> v4i {
+        // Step order: the blocks of the wave's list (V2Plan), one tap per block, one step per row tile of the block; a step issues
+        // the two digit-pair MFMAs
+        constexpr V2Plan P = BSKIP ? V2_PLAN[CLS] : v2_uniform_plan(NT);
+        constexpr int NBLK = P.nblk, NSTEP = v2_plan_start(P, NBLK);
+        constexpr int PF = PFX;
+        constexpr int NPIECES = NPA + NPW;
+        // what the schedule below relies on:
+        static_assert(P.nt[0] == NT, "the first block writes (not accumulates) every accumulator");
+        static_assert(2 * NBLK >= NPIECES, "two copy slots per block: every DMA piece of the wave gets one");
+        static_assert((!AH || NSTEP >= 2 * PF) && (!REC || NSTEP > SPK_V2_REC_STEP), "look-ahead slots; the record-count steps exist");
+        // AH, the chunk barrier at step NSTEP - PF: the copies are issued in front of it (it waits for them), and so is every read of
+        // the current buffers -- the last fragment at step NSTEP - PF - 1 by construction, the last weight tiles at the first step of
+        // the last block but one (8x8 bands, two tiles per wave: in the step that opens with the barrier; the first copy into these
+        // buffers is PF steps behind it)
+        static_assert(!AH || (v2_plan_start(P, (NPIECES + 1) / 2) <= NSTEP - PF && v2_plan_start(P, NBLK - 2) <= NSTEP - PF),
+                      "chunk barrier behind the copies and the last weight-tile read");
+        auto lda_at = [&](const uint8_t* base, auto s_tag) -> v4i {
           constexpr int s = decltype(s_tag)::value;
-          constexpr int blk = s / NT, i = s % NT;
-          return *reinterpret_cast<const v4i*>(A + a_off[i] + toff(blk));
+          constexpr int blk = v2_plan_blk(P, s), i = NT - P.nt[blk] + (s - v2_plan_start(P, blk));
+          return *reinterpret_cast<const v4i*>(base + a_off[i] + toff(P.tap[blk]));
         };
+        auto lda = [&](auto s_tag) -> v4i { return lda_at(A, s_tag); };
         auto ldb = [&](int tile) -> v6i {
           // 16 + 8 bytes per lane; the 8-byte read is volatile so that hipcc does not pair the tails of two tiles
           const uint8_t* p = Wb + tile * WT;
@@ -365,9 +459,8 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
           const v6i r = {x[0], x[1], x[2], x[3], y[0], y[1]};
           return r;
         };
-        constexpr int PF = PFX;
         if constexpr (!AH || FIRST) {
-          bp[0][0] = ldb(0); bp[0][1] = ldb(1);
+          bp[0][0] = ldb(2 * P.tap[0]); bp[0][1] = ldb(2 * P.tap[0] + 1);
           static_for<PF>([&](auto s_tag) { af[decltype(s_tag)::value] = lda(s_tag); });
         }
         // AH: the next chunk's buffers (this item's; the last chunk of an item reads nothing ahead)
@@ -376,7 +469,8 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
         const bool ahead = AH && c + 1 < nch;
         static_for<NSTEP>([&](auto s_tag) {
           constexpr int s = decltype(s_tag)::value;
-          constexpr int blk = s / NT, i = s % NT;
+          constexpr int blk = v2_plan_blk(P, s), nt = P.nt[blk], j = s - v2_plan_start(P, blk);   // step j of a block of nt tiles
+          constexpr int i = NT - nt + j;
           if constexpr (AH && s == NSTEP - PF) {
             // every read of this chunk's buffers is issued; this wave's copies of the next chunk have landed: the chunk barrier
             asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -387,25 +481,23 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
             // the slot just consumed takes the next chunk's step with the same slot number: steps NSTEP - 4 .. NSTEP - 1 free slots
             // (NSTEP - 4) % 4 ..., i.e. the next chunk's steps s' with s' % 4 == s % 4
             constexpr int k = s % PF;                         // (PF == 4: next step k lives in slot k)
-            if (ahead) af[k] = *reinterpret_cast<const v4i*>(An + a_off[k % NT] + toff(k / NT));
+            if (ahead) af[k] = lda_at(An, std::integral_constant<int, k>{});
           }
-          constexpr int NPIECES = NPA + NPW;
           // two copy slots per block (its first step and its middle step): 18 slots for the 11 pieces of the four-digit form
 #define V2_DMA_SLOT()                                                                              \
   do {                                                                                             \
-    if constexpr (i == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);     \
-    if constexpr (i == (NT > 1 ? NT / 2 : 0) && 2 * blk + 1 < NPIECES)                             \
+    if constexpr (j == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);     \
+    if constexpr (j == (nt > 1 ? nt / 2 : 0) && 2 * blk + 1 < NPIECES)                             \
       issue_piece(2 * blk + 1, n_aslab, n_wslab, n_dA, n_dW);                                      \
   } while (0)
           // the next block's weight tiles are requested at the first step of this block
 #define V2_NEXT_TILES()                                                                            \
   do {                                                                                             \
-    if constexpr (i == 0 && blk + 1 < NBLK) {                                                      \
-      bp[(blk + 1) & 1][0] = ldb(2 * (blk + 1));                                                   \
-      bp[(blk + 1) & 1][1] = ldb(2 * (blk + 1) + 1);                                               \
+    if constexpr (j == 0 && blk + 1 < NBLK) {                                                      \
+      bp[(blk + 1) & 1][0] = ldb(2 * P.tap[(blk + 1) % 9]);                                        \
+      bp[(blk + 1) & 1][1] = ldb(2 * P.tap[(blk + 1) % 9] + 1);                                    \
     }                                                                                              \
   } while (0)
-          constexpr int tap = blk;
           if constexpr (!REC) {
             // (volatile: left to itself hipcc defers the pure popcounts and keeps every fragment of the chunk alive)
             asm volatile("v_bcnt_u32_b32 %0, %1, %0\n\tv_bcnt_u32_b32 %0, %2, %0\n\tv_bcnt_u32_b32 %0, %3, %0\n\t"
@@ -413,12 +505,12 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
           }
 #define V2_PAIR_MFMA(J)                                                                                      \
 do {                                                                                                        \
-  if constexpr (FIRST && tap == 0) {                                                                        \
+  if constexpr (FIRST && blk == 0) {                                                                        \
     if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA2_Z("a", acc[i][J], av, bp[0][J], sc_a, sc_p);              \
     else SPK_MFMA2_Z("v", acc[i][J], av, bp[0][J], sc_a, sc_p);                                             \
   } else {                                                                                                  \
-    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA2("a", acc[i][J], av, bp[tap & 1][J], sc_a, sc_p);          \
-    else SPK_MFMA2("v", acc[i][J], av, bp[tap & 1][J], sc_a, sc_p);                                         \
+    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA2("a", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);          \
+    else SPK_MFMA2("v", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);                                         \
   }                                                                                                         \
 } while (0)
           V2_PAIR_MFMA(0);
@@ -449,7 +541,7 @@ do {                                                                            
                 const v6i r = {x[0], x[1], x[2], x[3], y[0], y[1]};
                 return r;
               };
-              bp[0][0] = ldb_n(0); bp[0][1] = ldb_n(1);
+              bp[0][0] = ldb_n(2 * P.tap[0]); bp[0][1] = ldb_n(2 * P.tap[0] + 1);
             }
           }
         });
@@ -505,7 +597,7 @@ do {                                                                            
         }
       }
       int nmax_rec = 0;
-      if constexpr (REC) nmax_rec = s_nmax[2 * (wave + NWV * i) + half];     // (position within the item)
+      if constexpr (REC) nmax_rec = s_nmax[BSKIP ? p_out[i] : 2 * (wave + NWV * i) + half];     // (position within the item)
       // z = Q4 * Ac4 + Bc, Q4 = P01 * 2^10 + P23 (two steps at a time on the packed fp32 pipe); the dropped
       // digits move z_t by at most c_t = cE + cT n_t (n_t active inputs of the row).  D_t = D_{t-1} / 2 + c_t + 4 eps (|z_t| +
       // |v_{t-1}|) and |v| <= max |z| give D_t <= 2 (cE + cT max_t n_t) + 16 eps max_t |z_t| for every t: track max |z|,
@@ -543,7 +635,7 @@ do {                                                                            
         float v2 = 0.f, dh = 0.f;
         bool f2 = false;
         if constexpr (REC) {
-          const v4i* rp = reinterpret_cast<const v4i*>(s_row + (2 * (wave + NWV * i) + half) * 16);
+          const v4i* rp = reinterpret_cast<const v4i*>(s_row + (BSKIP ? p_out[i] : 2 * (wave + NWV * i) + half) * 16);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const v4i c4 = rp[q];
@@ -570,7 +662,7 @@ do {                                                                            
       const int ti = wave + NWV * i;
       // accumulator lane half == position within the tile; a list that does not fill its last tiles repeats its last
       // position there: computed and dropped
-      const int p = PRUNE ? p_out[i] : 2 * ti + half + band * HWb;
+      const int p = (PRUNE || BSKIP) ? p_out[i] : 2 * ti + half + band * HWb;
       const bool listed = !PRUNE || 2 * ti + half < n_list;
       if (flg && listed) {
         const long long n = ((long long)b * a.Cout + co) * HW + p;
@@ -628,7 +720,20 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_kernel(V2Args a) {
   const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
   int g, il, lanes;
   fp6v2_wg_map(a, g, il, lanes);
-  fp6v2_body<H, W, NWV, SPLIT, 0>(a, g, il, lanes, Bn, nullptr);
+  if constexpr (NWV == 8 && !SPLIT) {
+    // full 7x7 items: every wave runs the body of its class (wave-uniform; the eight waves meet at the same barriers whichever
+    // body they are in: the zeroing, one per chunk, two per item, the hand-over).  Five bodies are 68 KB of code against 15 KB for
+    // one (216 registers, no scratch, as before).  Top, right and left sharing ONE body whose tap offsets and weight-tile offsets
+    // sit in SGPRs (one address add per LDS read, 43 KB) measured the same: 77.5-78.1 against 77.5-77.8 ms per dense reverse
+    // process (profiles/border_skip_ab.txt) -- the compile-time form is kept, it needs no second addressing path.
+    switch (__builtin_amdgcn_readfirstlane((int)V2_WAVE_CLS[(threadIdx.x >> 6) & 7])) {
+      case V2_TOP: fp6v2_body<H, W, NWV, false, 0, false, V2_TOP>(a, g, il, lanes, Bn, nullptr); break;
+      case V2_RIGHT: fp6v2_body<H, W, NWV, false, 0, false, V2_RIGHT>(a, g, il, lanes, Bn, nullptr); break;
+      case V2_LEFT: fp6v2_body<H, W, NWV, false, 0, false, V2_LEFT>(a, g, il, lanes, Bn, nullptr); break;
+      case V2_BOTTOM: fp6v2_body<H, W, NWV, false, 0, false, V2_BOTTOM>(a, g, il, lanes, Bn, nullptr); break;
+      default: fp6v2_body<H, W, NWV, false, 0, false, V2_INT>(a, g, il, lanes, Bn, nullptr); break;
+    }
+  } else fp6v2_body<H, W, NWV, SPLIT, 0>(a, g, il, lanes, Bn, nullptr);
   fp6v2_handover(a);
 }
 
