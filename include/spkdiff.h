@@ -539,7 +539,9 @@ int spk_den_build_input(const float* x_float_or_null, const long long* x_tokens_
  * passes offset + b0 * HW * K and draws exactly what the whole job would draw for its images: the sample does not depend
  * on how a batch is split over devices); philox_state optional device {seed, base offset} pair that overrides
  * the seed and is added to the offset (lets a captured hipGraph draw fresh noise on every replay);
- * x0_hat_out optional int64 [B*HW].  active / n_active (both or neither; not with x0_hat_out): logits hold one slot
+ * x0_hat_out optional int64 [B*HW].  The token of a position is argmax_k softmax(logits / temp)_k / q_k, lowest k on a tie;
+ * a NaN ratio never wins, and a position without a comparable ratio (a NaN logit, or every logit -inf, where the reference's
+ * Categorical raises) gets token 0: the token is always in [0, K).  active / n_active (both or neither; not with x0_hat_out): logits hold one slot
  * per active image (slot s = image active[s]); noise, x_t and unmasked stay indexed by image.
  * next_input_b2hw_or_null (not with active): also writes cat(x_t, t - 1) fp32 [B,2,h,w] -- what spk_den_build_input would
  * produce for the NEXT reverse step (:195-197 with the updated tokens): one launch less per step. */

@@ -89,7 +89,9 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
     for (int j = 0; j < KPL; ++j) { e[j] = (lane + 64 * j < K) ? expf(l[j] - mx2) : 0.f; se2 += e[j]; }
     se2 = wave_sum(se2);
     float best = -INFINITY;
-    int besti = 0x7fffffff;
+    // a position without a single comparable ratio (a NaN logit, or every logit -inf: all ratios NaN) gets token 0 --
+    // torch.argmax's answer for an all-NaN row; a valid ratio is >= 0 and always beats this start
+    int besti = 0;
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
       const int k = lane + 64 * j;

@@ -1,5 +1,5 @@
 // Noise and wave-reduction helpers shared by the sampler kernels (psample.hip, step_tail.hip): the Philox4x32-10 counter
-// scheme of spk_psample_step (u: stream 0, counter offset + position; q: stream 1, counter offset + position * K + class) and
+// scheme of spk_psample_step (u: stream 0, counter offset + position * K; q: stream 1, counter offset + position * K + class) and
 // the 64-lane max / sum by lane shuffles.  Every kernel that draws noise goes through these, so that the dense loop, the
 // active-set forms, the fused step tail and spk_philox_noise see the same draws.
 #pragma once

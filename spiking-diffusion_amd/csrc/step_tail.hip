@@ -247,7 +247,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
     for (int j = 0; j < NJ; ++j) { e[j] = (lane + 64 * j < K) ? expf(l[j] - mx2) : 0.f; se2 += e[j]; }
     se2 = wave_sum(se2);
     float best = -INFINITY;
-    int besti = 0x7fffffff;
+    int besti = 0;                                 // (no comparable ratio -- NaN logit, all -inf: token 0, as psample_kernel)
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int k = lane + 64 * j;
