@@ -588,6 +588,28 @@ int spk_philox_noise(unsigned long long philox_seed, unsigned long long philox_o
                      const unsigned long long* philox_state_or_null, float* u_out_or_null, float* q_out_or_null, int B, int HW,
                      int K, spk_stream_t stream);
 
+/* ---- completion of partly given images (csrc/completion.hip) ---------------------------------------- */
+/* Start state of a conditional reverse process: the loop of R/snn_model/vq_diffusion.py:110-140 run from
+ *   unmasked = known & (0 <= code < K),   x_t = unmasked ? code : mask_id
+ * instead of the all-masked state (:106-107).  codes int64 [B,h,w]; keep_mask u8 [B,Hm,Wm] (non-zero = given) at a resolution
+ * related to the tokens by (stride, radius): token (i,j) is known iff every mask byte in rows stride*i - radius .. stride*i +
+ * radius and columns stride*j - radius .. stride*j + radius, clipped to the mask, is non-zero.  (1, 0): a mask at latent
+ * resolution.  (4, 3): a pixel mask seen through the encoder's receptive field (Conv 3x3 s2 p1 twice, then 1x1,
+ * R/snn_model/vae_model.py:101-129: code (i,j) reads pixels 4i-3 .. 4i+3; the zero padding outside the image counts as given).
+ * A code outside [0, K) is never known, so no out-of-range index reaches an embedding gather later.  x_t_out int64 [B,1,h,w],
+ * unmasked_out u8 [B,1,h,w], n_known_out (optional) int32 [B] = known tokens per image (a second small launch).  One thread per
+ * token; deterministic; capturable in a hipGraph.  SPK_ERR_ARG also when a token's window misses the mask altogether
+ * (stride * (h - 1) - radius > Hm - 1, likewise for the columns). */
+int spk_completion_state(const long long* codes_bhw, const uint8_t* keep_mask, long long* x_t_out, uint8_t* unmasked_out,
+                         int* n_known_out_or_null, int B, int h, int w, int Hm, int Wm, int stride, int radius, int K,
+                         long long mask_id, spk_stream_t stream);
+/* The given pixels pasted over a decoded image: out[b,c,y,x] = keep[b,y,x] ? uint8(clip(image[b,c,y,x] + 0.5, 0, 1) * 255)
+ * : decoded_u8[b,c,y,x] -- the image conversion of R/main.py:401 (fp32, truncating cast; a NaN pixel gives 0) where the pixel
+ * is given, the decoder's uint8 elsewhere.  image fp32 [B,C,H,W] normalised (pixel - 0.5), keep u8 [B,H,W], decoded / out u8
+ * [B,C,H,W] (out is a buffer of its own). */
+int spk_completion_compose(const float* image_bchw, const uint8_t* keep_bhw, const uint8_t* decoded_u8_bchw, uint8_t* out_u8_bchw,
+                           int B, int C, int H, int W, spk_stream_t stream);
+
 /* Content checksum of n device tensors in one launch (host-side cache validation; no reference counterpart: the reference
  * re-reads its weights on every call, this library keeps derived forms of them).  table_dev: device array of n pairs
  * {address, number of 32-bit words}; out1: one device word.  Order-independent 64-bit sum. */

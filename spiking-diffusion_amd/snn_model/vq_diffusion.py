@@ -175,18 +175,28 @@ class AbsorbingDiffusion(Sampler):
         return stats
 
     @torch.no_grad()
-    def sample(self, temp=1.0, sample_steps=None, noise=None, record=None):
+    def sample(self, temp=1.0, sample_steps=None, noise=None, record=None, x_init=None, known=None):
         """Reverse absorbing diffusion (R/snn_model/vq_diffusion.py:103-142).  Returns x_t int64 [B,1,h,w].
 
         ``noise``: optional callable t -> (u [B,1,h,w], q [B*h*w, K]) of device tensors (tests inject fixtures).
-        ``record``: optional list receiving (t, x_t.clone(), unmasked.clone(), logits.clone()) per step."""
+        ``record``: optional list receiving (t, x_t.clone(), unmasked.clone(), logits.clone()) per step.
+        ``x_init`` / ``known`` (both or neither): complete a partly given latent.  ``x_init`` integer device tensor [B,1,h,w] or
+        [B,h,w], ``known`` bool / uint8 of the same shape, true where the token is given.  The loop above runs unchanged from
+        ``unmasked = known & (0 <= x_init < num_classes)``, ``x_t = where(unmasked, x_init, mask_id)`` instead of the
+        all-masked state (a "known" token outside the codebook counts as not known: decided on the device).  The batch is
+        ``x_init.shape[0]``; ``n_samples`` is neither read nor changed.  Same noise contract: one key draw, counters on the
+        global image index -- with ``known`` all false the tokens are those of ``sample(temp, sample_steps)`` at
+        ``n_samples = B`` under the same seed, and a shard (``set_shard``) gives the tokens the whole job gives."""
+        start = self._start_state_args(x_init, known)
         dn = self._denoise_fn
         dev = next(dn.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
-        b = int(self.n_samples)
+        b = int(self.n_samples) if start is None else int(start[0].shape[0])
         h, w = self.shape
         K = self.num_classes
+        if start is not None and (start[0].device != dev or start[1].device != dev):
+            raise ValueError(f'spkdiff: x_init / known must be on the denoiser\'s device {dev}')
         if sample_steps is None:
             sample_steps = self.num_timesteps
         seed, base = 0, 0
@@ -197,7 +207,7 @@ class AbsorbingDiffusion(Sampler):
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
-                return self._sample_graphed(dev, b, h, w, K, float(temp), int(sample_steps), seed, base)
+                return self._sample_graphed(dev, b, h, w, K, float(temp), int(sample_steps), seed, base, start=start)
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -215,8 +225,11 @@ class AbsorbingDiffusion(Sampler):
                 torch.cuda.synchronize(dev)
             finally:
                 self._capturing = False
-        x_t = torch.full((b, 1, h, w), int(self.mask_id), dtype=torch.int64, device=dev)
-        unmasked = torch.zeros((b, 1, h, w), dtype=torch.bool, device=dev)
+        if start is None:
+            x_t = torch.full((b, 1, h, w), int(self.mask_id), dtype=torch.int64, device=dev)
+            unmasked = torch.zeros((b, 1, h, w), dtype=torch.bool, device=dev)
+        else:
+            x_t, unmasked, _ = ops.completion_state(start[0], start[1], K, int(self.mask_id))
         skip = self._skip_ok(h, w) and record is None
         act = None
         need = ops.NeedLists(b, int(self.list_radii), dev) if skip and self._list_ok(h, w, b) else None
@@ -258,6 +271,34 @@ class AbsorbingDiffusion(Sampler):
             if record is not None:
                 record.append((t, x_t.clone(), unmasked.clone(), logits.clone()))
         return x_t
+
+    def _start_state_args(self, x_init, known):
+        """Argument checks of ``sample(x_init=, known=)``, before anything is drawn or launched: None for the unconditional call,
+        else (codes int64 [B,h,w], keep uint8 [B,h,w]) contiguous on the device."""
+        if x_init is None and known is None:
+            return None
+        if x_init is None or known is None:
+            raise ValueError('spkdiff: sample() takes x_init and known together (both or neither)')
+        if not isinstance(x_init, torch.Tensor) or not isinstance(known, torch.Tensor):
+            raise TypeError(f'x_init and known must be torch.Tensors, got {type(x_init)} and {type(known)}')
+        if x_init.shape != known.shape:
+            raise ValueError(f'spkdiff: x_init {tuple(x_init.shape)} and known {tuple(known.shape)} must have the same shape')
+        h, w = self.shape
+        if not ((x_init.dim() == 3 and tuple(x_init.shape[1:]) == (h, w)) or
+                (x_init.dim() == 4 and tuple(x_init.shape[1:]) == (1, h, w))) or x_init.shape[0] < 1:
+            raise ValueError(f'spkdiff: x_init {tuple(x_init.shape)} must be [B,1,{h},{w}] or [B,{h},{w}] (the sampler\'s shape)')
+        if x_init.is_floating_point() or x_init.is_complex() or x_init.dtype == torch.bool:
+            raise NotImplementedError(f'spkdiff: x_init must be an integer tensor, got {x_init.dtype}')
+        if known.dtype not in (torch.bool, torch.uint8):
+            raise NotImplementedError(f'spkdiff: known must be bool or uint8, got {known.dtype}')
+        for name, t in (('x_init', x_init), ('known', known)):
+            if not t.is_cuda:
+                raise RuntimeError(f"spkdiff: {name} is on '{t.device}'. The HIP kernels are the implementation; "
+                                   "there is no CPU path (move the module / tensors to a ROCm device).")
+        B = int(x_init.shape[0])
+        codes = x_init.reshape(B, h, w).to(torch.int64).contiguous()
+        keep = known.reshape(B, h, w).contiguous()
+        return codes, (keep.view(torch.uint8) if keep.dtype == torch.bool else keep)
 
     def _skip_ok(self, h, w):
         return bool(self.skip_untouched)            # every kernel family takes the device-side image count
@@ -342,14 +383,18 @@ def _weights_key(module):
     return tuple((p.data_ptr(), p._version) for p in list(module.parameters()) + list(module.buffers())) + derived_epoch(module)
 
 
-def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base):
+def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base, start=None):
     """Capture-once / replay-many form of the loop in ``sample``; same kernels, same results as the eager loop for the
-    same (seed, counter base)."""
+    same (seed, counter base).  ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static
+    buffers filled before each replay; spk_completion_state is the first node in place of the two fills) and the graph has a
+    cache key of its own."""
     dn = self._denoise_fn
     skip = self._skip_ok(h, w)
     lists = skip and self._list_ok(h, w, b)
     key = (str(dev), b, h, w, K, temp, sample_steps, int(self.mask_id), skip, lists, int(self.list_radii),
            bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, int(self.global_first), _weights_key(dn))
+    if start is not None:
+        key = key + ('x_init',)
     entry = self._graphs.get(key)
     if entry is None:
         if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
@@ -357,6 +402,8 @@ def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base):
         state = torch.zeros(2, dtype=torch.int64, device=dev)
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
+        start_in = None if start is None else (torch.empty((b, h, w), dtype=torch.int64, device=dev),
+                                               torch.empty((b, h, w), dtype=torch.uint8, device=dev))
 
         act = (torch.zeros(b, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)) if skip else None
         need = ops.NeedLists(b, int(self.list_radii), dev) if lists else None
@@ -368,8 +415,11 @@ def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base):
         inp = None if (skip or tail) else torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
 
         def body():
-            x_t.fill_(int(self.mask_id))
-            unmasked.zero_()
+            if start_in is None:
+                x_t.fill_(int(self.mask_id))
+                unmasked.zero_()
+            else:
+                ops.completion_state(start_in[0], start_in[1], K, int(self.mask_id), out=(x_t, unmasked))
             pre1 = None
             for t in reversed(range(1, sample_steps + 1)):
                 off = self._step_offset(sample_steps - t, b, h, w, K)
@@ -407,10 +457,13 @@ def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base):
         # hand its block to the next allocation (another sampler's state, say) while replays keep writing to it.  That
         # includes the denoiser's derived tensors (packed weights, BN terms: an invalidation re-keys the graph, and until the
         # stale entry is evicted its memory must not be recycled) and the flag workspaces of the certified kernels.
-        entry = (graph, state, x_t, (need, inp, unmasked, act, flag_ws, derived_refs(dn)))
+        entry = (graph, state, x_t, (need, inp, unmasked, act, flag_ws, derived_refs(dn)), start_in)
         self._graphs[key] = entry
     graph, state, x_t = entry[:3]
     state.copy_(torch.tensor([seed, base], dtype=torch.int64), non_blocking=False)
+    if start is not None:
+        entry[4][0].copy_(start[0])
+        entry[4][1].copy_(start[1])
     graph.replay()
     return x_t.clone()
 

@@ -132,6 +132,8 @@ _SIGS = {
     "spk_den_step_tail": (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, c_float, P, P, c_ulonglong, c_ulonglong, P, P, P,
                                   P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "spk_philox_noise": (c_int, [c_ulonglong, c_ulonglong, P, P, P, c_int, c_int, c_int, P]),
+    "spk_completion_state": (c_int, [P, P, P, P, P] + [c_int] * 8 + [c_longlong, P]),
+    "spk_completion_compose": (c_int, [P, P, P, P] + [c_int] * 4 + [P]),
     "spk_checksum_multi": (c_int, [P, c_int, P, P]),
     "spk_clock_probe": (c_int, [P, c_int, c_int, P]),
     "spk_count_spikes": (c_int, [P, c_longlong, c_longlong, c_int, c_int, P, P]),

@@ -1,0 +1,69 @@
+"""Completion of partly given images (inpainting / outpainting): encode the image, keep the code indices
+that no removed pixel reached, run the reverse process from that partly unmasked state, decode, paste the given pixels back.
+
+A fixed launch sequence on the current stream; nothing is read back inside the call:
+
+    model.encode_images -> spk_completion_state (4, 3) -> sampler.sample(x_init, known) -> model.decode_tokens
+                        -> spk_completion_compose (``paste``)
+
+The encoder is Conv 3x3 s2 p1, Conv 3x3 s2 p1, Conv 1x1 (R/snn_model/vae_model.py:101-129), so code (i, j) reads pixels
+4i - 3 .. 4i + 3 in both directions (and the zero padding outside the image, which is given by definition).  A code is trusted
+only if every pixel of that window is given: the result therefore does not depend on what the input holds inside the hole.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from . import ops
+
+ENC_STRIDE, ENC_RADIUS = 4, 3          # the encoder's receptive field on the pixel grid: centre 4i, 3 pixels either side
+
+
+class Completion(NamedTuple):
+    images_u8: torch.Tensor            # uint8 [B,C,H,W]: the completed images
+    tokens: torch.Tensor               # int64 [B,h,w]: the completed code indices
+    known: torch.Tensor                # bool  [B,h,w]: the codes taken from the input
+    n_known: torch.Tensor              # int32 [B]: their number per image
+
+
+def _check_inputs(images, keep):
+    if not isinstance(images, torch.Tensor) or not isinstance(keep, torch.Tensor):
+        raise TypeError(f"images and keep must be torch.Tensors, got {type(images)} and {type(keep)}")
+    if images.dim() != 4:
+        raise ValueError(f"complete_images: images {tuple(images.shape)} must be [B,C,H,W]")
+    B, C, H, W = (int(v) for v in images.shape)
+    if keep.dim() == 4 and keep.shape[1] == 1:
+        keep = keep[:, 0]
+    if tuple(keep.shape) != (B, H, W):
+        raise ValueError(f"complete_images: keep {tuple(keep.shape)} must be [{B},1,{H},{W}] or [{B},{H},{W}]")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError(f"spkdiff: keep must be bool or uint8, got {keep.dtype}")
+    if H % 4 or W % 4:
+        raise ValueError(f"complete_images: the encoder halves the image twice: H, W = {H}, {W} must be multiples of 4")
+    images = ops._dev(images, "images", torch.float32)
+    keep = ops._dev(keep, "keep")
+    return images, keep
+
+
+@torch.no_grad()
+def complete_images(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True):
+    """``images`` fp32 device tensor [B,C,H,W], normalised as everywhere (pixel - 0.5); ``keep`` bool / uint8 [B,1,H,W] or
+    [B,H,W], true = the pixel is given.  ``model``: the SNN_VQVAE, ``sampler``: the AbsorbingDiffusion of its latent shape.
+    Returns a ``Completion`` of device tensors.  ``paste``: the given pixels of ``images_u8`` are the input's
+    (uint8(clip(image + 0.5, 0, 1) * 255), R/main.py:401), the rest the decoder's; False: the decoder's image everywhere.
+    One key draw from torch's global CPU generator, as every ``sample()`` call."""
+    images, keep = _check_inputs(images, keep)
+    B, C, H, W = (int(v) for v in images.shape)
+    h, w = H // 4, W // 4
+    if [h, w] != [int(v) for v in sampler.shape]:
+        raise ValueError(f"complete_images: {H}x{W} images encode to {h}x{w} codes, the sampler's shape is {list(sampler.shape)}")
+    codes = model.encode_images(images, T)
+    x_init, known, n_known = ops.completion_state(codes, keep, int(sampler.num_classes), int(sampler.mask_id), ENC_STRIDE,
+                                                  ENC_RADIUS, want_counts=True)
+    tokens = sampler.sample(temp=temp, sample_steps=sample_steps, x_init=x_init, known=known).reshape(B, h, w)
+    _, u8 = model.decode_tokens(tokens, T)
+    if paste:
+        u8 = ops.completion_compose(images, keep, u8)
+    return Completion(u8, tokens, known.reshape(B, h, w), n_known)

@@ -82,6 +82,18 @@ def sample_images_sharded(generate_local, total: int, sampler=None):
     return gather_images(generate_local(lo, hi), total)
 
 
+def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True):
+    """``spkdiff.complete.complete_images`` of one job over the ranks: every rank holds the whole job's ``images`` / ``keep``,
+    completes its ``shard_range`` of them as a shard of the job (``set_shard``: shared key, counters on the global image index,
+    so the images do not depend on the split) and one gather returns all uint8 images [total, C, H, W] on every rank."""
+    from .complete import complete_images
+
+    def generate_local(lo, hi):
+        return complete_images(model, sampler, images[lo:hi], keep[lo:hi], temp=temp, sample_steps=sample_steps, T=T,
+                               paste=paste).images_u8
+    return sample_images_sharded(generate_local, int(images.shape[0]), sampler=sampler)
+
+
 def _mix64(x: torch.Tensor) -> torch.Tensor:
     """splitmix64 finaliser on int64 tensors (two's-complement wrap-around arithmetic)."""
     x = (x ^ ((x >> 30) & 0x3FFFFFFFF)) * -4658895280553007687        # 0xBF58476D1CE4E5B9

@@ -2039,6 +2039,79 @@ def philox_noise(seed, offset, B, HW, K, device, philox_state=None, want_q=True)
     return u, q
 
 
+def _keep_u8(keep, name):
+    """A bool / uint8 device mask as the contiguous uint8 bytes the kernels read (a view: no copy for a contiguous mask)."""
+    if not isinstance(keep, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(keep)}")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError(f"spkdiff: {name} must be bool or uint8, got {keep.dtype}")
+    keep = _dev(keep, name)
+    return keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+
+
+def completion_state(codes, keep, K, mask_id, stride=1, radius=0, out=None, want_counts=False):
+    """Start state of a conditional reverse process (spk_completion_state): ``codes`` int64 [B,h,w] or [B,1,h,w], ``keep``
+    bool / uint8 [B,Hm,Wm] or [B,1,Hm,Wm] (true = given) -> (x_t int64 [B,1,h,w], unmasked bool [B,1,h,w], n_known int32 [B] or
+    None).  Token (i,j) is known iff every mask byte within ``radius`` of (stride*i, stride*j), clipped to the mask, is set and
+    the code is inside [0, K); x_t holds ``mask_id`` elsewhere.  (1, 0): a latent-resolution mask; (4, 3): a pixel mask seen
+    through the encoder's receptive field.  ``out``: (x_t, unmasked) buffers to write (a captured graph's)."""
+    if not isinstance(codes, torch.Tensor) or not isinstance(keep, torch.Tensor):
+        raise TypeError(f"codes and keep must be torch.Tensors, got {type(codes)} and {type(keep)}")
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise NotImplementedError(f"spkdiff: keep must be bool or uint8, got {keep.dtype}")
+    codes = _dev(codes, "codes", torch.int64)
+    keep = _keep_u8(keep, "keep")
+    if codes.dim() == 4 and codes.shape[1] == 1:
+        codes = codes[:, 0]
+    if keep.dim() == 4 and keep.shape[1] == 1:
+        keep = keep[:, 0]
+    if codes.dim() != 3 or keep.dim() != 3 or keep.shape[0] != codes.shape[0]:
+        raise ValueError(f"completion_state: codes {tuple(codes.shape)} must be [B,h,w] and keep {tuple(keep.shape)} [B,Hm,Wm] "
+                         "with the same B")
+    if keep.device != codes.device:
+        raise ValueError("completion_state: codes and keep must be on one device")
+    B, h, w = (int(v) for v in codes.shape)
+    Hm, Wm = int(keep.shape[1]), int(keep.shape[2])
+    if out is None:
+        x_t = torch.empty((B, 1, h, w), dtype=torch.int64, device=codes.device)
+        unmasked = torch.empty((B, 1, h, w), dtype=torch.bool, device=codes.device)
+    else:
+        x_t, unmasked = out
+        if not (x_t.is_cuda and x_t.device == codes.device and x_t.dtype == torch.int64 and x_t.is_contiguous()
+                and x_t.numel() == B * h * w):
+            raise ValueError("completion_state: out[0] must be a contiguous int64 device tensor [B,1,h,w]")
+        if not (unmasked.is_cuda and unmasked.device == codes.device and unmasked.dtype in (torch.bool, torch.uint8)
+                and unmasked.is_contiguous() and unmasked.numel() == B * h * w):
+            raise ValueError("completion_state: out[1] must be a contiguous bool/uint8 device tensor [B,1,h,w]")
+    n_known = torch.empty(B, dtype=torch.int32, device=codes.device) if want_counts else None
+    check(lib.spk_completion_state(_p(codes.contiguous()), _p(keep.contiguous()), _p(x_t), _p(unmasked), _p(n_known), B, h, w,
+                                   Hm, Wm, int(stride), int(radius), int(K), int(mask_id), _stream(codes)), "spk_completion_state")
+    return x_t, unmasked, n_known
+
+
+def completion_compose(images, keep, decoded_u8):
+    """Given pixels pasted over a decoded image (spk_completion_compose): ``images`` fp32 [B,C,H,W] normalised (pixel - 0.5),
+    ``keep`` bool / uint8 [B,H,W] or [B,1,H,W], ``decoded_u8`` uint8 [B,C,H,W] -> uint8 [B,C,H,W]:
+    keep ? uint8(clip(image + 0.5, 0, 1) * 255) : decoded_u8."""
+    images = _dev(images, "images", torch.float32)
+    keep = _keep_u8(keep, "keep")
+    decoded_u8 = _dev(decoded_u8, "decoded_u8", torch.uint8)
+    if keep.dim() == 4 and keep.shape[1] == 1:
+        keep = keep[:, 0]
+    if images.dim() != 4 or decoded_u8.shape != images.shape:
+        raise ValueError(f"completion_compose: images {tuple(images.shape)} and decoded_u8 {tuple(decoded_u8.shape)} must be "
+                         "equal [B,C,H,W] shapes")
+    B, C, H, W = (int(v) for v in images.shape)
+    if tuple(keep.shape) != (B, H, W):
+        raise ValueError(f"completion_compose: keep {tuple(keep.shape)} must be [{B},{H},{W}] (or [B,1,H,W])")
+    if keep.device != images.device or decoded_u8.device != images.device:
+        raise ValueError("completion_compose: images, keep and decoded_u8 must be on one device")
+    out = torch.empty((B, C, H, W), dtype=torch.uint8, device=images.device)
+    check(lib.spk_completion_compose(_p(images), _p(keep.contiguous()), _p(decoded_u8), _p(out), B, C, H, W, _stream(images)),
+          "spk_completion_compose")
+    return out
+
+
 class TensorChecksum:
     """Content checksum of a fixed set of device tensors in one launch (spk_checksum_multi): ``value()`` synchronises."""
 
