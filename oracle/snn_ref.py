@@ -164,17 +164,45 @@ def bn_affine_terms(sd, prefix):
     """The fp32 form PyTorch-CPU eval BN evaluates, pinned bit-exactly by fixture F7
     (aten/native/cpu/batch_norm_kernel.cpp collect_linear_and_constant_terms + fmadd):
         a = (1 / sqrt(var + eps)) * gamma ;  b' = fma(-mean, a, beta) ;  y = fma(x, a, b').
-    The fused multiply-adds are emulated through float64 (products of two fp32 are exact there)."""
+    The fused multiply-adds are emulated with ONE rounding (``fma_f32``)."""
     var, mean = sd[prefix + ".running_var"], sd[prefix + ".running_mean"]
-    a = (1.0 / torch.sqrt(var + BN_EPS)) * sd[prefix + ".weight"]
-    b = ((-mean).double() * a.double() + sd[prefix + ".bias"].double()).float()
+    a = _inv_sqrt_f32(var + BN_EPS) * sd[prefix + ".weight"]
+    b = fma_f32(-mean, a, sd[prefix + ".bias"])
     return a, b
 
 
+def _inv_sqrt_f32(x):
+    """1 / sqrt(x) in fp32 with both operations CORRECTLY ROUNDED, as the scalar ``1 / std::sqrt`` of aten's eval BN is.  Each is
+    evaluated in fp64 and rounded to fp32 (for square root and division 53 >= 2 * 24 + 2 bits make the second rounding harmless).
+    ``torch.sqrt`` on an fp32 CPU tensor is not a substitute: depending on the host it returned the other fp32 neighbour for 21 to
+    1048 of 4096 variances in [0.5, 1), while the device's ``1.0f / sqrtf`` (spk_bn_prepare) is correctly rounded."""
+    r = np.sqrt(x.detach().cpu().numpy().astype(np.float64)).astype(np.float32)
+    return torch.from_numpy((1.0 / r.astype(np.float64)).astype(np.float32))
+
+
+def fma_f32(x, a, b):
+    """The fp32 fused multiply-add x * a + b (broadcast) with a SINGLE rounding.  The product of two fp32 values is exact in fp64,
+    but ``(x.double() * a.double() + b.double()).float()`` rounds the sum twice -- to fp64, then to fp32 -- and differs from the
+    fma where the fp64 sum s lands exactly midway between two fp32 values while the true sum does not.  TwoSum recovers the
+    residual err of p + b = s + err exactly; on such a tie its sign decides the direction (elsewhere both roundings agree)."""
+    p = x.double() * a.double()
+    b64 = b.double().expand_as(p)
+    s = p + b64
+    bb = s - p
+    err = (p - (s - bb)) + (b64 - bb)
+    r = s.float()
+    d = s - r.double()                                       # exact
+    up = torch.nextafter(r, torch.full_like(r, float("inf"))).double()
+    dn = torch.nextafter(r, torch.full_like(r, float("-inf"))).double()
+    tie_up = (d > 0) & ((up - s) == d) & (err > 0)
+    tie_dn = (d < 0) & ((s - dn) == -d) & (err < 0)
+    return torch.where(tie_up, up.float(), torch.where(tie_dn, dn.float(), r))
+
+
 def bn_apply_fma(x_seq, a, b):
-    """y = fma(x, a[c], b[c]) over [T,B,C,H,W] (float64 emulation of the fp32 fma)."""
+    """y = fma(x, a[c], b[c]) over [T,B,C,H,W]: the fp32 fma with its single rounding (``fma_f32``)."""
     c = a.numel()
-    return (x_seq.double() * a.double().view(1, 1, c, 1, 1) + b.double().view(1, 1, c, 1, 1)).float()
+    return fma_f32(x_seq, a.view(1, 1, c, 1, 1), b.view(1, 1, c, 1, 1))
 
 
 def conv_bn_lif(x_seq, sd, conv_prefix, bn_prefix, stride, padding, transposed=False, output_padding=0, state=None):
