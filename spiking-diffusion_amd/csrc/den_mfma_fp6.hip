@@ -344,7 +344,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_fp6_kernel(Fp6Args a) {
       const int ti = wave + 4 * (odd ? ib : ia);
       const int pl = 2 * ti + half;                 // accumulator lane-half == position within the tile
       const int p = pl + band * HWb;                // position in the image
-      const bool pos_ok = pl < HWb && (paired || !odd);
+      // NT == 6 is the form whose last position belongs to conv3x3_fp6_lastpos_kernel: on an odd map below 7x7 tile (H*W - 1) / 2
+      // still lies inside the 24 tiles, and stepping its first position here as well would advance a carried v twice
+      const bool pos_ok = pl < (NT == 6 ? HWb - 1 : HWb) && (paired || !odd);
       if constexpr (RAW) {
         // x[r] = pre-activation of neuron (b, p, co) at t = r; 16 consecutive channels (64 B) per 16-lane row and step
         if (pos_ok) {

@@ -7,7 +7,16 @@ Why dyadic: the kernels' contract is  exact dot product + bias -
 With spikes / pixels that are multiples of 2^-8, weights multiples of 2^-12 (|w| < 1), biases multiples of 2^-10 and BN terms
 multiples of 2^-6, every fp64 partial sum of the convolution is exact IN ANY ORDER (products are multiples of 2^-20 below 2^14: 34
 bits of 53), the gather kernel's 2^-30 fixed point holds the weights exactly, and x * a + b needs fewer than 53 bits.  So there is one
-correct spike train per neuron, bit for bit: no fragile set, no tolerance, nothing to exclude."""
+correct spike train per neuron, bit for bit: no fragile set, no tolerance, nothing to exclude.
+
+FULL-WIDTH weights (make_case(weights="full"); the denoiser's matrix-core kernels of csrc/den_mfma.hip, den_mfma_fp6.hip and
+den_mfma_fp6v2.hip, and a second pass over the gather and vae_fp6 rows).  Multiples of 2^-12 below 0.5 fill only the top ~12 bits of the
+kernels' per-channel fixed point (shift 29 - e for six radix-32 digits, 30 - e for four radix-256 digits, e = the frexp exponent of the
+channel maximum): the two or three lowest digit planes of every MFMA kernel are zero on them.  The full-width scheme draws, per output
+channel, an exponent e and integers q of log-uniform magnitude in [2^4, 2^29), rounded to fp32 (24 significant bits, still an integer),
+and sets w = q * 2^(e-29); one tap per channel is 2^29 - 2^5, so the channel maximum lies in [2^(e-1), 2^e).  Then w * 2^(29-e) and
+w * 2^(30-e) are integers (the packing is exact, all six / four digits in play), and with BINARY inputs (or spike counts <= 16) every
+fp64 partial sum is an integer multiple of 2^(e-29) below 2^46: exact in any order.  The contract again has ONE answer per neuron."""
 from fractions import Fraction
 from types import SimpleNamespace
 
@@ -103,13 +112,20 @@ def _pow2_floor(v):
     return 2.0 ** int(np.floor(np.log2(v)))
 
 
-def make_case(geo, seed, kind="spikes", T=T16, n_inputs=1):
+def make_case(geo, seed, kind="spikes", T=T16, n_inputs=1, weights="dyadic12"):
     """Inputs of one row.  kind 'spikes': binary [T,B,Cin,H,W] at density 0.15; 'seq': dyadic reals (multiples of 2^-8, |x| < 4);
     'pixels': ONE dyadic frame [B,Cin,H,W] (multiples of 2^-8, |x| < 1; the time-invariant layers).  Weights are multiples of 2^-12
     scaled (by a power of two) so that the pre-activation has a spread of about one; bias multiples of 2^-10; BN scale a = multiples
     of 2^-6 with 0.5 <= |a| < 2, a quarter of them negative; BN shift b multiples of 2^-6 in [-0.5, 1); v0 multiples of 2^-8 in
     [-1, 1) (below the threshold, as a carried membrane potential is).  ``xs`` holds n_inputs independent inputs (carried-state
-    tests call the layer twice); they are drawn last, so the parameters and input 0 do not depend on n_inputs."""
+    tests call the layer twice); they are drawn last, so the parameters and input 0 do not depend on n_inputs.
+    weights="full": the full-width scheme of make_full_case (spike inputs only); the default leaves every draw as it was."""
+    if weights == "full":
+        if kind != "spikes":
+            raise ValueError("full-width weights need binary inputs: with 'seq' / 'pixels' inputs the partial sums take 52 bits")
+        return make_full_case(geo, seed, T=T, n_inputs=n_inputs)
+    if weights != "dyadic12":
+        raise ValueError(weights)
     Cin, Cout, k, s, p, tr, op, H, W, B = geo
     g = torch.Generator().manual_seed(seed)
     taps = Cin * k * k / (s * s if tr else 1)                 # taps that reach one output of a transposed layer: k*k / s*s
@@ -130,7 +146,116 @@ def make_case(geo, seed, kind="spikes", T=T16, n_inputs=1):
         else:
             xs.append(dyadic((B, Cin, H, W), g, 8, 1.0))
     coef = torch.pow(torch.tensor(0.8), torch.arange(T - 1, -1, -1).float())      # the model's membrane read-out weights
-    return SimpleNamespace(geo=geo, kind=kind, T=T, xs=xs, x=xs[0], w=w, bias=bias, a=a, b=b, v0=v0, coef=coef, Ho=Ho, Wo=Wo)
+    return SimpleNamespace(geo=geo, kind=kind, T=T, xs=xs, x=xs[0], w=w, bias=bias, a=a, b=b, v0=v0, coef=coef, Ho=Ho, Wo=Wo,
+                           weights=weights, graze=[])
+
+
+# ------------------------------------------------------------------------------------------------ full-width weights
+FULL_STD = 0.17            # sqrt(E[w^2]) / 2^e of the scheme: |q| = 2^u, u uniform in [4, 29):  E[4^(u-29)] = 1 / (50 ln 2) = 0.0289
+Q_PIN = 2.0 ** 29 - 2.0 ** 5
+
+
+def full_width_weights(Cout, Cin, k, g, e_lo, e_hi):
+    """[Cout,Cin,k,k] fp32 weights w = q * 2^(e-29) and the int64 exponents e [Cout] (uniform in [e_lo, e_hi])."""
+    e = torch.randint(e_lo, e_hi + 1, (Cout,), generator=g)
+    bits = 4.0 + 25.0 * torch.rand((Cout, Cin, k, k), generator=g, dtype=torch.float64)
+    sign = torch.where(torch.rand((Cout, Cin, k, k), generator=g) < 0.5, -1.0, 1.0).double()
+    q = (torch.floor(torch.exp2(bits)) * sign).float().double()         # 24 significant bits: still an integer, |q| <= 2^29 - 2^5
+    q[:, 0, k // 2, k // 2] = Q_PIN                                      # pins the channel maximum into [2^(e-1), 2^e)
+    w = (q * torch.exp2((e - 29).double()).view(-1, 1, 1, 1)).float()
+    assert torch.equal(w.double(), q * torch.exp2((e - 29).double()).view(-1, 1, 1, 1))
+    return w, e
+
+
+def channel_exponent(w, transposed=False):
+    """The frexp exponent of every output channel's largest magnitude, as the pack kernels take it (m = f * 2^e, f in [0.5, 1))."""
+    m = (w.transpose(0, 1) if transposed else w).flatten(1).abs().amax(1).double().numpy()
+    return torch.from_numpy(np.frexp(m)[1].astype(np.int64))
+
+
+def lif_h0(z0):
+    """The charged potential of step 0 from the reset state, as ref.lif_multi_step computes it: h = v + (z - v) / 2 with v = 0."""
+    v = torch.zeros_like(z0)
+    return v + (z0 - v) / 2.0
+
+
+def _graze_pref(shape, pref):
+    """The neurons [B,H,W] a constructed channel should sit on, by preference: 0 the last position (the last-position launches of an
+    odd map), 1 a position below it in the last image, 2 row H/2 - 1 in image 0, 3 row H/2 in the last image (the two row bands
+    of an 8x8 map)."""
+    B, H, W = shape
+    m = torch.zeros(shape, dtype=torch.bool)
+    if pref == 0:
+        m[:, H - 1, W - 1] = True
+    elif pref == 1:
+        m[B - 1] = True
+        m[B - 1, H - 1, W - 1] = False
+    elif pref == 2:
+        m[0, max(H // 2 - 1, 0)] = True
+    else:
+        m[B - 1, H // 2] = True
+    return m
+
+
+def _graze_pick(cand, order, pref):
+    """(channel, image, y, x): the first channel of ``order`` with a candidate neuron on the preferred set; failing that, the first
+    channel with any candidate; None if no channel has one.  cand: bool [B,C,H,W]."""
+    m = _graze_pref(cand[:, 0].shape, pref)
+    for mask in (m, torch.ones_like(m)):
+        for c in order:
+            idx = (cand[:, c] & mask).nonzero()
+            if len(idx):
+                return (c,) + tuple(int(v) for v in idx[0])
+    return None
+
+
+def make_full_case(geo, seed, T=T16, n_inputs=1):
+    """make_case(weights="full").  Bias multiples of 2^-10; ordinary channels carry BN terms as in the 2^-12 scheme; v0 likewise.
+    The channel exponents lie in [e_hi - 3, e_hi] (clamped to [-6, 0]) with e_hi chosen so that the pre-activation of the widest
+    channels has a spread of about 2.5.
+
+    THRESHOLD-GRAZING CHANNELS.  A random draw no longer lands on h == 1.0, so it is built: in a quarter of the output channels
+    a = 1 and b = 2 - y32 for one neuron whose oracle pre-activation y32 of step 0 (input 0, reset state) lies in [1, 2): the
+    difference is exact, z = fma(y32, 1, b) = 2 and h = 1.0 exactly -- the neuron fires (>=).  In a further eighth b is the LARGEST
+    fp32 value for which the oracle's h at that neuron stays below 1, found by stepping down with nextafter (y32 + b may round
+    back up to 2).  ``graze`` lists them: (kind 'fire' | 'below', channel, image, y, x).  The channels are taken in a seeded order,
+    each slot preferring a channel that has such a neuron where _graze_pref wants one; a channel with no y32 in [1, 2) stays ordinary."""
+    Cin, Cout, k, s, p, tr, op, H, W, B = geo
+    g = torch.Generator().manual_seed(seed)
+    taps = Cin * k * k / (s * s if tr else 1)
+    e_hi = int(np.clip(np.round(np.log2(2.5 / (FULL_STD * np.sqrt(SPIKE_DENSITY * taps)))), -3, 0))
+    w, e = full_width_weights(Cout, Cin, k, g, max(e_hi - 3, -6), e_hi)
+    if tr:
+        w = w.transpose(0, 1).contiguous()
+    bias = dyadic((Cout,), g, 10, 0.25)
+    a = (torch.randint(32, 128, (Cout,), generator=g).float() / 64.0) * torch.where(torch.rand(Cout, generator=g) < 0.25, -1.0, 1.0)
+    b = torch.randint(-32, 64, (Cout,), generator=g).float() / 64.0
+    Ho, Wo = geo_out_hw(geo)
+    v0 = dyadic((B, Cout, Ho, Wo), g, 8, 1.0)
+    order = torch.randperm(Cout, generator=g).tolist()                   # which channels graze: a function of the seed alone
+    xs = [(torch.rand((T, B, Cin, H, W), generator=g) < SPIKE_DENSITY).float() for _ in range(n_inputs)]
+    y0 = conv64(xs[0][0], w, bias, geo).float()                          # [B,Cout,Ho,Wo]: the oracle's y32 of step 0
+    n_fire, n_below = Cout // 4, Cout // 8
+    cand = (y0 >= 1.0) & (y0 < 2.0)
+    graze = []
+    one = torch.ones(1)
+    for j in range(n_fire + n_below):
+        pick = _graze_pick(cand, order, j % 4)
+        if pick is None:
+            break
+        c = pick[0]
+        order.remove(c)
+        yv = y0[pick[1], c, pick[2], pick[3]].reshape(1)
+        bc = (2.0 - yv.double()).float()
+        assert float(bc.double() + yv.double()) == 2.0                    # exact: y32 in [1, 2), b in (0, 1] on a finer grid
+        kind = "fire" if j < n_fire else "below"
+        while kind == "below" and float(lif_h0(fma32(yv, one, bc))) >= 1.0:
+            bc = torch.from_numpy(np.nextafter(bc.numpy(), np.float32(-np.inf)))
+        a[c], b[c] = 1.0, float(bc)
+        graze.append((kind,) + pick)
+    coef = torch.pow(torch.tensor(0.8), torch.arange(T - 1, -1, -1).float())
+    return SimpleNamespace(geo=geo, kind="spikes", T=T, xs=xs, x=xs[0], w=w, bias=bias, a=a, b=b, v0=v0, coef=coef, Ho=Ho, Wo=Wo,
+                           weights="full", e=e, graze=graze)
 
 
 # ------------------------------------------------------------------------------------------------ the oracle
@@ -249,6 +374,41 @@ def bits_to_packed(bits, rec, T=T16):
     return by.permute(0, 4, 1, 2, 3, 5).contiguous()
 
 
+def from_cptc(p):
+    """u8 CPTC [B,C/chunk,H,W,T,chunk] -> fp32 [T,B,C,H,W]."""
+    B, nch, H, W, T, chunk = p.shape
+    return p.permute(4, 0, 1, 5, 2, 3).reshape(T, B, nch * chunk, H, W).contiguous().float()
+
+
+def packed_to_spikes(q):
+    """Nibble-packed records u8 [B,C/rec,H,W,T,rec/2] (S32: rec = 32, C4: rec = 64) -> fp32 [T,B,C,H,W]; a non-zero nibble is a spike,
+    and every nibble is 0x0 or 0x2 (checked: a record holds e2m1 codes of 0.0 and 1.0 only)."""
+    B, nrec, H, W, T, half = q.shape
+    lo, hi = q & 0xF, q >> 4
+    assert bool(((lo == 0) | (lo == 2)).all()) and bool(((hi == 0) | (hi == 2)).all()), "a nibble that is neither 0.0 nor 1.0"
+    ch = torch.stack([lo, hi], dim=-1).reshape(B, nrec, H, W, T, 2 * half)
+    return (ch != 0).permute(4, 0, 1, 5, 2, 3).reshape(T, B, nrec * 2 * half, H, W).contiguous().float()
+
+
+def to_counts(s):
+    """fp32 spikes [T,B,C,H,W] -> the spike-count record u8 [B,C/32,H,W,32] (the A operand of the time-collapsed logits layer)."""
+    T, B, C, H, W = s.shape
+    return s.sum(0).to(torch.uint8).view(B, C // 32, 32, H, W).permute(0, 1, 3, 4, 2).contiguous()
+
+
+def from_counts(cnt):
+    """u8 [B,C/32,H,W,32] -> fp32 counts [B,C,H,W]."""
+    B, nch, H, W, _ = cnt.shape
+    return cnt.permute(0, 1, 4, 2, 3).reshape(B, nch * 32, H, W).contiguous().float()
+
+
+def counts_logits(cnt_bchw, w, bias, geo, T=T16):
+    """The time-collapsed logits layer on the host: fp32(sum_t dot + T * bias) / T from the fp64 convolution of the COUNT tensor.
+    One rounding (the kernel rounds fma(s, scale, bias * T) once) and an exact division for T = 16.  Also returns the fp64 value."""
+    y64 = conv64(cnt_bchw, w, None, geo) + float(T) * bias.double().view(1, -1, 1, 1)
+    return y64.float() * (1.0 / T), y64 / T
+
+
 def spikes_to_bits(s):
     """fp32 [T,B,C,H,W] -> int32 [B,C,H,W]."""
     sh = torch.arange(s.shape[0], dtype=torch.int32).view(-1, 1, 1, 1, 1)
@@ -312,6 +472,84 @@ VAE_FP6_ROWS = [
     ("dec1", 16, 64, True, 1, 7),                # S32 output
     ("dec2", 64, 32, True, 1, 14),               # time-collapsed output
 ]
+
+
+# ---- the denoiser's 3x3 matrix-core family (stride 1, pad 1, T = 16): (Cin0, Cin1, Cout, H, W, B); full-width weights.
+# B = None: computed from the CU count at run time (den_rows(cus)); the host test takes 256 CUs.
+DEN_I8_ROWS = [
+    (32, 0, 32, 7, 7, 3),          # conv3x3_mfma_kernel<7,7>: the smallest
+    (64, 32, 64, 7, 7, 5),         # in1 concatenation, three K chunks (also MODE_MEAN)
+    (32, 0, 32, 8, 8, 2),          # <8,8>
+    (96, 0, 32, 5, 6, 2),          # <7,7> at 30 positions: 15 tiles, the fourth wave's last tile absent
+    (32, 0, 32, 3, 3, 1),          # <7,7> at 9 positions: the last tile half filled
+    (32, 0, 64, 7, 7, None),       # B = CUs / 4 + 1: CUs + 4 items on a persistent grid of CUs workgroups, the second trip
+]
+DEN_I8_MEAN_ROW = DEN_I8_ROWS[1]
+DEN_COUNTS_ROWS = [
+    (64, 32, 16, 7, 7, 3),         # conv3x3_counts_mfma_kernel (K chunks split over the four waves), with cnt1
+    (32, 0, 40, 7, 7, 2),          # through den_pack_weight_i8(pad_cout=True): 48 packed channels
+    (32, 0, 48, 7, 7, 105),        # B * HW = 5145 > 5120: conv3x3_counts_mfma_shared_kernel at HW = 49
+    (32, 0, 16, 8, 8, 81),         # ... at HW = 64 (5184 rows)
+    (32, 0, 16, 6, 7, 123),        # 5166 rows but HW = 42 < 43: the first kernel, one tile per wave (no K split)
+]
+STEP_TAIL_ROW = (256, 64, 16, 7, 7, 3)      # spk_den_step_tail's logits (cnt5 of 256 channels, cnt1 of 64)
+DEN_FP6_ROWS = [
+    (64, 0, 64, 7, 7, 3),          # conv3x3_fp6_kernel<6> + conv3x3_fp6_lastpos_kernel
+    (128, 0, 64, 9, 6, 2),         # <7>: 54 positions = 27 tiles, two K chunks (the largest even map the launcher's LDS check takes:
+                                   # 7x8, 56 positions, asks for 164 KB and is refused -- DEN_FP6_REFUSED)
+    (64, 0, 64, 8, 8, 3),          # <4, SPLIT>: two row bands per image
+    (64, 0, 64, 10, 6, 2),         # <4, SPLIT> away from 8x8: bands of 5 rows
+    (64, 0, 64, 5, 5, 2),          # <6> + last-position kernel with 12 full tiles
+    (64, 0, 64, 2, 2, 1),          # <7> with two tiles (4 positions: an even count has no last-position launch)
+    (64, 0, 128, 7, 7, 8),         # XCD-aware walk (64 workgroups, gx = 8)
+    (64, 0, 128, 7, 7, 7),         # ... 56 workgroups: S % gx != 0, image-major walk
+    (64, 0, 64, 7, 7, None),       # B = CUs / 4 + 1: second trip; the last-position grid's last workgroup half filled
+]
+DEN_FP6_REFUSED = (128, 0, 64, 7, 8, 2)
+DEN_FP6V2_ROWS = [
+    (32, 0, 32, 7, 7, 2),          # half-image kernel (form 0) / whole-image kernel (form 1); one K chunk: merged tail <7,7,0>
+    (96, 0, 64, 7, 7, 5),          # three K chunks (odd), merged tail <7,7,0>
+    (64, 0, 64, 7, 7, 64),         # B >= 64 and two K chunks: the LDS-shared last-position tail <7,7,3>
+    (64, 0, 64, 7, 7, 63),         # ... one image fewer: the merged tail
+    (32, 0, 64, 8, 8, 3),          # row bands <8,8,8,SPLIT>, repair-only tail <8,8,1>
+    (512, 0, 256, 7, 7, 5),        # conv5's own shape: 16 K chunks
+]
+DEN_LISTED_ROW = (64, 0, 64, 7, 7, 6)       # the listed launch (conv3x3_fp6v2_listed_kernel), through ops.active_set(need=...)
+DEN_NDYN_ROWS = {"i8": (32, 0, 32, 7, 7, 5), "counts": (64, 32, 16, 7, 7, 5), "fp6": (64, 0, 64, 7, 7, 5), "fp6v2": (32, 0, 32, 7, 7, 5)}
+HOST_CUS = 256
+
+
+def den_row(row, cus=HOST_CUS):
+    return row if row[5] is not None else row[:5] + (cus // 4 + 1,)
+
+
+def den_geo(row, cus=HOST_CUS):
+    """(Cin0, Cin1, Cout, H, W, B) -> the ten-field geometry tuple (Cin = Cin0 + Cin1)."""
+    C0, C1, Cout, H, W, B = den_row(row, cus)
+    return (C0 + C1, Cout, 3, 1, 1, False, 0, H, W, B)
+
+
+def all_den_rows(cus=HOST_CUS):
+    """(family, row) of every denoiser row, B resolved."""
+    rows = [("i8", r) for r in DEN_I8_ROWS] + [("counts", r) for r in DEN_COUNTS_ROWS + [STEP_TAIL_ROW]]
+    rows += [("fp6", r) for r in DEN_FP6_ROWS] + [("fp6v2", r) for r in DEN_FP6V2_ROWS + [DEN_LISTED_ROW]]
+    rows += [(f, r) for f, r in DEN_NDYN_ROWS.items()]
+    seen, out = set(), []
+    for f, r in rows:
+        r = den_row(r, cus)
+        if den_geo(r) not in seen:
+            seen.add(den_geo(r))
+            out.append((f, r))
+    return out
+
+
+# the rows of the 2^-12 tables that run a second time on full-width weights (tests/test_gpu_conv_bn_lif_oracle.py)
+GATHER_FULL_ROWS = [GATHER_ROWS[i] for i in (0, 2, 4, 6, 8, 11)]
+
+
+def full_seed(geo):
+    """The seed of a row's full-width case (its own stream: a row of the 2^-12 tables keeps its seed there)."""
+    return 7000 + row_seed(geo) % 1000
 
 
 def vae_fp6_geo(row, B):

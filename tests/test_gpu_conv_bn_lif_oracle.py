@@ -57,13 +57,15 @@ def _tally(fam, got, want, what):
     assert n_bad == 0, (what, f"{n_bad} of {want.numel()} differ; first at", bad.nonzero()[:8].tolist())
 
 
-def _oracle(fam, geo, kind="spikes", T=16):
+def _oracle(fam, geo, kind="spikes", T=16, weights="dyadic12"):
     """The case of a row and its oracle results, computed once per session and left unchanged: reset-state run on input 0, and the
-    carried-state pair (v0 -> input 0 -> v1 -> input 1 -> v2)."""
-    key = (geo, kind, T)
+    carried-state pair (v0 -> input 0 -> v1 -> input 1 -> v2).  weights="full": the row's full-width case (all digit planes of the MFMA
+    kernels in play, threshold-grazing channels; see the oracle module)."""
+    key = (geo, kind, T, weights)
     if key not in _ORACLE:
         t0 = time.perf_counter()
-        c = O.make_case(geo, O.row_seed(geo, T), kind=kind, T=T, n_inputs=2)
+        seed = O.row_seed(geo, T) if weights == "dyadic12" else O.full_seed(geo)
+        c = O.make_case(geo, seed, kind=kind, T=T, n_inputs=2, weights=weights)
         seqs = [x.unsqueeze(0).repeat(T, 1, 1, 1, 1) if kind == "pixels" else x for x in c.xs]
         c.y = [O.conv_fp32(x, c.w, c.bias, geo) for x in seqs]                 # MODE_RAW
         c.pre = [O.bn32(y, c.a, c.b) for y in c.y]                              # want_pre
@@ -115,7 +117,18 @@ def _gather_in(ops, dev, c, i=0):
 @pytest.mark.parametrize("geo", O.GATHER_ROWS, ids=_gid)
 def test_gather_lif_from_reset_state_all_output_forms(dev, ops, geo):
     """u8 PTC, S32 (Cout % 32 == 0) and the time-collapsed output of spk_conv_mfma_fused_fwd / _lif_s32 equal the oracle's spikes."""
-    c = _oracle("gather", geo)
+    _gather_reset(dev, ops, geo, "dyadic12")
+
+
+@pytest.mark.parametrize("geo", O.GATHER_FULL_ROWS, ids=_gid)
+def test_gather_lif_from_reset_state_full_width_weights(dev, ops, geo):
+    """The same on full-width weights: one spike-input row of each compile-time instance and one generic row, with all four int8 digit
+    planes in play (multiples of 2^-12 leave the low planes zero) and neurons built to sit exactly on the threshold."""
+    _gather_reset(dev, ops, geo, "full")
+
+
+def _gather_reset(dev, ops, geo, weights):
+    c = _oracle("gather", geo, weights=weights)
     Cout, kw = geo[1], _geo_kw(geo)
     ptc, pk = _gather_in(ops, dev, c)
     a, b = c.a.to(dev), c.b.to(dev)
@@ -133,7 +146,16 @@ def test_gather_lif_from_reset_state_all_output_forms(dev, ops, geo):
 @pytest.mark.parametrize("geo", O.GATHER_ROWS, ids=_gid)
 def test_gather_lif_with_carried_membrane_state(dev, ops, geo):
     """v carried over two calls on different spike inputs, starting from a non-zero dyadic v0: spikes and v bit-equal after each."""
-    c = _oracle("gather", geo)
+    _gather_carried(dev, ops, geo, "dyadic12")
+
+
+@pytest.mark.parametrize("geo", O.GATHER_FULL_ROWS, ids=_gid)
+def test_gather_lif_with_carried_membrane_state_full_width_weights(dev, ops, geo):
+    _gather_carried(dev, ops, geo, "full")
+
+
+def _gather_carried(dev, ops, geo, weights):
+    c = _oracle("gather", geo, weights=weights)
     Cout, kw = geo[1], _geo_kw(geo)
     ptc0, pk = _gather_in(ops, dev, c, 0)
     ptc1 = O.to_ptc(c.xs[1]).to(dev)
@@ -155,7 +177,16 @@ def test_gather_lif_with_carried_membrane_state(dev, ops, geo):
 @pytest.mark.parametrize("geo", O.MEMOUT_ROWS, ids=_gid)
 def test_gather_memout_within_the_fp32_evaluation_bound(dev, ops, geo):
     """MODE_MEMOUT (no BN, no LIF): sum_t coef[t] * y[t] with y the exact convolution rounded once; with and without tanh, plus u8."""
-    c = _oracle("gather", geo)
+    _gather_memout(dev, ops, geo, "dyadic12")
+
+
+@pytest.mark.parametrize("geo", [g for g in O.GATHER_FULL_ROWS if g in O.MEMOUT_ROWS], ids=_gid)
+def test_gather_memout_full_width_weights(dev, ops, geo):
+    _gather_memout(dev, ops, geo, "full")
+
+
+def _gather_memout(dev, ops, geo, weights):
+    c = _oracle("gather", geo, weights=weights)
     Cout, kw = geo[1], _geo_kw(geo)
     ptc, pk = _gather_in(ops, dev, c)
     m64, mag = O.memout64(c.y[0], c.coef)
@@ -167,7 +198,7 @@ def test_gather_memout_within_the_fp32_evaluation_bound(dev, ops, geo):
     own = float((rt["f32"].cpu().double() - torch.tanh(r["f32"].cpu().double())).abs().max())      # tanhf alone
     print(f"gather memout {geo}: max err {e0:.3e} (bound up to {float(bound.max()):.3e}); tanhf own error {own:.3e}")
     e1 = _readout_check("gather", ("memout+tanh", geo), rt["f32"].cpu(), rt["u8"].cpu(), torch.tanh(m64), bound, TANHF_ERR_ALLOWED)
-    parity(f"conv_bn_lif_oracle_gather_memout_{_gid(geo)}", max_err=e0, max_err_tanh=e1, tanhf_own_err=own,
+    parity(f"conv_bn_lif_oracle_gather_memout_{_gid(geo)}" + ("" if weights == "dyadic12" else "_full"), max_err=e0, max_err_tanh=e1, tanhf_own_err=own,
            tanhf_err_allowed=TANHF_ERR_ALLOWED)
     assert own <= TANHF_ERR_ALLOWED
 
@@ -398,11 +429,27 @@ def _flag_ws_clean(v):
 def test_vae_fp6_against_the_oracle(dev, ops, row, B):
     """spk_vae_fp6_fwd in its three geometries, each with its own output kind, straight against the host oracle (no gather kernel in
     between); the flag workspace comes back clean."""
+    _vae_fp6(dev, ops, row, B, "dyadic12")
+
+
+@pytest.mark.parametrize("B", [1, 5])
+@pytest.mark.parametrize("row", O.VAE_FP6_ROWS, ids=lambda r: r[0])
+def test_vae_fp6_against_the_oracle_full_width_weights(dev, ops, row, B):
+    """The same on full-width weights: the fifth and sixth radix-32 digit, which the certification drops and bounds and only the exact
+    repair reads, are non-zero, and the constructed threshold-grazing neurons must be flagged (word 1 of the workspace)."""
+    c = _vae_fp6(dev, ops, row, B, "full")
+    ws = [v for k, v in ops._FLAG_DEFAULT.items() if k[0] == "vae"]
+    flagged = max(int(v[1]) for v in ws)
+    print(f"vae_fp6 {row[0]} B={B} full-width: last calls flagged up to {flagged}; constructed neurons {len(c.graze)}")
+    assert len(c.graze) >= 1
+
+
+def _vae_fp6(dev, ops, row, B, weights):
     layer, Cin, Cout, tr, op, H = row
     geo = O.vae_fp6_geo(row, B)
     kind = {"enc2": ops.VAE_OUT_PTC, "dec1": ops.VAE_OUT_S32, "dec2": ops.VAE_OUT_COLLAPSED}[layer]
     assert ops.vae_fp6_kind(Cin, Cout, 3, 2, 1, op, tr, 16, H, H) == kind
-    c = _oracle("vae_fp6", geo)
+    c = _oracle("vae_fp6", geo, weights=weights)
     x = c.xs[0]
     if Cin % 32:                                              # zero nibbles beyond Cin
         x = torch.cat([x, torch.zeros(x.shape[0], B, 32 - Cin % 32, H, H)], dim=2)
@@ -419,6 +466,7 @@ def test_vae_fp6_against_the_oracle(dev, ops, row, B):
     torch.cuda.synchronize()
     ws = [v for k, v in ops._FLAG_DEFAULT.items() if k[0] == "vae"]
     assert ws and all(_flag_ws_clean(v) for v in ws), "live counter, overflow bitmap and hand-over ticket come back clean"
+    return c
 
 
 # ================================================================================================ d. module path
