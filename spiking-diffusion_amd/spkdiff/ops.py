@@ -984,9 +984,10 @@ NATIVE_WGRAD = True
 
 
 def conv3x3_wgrad(gy_cl, spikes_cl, Cout, Cin, want_bias=False):
-    """gw [Cout,Cin,3,3] (channels-last memory) of a 3x3 / s1 / p1 convolution from gy [N,Cout,H,W] and BINARY spikes
-    [N,Cin,H,W] (7x7 or 8x8 maps), both channels-last fp32 (spk_conv3x3_wgrad_bf16: bf16 matrix cores, exact three-term split of
-    gy)."""
+    """gw [Cout,Cin,3,3] (channels-last memory) of a 3x3 / s1 / p1 convolution from gy [N,Cout,H,W] and an operand [N,Cin,H,W]
+    whose values are exact in bf16 -- binary spikes, or integers up to 256 such as the spike counts the time-collapsed last layer
+    passes (the kernel truncates the operand to bf16) -- on 7x7 or 8x8 maps, both channels-last fp32 (spk_conv3x3_wgrad_bf16: bf16
+    matrix cores, exact three-term split of gy)."""
     N, H, W = int(gy_cl.shape[0]), int(gy_cl.shape[2]), int(gy_cl.shape[3])
     nb = int(lib.spk_conv3x3_wgrad_ws_bytes(N, int(Cout), int(Cin)))
     if nb <= 0:
