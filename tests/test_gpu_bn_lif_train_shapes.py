@@ -10,15 +10,13 @@ decide the spike differently; the oracle then takes the kernel's decision, so th
 gradient check is skipped because such a step exists somewhere in the batch."""
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import snn_ref as ref
+from _bn_lif_train_oracle import _inputs, _oracle, _rel_l2, _run_hip
 from parity_report import record as parity
 
 pytestmark = pytest.mark.gpu
 
 T = 16
-FRAGILE = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -33,10 +31,6 @@ def ops():
     return o
 
 
-def _rel_l2(got, want):
-    return float((got.double() - want.double()).norm() / (want.double().norm() + 1e-30))
-
-
 # (B, C, H, v_init, detach_reset)
 SHAPES = [
     (32, 32, 14, False, False), (32, 64, 7, False, False), (32, 16, 7, False, False), (32, 64, 14, False, False),
@@ -47,60 +41,6 @@ SHAPES = [
     (32, 64, 14, True, False),                                          # a carried membrane state (and its gradient)
     (32, 32, 16, False, True),                                          # detach_reset
 ]
-
-
-def _inputs(dev, B, C, H, with_v, seed):
-    g = torch.Generator(device=dev).manual_seed(seed)
-    shape = (T, B, C, H, H)
-    y = torch.randn(shape, generator=g, device=dev) * 2 + 0.3
-    gamma = 1 + 0.3 * torch.randn(C, generator=g, device=dev)
-    beta = 0.5 * torch.randn(C, generator=g, device=dev)
-    rm, rv = torch.randn(C, generator=g, device=dev), torch.rand(C, generator=g, device=dev) + 0.5
-    v0 = torch.rand(B, C, H, H, generator=g, device=dev) - 0.5 if with_v else None
-    gs = torch.randn(shape, generator=g, device=dev)
-    gv = torch.randn(B, C, H, H, generator=g, device=dev) if with_v else None
-    return y, gamma, beta, rm, rv, v0, gs, gv
-
-
-def _run_hip(ops, y, gamma, beta, rm, rv, v0, gs, gv, det):
-    """(spikes, v_last, save_mean, save_invstd, running mean, running var, grad_y, grad_gamma, grad_beta, grad_v_init)."""
-    yd, gd, bd = (t.clone().requires_grad_(True) for t in (y, gamma, beta))
-    vd = None if v0 is None else v0.clone().requires_grad_(True)
-    rmd, rvd = rm.clone(), rv.clone()
-    s, vl = ops.BNLIFTrainFunction.apply(yd, gd, bd, vd, rmd, rvd, 0.1, 1e-5, 2.0, 1.0, 0.0, 2.0, det)
-    mean, invstd = s.grad_fn.saved_tensors[3:5]
-    loss = (s * gs).sum() + ((vl * gv).sum() if gv is not None else 0)
-    loss.backward()
-    torch.cuda.synchronize()
-    return (s.detach(), vl.detach(), mean.clone(), invstd.clone(), rmd, rvd, yd.grad, gd.grad, bd.grad,
-            None if vd is None else vd.grad)
-
-
-def _oracle(y, gamma, beta, rm, rv, v0, gs, gv, det, s_hip):
-    """fp64 BatchNorm (batch statistics) + LIF with autograd; at fragile neuron-steps the spike is the kernel's."""
-    shape = y.shape
-    yo, go, bo = (t.double().requires_grad_(True) for t in (y, gamma, beta))
-    vo = None if v0 is None else v0.double().requires_grad_(True)
-    rmo, rvo = rm.double(), rv.double()
-    z = F.batch_norm(yo.flatten(0, 1), rmo, rvo, go, bo, True, 0.1, 1e-5).view(shape)
-    v = torch.zeros(shape[1:], dtype=torch.float64, device=y.device) if vo is None else vo
-    spikes, fragile = [], []
-    for t in range(shape[0]):
-        h = v + (z[t] - v) / 2.0
-        fr = (h.detach() - 1.0).abs() < FRAGILE
-        sp = ref._ATanSpike.apply(h - 1.0, 2.0)
-        sp = sp + (torch.where(fr, s_hip[t].double(), sp.detach()) - sp).detach()      # (value: the kernel's decision where fragile)
-        sd = sp.detach() if det else sp
-        v = (1.0 - sd) * h
-        spikes.append(sp)
-        fragile.append(fr)
-    so = torch.stack(spikes)
-    ((so * gs.double()).sum() + ((v * gv.double()).sum() if gv is not None else 0)).backward()
-    yd = yo.detach()
-    mean = yd.mean(dim=(0, 1, 3, 4))
-    invstd = 1.0 / torch.sqrt(yd.var(dim=(0, 1, 3, 4), unbiased=False) + 1e-5)
-    return (so.detach(), v.detach(), mean, invstd, rmo, rvo, yo.grad, go.grad, bo.grad, None if vo is None else vo.grad,
-            torch.stack(fragile))
 
 
 @pytest.mark.parametrize("B,C,H,with_v,det", SHAPES, ids=lambda v: str(int(v)))
