@@ -240,6 +240,61 @@ constexpr bool v2_full_map_ok() {
 }
 static_assert(v2_full_map_ok(), "full 7x7 items: position table and block lists");
 
+// COPY ROLES.  A chunk's LDS-DMA pieces (14 image-row pieces "A", then the 27 weight pieces "W") are divided among the first nca / ncww
+// waves of a workgroup: wave w owns A pieces w * npa + j (j < npa = ceil(14 / nca)) and W pieces w + ncww * q.  Every form but the full
+// 7x7 one uses all its waves.  On full 7x7 items the interior waves (27 steps per chunk) set the length of the chunk and the border wave
+// of their SIMD reaches the chunk barrier 9 steps (bottom: 6) before them: the three 18-step waves -- top, right, left -- issue ALL the
+// copies, 14 / 14 / 13 pieces, one per step from the chunk's first; the bottom wave and the interior waves issue none.  A border class
+// is ONE wave, so its piece table is a compile-time constant (scalar instructions of a den.conv4 launch 20.3 M -> 15.0 M).  Same box,
+// three alternating passes, B = 256 (profiles/copy_roles_ab.txt): dense reverse process 78.55-78.63 -> 77.11-77.35 ms, den.conv4 / conv5
+// main + tail 322-327 / 311-313 -> 317-321 / 306-307 us.  The same file has what paid less or not at all: the four border waves copying
+// (11 / 11 / 11 / 8 pieces) -0.8 ms where three waves give -1.2; two pieces per step, or the first piece at step 2, 0.1-0.4 ms slower
+// than one per step from step 0; and the input-record COUNTING moved to the border waves as well (four records per thread of 256):
+// +0.4 ms on its own, and the copies' gain gone when both move -- the counting keeps its symmetric form, thread tid of 512 counts
+// records tid and tid + 512.
+constexpr int V2_FULL_NCA = 3, V2_FULL_NCWW = 3;         // full 7x7 items: waves that copy A pieces / W pieces
+constexpr int v2_ceil_div(int a, int b) { return (a + b - 1) / b; }
+constexpr int v2_copy_na(int na, int ncw, int w) {       // A pieces wave w really has (the table repeats the last one beyond them)
+  const int npa = v2_ceil_div(na, ncw), left = na - w * npa;
+  return w >= ncw || left <= 0 ? 0 : (left < npa ? left : npa);
+}
+constexpr int v2_copy_nw(int nw, int ncw, int w) {       // W pieces wave w really has
+  return w >= ncw || w >= nw ? 0 : (nw - w + ncw - 1) / ncw;
+}
+// LDS byte offset of record r = (cell, step) inside a slab of width w; a thread without a record reads cell 0, a border cell (always
+// zero): an unconditional read (a conditional one is a branch with an LDS wait of its own, twice per chunk)
+constexpr int v2_rec_off(int r, int nrec, int w) {
+  const int cl = r >> 4, t = r & 15;
+  return r < nrec ? (((cl / w) + 1) * (w + 1) + 1 + (cl % w)) * POSB + t * 16 : 0;
+}
+// every piece of a chunk is issued by exactly one wave; every record of an item is counted by exactly one thread, inside the image;
+// a thread's slot without a record reads the zero cell
+constexpr bool v2_roles_ok(int nwv, int nca, int ncww, int na, int nw, int nrec, int w) {
+  int pa[64] = {}, pw[64] = {};
+  if (na > 64 || nw > 64 || nca > nwv || ncww > nwv) return false;
+  for (int wv = 0; wv < nwv; ++wv) {
+    for (int j = 0; j < v2_copy_na(na, nca, wv); ++j) ++pa[wv * v2_ceil_div(na, nca) + j];
+    for (int q = 0; q < v2_copy_nw(nw, ncww, wv); ++q) ++pw[wv + ncww * q];
+  }
+  for (int i = 0; i < na; ++i) if (pa[i] != 1) return false;
+  for (int i = 0; i < nw; ++i) if (pw[i] != 1) return false;
+  const int nct = 64 * nwv, nr = v2_ceil_div(nrec, nct);
+  int seen[1024] = {};
+  if (nrec > 1024) return false;
+  for (int tid = 0; tid < nct; ++tid)
+    for (int k = 0; k < nr; ++k) {
+      const int r = tid + k * nct, off = v2_rec_off(r, nrec, w);
+      if (r < nrec) {
+        const int cell = off / POSB, y = cell / (w + 1), x = cell % (w + 1);
+        if (y < 1 || x < 1 || x > w || (y - 1) * w + (x - 1) != (r >> 4) || (off % POSB) != (r & 15) * 16) return false;
+        ++seen[r];
+      } else if (off != 0) return false;
+    }
+  for (int r = 0; r < nrec; ++r) if (seen[r] != 1) return false;
+  return true;
+}
+static_assert(v2_roles_ok(8, V2_FULL_NCA, V2_FULL_NCWW, 7 * 2, W_PIECES, 7 * 7 * 16, 7), "full 7x7 items: 41 pieces, 784 records, one owner each");
+
 // CLS (full 7x7 items): the wave class this instance serves; the kernel branches once per wave, so that a class's K loop, scan and
 // register allocation are its own (one body whose chunk loops alone were per class spilled 109 registers at the joins).
 template <int H, int W, int NWV, bool SPLIT, int NTP, bool HALF = false, int CLS = V2_INT>
@@ -271,11 +326,18 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   constexpr int A_BYTES = NPP * POSB;                  //  column is shared by x = -1 of a row and x = W of the previous)
   constexpr int PPR = (W + 3) / 4;                     // DMA pieces per image row (4 positions per KiB piece)
   constexpr int NA = Hin * PPR;
-  constexpr int NPA = (NA + NWV - 1) / NWV;            // A pieces per wave
-  constexpr int NPW = (W_PIECES + NWV - 1) / NWV;      // W pieces per wave
   constexpr bool BSKIP = NWV == 8 && !PRUNE && !SPLIT;  // full 7x7 items: per-wave block lists without the pure-border taps (V2_PLAN)
   static_assert(!BSKIP || (H == 7 && W == 7 && NT == V2_FT), "border skip: the position table is for 7x7 items of three tiles per wave");
   static_assert(BSKIP || CLS == V2_INT, "wave classes: full 7x7 items only");
+  // copy roles (v2_roles_ok): full 7x7 items give the copies to border waves, whose class fixes the wave
+  constexpr int NCA = BSKIP ? V2_FULL_NCA : NWV, NCWW = BSKIP ? V2_FULL_NCWW : NWV;
+  constexpr bool KNOWN = BSKIP && CLS != V2_INT;       // a border class is ONE wave: its piece table is a constant
+  constexpr int CWV = KNOWN ? CLS - 1 : 0;
+  static_assert(!KNOWN || V2_WAVE_CLS[CWV] == CLS, "border class k is wave k - 1");
+  static_assert(!BSKIP || v2_roles_ok(NWV, NCA, NCWW, NA, W_PIECES, Hin * W * 16, W), "copy roles, record counting");
+  constexpr int NPA_T = (NA + NCA - 1) / NCA;          // A pieces per copying wave (the table's stride) ...
+  constexpr int NPA = KNOWN ? v2_copy_na(NA, NCA, CWV) : ((!BSKIP || NCA == NWV) ? NPA_T : 0);   // ... and what this body issues
+  constexpr int NPW = KNOWN ? v2_copy_nw(W_PIECES, NCWW, CWV) : ((!BSKIP || NCWW == NWV) ? (W_PIECES + NCWW - 1) / NCWW : 0);
   static_assert(NWV >= 8 || NACC * NT <= 16 || (NT - 1) * NACC <= N_AGPR + 2, "only the last tile may straddle the register files");
   constexpr bool AH = NWV == 8 && !PRUNE;                // (two waves per SIMD on full items)
   constexpr int NBUF = 2;                              // slab buffers: the copies of chunk c + 1 are issued during chunk c
@@ -290,6 +352,23 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nch = a.nch;
   const int G = a.Cout >> 5;
+  const int wave_s = KNOWN ? CWV : __builtin_amdgcn_readfirstlane(wave);
+  const unsigned lane16 = (unsigned)lane * 16u;
+  const unsigned wave_k = (unsigned)wave_s * 1024u;
+  const uint8_t* const wbase = a.wq + (long long)g * nch * W_SLAB;
+  const int nitems = (SPLIT || HALF) ? 2 * n_images : n_images;
+  auto issue_w = [&](int qw, const uint8_t* wslab, unsigned dW) {   // W piece qw of this wave (a table slot beyond the slab repeats the last)
+    unsigned ko = wave_k + 1024u * NCWW * (unsigned)qw;
+    if (NCWW * qw + NCWW - 1 >= W_PIECES) ko = ko < (unsigned)W_PIECES * 1024u ? ko : ko - 1024u * NCWW;
+    spk_dma16s(wslab + ko, lane16, dW + ko);
+  };
+  if constexpr (BSKIP && NPW > 0) {
+    // the first chunk's weight pieces do not land in anything the zeroing below touches: issued in front of it and of its barrier
+    if (il < nitems) {
+#pragma unroll
+      for (int q = 0; q < NPW; ++q) issue_w(q, wbase, sW_addr);
+    }
+  }
   // zero the A images once: the borders stay zero for the whole kernel, interiors are overwritten by DMA
   for (int i = tid; i < NBUF * A_BYTES / 16; i += NWV * 64) reinterpret_cast<uint4*>(sA)[i] = make_uint4(0, 0, 0, 0);
   if (REC)
@@ -311,38 +390,29 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
 
   // DMA piece table (wave-uniform): bits 0..13 source byte offset in the slab, 14..28 LDS byte offset in the image,
   // 29..30 positions in the piece - 1.  Pieces beyond the slab repeat the last one so that the K loop issues unconditionally.
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  unsigned pa_pk[NPA];
+  unsigned pa_pk[NPA > 0 ? NPA : 1];
 #pragma unroll
   for (int j = 0; j < NPA; ++j) {
-    int id = wave_s * NPA + j;
+    int id = wave_s * NPA_T + j;
     id = id < NA ? id : NA - 1;
     const int y = id / PPR, px = id - y * PPR;
     const int np = (W - 4 * px) < 4 ? (W - 4 * px) : 4;
     const unsigned src = (unsigned)((y * W + 4 * px) * POSB), dst = (unsigned)(((y + 1) * PW + 1 + 4 * px) * POSB);
     pa_pk[j] = src | (dst << 14) | ((unsigned)(np - 1) << 29);
   }
-  const unsigned lane16 = (unsigned)lane * 16u;
-  const unsigned wave_k = (unsigned)wave_s * 1024u;
   auto issue_piece = [&](int q, const uint8_t* aslab, const uint8_t* wslab, unsigned dA, unsigned dW) {
     if (q < NPA) {
       const unsigned pk = pa_pk[q];
       const unsigned np = ((pk >> 29) & 3u) + 1u;
       const unsigned long long mask = np == 4 ? ~0ull : ((1ull << (16 * np)) - 1ull);
       spk_dma16s_masked(aslab + (pk & 0x3fffu), lane16, dA + ((pk >> 14) & 0x7fffu), mask);
-    } else {
-      unsigned ko = wave_k + 1024u * NWV * (unsigned)(q - NPA);
-      if (NWV * (q - NPA) + NWV - 1 >= W_PIECES) ko = ko < (unsigned)W_PIECES * 1024u ? ko : ko - 1024u * NWV;
-      spk_dma16s(wslab + ko, lane16, dW + ko);
-    }
+    } else issue_w(q - NPA, wslab, dW);
   };
-  const uint8_t* const wbase = a.wq + (long long)g * nch * W_SLAB;
   // item index -> (image, band); the slab of a band starts (H/2 - 1) rows into the image for the bottom band
   auto aslab_of = [&](int itm, int c) -> const uint8_t* {
     const int b = HALF ? itm >> 1 : (PRUNE ? slots[itm] : (SPLIT ? itm >> 1 : itm)), band = SPLIT ? itm & 1 : 0;
     return a.in0 + ((long long)b * nch + c) * HW * POSB + band * (Hb - 1) * W * POSB;
   };
-  const int nitems = (SPLIT || HALF) ? 2 * n_images : n_images;
 
   // per-channel constants (the group is fixed: loaded once)
   const int co = g * 32 + (lane & 31);
@@ -363,7 +433,7 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   if (il < nitems) {
     const uint8_t* as0 = aslab_of(il, 0);
 #pragma unroll
-    for (int q = 0; q < NPA + NPW; ++q) issue_piece(q, as0, wbase, sA_addr, sW_addr);
+    for (int q = 0; q < (BSKIP ? NPA : NPA + NPW); ++q) issue_piece(q, as0, wbase, sA_addr, sW_addr);
     if constexpr (AH) {                                   // (the only chunks whose copies no chunk barrier has waited for)
       spk_dma_wait_all();
       __syncthreads();
@@ -392,15 +462,13 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
     constexpr int NREC = Hin * W * 16, NR = (NREC + NWV * 64 - 1) / (NWV * 64);
     int creg[NR];
     int rec_off[NR];                                      // LDS byte offset of the record inside a slab; threads without one read
-    bool rec_ok[NR];                                      //  cell 0, a border cell (always zero): an unconditional read (a conditional
-                                                          //  one is a branch with an LDS wait of its own, twice per chunk)
+    bool rec_ok[NR];                                      //  the zero cell (v2_rec_off)
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
       creg[k] = 0;
       const int r = tid + k * NWV * 64;
-      const int cl = r >> 4, t = r & 15;
       rec_ok[k] = r < NREC;
-      rec_off[k] = rec_ok[k] ? (((cl / W) + 1) * PW + 1 + (cl % W)) * POSB + t * 16 : 0;
+      rec_off[k] = v2_rec_off(r, NREC, W);
     }
     constexpr int PFX = NWV == 4 ? SPK_V2_PF : 4;
     v6i bp[2][2];                                         // digit-pair tiles of block parity [blk & 1][pair]  (AH: carried over the
@@ -436,13 +504,16 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
         constexpr int NPIECES = NPA + NPW;
         // what the schedule below relies on:
         static_assert(P.nt[0] == NT, "the first block writes (not accumulates) every accumulator");
-        static_assert(2 * NBLK >= NPIECES, "two copy slots per block: every DMA piece of the wave gets one");
+        // copy slots: two per block (its first step and its middle step), or, where three waves copy for eight (full 7x7 items), one per
+        // step from the chunk's first -- a wave's 14 pieces are out by step 13 of 18, the last step in front of the chunk barrier
+        constexpr bool SLOT1 = BSKIP && (NCA != NWV || NCWW != NWV);
+        static_assert(SLOT1 || 2 * NBLK >= NPIECES, "two copy slots per block: every DMA piece of the wave gets one");
         static_assert((!AH || NSTEP >= 2 * PF) && (!REC || NSTEP > SPK_V2_REC_STEP), "look-ahead slots; the record-count steps exist");
         // AH, the chunk barrier at step NSTEP - PF: the copies are issued in front of it (it waits for them), and so is every read of
         // the current buffers -- the last fragment at step NSTEP - PF - 1 by construction, the last weight tiles at the first step of
         // the last block but one (8x8 bands, two tiles per wave: in the step that opens with the barrier; the first copy into these
         // buffers is PF steps behind it)
-        static_assert(!AH || (v2_plan_start(P, (NPIECES + 1) / 2) <= NSTEP - PF && v2_plan_start(P, NBLK - 2) <= NSTEP - PF),
+        static_assert(!AH || ((SLOT1 ? NPIECES : v2_plan_start(P, (NPIECES + 1) / 2)) <= NSTEP - PF && v2_plan_start(P, NBLK - 2) <= NSTEP - PF),
                       "chunk barrier behind the copies and the last weight-tile read");
         auto lda_at = [&](const uint8_t* base, auto s_tag) -> v4i {
           constexpr int s = decltype(s_tag)::value;
@@ -483,11 +554,12 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
             constexpr int k = s % PF;                         // (PF == 4: next step k lives in slot k)
             if (ahead) af[k] = lda_at(An, std::integral_constant<int, k>{});
           }
-          // two copy slots per block (its first step and its middle step): 18 slots for the 11 pieces of the four-digit form
+          // (two per block: 18 slots for the 11 pieces of a wave of four)
 #define V2_DMA_SLOT()                                                                              \
   do {                                                                                             \
-    if constexpr (j == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);     \
-    if constexpr (j == (nt > 1 ? nt / 2 : 0) && 2 * blk + 1 < NPIECES)                             \
+    if constexpr (SLOT1 && s < NPIECES) issue_piece(s, n_aslab, n_wslab, n_dA, n_dW);                 \
+    if constexpr (!SLOT1 && j == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);     \
+    if constexpr (!SLOT1 && j == (nt > 1 ? nt / 2 : 0) && 2 * blk + 1 < NPIECES)                   \
       issue_piece(2 * blk + 1, n_aslab, n_wslab, n_dA, n_dW);                                      \
   } while (0)
           // the next block's weight tiles are requested at the first step of this block
