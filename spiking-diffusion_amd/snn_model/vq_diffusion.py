@@ -10,6 +10,8 @@ reverse process without any host synchronisation.  Latent size and T are paramet
 7x7 and 16: vq_diffusion.py:47-48,106,198,206).
 """
 import math
+import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -57,6 +59,43 @@ class Sampler(nn.Module):
         super().__init__()
 
 
+class SampleForm(NamedTuple):
+    """Launch form of one ``sample()`` call, decided by ``AbsorbingDiffusion._form`` (same tokens in every form)."""
+    skip: bool          # elimination: the denoiser runs on the images spk_select_active lists for the step
+    lists: bool         # ... and its MFMA layers on the positions spk_select_needed lists
+    tail: bool          # dense: conv6 + token update + the next step's first layer as one launch (spk_den_step_tail)
+    tail_act: bool      # elimination: conv6 + token update of the active images as one launch (step_tail_in_elimination)
+
+
+class _Noise(NamedTuple):
+    """u / q of a reverse step: ``draw`` t -> (u, q) (injected, or the host's); without it Philox on the device, keyed by ``seed``
+    or, with ``state``, by the 2-word device buffer {seed, counter base} a captured graph reads; counters at the step's offset."""
+    draw: object = None
+    seed: int = 0
+    state: object = None
+
+
+class _SamplerGraph:
+    """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
+    conditional form), its result ``x_t``, and every other buffer the captured launches address by raw pointer: freed earlier,
+    its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
+    (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
+    and the flag workspaces of the certified kernels (``flag_ws``)."""
+
+    def __init__(self, dev, b, h, w, form, radii, conditional):
+        self.graph = self.derived = None                            # set by the capture
+        self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
+        self.unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
+        self.start_in = (torch.empty((b, h, w), dtype=torch.int64, device=dev),
+                         torch.empty((b, h, w), dtype=torch.uint8, device=dev)) if conditional else None
+        self.act = (torch.zeros(b, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)) if form.skip else None
+        self.need = ops.NeedLists(b, radii, dev) if form.lists else None
+        # dense form without the fused step tail: every spk_psample_step also writes the next step's denoiser input
+        self.inp = None if (form.skip or form.tail) else torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
+        self.flag_ws = {}
+
+
 class AbsorbingDiffusion(Sampler):
     def __init__(self, denoise_fn, mask_id, latent_shape=(7, 7)):
         super().__init__()
@@ -69,7 +108,7 @@ class AbsorbingDiffusion(Sampler):
         self.mask_schedule = 'random'
         self.loss_type = 'reweighted_elbo'
         # 'philox': on-device counter-based noise (throughput); 'host': u and q drawn per step from torch's global
-        # CPU generator in the reference's order (rand_like, then multinomial's exponential_), which reproduces the
+        # CPU generator in the reference's order (rand_like, then multinomial's exponential draw), which reproduces the
         # reference CPU path token for token under the same torch.manual_seed.
         self.noise_source = 'philox'
         # Philox contract ('philox' mode): every sample() call takes ONE 62-bit draw from torch's global CPU generator as
@@ -84,7 +123,6 @@ class AbsorbingDiffusion(Sampler):
         #       see ``set_shard``); ranks must use the SAME key: seed them alike, or let ``sync_key`` broadcast rank 0's draw.
         #   'rank': the rounds 1-3 form -- local image index, step stride b*h*w*K, the RANK folded into the key
         #       (``philox_stream``): ranks seeded alike draw distinct noise, but the sample depends on the split.
-        import os
         self.noise_layout = 'global'
         self.global_first = 0
         # The key broadcast is a COLLECTIVE, so it is opt-in: it happens only in a sampler that ``set_shard`` declared a shard of a
@@ -112,7 +150,7 @@ class AbsorbingDiffusion(Sampler):
         self.list_positions = True
         # ... from this batch size on: below it every launch of a reverse step is latency bound and the list bookkeeping (one more
         # launch per step, per-class item division) costs more than the skipped positions save -- R/main.py's own n_samples = 16:
-        # 7.04 ms per 49-step sample without lists, 7.75 with; B = 32: 8.9 / 8.25 (tools/small_batch_time.py, profiles/r6_small_batch.txt)
+        # 7.04 ms per 49-step sample without lists, 7.75 with; B = 32: 8.9 / 8.25 (tools/small_batch_time.py, profiles/r6_ab_kernel_variants.txt (1))
         self.list_min_batch = 24
         # elimination forms: conv6 on the spike counts + the token update of the ACTIVE images as one launch per slot (spk_den_step_tail with
         # the active list) instead of two (spk_den_conv3x3_counts_mfma, spk_psample_step).  Same tokens -- and measured SLOWER (round 6, one
@@ -194,20 +232,20 @@ class AbsorbingDiffusion(Sampler):
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         h, w = self.shape
-        K = self.num_classes
         if start is not None and (start[0].device != dev or start[1].device != dev):
             raise ValueError(f'spkdiff: x_init / known must be on the denoiser\'s device {dev}')
         if sample_steps is None:
             sample_steps = self.num_timesteps
-        seed, base = 0, 0
+        seed = 0
         if noise is None and self.noise_source == 'philox':
             seed = self._philox_key()
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
+        form = self._form(b, h, w, record is not None)
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
-                return self._sample_graphed(dev, b, h, w, K, float(temp), int(sample_steps), seed, base, start=start)
+                return self._sample_graphed(dev, b, h, w, form, float(temp), int(sample_steps), seed, start=start)
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -225,52 +263,62 @@ class AbsorbingDiffusion(Sampler):
                 torch.cuda.synchronize(dev)
             finally:
                 self._capturing = False
+        return self._sample_eager(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed, start, record)
+
+    def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None):
+        """The reverse process launched kernel by kernel: fresh state buffers, the one step loop."""
+        x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
+        unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
+        self._fill_start(x_t, unmasked, start)
+        if noise is None and self.noise_source == 'host':
+            # u and q from torch's global CPU generator in the reference's order: rand_like(x_t.float()) (:116), then
+            # multinomial's one-draw fast path (:138); the denoiser call between them there draws nothing
+            K = self.num_classes
+            noise = lambda t: (torch.rand(b, 1, h, w).to(dev), torch.empty(b * h * w, K).exponential_(1).to(dev))      # noqa: E731
+        need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
+        self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record)
+        return x_t
+
+    def _fill_start(self, x_t, unmasked, start):
+        """Start state into the given buffers: all masked, or ``start = (codes, keep)`` through spk_completion_state."""
         if start is None:
-            x_t = torch.full((b, 1, h, w), int(self.mask_id), dtype=torch.int64, device=dev)
-            unmasked = torch.zeros((b, 1, h, w), dtype=torch.bool, device=dev)
+            x_t.fill_(int(self.mask_id))
+            unmasked.zero_()
         else:
-            x_t, unmasked, _ = ops.completion_state(start[0], start[1], K, int(self.mask_id))
-        skip = self._skip_ok(h, w) and record is None
-        act = None
-        need = ops.NeedLists(b, int(self.list_radii), dev) if skip and self._list_ok(h, w, b) else None
-        tail = (not skip) and dn.tail_fusable(h, w)                      # dense loop: the fused step tail (same tokens)
-        tail_act = skip and self.step_tail_in_elimination and dn.tail_fusable(h, w)
+            ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
+
+    def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None):
+        """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
+        in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
+        ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
+        ``inp``: dense form without the fused tail -- [B,2,h,w] buffer of the denoiser input, built once and then written by
+        every spk_psample_step (one launch less per step; None: every step builds its own); ``record``: see sample()."""
+        dn = self._denoise_fn
+        b, _, h, w = x_t.shape
+        K = self.num_classes
+        seed, state = src.seed, src.state
         pre1 = None
         for t in reversed(range(1, sample_steps + 1)):
-            u = q = None
-            if noise is not None:
-                u, q = noise(t)
-            elif self.noise_source == 'host':
-                u = torch.rand(b, 1, h, w).to(dev)                       # rand_like(x_t.float()), drawn first (:116)
-            off = base + self._step_offset(sample_steps - t, b, h, w, K)
-            if tail:
-                if noise is None and self.noise_source == 'host':
-                    q = torch.empty(b * h * w, K).exponential_(1).to(dev)    # (the denoiser call draws nothing: same order)
-                pre1, logits = dn.sample_step(x_t, unmasked, t, temp, u, q, seed, off, pre1=pre1, want_next=t > 1,
-                                              want_logits=record is not None)
-                if record is not None:
-                    record.append((t, x_t.clone(), unmasked.clone(), logits))
-                continue
-            if skip:
-                act = ops.select_active(unmasked, t, u, seed, off, out=act, K=K)
-                if need is not None:
-                    ops.select_needed(unmasked, t, act, need, u, seed, off, K=K)
-            with ops.active_set(*(act if skip else (None, None)), need=need):
-                if skip and tail_act:
-                    # elimination forms, round 6: conv6 on the counts + the token update as ONE launch per active slot (the step tail
-                    # without a next-step first layer: that belongs to the next step's active set)
-                    if noise is None and self.noise_source == 'host':
-                        q = torch.empty(b * h * w, K).exponential_(1).to(dev)
-                    _, logits = dn.sample_step(x_t, unmasked, t, temp, u, q, seed, off, want_next=False,
-                                               want_logits=record is not None)
+            u, q = (None, None) if src.draw is None else src.draw(t)
+            off = self._step_offset(sample_steps - t, b, h, w, K)
+            if form.skip:
+                act = ops.select_active(unmasked, t, u, seed, off, philox_state=state, out=act, K=K)
+                if form.lists:
+                    ops.select_needed(unmasked, t, act, need, u, seed, off, philox_state=state, K=K)
+            elif inp is not None and t == sample_steps:
+                ops.den_build_input(x_t, t, out=inp)
+            with ops.active_set(*(act if form.skip else (None, None)), need=need):
+                if form.tail or form.tail_act:
+                    # conv6 on the counts + the token update as ONE launch -- dense: with the next step's first layer (pre1);
+                    # elimination: per active slot, without it (that layer belongs to the next step's active set)
+                    pre1, logits = dn.sample_step(x_t, unmasked, t, temp, u, q, seed, off, philox_state=state, pre1=pre1,
+                                                  want_next=form.tail and t > 1, want_logits=record is not None)
                 else:
-                    logits = dn.logits_from_tokens(x_t, t)                   # denoiser + reset_net (:128-129)
-                    if noise is None and self.noise_source == 'host':
-                        q = torch.empty(b * h * w, K).exponential_(1).to(dev)    # multinomial's one-draw fast path (:138)
-                    ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off)
+                    logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
+                    ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
+                                     next_input=inp if t > 1 else None)
             if record is not None:
                 record.append((t, x_t.clone(), unmasked.clone(), logits.clone()))
-        return x_t
 
     def _start_state_args(self, x_init, known):
         """Argument checks of ``sample(x_init=, known=)``, before anything is drawn or launched: None for the unconditional call,
@@ -300,17 +348,24 @@ class AbsorbingDiffusion(Sampler):
         keep = known.reshape(B, h, w).contiguous()
         return codes, (keep.view(torch.uint8) if keep.dtype == torch.bool else keep)
 
-    def _skip_ok(self, h, w):
-        return bool(self.skip_untouched)            # every kernel family takes the device-side image count
-
     def _list_ok(self, h, w, b=None):
         return bool(self.list_positions) and (h, w) == (7, 7) and (b is None or b >= int(self.list_min_batch))
 
+    def _form(self, b, h, w, recording=False):
+        """THE decision of the launch form (SampleForm) for a batch of ``b`` on an h x w latent: the eager call, the captured
+        graph, its cache key and ``form_for`` read it.  Every kernel family takes the device-side image count, so
+        ``skip_untouched`` holds at any shape -- but not under ``record=``: a record holds the logits of EVERY image at every
+        step, and the elimination forms compute them per slot of the active list, for the touched images only."""
+        skip = bool(self.skip_untouched) and not recording
+        fused = (not skip or bool(self.step_tail_in_elimination)) and self._denoise_fn.tail_fusable(h, w)
+        return SampleForm(skip=skip, lists=skip and self._list_ok(h, w, b), tail=fused and not skip, tail_act=fused and skip)
+
     def form_for(self, b, h, w, sample_steps=None):
         """Name of the launch form ``sample()`` takes for a batch of ``b`` on an h x w latent (same tokens in every form)."""
-        if not self._skip_ok(h, w):
-            return 'dense_step_tail' if self._denoise_fn.tail_fusable(h, w) else 'dense'
-        return 'elimination_lists' if self._list_ok(h, w, b) else 'elimination'
+        form = self._form(b, h, w)
+        if not form.skip:
+            return 'dense_step_tail' if form.tail else 'dense'
+        return 'elimination_lists' if form.lists else 'elimination'
 
     STEP_STRIDE = 1 << 40        # 'global' layout: counters of one reverse step (images * h*w * K of them must fit)
 
@@ -378,97 +433,49 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional):
+        # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
+        dn = self._denoise_fn
+        weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
+        return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
+                bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, int(self.global_first), weights,
+                conditional)
 
-def _weights_key(module):
-    return tuple((p.data_ptr(), p._version) for p in list(module.parameters()) + list(module.buffers())) + derived_epoch(module)
+    def _graph_body(self, g, form, temp, sample_steps):
+        """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state."""
+        self._fill_start(g.x_t, g.unmasked, g.start_in)
+        self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp, sample_steps, act=g.act, need=g.need, inp=g.inp)
 
-
-def _sample_graphed(self, dev, b, h, w, K, temp, sample_steps, seed, base, start=None):
-    """Capture-once / replay-many form of the loop in ``sample``; same kernels, same results as the eager loop for the
-    same (seed, counter base).  ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static
-    buffers filled before each replay; spk_completion_state is the first node in place of the two fills) and the graph has a
-    cache key of its own."""
-    dn = self._denoise_fn
-    skip = self._skip_ok(h, w)
-    lists = skip and self._list_ok(h, w, b)
-    key = (str(dev), b, h, w, K, temp, sample_steps, int(self.mask_id), skip, lists, int(self.list_radii),
-           bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, int(self.global_first), _weights_key(dn))
-    if start is not None:
-        key = key + ('x_init',)
-    entry = self._graphs.get(key)
-    if entry is None:
-        if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
-            self._graphs.clear()                                #  elimination forms): their buffers are not small
-        state = torch.zeros(2, dtype=torch.int64, device=dev)
-        x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
-        unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
-        start_in = None if start is None else (torch.empty((b, h, w), dtype=torch.int64, device=dev),
-                                               torch.empty((b, h, w), dtype=torch.uint8, device=dev))
-
-        act = (torch.zeros(b, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)) if skip else None
-        need = ops.NeedLists(b, int(self.list_radii), dev) if lists else None
-
-        # dense form: the fused step tail where the architecture fits (conv6 + token update + the next step's first layer in
-        # one launch), else every spk_psample_step also writes the next step's denoiser input (one launch less per step)
-        tail = (not skip) and dn.tail_fusable(h, w)
-        tail_act = skip and self.step_tail_in_elimination and dn.tail_fusable(h, w)
-        inp = None if (skip or tail) else torch.empty((b, 2, h, w), dtype=torch.float32, device=dev)
-
-        def body():
-            if start_in is None:
-                x_t.fill_(int(self.mask_id))
-                unmasked.zero_()
-            else:
-                ops.completion_state(start_in[0], start_in[1], K, int(self.mask_id), out=(x_t, unmasked))
-            pre1 = None
-            for t in reversed(range(1, sample_steps + 1)):
-                off = self._step_offset(sample_steps - t, b, h, w, K)
-                if tail:
-                    pre1, _ = dn.sample_step(x_t, unmasked, t, temp, None, None, 0, off, philox_state=state, pre1=pre1,
-                                             want_next=t > 1)
-                    continue
-                if skip:
-                    ops.select_active(unmasked, t, None, 0, off, philox_state=state, out=act, K=K)
-                    if lists:
-                        ops.select_needed(unmasked, t, act, need, None, 0, off, philox_state=state, K=K)
-                elif t == sample_steps:
-                    ops.den_build_input(x_t, t, out=inp)
-                with ops.active_set(*(act if skip else (None, None)), need=need):
-                    if tail_act:
-                        dn.sample_step(x_t, unmasked, t, temp, None, None, 0, off, philox_state=state, want_next=False)
-                    else:
-                        logits = dn.logits_from_tokens(x_t, t, inp=inp)
-                        ops.psample_step(logits, x_t, unmasked, t, temp, None, None, 0, off, philox_state=state,
-                                         next_input=inp if t > 1 else None)
-
-        # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
-        flag_ws = {}
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side), ops.flag_scope(flag_ws):
-            dn.logits_from_tokens(torch.full((b, 1, h, w), int(self.mask_id), dtype=torch.int64, device=dev), 1)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        self._capturing = True
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"), ops.flag_scope(flag_ws):
-            body()
-        self._capturing = False
-        # every buffer the captured launches address by raw pointer lives as long as the graph: a tensor freed here would
-        # hand its block to the next allocation (another sampler's state, say) while replays keep writing to it.  That
-        # includes the denoiser's derived tensors (packed weights, BN terms: an invalidation re-keys the graph, and until the
-        # stale entry is evicted its memory must not be recycled) and the flag workspaces of the certified kernels.
-        entry = (graph, state, x_t, (need, inp, unmasked, act, flag_ws, derived_refs(dn)), start_in)
-        self._graphs[key] = entry
-    graph, state, x_t = entry[:3]
-    state.copy_(torch.tensor([seed, base], dtype=torch.int64), non_blocking=False)
-    if start is not None:
-        entry[4][0].copy_(start[0])
-        entry[4][1].copy_(start[1])
-    graph.replay()
-    return x_t.clone()
-
-
-AbsorbingDiffusion._sample_graphed = _sample_graphed
+    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None):
+        """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
+        ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
+        each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own."""
+        dn = self._denoise_fn
+        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None)
+        g = self._graphs.get(key)
+        if g is None:
+            if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
+                self._graphs.clear()                                #  elimination forms): their buffers are not small
+            g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None)
+            # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side), ops.flag_scope(g.flag_ws):
+                dn.logits_from_tokens(torch.full((b, 1, h, w), int(self.mask_id), dtype=torch.int64, device=dev), 1)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            g.graph = torch.cuda.CUDAGraph()
+            self._capturing = True
+            with torch.cuda.graph(g.graph, capture_error_mode="thread_local"), ops.flag_scope(g.flag_ws):
+                self._graph_body(g, form, temp, sample_steps)
+            self._capturing = False
+            g.derived = derived_refs(dn)
+            self._graphs[key] = g
+        g.state.copy_(torch.tensor([seed, 0], dtype=torch.int64), non_blocking=False)
+        if start is not None:
+            g.start_in[0].copy_(start[0])
+            g.start_in[1].copy_(start[1])
+        g.graph.replay()
+        return g.x_t.clone()
 
 
 class DummyModel(nn.Module):

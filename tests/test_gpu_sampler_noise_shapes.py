@@ -222,6 +222,46 @@ def test_timed_configuration_philox_graph_vs_oracle_on_host_made_noise(dev):
     assert all(v == 0 for v in bad.values()), bad
 
 
+LOOP_FORMS = [
+    # name, skip_untouched, list_positions, use_step_tail, step_tail_in_elimination, what form_for says
+    ("dense", False, False, False, False, "dense"),
+    ("dense+tail", False, False, True, False, "dense_step_tail"),
+    ("elim", True, False, True, False, "elimination"),
+    ("elim+lists", True, True, True, False, "elimination_lists"),
+    ("elim+lists+tail", True, True, True, True, "elimination_lists"),
+]
+
+
+def test_one_step_loop_eager_and_captured_in_every_form(dev):
+    """The one step loop behind sample(), driven captured (capture + replay, then a second replay) and eagerly (twice) under the
+    same seed, in each launch form: B = 3 on 7x7 (one image below and above ``list_min_batch = 1``), 5 steps (first step != a
+    middle step != last step).  First calls equal, second calls equal, first != second (a fresh key per call), and every
+    form equal to the dense eager result."""
+    from snn_model.vq_diffusion import AbsorbingDiffusion
+    den, _ = build_den(dev)
+    B, steps, K = 3, 5, 128
+    got = {}
+    for name, skip, lists, tail, tail_elim, form_name in LOOP_FORMS:
+        den.use_step_tail = tail
+        ab = AbsorbingDiffusion(den, mask_id=K)
+        ab.n_samples, ab.list_min_batch = B, 1
+        ab.skip_untouched, ab.list_positions, ab.step_tail_in_elimination = skip, lists, tail_elim
+        form = ab._form(B, 7, 7)
+        assert ab.form_for(B, 7, 7) == form_name and form.tail == (tail and not skip) and form.tail_act == tail_elim
+        for graph in (True, False):
+            ab.use_graph = graph
+            torch.manual_seed(4242)
+            for i in range(2):
+                got[name, graph, i] = ab.sample(temp=1.0, sample_steps=steps).cpu()
+            # (a failed capture would have switched use_graph off; the eager calls capture nothing more)
+            assert ab.use_graph is graph and len(ab._graphs) == 1
+    want = [got["dense", False, i] for i in range(2)]
+    assert not torch.equal(want[0], want[1]) and bool(((want[0] >= 0) & (want[0] < K)).all())
+    bad = {f"{name}_{'graph' if graph else 'eager'}_call{i}": int((tok != want[i]).sum()) for (name, graph, i), tok in got.items()}
+    parity("one_step_loop_eager_and_captured_forms", token_mismatches=bad, tokens=B * 49)
+    assert all(v == 0 for v in bad.values()), bad
+
+
 # =============================================================================================== d. spk_psample_step vs fp64
 # Fragile set.  A position's token is argmax_k r_k, r_k = softmax(l / temp)_k / q_k.  MEASURED on the CPU over the inputs of
 # the cases below (measure_fp32_error; tests/test_gpu_sampler_noise_shapes.py run on the host): the fp32 reference expression
