@@ -29,11 +29,12 @@ extern "C" {
 
 typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
 
-#define SPK_VERSION 105 /* 0.1.5 -- bumped whenever an exported signature changes or entry points are added (round 4 inserted `int K`
+#define SPK_VERSION 106 /* 0.1.6 -- bumped whenever an exported signature changes or entry points are added (round 4 inserted `int K`
                            * before the stream of spk_select_active / spk_select_needed: 101; round 5 added the VectorQuantizer's
                            * training branch and the training convolutions: 102, the token-table spike generator: 103; round 6: `int flag_cap` (and `int form` for spk_den_conv3x3_mfma_fp6v2) in front of the
                            * stream of the four certified-kernel entry points, spk_set_option / spk_get_option left the shipped library: 104;
-                           * `active` / `n_active` of spk_den_step_tail: 105); spkdiff/_lib.py refuses a library whose
+                           * `active` / `n_active` of spk_den_step_tail: 105; the host-side shape
+                           * predicates spk_*_supported / spk_vae_fp6_kind: 106); spkdiff/_lib.py refuses a library whose
                            * spk_version() differs from the signatures it declares.  Purely additive entry points (the SNN_VAE
                            * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
                            * symbol at import, so a library that lacks one fails there */
@@ -205,6 +206,14 @@ int spk_conv_fused_fwd(const void* in0, const uint8_t* in1, int C0, int C1, int 
                        spk_stream_t stream);
 
 /* ---- denoiser convolutions on the matrix cores ------------------------------------------------------------------ */
+/* Shape predicates.  Every matrix-core kernel family answers which layer shapes it takes through one host function -- 1 / 0
+ * (spk_vae_fp6_kind: the output form, or -1) from integers alone, no device needed -- and its entry point refuses exactly the shapes
+ * the predicate refuses (SPK_ERR_UNSUPPORTED, nothing launched).  What an entry point refuses beyond that depends on the call or the
+ * device, not on the shape: the batch size (grid and id widths), the device's LDS grant and CU count, the list arguments.
+ * The three denoiser forms (k, stride, pad: the layer's geometry, only 3 / 1 / 1 is taken; T: time steps; H x W: the latent): */
+int spk_den_conv3x3_mfma_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W);
+int spk_den_conv3x3_mfma_fp6_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W);
+int spk_den_conv3x3_mfma_fp6v2_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W);
 /* Bytes of the packed int8 digit-plane weights of one 3x3 layer ([Cout/16][Cin/32][9][2][32][32]); -1 if unsupported. */
 long long spk_den_packed_weight_bytes(int Cout, int Cin);
 /* fp32 conv weight [Cout,Cin,3,3] (+bias) -> four balanced base-256 int8 digit planes + per-channel 2^-s scale and
@@ -216,7 +225,7 @@ int spk_den_pack_weight_i8(const float* w, const float* bias, int8_t* wq, double
  * R/snn_model/vq_diffusion.py:166-187,201-206.  in1 (nch1 chunks) is concatenated after in0 along channels.
  * v_inout [B,Cout,h,w] or NULL (fresh LIF state, nothing written back).  out_counts (LIF mode, optional): per-neuron
  * spike counts over T as u8 [B,Cout/32,h*w,32], the input format of spk_den_conv3x3_counts_mfma.
- * n_dyn_or_null as in spk_conv_fused_fwd. */
+ * n_dyn_or_null as in spk_conv_fused_fwd.  SPK_ERR_UNSUPPORTED unless spk_den_conv3x3_mfma_supported (Cin = 32 * (nch0 + nch1)). */
 int spk_den_conv3x3_mfma(const uint8_t* in0_cptc, int nch0, const uint8_t* in1_cptc, int nch1, const int8_t* wq,
                          const double* scale, const double* bias_d, const float* bn_a, const float* bn_b,
                          float* v_inout, uint8_t* out_cptc, uint8_t* out_counts, float* out_f32, int mode, int T, int B,
@@ -252,8 +261,8 @@ int spk_den_pack_weight_fp6_cl_multi(const float* const* w_channels_last, const 
                                      double* const* scale, double* const* bias_d, const int* Cout, const int* Cin, int n,
                                      spk_stream_t stream);
 /* in_c4: nch chunks of 64 channels; out_c4 [B][Cout/64][h*w][16][32]; v_inout / out_counts as in spk_den_conv3x3_mfma.
- * SPK_ERR_UNSUPPORTED unless T == 16, Cout % 64 == 0 and the latent fits one of the kernel's LDS plans (up to 7x8 as
- * one item per image and channel group, 8x8 as two row bands).
+ * SPK_ERR_UNSUPPORTED unless spk_den_conv3x3_mfma_fp6_supported (Cin = 64 * nch): a latent runs as one item per image and channel
+ * group where that fits the kernel's LDS plan, 8x8 as two row bands.
  * n_dyn_or_null as in spk_conv_fused_fwd (the work items are then walked image-major). */
 int spk_den_conv3x3_mfma_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* scale, const double* bias_d,
                              const float* bn_a, const float* bn_b, float* v_inout, uint8_t* out_c4, uint8_t* out_counts,
@@ -277,7 +286,7 @@ int spk_den_conv3x3_mfma_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, c
  * form: 0 = automatic (7x7 latents with fewer items -- B x Cout / 32 -- than half the CUs run two half-image items per image on
  * four-wave workgroups: R/main.py's own n_samples = 16 leaves half the chip idle otherwise), 1 = whole-image items always (the
  * reference form for the bit-equality test of the split).  Same spikes bit for bit either way.
- * SPK_ERR_UNSUPPORTED unless T == 16, H == W == 7 or 8, Cout % 32 == 0 (Cin = 32 * nch). */
+ * SPK_ERR_UNSUPPORTED unless spk_den_conv3x3_mfma_fp6v2_supported (Cin = 32 * nch). */
 long long spk_den_packed_weight_fp6v2_bytes(int Cout, int Cin);
 int spk_den_pack_weight_fp6v2(const float* w, const float* bias, uint8_t* wq, double* scale, double* bias_d, float* wl1,
                               int* qtab, int Cout, int Cin, spk_stream_t stream);
@@ -318,12 +327,13 @@ long long spk_conv_packed_weight_i8_bytes(int Cout, int Cin, int k);
  * ceil(Cout/16)*16 entries (padding channels are zero). */
 int spk_pack_conv_weight_i8(const float* w, const float* bias, int8_t* wq, double* scale, double* bias_d, int Cout,
                             int Cin, int k, int transposed, spk_stream_t stream);
-/* (Conv2d | ConvTranspose2d) over binary spikes (plain PTC u8 [B,H*W,16,Cin], T = 16, Cin % 16 == 0) with exact int8
+/* (Conv2d | ConvTranspose2d) over binary spikes (plain PTC u8 [B,H*W,16,Cin]; spk_conv_mfma_fused_supported) with exact int8
  * MFMA accumulation, fused with BN + LIF (mode SPK_MODE_LIF -> out_ptc [B,Ho*Wo,16,Cout]) or with the membrane
  * read-out (mode SPK_MODE_MEMOUT: coef[16] -> out_f32 [B,Cout,Ho,Wo] (+tanh), out_u8): Encoder conv2/conv3, Decoder
  * convT1/convT2/convT3 of R/snn_model/vae_model.py:115-124,139-155,186.
  * SPK_MODE_LIF with coef AND out_f32 given: out_f32 [B,Ho*Wo,Cout] also receives sum_t coef[t] * spike[t] (the input of
  * spk_readout_collapsed_fwd); out_ptc may then be NULL (the spike frames are not stored). */
+int spk_conv_mfma_fused_supported(int Cin, int Cout, int T, int mode);
 int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, const double* scale, const double* bias_d,
                             const float* bn_a, const float* bn_b, float* v_inout, uint8_t* out_ptc, const float* coef,
                             float* out_f32, uint8_t* out_u8, int apply_tanh, int mode, int T, int B, int H, int W, int Cin,
@@ -333,7 +343,9 @@ int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, const doubl
  * x_bpc fp32 [B,H*W,Cin] = sum_t coef[t] * s_t (see spk_conv_mfma_fused_fwd); w = the layer's fp32 weight, Conv2d
  * [Cout,Cin,k,k] or ConvTranspose2d [Cin,Cout,k,k] (transposed = 1); coef_sum = sum_t coef[t]; stride 1, pad == k / 2.
  * out_f32 [B,Cout,H,W] (tanh if apply_tanh), out_u8 = uint8(clip(p + 0.5, 0, 1) * 255) (R/main.py:401).  fp32 arithmetic:
- * equal to the frame-by-frame sum up to fp32 round-off. */
+ * equal to the frame-by-frame sum up to fp32 round-off.  spk_readout_collapsed_supported: whether (Cin, Cout, k) fits the kernel at
+ * image width W; W <= 0 asks for every width up to 64. */
+int spk_readout_collapsed_supported(int Cin, int Cout, int k, int W);
 int spk_readout_collapsed_fwd(const float* x_bpc, const float* w, const float* bias_or_null, float coef_sum, float* out_f32,
                               uint8_t* out_u8, int apply_tanh, int B, int H, int W, int Cin, int Cout, int k, int pad,
                               int transposed, spk_stream_t stream);
@@ -345,16 +357,18 @@ int spk_conv_mfma_fused_lif_s32(const uint8_t* in_ptc, const int8_t* wq, const d
                                 spk_stream_t stream);
 /* The spike-input 3x3 stride-2 layers of the spiking VQ-VAE from the reset state on the block-scaled fp6 x fp4 MFMA
  * (csrc/vae_fp6.hip): the same spikes as spk_conv_mfma_fused_fwd -- five digit planes on the matrix cores, certified decisions,
- * exact recomputation of the flagged neurons.  Supported (T == 16, Cout % 32 == 0):
- *   transposed = 1, Cin = 64, (H, W) in {(14,14), (16,16)}, out_kind 0: Decoder convT2 (R/snn_model/vae_model.py:146-150) -> out =
- *       fp32 [B][4*H*W][Cout] = sum_t coef[t] * spike[t], the input of spk_readout_collapsed_fwd (the spike frames are not stored);
- *   transposed = 1, Cin = 16, (H, W) in {(7,7), (8,8)}, out_kind 1: Decoder convT1 (:139-144) -> out = S32 spikes [B][Cout/32][4*H*W][16][16 B];
- *   transposed = 0, Cin = 32, (H, W) in {(14,14), (16,16)}, out_kind 2: Encoder conv2 (:115-118) -> out = u8 PTC [B][H*W/4][16][Cout].
+ * exact recomputation of the flagged neurons.  spk_vae_fp6_kind answers which instance exists for a layer -- its out_kind, or -1:
+ *   out_kind 0: Decoder convT2 (R/snn_model/vae_model.py:146-150) -> out = fp32 [B][4*H*W][Cout] = sum_t coef[t] * spike[t], the input
+ *       of spk_readout_collapsed_fwd (the spike frames are not stored);
+ *   out_kind 1: Decoder convT1 (:139-144) -> out = S32 spikes [B][Cout/32][4*H*W][16][16 B];
+ *   out_kind 2: Encoder conv2 (:115-118) -> out = u8 PTC [B][H*W/4][16][Cout].
+ * spk_vae_fp6_fwd takes the out_kind that spk_vae_fp6_kind names for its layer (k 3, stride 2, pad 1; out_pad 1 if transposed).
  * in_s32: S32 spikes [B][ceil(Cin/32)][H*W][16][16 B] with zero nibbles in the channels beyond Cin (spk_ptc_to_s32 converts u8
  * PTC spikes).  spk_vae_fp6_pack: fp32 weight (Conv2d [Cout][Cin][3][3] / ConvTranspose2d [Cin][Cout][3][3]) (+bias) -> digit
  * tiles (spk_vae_fp6_packed_bytes), fp64 scale / bias [Cout], qtab int32 [Cout][9][Cin].  flag_words: zero-initialised u32
  * workspace of spk_vae_fp6_flag_words(B, Cout, Ho, Wo) words, clean again after the call; flag_cap as for
  * spk_den_conv3x3_mfma_fp6v2 (< 0: the whole id list). */
+int spk_vae_fp6_kind(int Cin, int Cout, int k, int stride, int pad, int out_pad, int transposed, int T, int H, int W);
 long long spk_vae_fp6_packed_bytes(int Cout, int Cin);
 int spk_vae_fp6_pack(const float* w, const float* bias, uint8_t* wq, double* scale, double* bias_d, int* qtab, int Cout, int Cin,
                      int transposed, spk_stream_t stream);
@@ -427,11 +441,12 @@ int spk_vq_train_bwd(const float* gout_bdhw, const float* gloss_or_null, const f
  * gw[co][ky][kx][ci] = sum_{n,y,x} gy[n,co,y,x] * s[n,ci,y+ky-1,x+kx-1] on the bf16 matrix cores -- the spikes are exact in bf16,
  * the fp32 output gradient is split into three bf16 terms exactly, so only the fp32 accumulation rounds.  gy_cl / spikes_cl:
  * channels-last fp32 [N = T*B][H*W][C]; gw_out fp32 [Cout][3][3][Cin] (= a channels-last [Cout,Cin,3,3] tensor); ws: scratch of
- * spk_conv3x3_wgrad_ws_bytes (split-K partial sums, added in a fixed order: deterministic).  7x7 or 8x8 maps (H == W),
- * Cout % 128 == 0, Cin % 64 == 0; otherwise SPK_ERR_UNSUPPORTED (use the framework's operator).
+ * spk_conv3x3_wgrad_ws_bytes (split-K partial sums, added in a fixed order: deterministic).  Shapes:
+ * spk_conv3x3_wgrad_supported; otherwise SPK_ERR_UNSUPPORTED (use the framework's operator).
  * The spike operand may also hold small non-negative integers (spike counts up to 256: exact in bf16) -- the time-collapsed
  * backward of the denoiser's last layer.
  * gb_out_or_null [Cout]: the bias gradient (sum of gy over images and positions), from the same pass over gy. */
+int spk_conv3x3_wgrad_supported(int Cout, int Cin, int H, int W);
 long long spk_conv3x3_wgrad_ws_bytes(int N, int Cout, int Cin);
 int spk_conv3x3_wgrad_bf16(const float* gy_cl, const float* spikes_cl, float* ws, long long ws_bytes, float* gw_out,
                            float* gb_out_or_null, int N, int H, int W, int Cout, int Cin, spk_stream_t stream);
@@ -441,8 +456,9 @@ int spk_conv3x3_wgrad_bf16(const float* gy_cl, const float* spikes_cl, float* ws
  * w[co][ky][kx][ci], channels-last fp32 tensors (gy [N][49][Cout], w [Cout][3][3][Cin], gi [N][49][Cin]).  Both operands are
  * split into three bf16 terms exactly and six cross products run on the bf16 matrix cores with fp32 accumulation (what is
  * dropped is below 2^-24 of a product): an fp32 GEMM's accuracy.  ws: spk_conv3x3_dgrad_ws_bytes(Cout, Cin) bytes (the packed
- * weight terms, rewritten by every call).  Deterministic.  7x7 or 8x8 maps (49 -> H * W), Cout % 16 == 0, Cin % 32 == 0; otherwise
- * SPK_ERR_UNSUPPORTED (use the framework's operator). */
+ * weight terms, rewritten by every call).  Deterministic.  Shapes (49 -> H * W on the other map size) and image counts N:
+ * spk_conv3x3_dgrad_supported; otherwise SPK_ERR_UNSUPPORTED (use the framework's operator). */
+int spk_conv3x3_dgrad_supported(int Cout, int Cin, int H, int W, int N);
 long long spk_conv3x3_dgrad_ws_bytes(int Cout, int Cin);
 int spk_conv3x3_dgrad_bf16(const float* gy_cl, const float* w_cl, uint8_t* ws, long long ws_bytes, float* gi_out, int N, int H,
                            int W, int Cout, int Cin, spk_stream_t stream);

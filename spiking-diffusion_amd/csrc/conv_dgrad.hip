@@ -454,8 +454,7 @@ template <bool F16>
 int dgrad_launch(const float* gy_cl, const float* w_cl, uint8_t* ws, long long ws_bytes, float* gi_out, int N, int H, int W,
                  int Cout, int Cin, hipStream_t stream, bool prepacked = false) {
   if (!gy_cl || (!w_cl && !prepacked) || !ws || !gi_out || N <= 0) return SPK_ERR_ARG;
-  if (H != W || (H != 7 && H != 8) || Cout <= 0 || Cin <= 0 || (Cout % KC) || (Cin % 32)) return SPK_ERR_UNSUPPORTED;
-  if ((long long)N * H * W * Cout >= (1LL << 31)) return SPK_ERR_UNSUPPORTED;    // (32-bit element offsets in the staging table)
+  if (!spk_conv3x3_dgrad_supported(Cout, Cin, H, W, N)) return SPK_ERR_UNSUPPORTED;
   if (ws_bytes < spk_conv3x3_dgrad_ws_bytes(Cout, Cin)) return SPK_ERR_ARG;
   const int nt = dgrad_nt(F16, N, Cin), CI = 32 * nt;
   const long long n = (long long)Cout * 9 * Cin;
@@ -480,7 +479,8 @@ int dgrad_launch(const float* gy_cl, const float* w_cl, uint8_t* ws, long long w
   if (!prepacked) SPK_LAUNCH_CHECK();
   const int grid = ((N + NIMG - 1) / NIMG) * (Cin / CI);
   const size_t lds = 2 * (size_t)w_blob(F16 ? 2 : 3, nt) + (size_t)NIMG * g_img(F16 ? 2 : 3, H) + 64;
-  if ((long long)lds > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;     // (only the workspace has been written so far)
+  // (not in the predicate: the device's LDS grant; only the workspace has been written so far)
+  if ((long long)lds > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;
   if (H == 7) {
     if (F16 && nt == 2) hipLaunchKernelGGL((dgrad3x3_kernel<2, true, 7>), dim3(grid), dim3(NTHR), lds, stream, a);
     else if (F16) hipLaunchKernelGGL((dgrad3x3_kernel<1, true, 7>), dim3(grid), dim3(NTHR), lds, stream, a);
@@ -495,6 +495,11 @@ int dgrad_launch(const float* gy_cl, const float* w_cl, uint8_t* ws, long long w
 }
 
 }  // namespace
+
+extern "C" int spk_conv3x3_dgrad_supported(int Cout, int Cin, int H, int W, int N) {
+  return H == W && (H == 7 || H == 8) && Cout > 0 && Cin > 0 && N > 0 && (Cout % KC) == 0 && (Cin % 32) == 0 &&
+         (long long)N * H * W * Cout < (1LL << 31);             // (32-bit element offsets in the staging table)
+}
 
 extern "C" long long spk_conv3x3_dgrad_ws_bytes(int Cout, int Cin) {
   if (Cout <= 0 || Cin <= 0 || (Cout % KC) || (Cin % 32)) return -1;

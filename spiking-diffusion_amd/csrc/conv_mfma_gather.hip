@@ -605,14 +605,25 @@ __global__ __launch_bounds__(256) void readout_collapsed_k3_kernel(ROArgs a) {
 
 }  // namespace
 
+// LDS of the generic read-out kernel: RO_RB + k - 1 input rows of W positions (channels padded by 4) and the whole weight
+static size_t readout_lds_bytes(int Cin, int Cout, int k, int W) {
+  return ((size_t)(RO_RB + k - 1) * W * (Cin + 4) + (size_t)Cout * k * k * Cin) * sizeof(float);
+}
+
+// W <= 0: any image width up to 64 (the widest the callers plan for)
+extern "C" int spk_readout_collapsed_supported(int Cin, int Cout, int k, int W) {
+  if (Cin <= 0 || Cout <= 0 || k <= 0) return 0;
+  return (k & 1) == 1 && (Cin % 8) == 0 && readout_lds_bytes(Cin, Cout, k, W > 0 ? W : 64) <= 64 * 1024;
+}
+
 extern "C" int spk_readout_collapsed_fwd(const float* x_bpc, const float* w, const float* bias, float coef_sum,
                                          float* out_f32, uint8_t* out_u8, int apply_tanh, int B, int H, int W, int Cin,
                                          int Cout, int k, int pad, int transposed, hipStream_t stream) {
   if (!x_bpc || !w || (!out_f32 && !out_u8) || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 || pad < 0)
     return SPK_ERR_ARG;
-  if ((k & 1) == 0 || pad != k / 2 || (Cin % 8) != 0) return SPK_ERR_UNSUPPORTED;       // "same" geometry, stride 1
-  const size_t lds = ((size_t)(RO_RB + k - 1) * W * (Cin + 4) + (size_t)Cout * k * k * Cin) * sizeof(float);
-  if (lds > 64 * 1024) return SPK_ERR_UNSUPPORTED;
+  if (!spk_readout_collapsed_supported(Cin, Cout, k, W)) return SPK_ERR_UNSUPPORTED;
+  if (pad != k / 2) return SPK_ERR_UNSUPPORTED;         // "same" geometry, stride 1 (not in the predicate: it takes no padding)
+  const size_t lds = readout_lds_bytes(Cin, Cout, k, W);
   ROArgs a;
   a.x = x_bpc; a.w = w; a.bias = bias; a.coef_sum = coef_sum; a.out_f32 = out_f32; a.out_u8 = out_u8; a.apply_tanh = apply_tanh;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.k = k; a.pad = pad; a.transposed = transposed;
@@ -633,7 +644,7 @@ extern "C" int spk_readout_collapsed_fwd(const float* x_bpc, const float* w, con
     }
   }
   const long long blocks = (long long)B * ((H + RO_RB - 1) / RO_RB);
-  if (blocks > 0x7fffffffLL) return SPK_ERR_UNSUPPORTED;
+  if (blocks > 0x7fffffffLL) return SPK_ERR_UNSUPPORTED;       // (not in the predicate: grid size, grows with the batch)
   hipLaunchKernelGGL(readout_collapsed_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, a);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
@@ -720,6 +731,10 @@ extern "C" int spk_pack_conv_weight_i8(const float* w, const float* bias, int8_t
   return SPK_OK;
 }
 
+extern "C" int spk_conv_mfma_fused_supported(int Cin, int Cout, int T, int mode) {
+  return T == T16 && Cin > 0 && Cout > 0 && (Cin % 16) == 0 && (mode == SPK_MODE_LIF || mode == SPK_MODE_MEMOUT);
+}
+
 extern "C" int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, const double* scale,
                                        const double* bias_d, const float* bn_a, const float* bn_b, float* v_inout,
                                        uint8_t* out_ptc, const float* coef, float* out_f32, uint8_t* out_u8,
@@ -728,7 +743,7 @@ extern "C" int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, 
   if (!in_ptc || !wq || !scale || !bias_d || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 ||
       stride <= 0 || pad < 0)
     return SPK_ERR_ARG;
-  if (T != T16 || (Cin % 16) != 0) return SPK_ERR_UNSUPPORTED;
+  if (!spk_conv_mfma_fused_supported(Cin, Cout, T, mode)) return SPK_ERR_UNSUPPORTED;
   GArgs a;
   a.out_s32 = nullptr;
   a.in = in_ptc; a.wq = wq; a.scale = scale; a.bias = bias_d; a.bn_a = bn_a; a.bn_b = bn_b; a.v_io = v_inout;
@@ -744,7 +759,7 @@ extern "C" int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, 
   const long long groups = ((long long)Hc0 * Wc0 + 3) / 4;
   const long long tasks = (long long)B * ncls * groups * ((Cout + 15) / 16);
   const long long blocks = (tasks + 3) / 4;
-  if (blocks > 0x7fffffffLL) return SPK_ERR_UNSUPPORTED;
+  if (blocks > 0x7fffffffLL) return SPK_ERR_UNSUPPORTED;       // (not in the predicate: grid size, grows with the batch)
   dim3 grid((unsigned)blocks), blk(256);
   if (mode == SPK_MODE_LIF) {
     // (coef AND out_f32 given: out_f32 receives sum_t coef[t] * spike[t] as [B][Ho*Wo][Cout]; out_ptc may then be null)
@@ -752,12 +767,10 @@ extern "C" int spk_conv_mfma_fused_fwd(const uint8_t* in_ptc, const int8_t* wq, 
     if (!coef) a.out_f32 = nullptr;
     if (dispatch_gather2<SPK_MODE_LIF>(a, stream) == SPK_OK) return SPK_OK;          // compile-time geometry
     hipLaunchKernelGGL(conv_mfma_gather_kernel<SPK_MODE_LIF>, grid, blk, 0, stream, a);
-  } else if (mode == SPK_MODE_MEMOUT) {
+  } else {                                                     // SPK_MODE_MEMOUT
     if (!coef || (!out_f32 && !out_u8)) return SPK_ERR_ARG;
     if (dispatch_gather2<SPK_MODE_MEMOUT>(a, stream) == SPK_OK) return SPK_OK;
     hipLaunchKernelGGL(conv_mfma_gather_kernel<SPK_MODE_MEMOUT>, grid, blk, 0, stream, a);
-  } else {
-    return SPK_ERR_UNSUPPORTED;
   }
   SPK_LAUNCH_CHECK();
   return SPK_OK;

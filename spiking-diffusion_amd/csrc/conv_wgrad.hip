@@ -286,6 +286,10 @@ int wgrad_ksplit(int TB, int Cout, int Cin) {
 
 }  // namespace
 
+extern "C" int spk_conv3x3_wgrad_supported(int Cout, int Cin, int H, int W) {
+  return H == W && (H == 7 || H == 8) && Cout > 0 && Cin > 0 && (Cout % WG_CO) == 0 && (Cin % WG_CI) == 0;
+}
+
 extern "C" long long spk_conv3x3_wgrad_ws_bytes(int TB, int Cout, int Cin) {
   if (TB <= 0 || Cout <= 0 || Cin <= 0 || (Cout % WG_CO) || (Cin % WG_CI)) return -1;
   return (long long)wgrad_ksplit(TB, Cout, Cin) * ((long long)Cout * 9 * Cin + Cout) * 4;      // weight + bias partial sums
@@ -295,7 +299,7 @@ extern "C" int spk_conv3x3_wgrad_bf16(const float* gy_cl, const float* spikes_cl
                                       float* gw_out, float* gb_out_or_null, int TB, int H, int W, int Cout, int Cin,
                                       hipStream_t stream) {
   if (!gy_cl || !spikes_cl || !ws || !gw_out || TB <= 0) return SPK_ERR_ARG;
-  if (H != W || (H != 7 && H != 8) || (Cout % WG_CO) || (Cin % WG_CI)) return SPK_ERR_UNSUPPORTED;
+  if (!spk_conv3x3_wgrad_supported(Cout, Cin, H, W)) return SPK_ERR_UNSUPPORTED;
   const int tiles = (Cout / WG_CO) * (Cin / WG_CI);
   const int ks = wgrad_ksplit(TB, Cout, Cin);
   const long long n = (long long)Cout * 9 * Cin;
@@ -303,7 +307,7 @@ extern "C" int spk_conv3x3_wgrad_bf16(const float* gy_cl, const float* spikes_cl
   WgArgs a;
   a.gy = gy_cl; a.s = spikes_cl; a.part = ws;
   a.part_gb = gb_out_or_null ? ws + (long long)ks * n : nullptr; a.TB = TB; a.Cout = Cout; a.Cin = Cin; a.ksplit = ks;
-  if ((long long)lds_bytes(H) > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;
+  if ((long long)lds_bytes(H) > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;     // (not in the predicate: the device's LDS grant)
   if (H == 7) hipLaunchKernelGGL(wgrad3x3_bf16_kernel<7>, dim3(tiles * ks), dim3(NTHR), (size_t)lds_bytes(7), stream, a);
   else hipLaunchKernelGGL(wgrad3x3_bf16_kernel<8>, dim3(tiles * ks), dim3(NTHR), (size_t)lds_bytes(8), stream, a);
   SPK_LAUNCH_CHECK();

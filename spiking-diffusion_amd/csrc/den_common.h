@@ -1,4 +1,5 @@
-// Helpers shared by the two matrix-core denoiser kernels (den_mfma.hip: int8 digit planes, den_mfma_fp6.hip: fp6).
+// Helpers shared by the matrix-core kernels: the denoiser convolutions (den_mfma.hip: int8 digit planes, den_mfma_fp6.hip and
+// den_mfma_fp6v2.hip: fp6), the VQ-VAE layers (vae_fp6.hip) and the training gradients (conv_wgrad.hip, conv_dgrad.hip).
 #pragma once
 #include "spk_common.h"
 
@@ -6,6 +7,10 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+// LDS of one gfx950 compute unit: what the LDS plan of a one-workgroup-per-CU kernel may add up to.  A constant of the target, not
+// a device query: the shape predicates (spk_*_supported) answer on a machine without a GPU.
+constexpr int SPK_CU_LDS_BYTES = 160 * 1024;
 
 #define SPK_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 #define SPK_GLB(p) ((const __attribute__((address_space(1))) void*)(p))

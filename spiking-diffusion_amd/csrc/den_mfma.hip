@@ -552,29 +552,33 @@ __global__ __launch_bounds__(256) void pack_i8_kernel(const float* __restrict__ 
   }
 }
 
+// tiles (pairs of latent positions) and input-slab copy pieces per wave: the kernel is instantiated for up to 7 and up to 8 of both
+inline int tiles_per_wave(int H, int W) { return ((H * W + 1) / 2 + 3) / 4; }
+inline int pieces_per_wave(int H, int W) { return (H * ((W + 1) / 2) + 3) / 4; }
+inline size_t lds_bytes(int H, int W) { return 2 * ((size_t)(H + 2) * (W + 2) * POS_BYTES + W_CHUNK_BYTES); }
+
 template <int MODE>
 int launch(const MfmaArgs& a, hipStream_t stream) {
-  const int HW = a.H * a.W;
-  const int ntiles = (HW + 1) / 2;
-  const int nt = (ntiles + 3) / 4;
-  const size_t lds = 2 * ((size_t)(a.H + 2) * (a.W + 2) * POS_BYTES + W_CHUNK_BYTES);
-  if (lds > 160 * 1024) return SPK_ERR_UNSUPPORTED;
   const int cus = spk_cu_count();
   const int total = a.B * (a.Cout / 16);
   dim3 grid(total < cus ? total : cus), blk(256);          // persistent: one workgroup per CU
-  const int npa = (a.H * ((a.W + 1) / 2) + 3) / 4;
-  if (nt <= 7 && npa <= 7) {
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE>), grid, blk, lds, stream, a);
-  } else if (nt <= 8 && npa <= 8) {
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<8, 8, MODE>), grid, blk, lds, stream, a);
-  } else {
-    return SPK_ERR_UNSUPPORTED;
+  if (tiles_per_wave(a.H, a.W) <= 7 && pieces_per_wave(a.H, a.W) <= 7) {
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<7, 7, MODE>), grid, blk, lds_bytes(a.H, a.W), stream, a);
+  } else {                                                 // (spk_den_conv3x3_mfma_supported: at most 8 of both)
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<8, 8, MODE>), grid, blk, lds_bytes(a.H, a.W), stream, a);
   }
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }
 
 }  // namespace
+
+extern "C" int spk_den_conv3x3_mfma_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W) {
+  if (Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0) return 0;
+  // (the LDS plan first: it bounds H * W, so the int products behind it cannot overflow)
+  return k == 3 && stride == 1 && pad == 1 && T == T16 && (Cout % 32) == 0 && (Cin % CK) == 0 &&
+         lds_bytes(H, W) <= (size_t)SPK_CU_LDS_BYTES && tiles_per_wave(H, W) <= 8 && pieces_per_wave(H, W) <= 8;
+}
 
 extern "C" long long spk_den_packed_weight_bytes(int Cout, int Cin) {
   if (Cout <= 0 || Cin <= 0 || (Cout % 16) || (Cin % CK)) return -1;
@@ -624,7 +628,7 @@ extern "C" int spk_den_conv3x3_mfma(const uint8_t* in0_cptc, int nch0, const uin
   if (!in0_cptc || nch0 <= 0 || nch1 < 0 || (nch1 > 0 && !in1_cptc) || !wq || !scale || !bias_d || B <= 0 || H <= 0 ||
       W <= 0 || Cout <= 0)
     return SPK_ERR_ARG;
-  if (T != T16 || (Cout % 32)) return SPK_ERR_UNSUPPORTED;
+  if (!spk_den_conv3x3_mfma_supported(Cout, (nch0 + nch1) * CK, 3, 1, 1, T, H, W)) return SPK_ERR_UNSUPPORTED;
   MfmaArgs a;
   a.in0 = in0_cptc; a.in1 = in1_cptc; a.nch0 = nch0; a.nch1 = nch1; a.wq = wq; a.scale = scale; a.bias = bias_d;
   a.bn_a = bn_a; a.bn_b = bn_b; a.out = out_cptc; a.out_f32 = out_f32; a.v_io = v_inout; a.out_cnt = out_counts; a.B = B; a.H = H; a.W = W;

@@ -662,19 +662,36 @@ extern "C" int spk_den_pack_weight_fp6_cl_multi(const float* const* w_cl, const 
 }
 
 namespace {
-template <bool RAW>
-int launch_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* scale, const double* bias_d, const float* bn_a,
-               const float* bn_b, float* v_inout, uint8_t* out_c4, uint8_t* out_counts, float* pre, const int* n_dyn, int T,
-               int B, int H, int W, int Cout, hipStream_t stream) {
-  if (T != T16 || (Cout % 64)) return SPK_ERR_UNSUPPORTED;
+// The kernel's plan for an H x W latent: one item per image and channel group, or -- latents that do not fit one item (8x8) -- two
+// row bands per image, 4 tiles per wave each (see the kernel).  lds = 0: outside the kernel's tile, copy-piece or LDS limits.
+struct Fp6Plan { bool bands; size_t lds; };
+Fp6Plan fp6_plan(int H, int W) {
+  if ((long long)H * W > 64) return {false, 0};              // (more than 8 tiles per wave; also bounds the products below)
   const int ntiles = (H * W + 1) / 2;
-  // latents that do not fit one item (8x8): two row bands per image, 4 tiles per wave each (see the kernel)
   const bool bands = (ntiles + 3) / 4 > 7 && (H % 2) == 0 && (H / 2) * W <= 32 && H >= 4;
   const int Hin = bands ? H / 2 + 1 : H;
   const int npa = (Hin * ((W + 1) / 2) + 3) / 4;
   const size_t lds = 2 * ((size_t)((Hin + 2) * (W + 1) + 1) * POS_BYTES + W_CHUNK_BYTES);
-  if ((!bands && (ntiles + 3) / 4 > 7) || npa > NPA || lds > 160 * 1024) return SPK_ERR_UNSUPPORTED;
-  if (bands && ((Hin * W + 2 * (W + 1)) * POS_BYTES >= 32768)) return SPK_ERR_UNSUPPORTED;     // piece-table field widths
+  const bool fits = (bands || (ntiles + 3) / 4 <= 7) && npa <= NPA && lds <= (size_t)SPK_CU_LDS_BYTES &&
+                    !(bands && (Hin * W + 2 * (W + 1)) * POS_BYTES >= 32768);     // (piece-table field widths)
+  return {bands, fits ? lds : 0};
+}
+}  // namespace
+
+extern "C" int spk_den_conv3x3_mfma_fp6_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W) {
+  if (Cout <= 0 || Cin <= 0 || H <= 0 || W <= 0) return 0;
+  return k == 3 && stride == 1 && pad == 1 && T == T16 && (Cout % 64) == 0 && (Cin % CK) == 0 && fp6_plan(H, W).lds != 0;
+}
+
+namespace {
+template <bool RAW>
+int launch_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* scale, const double* bias_d, const float* bn_a,
+               const float* bn_b, float* v_inout, uint8_t* out_c4, uint8_t* out_counts, float* pre, const int* n_dyn, int T,
+               int B, int H, int W, int Cout, hipStream_t stream) {
+  if (!spk_den_conv3x3_mfma_fp6_supported(Cout, nch * CK, 3, 1, 1, T, H, W)) return SPK_ERR_UNSUPPORTED;
+  const Fp6Plan plan = fp6_plan(H, W);
+  const bool bands = plan.bands;
+  const size_t lds = plan.lds;
   // odd position count with at most 24 full tiles: 6 tiles per wave + the last-position kernel (see there)
   const bool split_last = !bands && ((H * W) & 1) && (H * W) / 2 <= 24 && H >= 2 && W >= 2;
   Fp6Args a;

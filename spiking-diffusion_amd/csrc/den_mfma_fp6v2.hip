@@ -1386,6 +1386,11 @@ extern "C" long long spk_den_fp6v2_flag_words(int B, int Cout, int H, int W) {
   return words;
 }
 
+extern "C" int spk_den_conv3x3_mfma_fp6v2_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W) {
+  return k == 3 && stride == 1 && pad == 1 && T == T16 && H == W && (H == 7 || H == 8) && Cout > 0 && Cin > 0 &&
+         (Cout % 32) == 0 && (Cin % CK) == 0;
+}
+
 static int fp6v2_launch(const uint8_t* in_s32, int nch, const uint8_t* wq, const double* scale, const double* bias_d,
                         const float* wl1, const int* qtab, const float* bn_a, const float* bn_b, uint8_t* out_s32,
                         uint8_t* out_counts, unsigned* flag_words, int T, int B, int H, int W, int Cout,
@@ -1395,9 +1400,9 @@ static int fp6v2_launch(const uint8_t* in_s32, int nch, const uint8_t* wq, const
   if (!in_s32 || nch <= 0 || !wq || !scale || !bias_d || !wl1 || !qtab || !bn_a || !bn_b || !out_s32 || !flag_words ||
       B <= 0 || H <= 0 || W <= 0 || Cout <= 0)
     return SPK_ERR_ARG;
-  const bool bands = H == 8 && W == 8;
-  if (T != T16 || (Cout % 32) || !((H == 7 && W == 7) || bands)) return SPK_ERR_UNSUPPORTED;
-  if (need && (bands || !n_dyn_or_null)) return SPK_ERR_UNSUPPORTED;
+  if (!spk_den_conv3x3_mfma_fp6v2_supported(Cout, nch * CK, 3, 1, 1, T, H, W)) return SPK_ERR_UNSUPPORTED;
+  const bool bands = H == 8;                                 // (8x8: two row bands per image; else 7x7)
+  if (need && (bands || !n_dyn_or_null)) return SPK_ERR_UNSUPPORTED;   // (not in the predicate: a property of the call's lists, not of the shape)
   V2Args a;
   a.in0 = in_s32; a.nch = nch; a.wq = wq; a.scale = scale; a.bias = bias_d; a.wl1 = wl1; a.qtab = qtab;
   a.bn_a = bn_a; a.bn_b = bn_b; a.out = out_s32; a.out_cnt = out_counts; a.flags = flag_words;
@@ -1464,7 +1469,7 @@ static int fp6v2_launch(const uint8_t* in_s32, int nch, const uint8_t* wq, const
   // tiles, lose 11 %: den.conv4 launch 417-466 against 383-387 us, round 3; the staggered, duo and deferred-scan forms of round 5
   // are 4 - 40 % slower: profiles/r5_ab_duo_*.txt, profiles/r5_ab_defer_builds.txt.)
   if (need) {
-    if (grid / G < 6) return SPK_ERR_UNSUPPORTED;           // one image lane per tile-count class at least
+    if (grid / G < 6) return SPK_ERR_UNSUPPORTED;           // one image lane per tile-count class at least (not in the predicate: the device's CU count)
     hipLaunchKernelGGL((conv3x3_fp6v2_listed_kernel<7, 7, 8>), dim3(grid), dim3(512), lds, stream, a);
   } else if (split_small && (long long)B * G * SPK_V2_HALF_FILL <= grid) {
     // fewer items than workgroups: two half-image items per image on four-wave workgroups (B = 16: conv2 / conv3 / conv5)

@@ -676,9 +676,9 @@ int launch_vae(const TArgs& a, long long n_words, hipStream_t stream) {
   constexpr int SROWS = GEO == 0 ? H / SPLIT + 1 : H + 1;
   constexpr int NPOS = GEO == 0 ? (H / SPLIT) * W : (H / 2) * (W / 2), NCLS = GEO == 0 ? 4 : 1;
   // (+ the four-digit form's counters: u8 [cells][16] and int [classes][positions])
-  const size_t lds = (size_t)(DB ? 2 : 1) * NCH * SROWS * (W + 1) * POSB + 9 * TPL * WT +
-                     (size_t)((SROWS * (W + 1) * 16 + 15) & ~15) + (size_t)NCLS * NPOS * 4 + 16;
-  if (lds > 160 * 1024) return SPK_ERR_UNSUPPORTED;
+  constexpr size_t lds = (size_t)(DB ? 2 : 1) * NCH * SROWS * (W + 1) * POSB + 9 * TPL * WT +
+                         (size_t)((SROWS * (W + 1) * 16 + 15) & ~15) + (size_t)NCLS * NPOS * 4 + 16;
+  static_assert(lds <= (size_t)SPK_CU_LDS_BYTES, "this instance's LDS plan does not fit a compute unit");
   const int cus = spk_cu_count(), G = a.Cout / 32;
   const int grid = cus >= G ? (cus / G) * G : G;
   hipLaunchKernelGGL((vae_fp6_kernel<GEO, H, W, NCH, OUT, SPLIT, DB>), dim3(grid), dim3(SPK_VT_NWV * 64), lds, stream, a);
@@ -727,29 +727,39 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
                                int flag_cap, hipStream_t stream) {
   if (!in_s32 || !wq || !scale || !bias_d || !qtab || !bn_a || !bn_b || !out || !flag_words || B <= 0) return SPK_ERR_ARG;
   if (out_kind == OUT_COLLAPSED && !coef_or_null) return SPK_ERR_ARG;
-  if (T != T16 || (Cout % 32) || B > (1 << 22)) return SPK_ERR_UNSUPPORTED;
+  const int kind = spk_vae_fp6_kind(Cin, Cout, 3, 2, 1, transposed ? 1 : 0, transposed, T, H, W);
+  if (kind < 0 || kind != out_kind) return SPK_ERR_UNSUPPORTED;
+  if (B > (1 << 22)) return SPK_ERR_UNSUPPORTED;             // (not in the predicate: the batch is no part of the layer's shape)
   TArgs a;
   a.in = in_s32; a.wq = wq; a.scale = scale; a.bias = bias_d; a.bn_a = bn_a; a.bn_b = bn_b; a.coef = coef_or_null; a.out = out;
   a.flags = flag_words; a.qtab = qtab; a.B = B; a.Cout = Cout; a.Cin = Cin;
   a.flag_cap = flag_cap < 0 || (unsigned)flag_cap > FLAG_CAP ? FLAG_CAP : (unsigned)flag_cap;   // id-list entries used (< 0: all); layout fixed
   const int Ho = transposed ? 2 * H : H / 2, Wo = transposed ? 2 * W : W / 2;
   const long long neurons = (long long)B * Cout * Ho * Wo;
-  if (neurons >= (1ll << 32)) return SPK_ERR_UNSUPPORTED;                                   // neuron ids are 32-bit
+  if (neurons >= (1ll << 32)) return SPK_ERR_UNSUPPORTED;          // neuron ids are 32-bit (not in the predicate: grows with the batch)
   const long long n_words = (neurons + 31) / 32;
   a.ticket_idx = 2 + (long long)FLAG_CAP + n_words;
-  if (transposed && Cin == 64 && out_kind == OUT_COLLAPSED) {                                // decoder convT2
+  // one instance per (kind, H): spk_vae_fp6_kind has checked that this one exists
+  if (kind == OUT_COLLAPSED) {                                                               // decoder convT2
     // half images per item, one input slab (two do not fit beside the weights); two class rows per item with two slabs measured
     // 231 against 195 us (profiles/r5_ab_kernel_variants.txt (7))
-    if (H == 14 && W == 14) return launch_vae<0, 14, 14, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
-    if (H == 16 && W == 16) return launch_vae<0, 16, 16, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
+    return H == 14 ? launch_vae<0, 14, 14, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream)
+                   : launch_vae<0, 16, 16, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
   }
-  if (transposed && Cin == 16 && out_kind == OUT_S32) {                                      // decoder convT1
-    if (H == 7 && W == 7) return launch_vae<0, 7, 7, 1, OUT_S32, 1, true>(a, n_words, stream);
-    if (H == 8 && W == 8) return launch_vae<0, 8, 8, 1, OUT_S32, 1, true>(a, n_words, stream);
+  if (kind == OUT_S32) {                                                                     // decoder convT1
+    return H == 7 ? launch_vae<0, 7, 7, 1, OUT_S32, 1, true>(a, n_words, stream)
+                  : launch_vae<0, 8, 8, 1, OUT_S32, 1, true>(a, n_words, stream);
   }
-  if (!transposed && Cin == 32 && out_kind == OUT_PTC) {                                     // encoder conv2
-    if (H == 14 && W == 14) return launch_vae<1, 14, 14, 1, OUT_PTC, 1, true>(a, n_words, stream);
-    if (H == 16 && W == 16) return launch_vae<1, 16, 16, 1, OUT_PTC, 1, false>(a, n_words, stream);   // (two slabs do not fit)
-  }
-  return SPK_ERR_UNSUPPORTED;
+  return H == 14 ? launch_vae<1, 14, 14, 1, OUT_PTC, 1, true>(a, n_words, stream)           // encoder conv2
+                 : launch_vae<1, 16, 16, 1, OUT_PTC, 1, false>(a, n_words, stream);         // (two slabs do not fit)
+}
+
+// Which instance exists for a layer: its output form, or -1.  The whole dispatch table of spk_vae_fp6_fwd.
+extern "C" int spk_vae_fp6_kind(int Cin, int Cout, int k, int stride, int pad, int out_pad, int transposed, int T, int H, int W) {
+  if (k != 3 || stride != 2 || pad != 1 || T != T16 || Cout <= 0 || (Cout % 32) || H != W) return -1;
+  const bool mid = H == 14 || H == 16, small = H == 7 || H == 8;
+  if (transposed && out_pad == 1 && Cin == 64 && mid) return OUT_COLLAPSED;     // decoder convT2
+  if (transposed && out_pad == 1 && Cin == 16 && small) return OUT_S32;         // decoder convT1
+  if (!transposed && Cin == 32 && mid) return OUT_PTC;                          // encoder conv2
+  return -1;
 }

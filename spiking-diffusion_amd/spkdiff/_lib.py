@@ -155,6 +155,15 @@ _SIGS = {
     "spk_vq_code_usage": (c_int, [P, c_longlong, c_int, P, P, P, P]),
     "spk_ssim_mse_ws_bytes": (c_longlong, [c_int] * 5),
     "spk_ssim_mse": (c_int, [P] * 6 + [c_int] * 5 + [P]),
+    # shape predicates: pure host functions, one per matrix-core kernel family, called by that family's entry point itself
+    "spk_den_conv3x3_mfma_supported": (c_int, [c_int] * 8),
+    "spk_den_conv3x3_mfma_fp6_supported": (c_int, [c_int] * 8),
+    "spk_den_conv3x3_mfma_fp6v2_supported": (c_int, [c_int] * 8),
+    "spk_vae_fp6_kind": (c_int, [c_int] * 10),
+    "spk_conv_mfma_fused_supported": (c_int, [c_int] * 4),
+    "spk_readout_collapsed_supported": (c_int, [c_int] * 4),
+    "spk_conv3x3_wgrad_supported": (c_int, [c_int] * 4),
+    "spk_conv3x3_dgrad_supported": (c_int, [c_int] * 5),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -186,7 +195,7 @@ def version() -> int:
 
 # The signatures declared above are those of include/spkdiff.h at this version.  A stale libspkdiff.so or an SPKDIFF_LIB A/B
 # variant built from another header would take arguments at the wrong positions (silently wrong results): refuse it here.
-EXPECTED_VERSION = 105
+EXPECTED_VERSION = 106
 if version() != EXPECTED_VERSION:
     raise ImportError(f"spkdiff: {LIB_PATH} reports C-ABI version {version()}, this binding declares version "
                       f"{EXPECTED_VERSION} (include/spkdiff.h SPK_VERSION). Rebuild the library: make -C "

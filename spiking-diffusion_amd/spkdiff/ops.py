@@ -817,12 +817,26 @@ def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transpo
 
 
 # ---------------------------------------------------------------------------------------------- MFMA denoiser convs
+# Which shapes a kernel family takes is answered by the library (spk_*_supported / spk_vae_fp6_kind: host functions its entry points
+# call themselves); what is added to an answer here is policy -- which of the supported shapes this package sends there.
 def den_mfma_supported(Cout, Cin, k, stride, pad, T, H, W):
-    ntiles = (H * W + 1) // 2
-    nt = (ntiles + 3) // 4
-    lds = 2 * ((H + 2) * (W + 2) * 512 + 18432)
-    return (k == 3 and stride == 1 and pad == 1 and T == 16 and Cout % 32 == 0 and Cin % 32 == 0
-            and nt <= 8 and lds <= 160 * 1024)
+    return bool(lib.spk_den_conv3x3_mfma_supported(Cout, Cin, k, stride, pad, T, H, W))
+
+
+def _pack_weight(w, bias, nbytes, n_scale, plane_dtype, pack, what, unsupported, extra=()):
+    """The part every weight packer shares.  w: the fp32 weight on its device; nbytes: the library's size answer for the digit
+    planes (negative / zero: NotImplementedError(unsupported)); n_scale: entries of the fp64 scale and bias vectors; extra:
+    (shape, dtype) of further outputs.  pack(w, bias, planes, scale, bias_d, *extra outputs) makes the library call.
+    Returns (planes, scale, bias_d, *extra outputs)."""
+    if nbytes <= 0:
+        raise NotImplementedError(unsupported)
+    wq = torch.empty(nbytes, dtype=plane_dtype, device=w.device)
+    scale = torch.empty(n_scale, dtype=torch.float64, device=w.device)
+    bias_d = torch.empty(n_scale, dtype=torch.float64, device=w.device)
+    more = tuple(torch.empty(shape, dtype=dtype, device=w.device) for shape, dtype in extra)
+    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
+    check(pack(_p(w), _p(b), _p(wq), _p(scale), _p(bias_d), *(_p(t) for t in more)), what)
+    return (wq, scale, bias_d) + more
 
 
 def den_pack_weight_i8(w, bias, pad_cout=False):
@@ -837,16 +851,9 @@ def den_pack_weight_i8(w, bias, pad_cout=False):
         if bias is not None:
             bias = torch.cat([bias.detach(), bias.detach().new_zeros(kp - Cout)], 0)
         Cout = kp
-    nbytes = lib.spk_den_packed_weight_bytes(Cout, Cin)
-    if nbytes < 0:
-        raise NotImplementedError("spkdiff: MFMA conv needs Cout % 16 == 0 and Cin % 32 == 0")
-    wq = torch.empty(nbytes, dtype=torch.int8, device=w.device)
-    scale = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    bias_d = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
-    check(lib.spk_den_pack_weight_i8(_p(w), _p(b), _p(wq), _p(scale), _p(bias_d), Cout, Cin, _stream(w)),
-          "spk_den_pack_weight_i8")
-    return wq, scale, bias_d
+    return _pack_weight(w, bias, lib.spk_den_packed_weight_bytes(Cout, Cin), Cout, torch.int8,
+                        lambda *t: lib.spk_den_pack_weight_i8(*t, Cout, Cin, _stream(w)), "spk_den_pack_weight_i8",
+                        "spkdiff: MFMA conv needs Cout % 16 == 0 and Cin % 32 == 0")
 
 
 def den_conv3x3_mfma(in0, packed, Cout, *, mode, in1=None, bn_a=None, bn_b=None, v=None, out=None, want_counts=False):
@@ -901,13 +908,7 @@ def den_conv3x3_counts(cnt0, packed, Cout, T, cnt1=None):
 
 # ------------------------------------------------------------------------------- fp6/fp4 block-scaled MFMA denoiser convs
 def den_fp6_supported(Cout, Cin, k, stride, pad, T, H, W):
-    ntiles = (H * W + 1) // 2
-    bands = (ntiles + 3) // 4 > 7 and H % 2 == 0 and (H // 2) * W <= 32 and H >= 4     # 8x8: two row bands per image
-    Hin = H // 2 + 1 if bands else H
-    npa = (Hin * ((W + 1) // 2) + 3) // 4
-    lds = 2 * (((Hin + 2) * (W + 1) + 1) * 512 + 41984)
-    return (k == 3 and stride == 1 and pad == 1 and T == 16 and Cout % 64 == 0 and Cin % 64 == 0
-            and (bands or (ntiles + 3) // 4 <= 7) and npa <= 7 and lds <= 160 * 1024)
+    return bool(lib.spk_den_conv3x3_mfma_fp6_supported(Cout, Cin, k, stride, pad, T, H, W))
 
 
 def den_pack_weight_fp6(w, bias):
@@ -918,16 +919,10 @@ def den_pack_weight_fp6(w, bias):
           and wd.is_contiguous(memory_format=torch.channels_last))
     w = wd if cl else _dev(wd, "weight", torch.float32)
     Cout, Cin = w.shape[0], w.shape[1]
-    nbytes = lib.spk_den_packed_weight_fp6_bytes(Cout, Cin)
-    if nbytes < 0:
-        raise NotImplementedError("spkdiff: fp6 MFMA conv needs Cout % 16 == 0 and Cin % 64 == 0")
-    wq = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    scale = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    bias_d = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
-    check((lib.spk_den_pack_weight_fp6_cl if cl else lib.spk_den_pack_weight_fp6)(
-        _p(w), _p(b), _p(wq), _p(scale), _p(bias_d), Cout, Cin, _stream(w)), "spk_den_pack_weight_fp6")
-    return wq, scale, bias_d
+    pack = lib.spk_den_pack_weight_fp6_cl if cl else lib.spk_den_pack_weight_fp6
+    return _pack_weight(w, bias, lib.spk_den_packed_weight_fp6_bytes(Cout, Cin), Cout, torch.uint8,
+                        lambda *t: pack(*t, Cout, Cin, _stream(w)), "spk_den_pack_weight_fp6",
+                        "spkdiff: fp6 MFMA conv needs Cout % 16 == 0 and Cin % 64 == 0")
 
 
 def den_conv3x3_mfma_fp6(in0, packed, Cout, *, bn_a, bn_b, v=None, want_counts=False):
@@ -976,7 +971,7 @@ def den_conv3x3_fp6_raw(in0, packed, Cout):
 
 
 def conv3x3_wgrad_supported(Cout, Cin, H, W):
-    return (H, W) in ((7, 7), (8, 8)) and Cout % 128 == 0 and Cin % 64 == 0
+    return bool(lib.spk_conv3x3_wgrad_supported(Cout, Cin, H, W))
 
 
 # False: the weight gradient of the spike-input convolutions comes from the framework's operator (as in rounds 1-2)
@@ -1002,9 +997,8 @@ def conv3x3_wgrad(gy_cl, spikes_cl, Cout, Cin, want_bias=False):
 
 
 def conv3x3_dgrad_supported(Cout, Cin, H, W, N):
-    # (small batches: the framework's operator is as fast)
-    return ((H, W) in ((7, 7), (8, 8)) and Cout % 16 == 0 and Cin % 32 == 0 and Cout * Cin >= 8192 and N >= 64
-            and N * H * W * Cout < 2 ** 31)              # (32-bit element offsets in the kernel's staging table)
+    # policy (small layers and small batches: the framework's operator is as fast)
+    return bool(lib.spk_conv3x3_dgrad_supported(Cout, Cin, H, W, N)) and Cout * Cin >= 8192 and N >= 64
 
 
 # False: the data gradient of the spike-input convolutions comes from the framework's operator (as in rounds 1-2)
@@ -1260,8 +1254,7 @@ def c4_to_spikes(q):
 
 # ------------------------------------------------------------------------------- fp6v2: the sampler's denoiser convolutions
 def den_fp6v2_supported(Cout, Cin, k, stride, pad, T, H, W):
-    return (k == 3 and stride == 1 and pad == 1 and T == 16 and (H, W) in ((7, 7), (8, 8)) and Cout % 32 == 0 and
-            Cin % 32 == 0)
+    return bool(lib.spk_den_conv3x3_mfma_fp6v2_supported(Cout, Cin, k, stride, pad, T, H, W))
 
 
 def den_pack_weight_fp6v2(w, bias):
@@ -1269,18 +1262,10 @@ def den_pack_weight_fp6v2(w, bias):
     weights as int32 [Cout, 9, Cin]: the exact recomputation of flagged neurons reads them)."""
     w = _dev(w.detach(), "weight", torch.float32)
     Cout, Cin = w.shape[0], w.shape[1]
-    nbytes = lib.spk_den_packed_weight_fp6v2_bytes(Cout, Cin)
-    if nbytes < 0:
-        raise NotImplementedError("spkdiff: fp6v2 MFMA conv needs Cout % 32 == 0 and Cin % 32 == 0")
-    wq = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    scale = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    bias_d = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    wl1 = torch.empty(Cout, dtype=torch.float32, device=w.device)
-    qtab = torch.empty((Cout, 9, Cin), dtype=torch.int32, device=w.device)
-    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
-    check(lib.spk_den_pack_weight_fp6v2(_p(w), _p(b), _p(wq), _p(scale), _p(bias_d), _p(wl1), _p(qtab), Cout, Cin, _stream(w)),
-          "spk_den_pack_weight_fp6v2")
-    return wq, scale, bias_d, wl1, qtab
+    return _pack_weight(w, bias, lib.spk_den_packed_weight_fp6v2_bytes(Cout, Cin), Cout, torch.uint8,
+                        lambda *t: lib.spk_den_pack_weight_fp6v2(*t, Cout, Cin, _stream(w)), "spk_den_pack_weight_fp6v2",
+                        "spkdiff: fp6v2 MFMA conv needs Cout % 32 == 0 and Cin % 32 == 0",
+                        extra=(((Cout,), torch.float32), ((Cout, 9, Cin), torch.int32)))          # wl1, qtab
 
 
 # Flagged-neuron workspaces of the certified kernels (fp6v2 / vae_fp6: live counter, id list, overflow bitmap, hand-over
@@ -1425,7 +1410,8 @@ def s32_to_spikes(q):
 
 # ---------------------------------------------------------------------------------------------- MFMA VQ-VAE layers
 def conv_mfma_supported(Cin, Cout, T, mode):
-    return T == 16 and Cin % 16 == 0 and (mode == MODE_MEMOUT or Cout % 16 == 0)
+    # policy: a spiking layer goes there only with whole 16-channel groups of output (the kernel itself pads any Cout)
+    return bool(lib.spk_conv_mfma_fused_supported(Cin, Cout, T, mode)) and (mode == MODE_MEMOUT or Cout % 16 == 0)
 
 
 def pack_conv_weight_i8(w, bias, transposed):
@@ -1437,15 +1423,9 @@ def pack_conv_weight_i8(w, bias, transposed):
         Cout, Cin, k, k2 = w.shape
     if k != k2:
         raise NotImplementedError("square kernels only")
-    nbytes = lib.spk_conv_packed_weight_i8_bytes(Cout, Cin, k)
-    cpad = (Cout + 15) // 16 * 16
-    wq = torch.empty(nbytes, dtype=torch.int8, device=w.device)
-    scale = torch.empty(cpad, dtype=torch.float64, device=w.device)
-    bias_d = torch.empty(cpad, dtype=torch.float64, device=w.device)
-    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
-    check(lib.spk_pack_conv_weight_i8(_p(w), _p(b), _p(wq), _p(scale), _p(bias_d), Cout, Cin, k, int(transposed),
-                                      _stream(w)), "spk_pack_conv_weight_i8")
-    return wq, scale, bias_d
+    return _pack_weight(w, bias, lib.spk_conv_packed_weight_i8_bytes(Cout, Cin, k), (Cout + 15) // 16 * 16, torch.int8,
+                        lambda *t: lib.spk_pack_conv_weight_i8(*t, Cout, Cin, k, int(transposed), _stream(w)),
+                        "spk_pack_conv_weight_i8", "spk_pack_conv_weight_i8: unsupported shape")
 
 
 def conv_mfma_fused(in_ptc, packed, Cout, *, mode, k, stride, pad, transposed=False, out_pad=0, bn_a=None, bn_b=None,
@@ -1491,15 +1471,8 @@ VAE_OUT_COLLAPSED, VAE_OUT_S32, VAE_OUT_PTC = 0, 1, 2
 def vae_fp6_kind(Cin, Cout, k, stride, pad, out_pad, transposed, T, H, W):
     """Which output form of the fp6 VQ-VAE kernel (csrc/vae_fp6.hip) exists for this 3x3 stride-2 layer on an H x W input:
     VAE_OUT_COLLAPSED (decoder convT2), VAE_OUT_S32 (decoder convT1), VAE_OUT_PTC (encoder conv2), or None."""
-    if k != 3 or stride != 2 or pad != 1 or T != 16 or Cout % 32:
-        return None
-    if transposed and out_pad == 1 and Cin == 64 and (H, W) in ((14, 14), (16, 16)):
-        return VAE_OUT_COLLAPSED
-    if transposed and out_pad == 1 and Cin == 16 and (H, W) in ((7, 7), (8, 8)):
-        return VAE_OUT_S32
-    if not transposed and Cin == 32 and (H, W) in ((14, 14), (16, 16)):
-        return VAE_OUT_PTC
-    return None
+    kind = lib.spk_vae_fp6_kind(Cin, Cout, k, stride, pad, out_pad, int(bool(transposed)), T, H, W)
+    return None if kind < 0 else kind
 
 
 def convT_fp6_supported(Cin, Cout, k, stride, pad, out_pad, transposed, T, H, W):
@@ -1510,17 +1483,9 @@ def vae_fp6_pack(w, bias, transposed):
     """Conv2d [Cout,Cin,3,3] / ConvTranspose2d [Cin,Cout,3,3] fp32 (+bias) -> (digit tiles, scale f64, bias f64, qtab int32)."""
     w = _dev(w.detach(), "weight", torch.float32)
     Cin, Cout = (int(w.shape[0]), int(w.shape[1])) if transposed else (int(w.shape[1]), int(w.shape[0]))
-    n = lib.spk_vae_fp6_packed_bytes(Cout, Cin)
-    if n <= 0:
-        raise NotImplementedError("spk_vae_fp6_pack: unsupported shape")
-    wq = torch.empty(n, dtype=torch.uint8, device=w.device)
-    scale = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    bias_d = torch.empty(Cout, dtype=torch.float64, device=w.device)
-    qtab = torch.empty((Cout, 9, Cin), dtype=torch.int32, device=w.device)
-    b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
-    check(lib.spk_vae_fp6_pack(_p(w), _p(b), _p(wq), _p(scale), _p(bias_d), _p(qtab), Cout, Cin, int(transposed), _stream(w)),
-          "spk_vae_fp6_pack")
-    return wq, scale, bias_d, qtab, Cin
+    return _pack_weight(w, bias, lib.spk_vae_fp6_packed_bytes(Cout, Cin), Cout, torch.uint8,
+                        lambda *t: lib.spk_vae_fp6_pack(*t, Cout, Cin, int(transposed), _stream(w)), "spk_vae_fp6_pack",
+                        "spk_vae_fp6_pack: unsupported shape", extra=(((Cout, 9, Cin), torch.int32),)) + (Cin,)
 
 
 def convT_fp6_pack(w, bias):
@@ -1569,7 +1534,8 @@ _COEF_SUMS = {}
 
 
 def readout_collapsed_supported(Cin, Cout, k):
-    return Cin % 8 == 0 and k % 2 == 1 and ((4 + k - 1) * 64 * (Cin + 4) + Cout * k * k * Cin) * 4 <= 64 * 1024
+    """At any image width up to 64 (the library's W <= 0); readout_collapsed refuses wider images."""
+    return bool(lib.spk_readout_collapsed_supported(Cin, Cout, k, 0))
 
 
 def readout_collapsed(x_bhwc, weight, bias, coef, *, apply_tanh=False, want_u8=False, k=3, pad=1, transposed=True):

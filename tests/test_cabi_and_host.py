@@ -26,7 +26,7 @@ def test_library_exports_exactly_the_declared_symbols():
         assert hasattr(_lib.lib, n), f"{n} declared in include/spkdiff.h but not exported by libspkdiff.so"
         assert n in _lib.EXPORTS, f"{n} has no ctypes signature in spkdiff/_lib.py"
     assert set(_lib.EXPORTS) == set(names)
-    assert _lib.version() == _lib.EXPECTED_VERSION == 105
+    assert _lib.version() == _lib.EXPECTED_VERSION == 106
     # the shipped library keeps no process-wide state: no option entry points, no settable launch shapes in the binding
     if not os.environ.get("SPKDIFF_LIB"):
         assert not hasattr(_lib.lib, "spk_set_option") and not hasattr(_lib.lib, "spk_get_option")
@@ -123,6 +123,26 @@ def test_workspace_sizes_and_shape_support_are_host_side():
     assert kind(64, 32, 3, 2, 1, 1, True, 4, 14, 14) is None and kind(64, 32, 3, 1, 1, 0, True, 16, 14, 14) is None
     assert kind(32, 64, 3, 2, 1, 0, False, 16, 12, 12) is None
     assert ops.readout_collapsed_supported(32, 1, 3) and not ops.readout_collapsed_supported(30, 1, 3)
+    # the same cases asked of the library itself: the predicates its entry points call (pure host functions)
+    lkind = lib.spk_vae_fp6_kind
+    assert lkind(64, 32, 3, 2, 1, 1, 1, 16, 14, 14) == ops.VAE_OUT_COLLAPSED
+    assert lkind(16, 64, 3, 2, 1, 1, 1, 16, 7, 7) == ops.VAE_OUT_S32
+    assert lkind(32, 64, 3, 2, 1, 0, 0, 16, 14, 14) == ops.VAE_OUT_PTC
+    assert lkind(64, 32, 3, 2, 1, 1, 1, 4, 14, 14) == -1 and lkind(64, 32, 3, 1, 1, 0, 1, 16, 14, 14) == -1
+    assert lkind(32, 64, 3, 2, 1, 0, 0, 16, 12, 12) == -1
+    assert lib.spk_readout_collapsed_supported(32, 1, 3, 0) == 1 and lib.spk_readout_collapsed_supported(30, 1, 3, 0) == 0
+    assert lib.spk_readout_collapsed_supported(32, 1, 3, 28) == 1 and lib.spk_readout_collapsed_supported(32, 1, 4, 28) == 0
+    for sup in (lib.spk_den_conv3x3_mfma_supported, lib.spk_den_conv3x3_mfma_fp6_supported, lib.spk_den_conv3x3_mfma_fp6v2_supported):
+        assert sup(128, 64, 3, 1, 1, 16, 7, 7) == 1 and sup(128, 64, 3, 1, 1, 16, 8, 8) == 1
+        assert sup(128, 64, 3, 1, 1, 4, 7, 7) == 0 and sup(128, 64, 3, 2, 1, 16, 7, 7) == 0 and sup(128, 48, 3, 1, 1, 16, 7, 7) == 0
+        assert sup(128, 64, 3, 1, 1, 16, 9, 7) == 0 and sup(128, 64, 3, 1, 1, 16, 0, 7) == 0 and sup(0, 64, 3, 1, 1, 16, 7, 7) == 0
+    assert lib.spk_den_conv3x3_mfma_supported(128, 64, 3, 1, 1, 16, 7, 8) == 1 == lib.spk_den_conv3x3_mfma_fp6_supported(128, 64, 3, 1, 1, 16, 6, 8)
+    assert lib.spk_den_conv3x3_mfma_fp6_supported(128, 64, 3, 1, 1, 16, 7, 8) == 0 == lib.spk_den_conv3x3_mfma_fp6v2_supported(128, 64, 3, 1, 1, 16, 7, 8)
+    assert lib.spk_den_conv3x3_mfma_supported(128, 64, 3, 1, 1, 16, 1 << 16, 1 << 16) == 0          # (no overflow into "fits")
+    assert lib.spk_den_conv3x3_mfma_fp6_supported(128, 64, 3, 1, 1, 16, 1 << 16, 1 << 16) == 0
+    assert lib.spk_conv_mfma_fused_supported(32, 64, 16, ops.MODE_LIF) == 1 and lib.spk_conv_mfma_fused_supported(24, 64, 16, ops.MODE_LIF) == 0
+    assert lib.spk_conv3x3_wgrad_supported(128, 64, 7, 7) == 1 and lib.spk_conv3x3_wgrad_supported(64, 64, 7, 7) == 0
+    assert lib.spk_conv3x3_dgrad_supported(16, 32, 8, 8, 1) == 1 and lib.spk_conv3x3_dgrad_supported(16, 32, 7, 8, 1) == 0
 
 
 def test_state_dict_keys_match_reference():

@@ -121,7 +121,7 @@ def test_entry_points_declared_exported_and_bound():
         assert name in _lib.EXPORTS
     assert _lib.lib.spk_ssim_mse_ws_bytes.restype is ctypes.c_longlong
     assert len(_lib.lib.spk_ssim_mse.argtypes) == 12
-    assert _lib.version() == _lib.EXPECTED_VERSION == 105
+    assert _lib.version() == _lib.EXPECTED_VERSION == 106
 
 
 def test_host_rejection_before_any_launch():
