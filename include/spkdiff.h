@@ -566,6 +566,24 @@ int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, uint8_t* un
                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                      long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
                      const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
+/* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
+ * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
+ * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
+ *   logp_out[p] = log softmax(logits / temp)[x0[p]]   fp64, in nats: z_k = logits_k / temp in fp32 (the value the sampler races
+ *                 with), then (z_x0 - m) - log sum_k exp(z_k - m) in fp64 with m = max_k z_k, summed in a fixed order;
+ *   step_out[p] = t (optional int32);   x_t[p] = x0[p];   unmasked[p] = 1.
+ * Every other position writes nothing to logp_out / step_out and evaluates no softmax.  Special values are what the formula gives
+ * in IEEE fp64 (a NaN logit: NaN; target logit -inf: -inf; every logit -inf: NaN); a target outside [0, K) scores -inf, and x_t
+ * still takes it as given (nothing gathers through x_t: the denoiser reads the token as a float).  Summed over the positions
+ * after steps t = S .. 1 from the all-masked (or a partly known, spk_completion_state) start this is a one-sample estimate of the
+ * sampler's likelihood bound E_order[sum_i log p(x0_i | x0 at the positions revealed before i)] <= log p(x0).
+ * active / n_active, philox_state, next_input_b2hw_or_null (not with active): as spk_psample_step.  K <= 512
+ * (SPK_ERR_UNSUPPORTED beyond).  Deterministic; capturable in a hipGraph; allocates nothing. */
+int spk_pscore_step(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                    float temp, const float* u_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                    const unsigned long long* philox_state_or_null, double* logp_out, int* step_out_or_null, int B, int HW,
+                    int K, const int* active_or_null, const int* n_active_or_null, float* next_input_b2hw_or_null,
+                    spk_stream_t stream);
 
 /* The tail of one DENSE reverse step as one launch per image: conv6 on the spike counts + mean over T (as
  * spk_den_conv3x3_counts_mfma; R/snn_model/vq_diffusion.py:185-187,205-206), the token update (as spk_psample_step: :113-124,

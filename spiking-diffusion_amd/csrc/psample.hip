@@ -50,9 +50,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
     if (!x0_hat_out) {
       // only positions that change consume the sample (:140): skip the rest before the softmax (wave-uniform test;
       // the noise is counter-based / injected per position, so skipping a draw does not move any other)
-      float u;
-      if (u_in) u = u_in[p];
-      else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r); u = u01_open_right(r[0]); }
+      const float u = reveal_u(u_in, seed, offset, p, K);
       if (!((u < inv_t) && !unmasked[p])) {
         // (dense form) the denoiser input of the next reverse step, cat(x_t, t - 1): this position keeps its token
         if (next_input && lane == 0) {
@@ -115,14 +113,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
     }
     if (lane == 0) {
-      float u;
-      if (u_in) {
-        u = u_in[p];
-      } else {
-        uint32_t r[4];
-        philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r);
-        u = u01_open_right(r[0]);
-      }
+      const float u = reveal_u(u_in, seed, offset, p, K);
       bool ch = (u < inv_t) && !unmasked[p];
       if (ch) { unmasked[p] = 1; x_t[p] = (long long)besti; }
       if (x0_hat_out) x0_hat_out[p] = (long long)besti;
@@ -185,18 +176,14 @@ __global__ __launch_bounds__(64) void select_active_kernel(const uint8_t* __rest
     for (int k = 0; k < 8; ++k) {
       if (!um[k]) {
         const long long p = (long long)b * HW + q + 8 * k;
-        float u;
-        if (u_in) u = u_in[p];
-        else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r); u = u01_open_right(r[0]); }
+        const float u = reveal_u(u_in, seed, offset, p, K);
         any = any || (u < inv_t);
       }
     }
     for (int hw = q + 64; hw < HW; hw += 8) {                   // (latents beyond 64 positions)
       const long long p = (long long)b * HW + hw;
       if (unmasked[p]) continue;
-      float u;
-      if (u_in) u = u_in[p];
-      else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r); u = u01_open_right(r[0]); }
+      const float u = reveal_u(u_in, seed, offset, p, K);
       any = any || (u < inv_t);
     }
   }
@@ -247,9 +234,7 @@ __global__ __launch_bounds__(256) void select_needed_kernel(const uint8_t* __res
     if (lane < HW) {
       const long long p = (long long)b * HW + lane;
       if (!unmasked[p]) {
-        float u;
-        if (u_in) u = u_in[p];
-        else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r); u = u01_open_right(r[0]); }
+        const float u = reveal_u(u_in, seed, offset, p, K);
         ch = u < 1.0f / (float)t;
       }
     }
@@ -313,7 +298,7 @@ __global__ __launch_bounds__(256) void philox_noise_kernel(unsigned long long se
   const long long total = nq > npos ? nq : npos;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     uint32_t r[4];
-    if (u_out && i < npos) { philox4x32(seed, offset + (unsigned long long)i * (unsigned long long)K, 0u, r); u_out[i] = u01_open_right(r[0]); }
+    if (u_out && i < npos) u_out[i] = reveal_u(nullptr, seed, offset, i, K);
     if (i < nq) { philox4x32(seed, offset + (unsigned long long)i, 1u, r); q_out[i] = -logf(u01_open_left(r[0])); }
   }
 }

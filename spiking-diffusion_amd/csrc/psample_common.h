@@ -1,4 +1,4 @@
-// Noise and wave-reduction helpers shared by the sampler kernels (psample.hip, step_tail.hip): the Philox4x32-10 counter
+// Noise and wave-reduction helpers shared by the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10 counter
 // scheme of spk_psample_step (u: stream 0, counter offset + position * K; q: stream 1, counter offset + position * K + class) and
 // the 64-lane max / sum by lane shuffles.  Every kernel that draws noise goes through these, so that the dense loop, the
 // active-set forms, the fused step tail and spk_philox_noise see the same draws.
@@ -34,6 +34,17 @@ __device__ __forceinline__ float u01_open_left(uint32_t r) {   // (0, 1]
 }
 __device__ __forceinline__ float u01_open_right(uint32_t r) {  // [0, 1)
   return (float)(r >> 8) * (1.0f / 16777216.0f);
+}
+
+// The uniform of the `changes` test of a reverse step at image position p (R/snn_model/vq_diffusion.py:116): injected, or stream 0
+// at counter offset + p * K.  changes = (u < 1.0f / (float)t) & ~unmasked in fp32; the sampling kernel, the scoring kernel
+// (pscore.hip) and the two select kernels all take their u from here.
+__device__ __forceinline__ float reveal_u(const float* __restrict__ u_in, unsigned long long seed, unsigned long long offset,
+                                          long long p, int K) {
+  if (u_in) return u_in[p];
+  uint32_t r[4];
+  philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r);
+  return u01_open_right(r[0]);
 }
 
 __device__ __forceinline__ float wave_max(float v) {

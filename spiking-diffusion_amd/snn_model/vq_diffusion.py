@@ -6,7 +6,8 @@ attributes (``num_embeddings``, ``n_samples``, ``mask_id``, ``shape``...) and ``
 
 The denoiser runs as fused Conv+BN+LIF kernels (conv1 sees a time-invariant input, conv6 + the time mean are one
 kernel), the per-step token update is one ``spk_psample_step`` launch, and ``sample()`` enqueues the whole
-reverse process without any host synchronisation.  Latent size and T are parameters (the reference hard-codes
+reverse process without any host synchronisation.  ``score()`` runs the same loop teacher-forced on given tokens (the token
+update is one ``spk_pscore_step`` launch) and returns the sampler's likelihood bound for them.  Latent size and T are parameters (the reference hard-codes
 7x7 and 16: vq_diffusion.py:47-48,106,198,206).
 """
 import math
@@ -75,20 +76,41 @@ class _Noise(NamedTuple):
     state: object = None
 
 
+class Score(NamedTuple):
+    """Result of ``AbsorbingDiffusion.score``: per reveal order o, image b and position (i, j) the log-probability (nats) of the
+    given token at the step the order revealed it, and that step; 0 / 0 at the positions given as known."""
+    position_log_prob: torch.Tensor     # fp64 [orders,B,h,w]
+    reveal_step: torch.Tensor           # int32 [orders,B,h,w]
+    log_prob: torch.Tensor              # fp64 [orders,B]: sum over the positions -- one estimate of the bound on log p(x_0) each
+
+    def bits_per_dim(self, n_dims=None):
+        """-mean over orders and images of ``log_prob`` / (ln 2 * n_dims) as a 0-dim device tensor; ``n_dims`` defaults to h * w
+        (the unit of the reference's training loss, R/snn_model/vq_diffusion.py:85-101)."""
+        if n_dims is None:
+            n_dims = self.position_log_prob.shape[-2] * self.position_log_prob.shape[-1]
+        return -self.log_prob.mean() / (math.log(2) * int(n_dims))
+
+
 class _SamplerGraph:
     """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
-    conditional form), its result ``x_t``, and every other buffer the captured launches address by raw pointer: freed earlier,
+    conditional form; ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
+    score graph: ``target[1:]`` = (logp, step), zeroed inside the graph), and every other buffer the captured launches address by raw pointer: freed earlier,
     its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
     (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
-    def __init__(self, dev, b, h, w, form, radii, conditional):
+    def __init__(self, dev, b, h, w, form, radii, conditional, score=False):
         self.graph = self.derived = None                            # set by the capture
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         self.x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         self.unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self.start_in = (torch.empty((b, h, w), dtype=torch.int64, device=dev),
                          torch.empty((b, h, w), dtype=torch.uint8, device=dev)) if conditional else None
+        self.target = None
+        if score:
+            x0 = self.start_in[0] if conditional else torch.empty((b, h, w), dtype=torch.int64, device=dev)
+            self.target = (x0, torch.empty((b, h, w), dtype=torch.float64, device=dev),
+                           torch.empty((b, h, w), dtype=torch.int32, device=dev))
         self.act = (torch.zeros(b, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)) if form.skip else None
         self.need = ops.NeedLists(b, radii, dev) if form.lists else None
         # dense form without the fused step tail: every spk_psample_step also writes the next step's denoiser input
@@ -242,10 +264,60 @@ class AbsorbingDiffusion(Sampler):
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
         form = self._form(b, h, w, record is not None)
+        return self._reverse_process(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed, start, record)
+
+    @torch.no_grad()
+    def score(self, x_0, temp=1.0, sample_steps=None, orders=1, noise=None, record=None, known=None):
+        """The reverse process of ``sample(temp, sample_steps)`` run teacher-forced on the tokens ``x_0``: a lower bound on
+        log p(x_0) under the sampler.  Same unmask draws and denoiser calls as sample(); the token written at a
+        revealed position is x_0's, and its log-probability under softmax(logits / temp) is kept (spk_pscore_step).  Returns
+        ``Score(position_log_prob fp64 [orders,B,h,w] nats, reveal_step int32 [orders,B,h,w], log_prob fp64 [orders,B])``, all on
+        the device, no host synchronisation; every order is one unbiased estimate of the bound (averaging orders tightens the
+        estimate, not the bound).
+
+        ``x_0``: integer device tensor [B,1,h,w] or [B,h,w]; the batch is its first dimension (``n_samples`` is neither read nor
+        changed).  A token outside [0, num_classes) scores -inf.  ``known`` (bool / uint8, x_0's shape): the loop starts from the
+        completion start state of sample(x_init=x_0, known=known) and bounds log p(x_unknown | x_known); known positions hold 0 / 0.
+        Noise: sample()'s contract -- one key draw per order from torch's global CPU generator ('philox' mode; ``last_key`` keeps
+        the last), counters on the global image index (``set_shard``), the same key broadcast rule; ``noise`` = t -> (u, q) injects
+        (only u is read); ``noise_source = 'host'`` draws u only.  ``record`` receives (t, x_t, unmasked, logits) per step as in
+        sample() (dense form).  With ``use_graph`` and neither ``noise`` nor ``record`` an order is one replay of a captured graph
+        that takes x_0 and ``known`` as inputs (a key of its own; sample()'s graphs and keys are untouched)."""
+        start = self._start_state_args(x_0, known, what='x_0', call='score()', alone=True)
+        orders = int(orders)
+        if orders < 1:
+            raise ValueError(f'spkdiff: score() takes orders >= 1, got {orders}')
+        dn = self._denoise_fn
+        dev = next(dn.parameters()).device
+        if dev.type != 'cuda':
+            raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
+        if any(t is not None and t.device != dev for t in start):
+            raise ValueError(f'spkdiff: x_0 / known must be on the denoiser\'s device {dev}')
+        x0 = start[0]
+        b = int(x0.shape[0])
+        h, w = self.shape
+        if sample_steps is None:
+            sample_steps = self.num_timesteps
+        self._check_weights(dn)
+        # (a score call never takes the fused-tail forms: their launch samples the token itself)
+        form = self._form(b, h, w, record is not None)._replace(tail=False, tail_act=False)
+        logp = torch.zeros((orders, b, h, w), dtype=torch.float64, device=dev)
+        step = torch.zeros((orders, b, h, w), dtype=torch.int32, device=dev)
+        for o in range(orders):
+            seed = 0
+            if noise is None and self.noise_source == 'philox':
+                seed = self._philox_key()
+                self.last_key = seed
+            self._reverse_process(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed,
+                                  None if known is None else start, record, target=(x0, logp[o], step[o]))
+        return Score(logp, step, logp.sum(dim=(2, 3)))
+
+    def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None):
+        """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
-                return self._sample_graphed(dev, b, h, w, form, float(temp), int(sample_steps), seed, start=start)
+                return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target)
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -263,10 +335,11 @@ class AbsorbingDiffusion(Sampler):
                 torch.cuda.synchronize(dev)
             finally:
                 self._capturing = False
-        return self._sample_eager(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed, start, record)
+        return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target)
 
-    def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None):
-        """The reverse process launched kernel by kernel: fresh state buffers, the one step loop."""
+    def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None):
+        """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
+        the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self._fill_start(x_t, unmasked, start)
@@ -274,9 +347,12 @@ class AbsorbingDiffusion(Sampler):
             # u and q from torch's global CPU generator in the reference's order: rand_like(x_t.float()) (:116), then
             # multinomial's one-draw fast path (:138); the denoiser call between them there draws nothing
             K = self.num_classes
-            noise = lambda t: (torch.rand(b, 1, h, w).to(dev), torch.empty(b * h * w, K).exponential_(1).to(dev))      # noqa: E731
+            if target is None:
+                noise = lambda t: (torch.rand(b, 1, h, w).to(dev), torch.empty(b * h * w, K).exponential_(1).to(dev))      # noqa: E731
+            else:
+                noise = lambda t: (torch.rand(b, 1, h, w).to(dev), None)      # noqa: E731
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
-        self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record)
+        self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target)
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -287,12 +363,15 @@ class AbsorbingDiffusion(Sampler):
         else:
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
-    def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None):
+    def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
         ``inp``: dense form without the fused tail -- [B,2,h,w] buffer of the denoiser input, built once and then written by
-        every spk_psample_step (one launch less per step; None: every step builds its own); ``record``: see sample()."""
+        every spk_psample_step (one launch less per step; None: every step builds its own); ``record``: see sample();
+        ``target = (x0, logp, step)``: teacher-forced (score()) -- the token update of every step is spk_pscore_step, which writes
+        the given token x0 where spk_psample_step writes a sampled one and leaves its log-probability in logp, t in step (never a
+        fused-tail form: ``form.tail`` / ``form.tail_act`` are off there)."""
         dn = self._denoise_fn
         b, _, h, w = x_t.shape
         K = self.num_classes
@@ -315,36 +394,45 @@ class AbsorbingDiffusion(Sampler):
                                                   want_next=form.tail and t > 1, want_logits=record is not None)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
-                    ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
-                                     next_input=inp if t > 1 else None)
+                    if target is None:
+                        ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
+                                         next_input=inp if t > 1 else None)
+                    else:
+                        ops.pscore_step(logits, target[0], x_t, unmasked, t, temp, target[1], target[2], u, seed, off,
+                                        philox_state=state, next_input=inp if t > 1 else None)
             if record is not None:
                 record.append((t, x_t.clone(), unmasked.clone(), logits.clone()))
 
-    def _start_state_args(self, x_init, known):
+    def _start_state_args(self, x_init, known, what='x_init', call='sample()', alone=False):
         """Argument checks of ``sample(x_init=, known=)``, before anything is drawn or launched: None for the unconditional call,
-        else (codes int64 [B,h,w], keep uint8 [B,h,w]) contiguous on the device."""
-        if x_init is None and known is None:
+        else (codes int64 [B,h,w], keep uint8 [B,h,w]) contiguous on the device.  ``alone`` (score(): ``what`` = 'x_0' is the
+        tokens to score and ``known`` optional): x alone is a call too and gives (codes, None)."""
+        if x_init is None and known is None and not alone:
             return None
-        if x_init is None or known is None:
-            raise ValueError('spkdiff: sample() takes x_init and known together (both or neither)')
-        if not isinstance(x_init, torch.Tensor) or not isinstance(known, torch.Tensor):
-            raise TypeError(f'x_init and known must be torch.Tensors, got {type(x_init)} and {type(known)}')
-        if x_init.shape != known.shape:
-            raise ValueError(f'spkdiff: x_init {tuple(x_init.shape)} and known {tuple(known.shape)} must have the same shape')
+        if (x_init is None or known is None) and not (alone and x_init is not None):
+            raise ValueError(f'spkdiff: {call} takes {what} and known together (both or neither)' if not alone else
+                             f'spkdiff: {call} takes the tokens {what} to score')
+        given = ((what, x_init),) if known is None else ((what, x_init), ('known', known))
+        if not all(isinstance(t, torch.Tensor) for _, t in given):
+            raise TypeError(f'{" and ".join(n for n, _ in given)} must be torch.Tensors, got {" and ".join(str(type(t)) for _, t in given)}')
+        if known is not None and x_init.shape != known.shape:
+            raise ValueError(f'spkdiff: {what} {tuple(x_init.shape)} and known {tuple(known.shape)} must have the same shape')
         h, w = self.shape
         if not ((x_init.dim() == 3 and tuple(x_init.shape[1:]) == (h, w)) or
                 (x_init.dim() == 4 and tuple(x_init.shape[1:]) == (1, h, w))) or x_init.shape[0] < 1:
-            raise ValueError(f'spkdiff: x_init {tuple(x_init.shape)} must be [B,1,{h},{w}] or [B,{h},{w}] (the sampler\'s shape)')
+            raise ValueError(f'spkdiff: {what} {tuple(x_init.shape)} must be [B,1,{h},{w}] or [B,{h},{w}] (the sampler\'s shape)')
         if x_init.is_floating_point() or x_init.is_complex() or x_init.dtype == torch.bool:
-            raise NotImplementedError(f'spkdiff: x_init must be an integer tensor, got {x_init.dtype}')
-        if known.dtype not in (torch.bool, torch.uint8):
+            raise NotImplementedError(f'spkdiff: {what} must be an integer tensor, got {x_init.dtype}')
+        if known is not None and known.dtype not in (torch.bool, torch.uint8):
             raise NotImplementedError(f'spkdiff: known must be bool or uint8, got {known.dtype}')
-        for name, t in (('x_init', x_init), ('known', known)):
+        for name, t in given:
             if not t.is_cuda:
                 raise RuntimeError(f"spkdiff: {name} is on '{t.device}'. The HIP kernels are the implementation; "
                                    "there is no CPU path (move the module / tensors to a ROCm device).")
         B = int(x_init.shape[0])
         codes = x_init.reshape(B, h, w).to(torch.int64).contiguous()
+        if known is None:
+            return codes, None
         keep = known.reshape(B, h, w).contiguous()
         return codes, (keep.view(torch.uint8) if keep.dtype == torch.bool else keep)
 
@@ -433,30 +521,37 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
-    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional):
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, int(self.global_first), weights,
-                conditional)
+                conditional) + (('score',) if score else ())
 
     def _graph_body(self, g, form, temp, sample_steps):
-        """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state."""
+        """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
+        (a score graph: its logp / step outputs zeroed first -- the loop writes them at the revealed positions only)."""
         self._fill_start(g.x_t, g.unmasked, g.start_in)
-        self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp, sample_steps, act=g.act, need=g.need, inp=g.inp)
+        if g.target is not None:
+            g.target[1].zero_()
+            g.target[2].zero_()
+        self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp, sample_steps, act=g.act, need=g.need, inp=g.inp,
+                            target=g.target)
 
-    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None):
+    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
-        each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own."""
+        each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
+        ``target = (x0, logp, step)``: a score graph (again a key of its own) -- x0 is one more input (with ``start`` it IS the
+        codes input), logp / step receive the graph's outputs."""
         dn = self._denoise_fn
-        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None)
+        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None)
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
-            g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None)
+            g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None)
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -474,6 +569,12 @@ class AbsorbingDiffusion(Sampler):
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
+        if target is not None:
+            g.target[0].copy_(target[0])
+            g.graph.replay()
+            target[1].copy_(g.target[1])
+            target[2].copy_(g.target[2])
+            return g.x_t
         g.graph.replay()
         return g.x_t.clone()
 

@@ -4,8 +4,13 @@ end ``round(sum / len, 3)`` of both lists) without a host synchronisation per ba
 The reference's loop reads two ``.item()`` per batch and builds the SSIM from ~20 launches.  Here a batch adds to the model's
 own launches one ``ops.ssim_mse`` launch (fp64 sums per image) and one fixed-order sum of them into slot ``i`` of a device
 buffer; after the last batch one vectorised epilogue rounds every slot to the fp32 values ``.item()`` would have returned
-(``mse_i``, ``1 - ssim_i``) and ONE copy brings them to the host."""
+(``mse_i``, ``1 - ssim_i``) and ONE copy brings them to the host.
+
+``token_nll_eval`` is the denoiser's counterpart, which the reference lacks: the test set's code indices scored under the sampler's
+own reverse process (``AbsorbingDiffusion.score``), again with one read at the end."""
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -58,3 +63,30 @@ def reconstruction_eval(model, batches, T=16, window_size=11):
         means = (totals / torch.tensor(denoms, dtype=torch.float64).to(device)).float()     # fp32 ssim_i, mse_i
         host = torch.stack((1 - means[:, 0], means[:, 1]), dim=1).cpu()                     # fp32 1 - ssim_i, as the script forms it
     return aggregate(host[:, 0].tolist(), host[:, 1].tolist())
+
+
+def token_nll_eval(model, sampler, batches, temp=1.0, sample_steps=None, orders=1, T=16):
+    """How well the denoiser models the VQ-VAE's codes, without a sample: every batch is encoded (``model.encode_images``) and its
+    codes scored under the sampler's reverse process (``AbsorbingDiffusion.score``: a lower bound on log p(codes), ``orders``
+    reveal orders per image -- DESIGN.md §4.10).  ``batches`` as for ``reconstruction_eval`` (images in [0, 1]; the last batch
+    may be smaller).  The per-batch sums stay on the device and ONE copy at the end brings the total to the host.  Returns
+    {"bits_per_dim": -mean(log_prob) / (ln 2 * h * w) -- the unit of the reference's training loss, lower is better --,
+    "nats_per_image": -mean(log_prob), "n_images", "orders"}; the mean runs over images and orders."""
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("spkdiff: token_nll_eval runs the encoder and the denoiser on a ROCm device; there is no CPU path")
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    n_images = 0
+    # (no_grad, not inference_mode: the sampler keeps the buffers of a graph it captures here and writes them in later calls,
+    #  which inference tensors would refuse outside this block)
+    with torch.no_grad():
+        for batch in batches:
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            codes = model.encode_images((images - 0.5).to(device).float().contiguous(), T)
+            total += sampler.score(codes, temp=temp, sample_steps=sample_steps, orders=orders).log_prob.sum()
+            n_images += int(images.shape[0])
+        if not n_images:
+            raise ValueError("token_nll_eval: no batches")
+        nats = -float(total.item()) / (n_images * int(orders))
+    h, w = sampler.shape
+    return {"bits_per_dim": nats / (math.log(2) * h * w), "nats_per_image": nats, "n_images": n_images, "orders": int(orders)}

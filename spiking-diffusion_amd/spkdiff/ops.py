@@ -1938,6 +1938,45 @@ def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, off
     return x_t, unmasked
 
 
+def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, seed=0, offset=0, philox_state=None,
+                next_input=None):
+    """``psample_step`` run teacher-forced (spk_pscore_step): the positions reverse step ``t`` reveals -- the same u / Philox
+    arguments, the same test -- take the GIVEN token ``x0`` (int64, one per position) instead of a sampled one, and its
+    log-probability under softmax(logits / temp) goes to ``logp`` (fp64, nats) and ``t`` to ``step`` (int32, optional); the other
+    positions of ``logp`` / ``step`` are not written.  x_t / unmasked in place; ``next_input`` and the ``active_set`` scope as
+    for psample_step."""
+    logits = _dev(logits, "logits", torch.float32)
+    B, K = logits.shape[0], logits.shape[1]
+    HW = logits[0, 0].numel()
+    n = B * HW
+    x0 = _dev(x0, "x0", torch.int64)
+    if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
+        raise ValueError("x_t must be a contiguous int64 device tensor (updated in place)")
+    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_cuda or not unmasked.is_contiguous():
+        raise ValueError("unmasked must be a contiguous bool/uint8 device tensor (updated in place)")
+    if not isinstance(logp, torch.Tensor) or logp.dtype != torch.float64 or not logp.is_cuda or not logp.is_contiguous():
+        raise ValueError("logp must be a contiguous fp64 device tensor (written where a position is revealed)")
+    if step is not None and (step.dtype != torch.int32 or not step.is_cuda or not step.is_contiguous()):
+        raise ValueError("step must be a contiguous int32 device tensor (written where a position is revealed)")
+    if x0.numel() != n or x_t.numel() != n or unmasked.numel() != n or logp.numel() != n or (step is not None and step.numel() != n):
+        raise ValueError("x0 / x_t / unmasked / logp / step size mismatch: one entry per position of the logits' batch")
+    if u is not None:
+        u = _dev(u, "u", torch.float32)
+        if u.numel() != n:
+            raise ValueError("u must have B*HW entries")
+    if philox_state is not None and (philox_state.dtype != torch.int64 or philox_state.numel() != 2):
+        raise ValueError("philox_state must be an int64 device tensor {seed, base offset}")
+    act, nact = (None, None) if ACTIVE is None else ACTIVE
+    if next_input is not None:
+        next_input = _dev(next_input, "next_input", torch.float32)
+        if next_input.numel() != 2 * n or not next_input.is_contiguous():
+            raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
+    check(lib.spk_pscore_step(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), float(temp), _p(u), int(seed), int(offset),
+                              _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact), _p(next_input),
+                              _stream(logits)), "spk_pscore_step")
+    return logp, step
+
+
 def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
                   conv1=None, want_logits=False):
     """The tail of one dense reverse step as one launch (spk_den_step_tail): conv6 on the spike counts + time mean, the token
