@@ -566,6 +566,22 @@ int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, uint8_t* un
                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                      long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
                      const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
+/* Per-image temperature: spk_psample_step_temps, spk_pscore_step_temps and spk_den_step_tail_temps take the
+ * arguments of spk_psample_step / spk_pscore_step / spk_den_step_tail with `float temp` replaced by `const float* temp_b`, a device
+ * array of B fp32 values -- the reference's `x_0_logits / temp` (R/snn_model/vq_diffusion.py:134) with a [B,1,1,1] tensor in place
+ * of the scalar.  temp_b is indexed by IMAGE, never by slot of the active list: in the active-set forms slot s reads
+ * temp_b[active[s]], as it reads x_t, unmasked and the noise.  The logit is divided by the entry in the same single fp32 division
+ * the scalar entry point makes, so for an image whose entry equals the scalar every output (token, unmasked, x0_hat, fp64 logp,
+ * step, next_input, the fused first layer's spikes and counts) is bit for bit the scalar entry point's.  The host cannot see
+ * device values: the only check on temp_b is for NULL (SPK_ERR_ARG before any launch, as for the other pointers); a non-positive,
+ * infinite or NaN entry gives whatever the IEEE division gives, and the kernels' rules for special values then apply -- the token
+ * is always in [0, K), the score is the formula evaluated in IEEE fp64.  Every other argument, check and property (all codebook
+ * sizes, active lists, philox_state, injected u / q, hipGraph capture) is the sibling's. */
+int spk_psample_step_temps(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                           const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                           unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                           long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
+                           const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -584,6 +600,12 @@ int spk_pscore_step(const float* logits_bkhw, const long long* x0, long long* x_
                     const unsigned long long* philox_state_or_null, double* logp_out, int* step_out_or_null, int B, int HW,
                     int K, const int* active_or_null, const int* n_active_or_null, float* next_input_b2hw_or_null,
                     spk_stream_t stream);
+/* spk_pscore_step with one temperature per image: see spk_psample_step_temps. */
+int spk_pscore_step_temps(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                          const float* temp_b, const float* u_or_null, unsigned long long philox_seed,
+                          unsigned long long philox_offset, const unsigned long long* philox_state_or_null, double* logp_out,
+                          int* step_out_or_null, int B, int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                          float* next_input_b2hw_or_null, spk_stream_t stream);
 
 /* The tail of one DENSE reverse step as one launch per image: conv6 on the spike counts + mean over T (as
  * spk_den_conv3x3_counts_mfma; R/snn_model/vq_diffusion.py:185-187,205-206), the token update (as spk_psample_step: :113-124,
@@ -609,6 +631,16 @@ int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nc
                       const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a,
                       const float* bn1_b, uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W,
                       int K, const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
+/* spk_den_step_tail with one temperature per image (workgroup s of the active-set form reads temp_b[active[s]]): see
+ * spk_psample_step_temps. */
+int spk_den_step_tail_temps(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                            const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                            int t, const float* temp_b, const float* u_or_null, const float* q_or_null,
+                            unsigned long long philox_seed, unsigned long long philox_offset,
+                            const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                            const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                            uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                            const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
 /* q_sample of the diffusion training step, R/snn_model/vq_diffusion.py:61-75: mask = u < t[b] / num_timesteps (fp32, as there);
  * x_t = mask ? mask_id : x_0;  x_0_ignore = mask ? x_0 : -1 (the loss's ignore index).  x0 / u / outputs fp32 [B*HW], t int64 [B],
  * mask_out optional u8.  u is the caller's draw (torch.rand_like in the reference's order). */

@@ -25,10 +25,13 @@ __device__ __forceinline__ bool __any_sync_quad(bool v) {      // OR over the 4 
 }
 
 // KPL = classes per lane (K <= 64 * KPL): 4 covers the reference's default codebook (--codebook_size 128, R/main.py:58);
-// 8 / 16 / 32 are instantiated for larger codebooks (K <= 2048)
-template <int KPL>
+// 8 / 16 / 32 are instantiated for larger codebooks (K <= 2048).
+// PT = per-image temperature (spk_psample_step_temps): `temp` is then a device array indexed by IMAGE (active[slot] in the
+// active-set form, like x_t / unmasked / the noise), read once per position; the division below is the same fp32 division.  A
+// separate instantiation: the scalar kernel's code does not change.
+template <int KPL, bool PT = false>
 __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
-                                                      uint8_t* __restrict__ unmasked, int t, float temp,
+                                                      uint8_t* __restrict__ unmasked, int t, spk_temp_arg_t<PT> temp,
                                                       const float* __restrict__ u_in, const float* __restrict__ q_in,
                                                       unsigned long long seed, unsigned long long offset,
                                                       const unsigned long long* __restrict__ philox_state,
@@ -62,12 +65,13 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
     }
     float l[KPL];
     float mx = -INFINITY;
+    const float tp = spk_temp_of<PT>(temp, active ? active[b] : b);
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
       const int k = lane + 64 * j;
       // (unconditional load from a clamped index + select: hipcc waits for a conditional load on its own)
       const float lg = logits[((long long)b * K + (k < K ? k : K - 1)) * HW + hw];
-      l[j] = k < K ? lg / temp : -INFINITY;
+      l[j] = k < K ? lg / tp : -INFINITY;
       mx = fmaxf(mx, l[j]);
     }
     mx = wave_max(mx);
@@ -385,13 +389,14 @@ extern "C" int spk_den_build_input(const float* x_float_or_null, const long long
   return SPK_OK;
 }
 
-extern "C" int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
-                                float temp, const float* u_or_null, const float* q_or_null,
-                                unsigned long long philox_seed, unsigned long long philox_offset,
-                                const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B,
-                                int HW, int K, const int* active_or_null, const int* n_active_or_null,
-                                float* next_input_b2hw_or_null, hipStream_t stream) {
-  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !(temp > 0.f) || B <= 0 || HW <= 0 || K <= 0)
+namespace {
+template <bool PT>
+int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_arg_t<PT> temp,
+                   const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                   unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                   long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                   float* next_input_b2hw_or_null, hipStream_t stream) {
+  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT>(temp) || B <= 0 || HW <= 0 || K <= 0)
     return SPK_ERR_ARG;
   if (next_input_b2hw_or_null && active_or_null) return SPK_ERR_ARG;      // (the active-set form gathers its input by slot)
   if ((active_or_null == nullptr) != (n_active_or_null == nullptr) || (active_or_null && x0_hat_out_or_null))
@@ -401,8 +406,8 @@ extern "C" int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, 
   int grid = (int)((npos + 3) / 4);
   if (grid > 4096) grid = 4096;
 #define SPK_PSAMPLE_LAUNCH(KPL)                                                                                          \
-  hipLaunchKernelGGL(psample_kernel<KPL>, dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, t,   \
-                     temp, u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,   \
+  hipLaunchKernelGGL((psample_kernel<KPL, PT>), dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, \
+                     t, temp, u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, \
                      active_or_null, n_active_or_null, B, HW, K, next_input_b2hw_or_null, (float)(t - 1))
   if (K <= 256) SPK_PSAMPLE_LAUNCH(4);
   else if (K <= 512) SPK_PSAMPLE_LAUNCH(8);
@@ -411,4 +416,28 @@ extern "C" int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, 
 #undef SPK_PSAMPLE_LAUNCH
   SPK_LAUNCH_CHECK();
   return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_psample_step(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                float temp, const float* u_or_null, const float* q_or_null,
+                                unsigned long long philox_seed, unsigned long long philox_offset,
+                                const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B,
+                                int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                                float* next_input_b2hw_or_null, hipStream_t stream) {
+  return psample_launch<false>(logits_bkhw, x_t_inout, unmasked_inout, t, temp, u_or_null, q_or_null, philox_seed, philox_offset,
+                               philox_state_or_null, x0_hat_out_or_null, B, HW, K, active_or_null, n_active_or_null,
+                               next_input_b2hw_or_null, stream);
+}
+
+// The same step with one temperature per IMAGE: temp_b fp32 [B] on the device (include/spkdiff.h).
+extern "C" int spk_psample_step_temps(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                      const float* temp_b, const float* u_or_null, const float* q_or_null,
+                                      unsigned long long philox_seed, unsigned long long philox_offset,
+                                      const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B,
+                                      int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                                      float* next_input_b2hw_or_null, hipStream_t stream) {
+  return psample_launch<true>(logits_bkhw, x_t_inout, unmasked_inout, t, temp_b, u_or_null, q_or_null, philox_seed, philox_offset,
+                              philox_state_or_null, x0_hat_out_or_null, B, HW, K, active_or_null, n_active_or_null,
+                              next_input_b2hw_or_null, stream);
 }

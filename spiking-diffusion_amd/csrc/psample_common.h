@@ -47,6 +47,25 @@ __device__ __forceinline__ float reveal_u(const float* __restrict__ u_in, unsign
   return u01_open_right(r[0]);
 }
 
+// The temperature argument of the token-update kernels (psample.hip, pscore.hip, step_tail.hip): one fp32 value for the call, or --
+// PT, the `_temps` entry points -- a device array fp32 [B] indexed by IMAGE (the index of x_t / unmasked / the noise, not the slot of
+// an active list).  Both forms divide the logit by the value in the same fp32 division, so an image whose entry equals the scalar
+// gets the scalar call's results bit for bit.  The host can check a value (> 0), of an array only the pointer.
+template <bool PT> struct spk_temp_arg { using type = float; };
+template <> struct spk_temp_arg<true> { using type = const float*; };
+template <bool PT> using spk_temp_arg_t = typename spk_temp_arg<PT>::type;
+
+template <bool PT>
+__device__ __forceinline__ float spk_temp_of(spk_temp_arg_t<PT> temp, int image) {
+  if constexpr (PT) return temp[image];
+  else return temp;
+}
+template <bool PT>
+inline bool spk_temp_arg_ok(spk_temp_arg_t<PT> temp) {
+  if constexpr (PT) return temp != nullptr;
+  else return temp > 0.f;
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));

@@ -23,9 +23,12 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// PT = per-image temperature (spk_pscore_step_temps): `temp` is a device array indexed by IMAGE, read once per revealed position
+// (psample_common.h); a separate instantiation, the scalar kernel's code does not change
+template <bool PT>
 __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ logits, const long long* __restrict__ x0,
                                                      long long* __restrict__ x_t, uint8_t* __restrict__ unmasked, int t,
-                                                     float temp, const float* __restrict__ u_in, unsigned long long seed,
+                                                     spk_temp_arg_t<PT> temp_arg, const float* __restrict__ u_in, unsigned long long seed,
                                                      unsigned long long offset,
                                                      const unsigned long long* __restrict__ philox_state,
                                                      double* __restrict__ logp_out, int* __restrict__ step_out,
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ l
       }
       continue;
     }
+    const float temp = spk_temp_of<PT>(temp_arg, active ? active[b] : b);
     const float* row = logits + (long long)b * K * HW + hw;         // class k at row[k * HW]
     float mx = -INFINITY;
     for (int k = lane; k < K; k += 64) mx = fmaxf(mx, row[(long long)k * HW] / temp);
@@ -73,21 +77,45 @@ __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ l
 
 }  // namespace
 
-extern "C" int spk_pscore_step(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout,
-                               int t, float temp, const float* u_or_null, unsigned long long philox_seed,
-                               unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
-                               double* logp_out, int* step_out_or_null, int B, int HW, int K, const int* active_or_null,
-                               const int* n_active_or_null, float* next_input_b2hw_or_null, hipStream_t stream) {
-  if (!logits_bkhw || !x0 || !x_t_inout || !unmasked_inout || !logp_out || t <= 0 || !(temp > 0.f) || B <= 0 || HW <= 0 || K <= 0)
+namespace {
+template <bool PT>
+int pscore_launch(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                  spk_temp_arg_t<PT> temp, const float* u_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                  const unsigned long long* philox_state_or_null, double* logp_out, int* step_out_or_null, int B, int HW, int K,
+                  const int* active_or_null, const int* n_active_or_null, float* next_input_b2hw_or_null, hipStream_t stream) {
+  if (!logits_bkhw || !x0 || !x_t_inout || !unmasked_inout || !logp_out || t <= 0 || !spk_temp_arg_ok<PT>(temp) || B <= 0 || HW <= 0 ||
+      K <= 0)
     return SPK_ERR_ARG;
   if ((active_or_null == nullptr) != (n_active_or_null == nullptr)) return SPK_ERR_ARG;
   if (next_input_b2hw_or_null && active_or_null) return SPK_ERR_ARG;      // (the active-set form gathers its input by slot)
   if (K > 512) return SPK_ERR_UNSUPPORTED;
   const long long npos = (long long)B * HW;
   const int grid = npos > 4 * 4096 ? 4096 : (int)((npos + 3) / 4);    // four positions (waves) per workgroup, grid-stride beyond
-  hipLaunchKernelGGL(pscore_kernel, dim3(grid), dim3(256), 0, stream, logits_bkhw, x0, x_t_inout, unmasked_inout, t, temp,
+  hipLaunchKernelGGL(pscore_kernel<PT>, dim3(grid), dim3(256), 0, stream, logits_bkhw, x0, x_t_inout, unmasked_inout, t, temp,
                      u_or_null, philox_seed, philox_offset, philox_state_or_null, logp_out, step_out_or_null, active_or_null,
                      n_active_or_null, B, HW, K, next_input_b2hw_or_null, (float)(t - 1));
   SPK_LAUNCH_CHECK();
   return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_pscore_step(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout,
+                               int t, float temp, const float* u_or_null, unsigned long long philox_seed,
+                               unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                               double* logp_out, int* step_out_or_null, int B, int HW, int K, const int* active_or_null,
+                               const int* n_active_or_null, float* next_input_b2hw_or_null, hipStream_t stream) {
+  return pscore_launch<false>(logits_bkhw, x0, x_t_inout, unmasked_inout, t, temp, u_or_null, philox_seed, philox_offset,
+                              philox_state_or_null, logp_out, step_out_or_null, B, HW, K, active_or_null, n_active_or_null,
+                              next_input_b2hw_or_null, stream);
+}
+
+// The same step with one temperature per IMAGE: temp_b fp32 [B] on the device (include/spkdiff.h).
+extern "C" int spk_pscore_step_temps(const float* logits_bkhw, const long long* x0, long long* x_t_inout, uint8_t* unmasked_inout,
+                                     int t, const float* temp_b, const float* u_or_null, unsigned long long philox_seed,
+                                     unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                     double* logp_out, int* step_out_or_null, int B, int HW, int K, const int* active_or_null,
+                                     const int* n_active_or_null, float* next_input_b2hw_or_null, hipStream_t stream) {
+  return pscore_launch<true>(logits_bkhw, x0, x_t_inout, unmasked_inout, t, temp_b, u_or_null, philox_seed, philox_offset,
+                             philox_state_or_null, logp_out, step_out_or_null, B, HW, K, active_or_null, n_active_or_null,
+                             next_input_b2hw_or_null, stream);
 }

@@ -30,11 +30,14 @@ constexpr int TNCH = 10;                          // 8 chunks of conv5 counts + 
 constexpr int TK_MAX = 512;                       // classes = conv6 output channels (KG = groups per wave = ceil(K / 128) <= 4)
 constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested this many taps ahead of their MFMAs
 
-struct TailArgs {
+// PT = per-image temperature (spk_den_step_tail_temps): `temp` is a device array fp32 [B] indexed by IMAGE (psample_common.h); the
+// scalar form's argument block is the one it always was
+template <bool PT>
+struct TailArgsT {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
   const int8_t* wq; const double* scale; const double* bias;
   float* logits_out;                              // optional fp32 [B][128][HW]
-  long long* x_t; uint8_t* unmasked; int t; float temp;
+  long long* x_t; uint8_t* unmasked; int t; spk_temp_arg_t<PT> temp;
   const float* u_in; const float* q_in;
   unsigned long long seed, offset; const unsigned long long* philox_state;
   const float* w1; const float* b1; const float* bn1_a; const float* bn1_b;   // next step's conv1 (packed [9][2][64]); null: none
@@ -48,8 +51,8 @@ struct TailArgs {
 };
 
 // KG = channel groups per wave (1: K <= 128, the reference's default; 2 .. 4: K <= 256 / 384 / 512)
-template <int H, int W, int KG>
-__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
+template <int H, int W, int KG, bool PT = false>
+__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT> a) {
   constexpr int HW = H * W;
   static_assert(HW <= 64, "an image is at most two 32-row tiles");
   constexpr int AV = HW * 2 + 1;                  // 16-byte vectors of a chunk's count records + one zero vector
@@ -103,6 +106,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
   unsigned long long seed = a.seed, offset = a.offset;
   if (a.philox_state) { seed = a.philox_state[0]; offset += a.philox_state[1]; }
   const float inv_t = 1.0f / (float)a.t;
+  const float temp = spk_temp_of<PT>(a.temp, bi);  // (per image: requested here, read by the sampling after the K loop)
   if (tid < HW) {
     const long long pi = (long long)bi * HW + tid;
     const uint8_t um = a.unmasked[pi];
@@ -229,7 +233,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int k = lane + 64 * j;
-      l[j] = k < K ? s_logit[p][k] / a.temp : -INFINITY;
+      l[j] = k < K ? s_logit[p][k] / temp : -INFINITY;
       mx = fmaxf(mx, l[j]);
     }
     mx = wave_max(mx);
@@ -313,15 +317,17 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgs a) {
 
 }  // namespace
 
-extern "C" int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
-                                 const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
-                                 uint8_t* unmasked_inout, int t, float temp, const float* u_or_null, const float* q_or_null,
-                                 unsigned long long philox_seed, unsigned long long philox_offset,
-                                 const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
-                                 const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
-                                 uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
-                                 const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
-  if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !(temp > 0.f) || B <= 0 || T <= 0)
+namespace {
+template <bool PT>
+int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                     const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                     spk_temp_arg_t<PT> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                     unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                     const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                     uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                     const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
+  if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT>(temp) || B <= 0 ||
+      T <= 0)
     return SPK_ERR_ARG;
   if ((x1_s32_out_or_null == nullptr) != (cnt1_out_or_null == nullptr)) return SPK_ERR_ARG;
   if ((active_or_null == nullptr) != (n_active_or_null == nullptr)) return SPK_ERR_ARG;
@@ -332,7 +338,7 @@ extern "C" int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* c
   // the fused first layer writes sixteen 16-byte step records per position and scans with the module-default LIF constants
   // (spk_lif_const_input_bits16): any other step count would write outside x1_s32_out (T < 16) or give wrong spikes (T > 16)
   if (x1_s32_out_or_null && T != 16) return SPK_ERR_UNSUPPORTED;
-  TailArgs a;
+  TailArgsT<PT> a;
   a.c5 = cnt5; a.c1 = cnt1; a.wq = wq; a.scale = scale; a.bias = bias_d; a.logits_out = logits_out_or_null;
   a.x_t = x_t_inout; a.unmasked = unmasked_inout; a.t = t; a.temp = temp; a.u_in = u_or_null; a.q_in = q_or_null;
   a.seed = philox_seed; a.offset = philox_offset; a.philox_state = philox_state_or_null;
@@ -343,7 +349,7 @@ extern "C" int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* c
   a.K = K; a.ng = (K + 15) / 16;                    // wq / scale / bias_d hold ng * 16 channels (zero weights beyond K)
   const int kg = (a.ng + 7) / 8;
 #define SPK_TAIL_LAUNCH(H_, W_, KG_)                                                                                          \
-  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
+  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
   if (H == 7) {
     if (kg == 1) SPK_TAIL_LAUNCH(7, 7, 1); else if (kg == 2) SPK_TAIL_LAUNCH(7, 7, 2);
     else if (kg == 3) SPK_TAIL_LAUNCH(7, 7, 3); else SPK_TAIL_LAUNCH(7, 7, 4);
@@ -354,4 +360,34 @@ extern "C" int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* c
 #undef SPK_TAIL_LAUNCH
   SPK_LAUNCH_CHECK();
   return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                 const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                 uint8_t* unmasked_inout, int t, float temp, const float* u_or_null, const float* q_or_null,
+                                 unsigned long long philox_seed, unsigned long long philox_offset,
+                                 const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                                 const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                                 uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                                 const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
+  return step_tail_launch<false>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout, unmasked_inout, t, temp,
+                                 u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, conv1_w_packed_or_null,
+                                 conv1_bias_or_null, bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K,
+                                 active_or_null, n_active_or_null, stream);
+}
+
+// The same launch with one temperature per IMAGE: temp_b fp32 [B] on the device (include/spkdiff.h).
+extern "C" int spk_den_step_tail_temps(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                       const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                       uint8_t* unmasked_inout, int t, const float* temp_b, const float* u_or_null,
+                                       const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                       const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                                       const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                                       uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                                       const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
+  return step_tail_launch<true>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout, unmasked_inout, t, temp_b,
+                                u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, conv1_w_packed_or_null,
+                                conv1_bias_or_null, bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K,
+                                active_or_null, n_active_or_null, stream);
 }

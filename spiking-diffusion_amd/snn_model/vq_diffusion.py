@@ -10,6 +10,7 @@ reverse process without any host synchronisation.  ``score()`` runs the same loo
 update is one ``spk_pscore_step`` launch) and returns the sampler's likelihood bound for them.  Latent size and T are parameters (the reference hard-codes
 7x7 and 16: vq_diffusion.py:47-48,106,198,206).
 """
+import contextlib
 import math
 import os
 from typing import NamedTuple
@@ -93,15 +94,17 @@ class Score(NamedTuple):
 
 class _SamplerGraph:
     """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
-    conditional form; ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
+    conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
     score graph: ``target[1:]`` = (logp, step), zeroed inside the graph), and every other buffer the captured launches address by raw pointer: freed earlier,
     its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
     (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
-    def __init__(self, dev, b, h, w, form, radii, conditional, score=False):
+    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False):
         self.graph = self.derived = None                            # set by the capture
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
+        # per-image temperatures are one more INPUT: the captured token updates read this buffer, filled before each replay
+        self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp else None
         self.x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         self.unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self.start_in = (torch.empty((b, h, w), dtype=torch.int64, device=dev),
@@ -188,6 +191,7 @@ class AbsorbingDiffusion(Sampler):
         # one the derived forms were built from and rebuilds them when it differs.
         self.verify_weights = True
         self._wsum = None
+        self._pinned_key = None             # see _one_key()
 
     # ---- training step (R/snn_model/vq_diffusion.py:56-101,144-147) -------------------------
     def sample_time(self, b, device):
@@ -246,13 +250,18 @@ class AbsorbingDiffusion(Sampler):
         all-masked state (a "known" token outside the codebook counts as not known: decided on the device).  The batch is
         ``x_init.shape[0]``; ``n_samples`` is neither read nor changed.  Same noise contract: one key draw, counters on the
         global image index -- with ``known`` all false the tokens are those of ``sample(temp, sample_steps)`` at
-        ``n_samples = B`` under the same seed, and a shard (``set_shard``) gives the tokens the whole job gives."""
+        ``n_samples = B`` under the same seed, and a shard (``set_shard``) gives the tokens the whole job gives.
+        ``temp``: a number, or one temperature per image of the call's batch (``_temp_arg``): image i is
+        sampled as ``sample(temp[i])`` samples it -- the same tokens under the same key and global image index, in every launch
+        form, and one captured graph serves every vector."""
         start = self._start_state_args(x_init, known)
+        b = int(self.n_samples) if start is None else int(start[0].shape[0])
+        temp = self._temp_arg(temp, b)
         dn = self._denoise_fn
         dev = next(dn.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
-        b = int(self.n_samples) if start is None else int(start[0].shape[0])
+        temp = self._temp_on(temp, dev)
         h, w = self.shape
         if start is not None and (start[0].device != dev or start[1].device != dev):
             raise ValueError(f'spkdiff: x_init / known must be on the denoiser\'s device {dev}')
@@ -264,7 +273,44 @@ class AbsorbingDiffusion(Sampler):
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
         form = self._form(b, h, w, record is not None)
-        return self._reverse_process(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed, start, record)
+        return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record)
+
+    def _temp_arg(self, temp, b):
+        """The ``temp`` of sample() / score() for a batch of ``b``, checked before anything is drawn or launched.  Anything
+        ``float()`` takes -- a number, a 0-dim or one-element tensor or array -- is the scalar call, as ever: returns the float.
+        Otherwise one entry per image: host data (a list / tuple, a numpy array, a CPU tensor) must have ``b`` finite entries
+        > 0 (ValueError otherwise) and comes back as a CPU fp32 tensor [b]; a device tensor is taken as given -- fp32 [b], its
+        values are not read (the kernels divide by whatever is there: include/spkdiff.h)."""
+        if isinstance(temp, torch.Tensor):
+            if temp.dim() == 0 or (temp.numel() == 1 and b != 1):
+                return float(temp)
+            if temp.is_cuda:
+                if temp.dim() != 1 or int(temp.numel()) != b or temp.dtype != torch.float32:
+                    raise ValueError(f'spkdiff: a per-image temp on the device must be fp32 [{b}] (one entry per image of the '
+                                     f'call), got {temp.dtype} {tuple(temp.shape)}')
+                return temp.contiguous()
+            v = temp.detach().to(torch.float64)
+        elif isinstance(temp, (list, tuple)) or (hasattr(temp, '__array__') and getattr(temp, 'ndim', 0) > 0 and
+                                                 not (getattr(temp, 'size', 0) == 1 and b != 1)):
+            v = torch.as_tensor(temp, dtype=torch.float64)
+        else:
+            return float(temp)
+        if v.dim() != 1 or int(v.numel()) != b:
+            raise ValueError(f'spkdiff: a per-image temp takes one entry per image of the call: {b}, got shape {tuple(v.shape)}')
+        if not bool(torch.isfinite(v).all()) or not bool((v > 0).all()):
+            raise ValueError('spkdiff: every per-image temperature must be finite and > 0')
+        return v.to(torch.float32)
+
+    @staticmethod
+    def _temp_on(temp, dev):
+        """``_temp_arg``'s result for the kernels: the float, or the vector on the denoiser's device (host data: its one copy)."""
+        if not isinstance(temp, torch.Tensor):
+            return temp
+        if temp.is_cuda and temp.device != dev:
+            raise ValueError(f'spkdiff: a per-image temp must be on the denoiser\'s device {dev}, got {temp.device}')
+        if temp.numel() == 1:                  # (a batch of one: the scalar call)
+            return float(temp)
+        return temp.to(dev)
 
     @torch.no_grad()
     def score(self, x_0, temp=1.0, sample_steps=None, orders=1, noise=None, record=None, known=None):
@@ -282,7 +328,10 @@ class AbsorbingDiffusion(Sampler):
         the last), counters on the global image index (``set_shard``), the same key broadcast rule; ``noise`` = t -> (u, q) injects
         (only u is read); ``noise_source = 'host'`` draws u only.  ``record`` receives (t, x_t, unmasked, logits) per step as in
         sample() (dense form).  With ``use_graph`` and neither ``noise`` nor ``record`` an order is one replay of a captured graph
-        that takes x_0 and ``known`` as inputs (a key of its own; sample()'s graphs and keys are untouched)."""
+        that takes x_0 and ``known`` as inputs (a key of its own; sample()'s graphs and keys are untouched).
+        ``temp``: a number or one temperature per image, as in sample() (every order scores image i at ``temp[i]``)."""
+        if isinstance(x_0, torch.Tensor) and x_0.dim() in (3, 4):      # (host checks of a per-image temp: before the device is looked at)
+            temp = self._temp_arg(temp, int(x_0.shape[0]))
         start = self._start_state_args(x_0, known, what='x_0', call='score()', alone=True)
         orders = int(orders)
         if orders < 1:
@@ -295,6 +344,7 @@ class AbsorbingDiffusion(Sampler):
             raise ValueError(f'spkdiff: x_0 / known must be on the denoiser\'s device {dev}')
         x0 = start[0]
         b = int(x0.shape[0])
+        temp = self._temp_on(temp, dev)
         h, w = self.shape
         if sample_steps is None:
             sample_steps = self.num_timesteps
@@ -308,7 +358,7 @@ class AbsorbingDiffusion(Sampler):
             if noise is None and self.noise_source == 'philox':
                 seed = self._philox_key()
                 self.last_key = seed
-            self._reverse_process(dev, b, h, w, form, float(temp), int(sample_steps), noise, seed,
+            self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed,
                                   None if known is None else start, record, target=(x0, logp[o], step[o]))
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
@@ -476,7 +526,22 @@ class AbsorbingDiffusion(Sampler):
             raise ValueError("noise_layout must be 'global' or 'rank'")
         return step_index * (b * h * w * K)
 
+    @contextlib.contextmanager
+    def _one_key(self):
+        """Context: ONE noise key for every sample() / score() call inside -- the calls of a job that runs as several shards of one
+        sampler (spkdiff.evaluate.temperature_sweep).  The key is an ordinary draw, made here (one draw from torch's CPU generator,
+        broadcast under ``_philox_key``'s rule: call ``set_shard`` first); the calls inside draw nothing."""
+        if self._pinned_key is not None:
+            raise RuntimeError('spkdiff: _one_key() does not nest')
+        self._pinned_key = self._philox_key()
+        try:
+            yield self._pinned_key
+        finally:
+            self._pinned_key = None
+
     def _philox_key(self):
+        if self._pinned_key is not None:
+            return self._pinned_key
         draw = int(torch.randint(0, 1 << 62, (1,), dtype=torch.int64))
         if self.noise_layout == 'global':
             import torch.distributed as dist
@@ -525,8 +590,13 @@ class AbsorbingDiffusion(Sampler):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
+        first = int(self.global_first)
+        if isinstance(temp, torch.Tensor):
+            # per-image temperatures are a graph input: one graph for every vector -- and for every shard of a job that runs as
+            # several calls (temperature_sweep): such a graph takes the shard's counter base as an input too (_sample_graphed)
+            temp, first = 'per-image', 'any-shard'
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
-                bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, int(self.global_first), weights,
+                bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
                 conditional) + (('score',) if score else ())
 
     def _graph_body(self, g, form, temp, sample_steps):
@@ -536,13 +606,17 @@ class AbsorbingDiffusion(Sampler):
         if g.target is not None:
             g.target[1].zero_()
             g.target[2].zero_()
-        self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp, sample_steps, act=g.act, need=g.need, inp=g.inp,
-                            target=g.target)
+        self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
+                            act=g.act, need=g.need, inp=g.inp, target=g.target)
 
     def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
+        A per-image ``temp`` (device tensor [B]) is an input in the same way: the key carries a marker in place of the value and the
+        vector is copied into the graph's ``temps`` buffer before each replay.  Such a graph is captured at ``global_first = 0`` and
+        takes the shard's counter base ``global_first * h * w * K`` through the second word of ``state`` (the kernels add it to
+        every step's offset: the same counters), so the calls of a sharded job share it; scalar calls keep the shard in the key.
         ``target = (x0, logp, step)``: a score graph (again a key of its own) -- x0 is one more input (with ``start`` it IS the
         codes input), logp / step receive the graph's outputs."""
         dn = self._denoise_fn
@@ -551,7 +625,8 @@ class AbsorbingDiffusion(Sampler):
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
-            g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None)
+            g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
+                              per_image_temp=isinstance(temp, torch.Tensor))
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -560,12 +635,22 @@ class AbsorbingDiffusion(Sampler):
             torch.cuda.current_stream(dev).wait_stream(side)
             g.graph = torch.cuda.CUDAGraph()
             self._capturing = True
-            with torch.cuda.graph(g.graph, capture_error_mode="thread_local"), ops.flag_scope(g.flag_ws):
-                self._graph_body(g, form, temp, sample_steps)
+            first = self.global_first
+            if g.temps is not None:
+                self.global_first = 0                               # (the shard's base is the graph's input)
+            try:
+                with torch.cuda.graph(g.graph, capture_error_mode="thread_local"), ops.flag_scope(g.flag_ws):
+                    self._graph_body(g, form, temp, sample_steps)
+            finally:
+                self.global_first = first
             self._capturing = False
             g.derived = derived_refs(dn)
             self._graphs[key] = g
-        g.state.copy_(torch.tensor([seed, 0], dtype=torch.int64), non_blocking=False)
+        # (step 0's offset is the shard's counter base, range-checked as every step's is)
+        base = 0 if g.temps is None else self._step_offset(0, b, h, w, self.num_classes)
+        g.state.copy_(torch.tensor([seed, base], dtype=torch.int64), non_blocking=False)
+        if g.temps is not None:
+            g.temps.copy_(temp)
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
@@ -722,7 +807,7 @@ class DummyModel(nn.Module):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1.  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor.  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -733,7 +818,7 @@ class DummyModel(nn.Module):
             a1, b1 = bn1.affine_terms()
             nxt = (conv1._spk_params.get(conv1), None if conv1.bias is None else conv1.bias.detach(), a1, b1)
         with ops.timed('den.tail'):
-            return ops.den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, int(t), float(temp), T=self.n_steps,
+            return ops.den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
                                      K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,
                                      conv1=nxt, want_logits=want_logits)
 

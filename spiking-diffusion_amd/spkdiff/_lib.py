@@ -133,6 +133,13 @@ _SIGS = {
                                 P, P, P, P]),
     "spk_den_step_tail": (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, c_float, P, P, c_ulonglong, c_ulonglong, P, P, P,
                                   P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    # per-image temperature: `float temp` of the three entry points above replaced by a device array fp32 [B]
+    "spk_psample_step_temps": (c_int, [P, P, P, c_int, P, P, P, c_ulonglong, c_ulonglong, P, P, c_int, c_int, c_int,
+                                       P, P, P, P]),
+    "spk_pscore_step_temps": (c_int, [P, P, P, P, c_int, P, P, c_ulonglong, c_ulonglong, P, P, P, c_int, c_int, c_int,
+                                      P, P, P, P]),
+    "spk_den_step_tail_temps": (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, P, P, P, c_ulonglong, c_ulonglong, P, P, P,
+                                        P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "spk_philox_noise": (c_int, [c_ulonglong, c_ulonglong, P, P, P, c_int, c_int, c_int, P]),
     "spk_completion_state": (c_int, [P, P, P, P, P] + [c_int] * 8 + [c_longlong, P]),
     "spk_completion_compose": (c_int, [P, P, P, P] + [c_int] * 4 + [P]),

@@ -53,6 +53,7 @@ def complete_images(model, sampler, images, keep, temp=1.0, sample_steps=None, T
     [B,H,W], true = the pixel is given.  ``model``: the SNN_VQVAE, ``sampler``: the AbsorbingDiffusion of its latent shape.
     Returns a ``Completion`` of device tensors.  ``paste``: the given pixels of ``images_u8`` are the input's
     (uint8(clip(image + 0.5, 0, 1) * 255), R/main.py:401), the rest the decoder's; False: the decoder's image everywhere.
+    ``temp``: a number or one temperature per image, as ``sample()`` takes it.
     One key draw from torch's global CPU generator, as every ``sample()`` call."""
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)

@@ -7,7 +7,10 @@ buffer; after the last batch one vectorised epilogue rounds every slot to the fp
 (``mse_i``, ``1 - ssim_i``) and ONE copy brings them to the host.
 
 ``token_nll_eval`` is the denoiser's counterpart, which the reference lacks: the test set's code indices scored under the sampler's
-own reverse process (``AbsorbingDiffusion.score``), again with one read at the end."""
+own reverse process (``AbsorbingDiffusion.score``), again with one read at the end.
+
+``temperature_sweep`` is the sampling sweep of R/main.py:379-443 (per temperature: many ``abdiff.sample(temp=tem)`` calls of 16
+images, decoded) run as ONE job with a per-image temperature."""
 from __future__ import annotations
 
 import math
@@ -65,17 +68,87 @@ def reconstruction_eval(model, batches, T=16, window_size=11):
     return aggregate(host[:, 0].tolist(), host[:, 1].tolist())
 
 
-def token_nll_eval(model, sampler, batches, temp=1.0, sample_steps=None, orders=1, T=16):
+def _sweep_temps(temps, n_per_temp):
+    """fp32 [len(temps) * n_per_temp] on the host: image g * n_per_temp + j of the sweep job has temperature temps[g]."""
+    tv = torch.as_tensor(temps, dtype=torch.float64).reshape(-1)
+    n_per_temp = int(n_per_temp)
+    if tv.numel() < 1 or n_per_temp < 1:
+        raise ValueError("temperature_sweep: needs at least one temperature and n_per_temp >= 1")
+    if not bool(torch.isfinite(tv).all()) or not bool((tv > 0).all()):
+        raise ValueError("temperature_sweep: every temperature must be finite and > 0")
+    return tv.to(torch.float32).repeat_interleave(n_per_temp)
+
+
+@torch.no_grad()
+def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_steps=None, batch=256, T=16):
+    """Images [lo, hi) of the job ``temperature_sweep`` describes -- what one rank of ``spkdiff.dist.temperature_sweep_sharded``
+    runs: (uint8 [hi - lo, C, H, W], tokens int64 [hi - lo, h, w]).  Calls of at most ``batch`` images (None: one call), each a
+    shard of the job (``set_shard(first, count)``) with its slice of the per-image temperature vector, all under ONE noise key
+    (``AbsorbingDiffusion._one_key``: one draw from torch's CPU generator, broadcast from rank 0 inside a process group), so the
+    images depend on neither ``batch`` nor the range.  ``n_samples`` / ``global_first`` of the sampler are restored."""
+    tv = _sweep_temps(temps, n_per_temp)
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= tv.numel():
+        raise ValueError(f"temperature_sweep: the range [{lo}, {hi}) is not inside the job's {tv.numel()} images")
+    if getattr(sampler, "noise_source", "philox") != "philox":
+        raise ValueError("temperature_sweep: one job in several calls needs the counter-based noise (noise_source = 'philox')")
+    step = hi - lo if batch is None else int(batch)
+    if step < 1:
+        raise ValueError("temperature_sweep: batch must be >= 1 or None")
+    tv = tv.to(next(model.parameters()).device)        # one copy: every call takes a slice
+    keep = (sampler.n_samples, sampler.global_first)
+    images, tokens = [], []
+    try:
+        sampler.set_shard(lo, min(step, hi - lo))       # (declares the shard before the key is drawn: the broadcast rule)
+        with sampler._one_key():
+            for first in range(lo, hi, step):
+                count = min(step, hi - first)
+                sampler.set_shard(first, count)
+                tok = sampler.sample(temp=tv[first:first + count], sample_steps=sample_steps)
+                tok = tok.reshape(count, tok.shape[-2], tok.shape[-1])
+                images.append(model.decode_tokens(tok, T, want_u8=True)[1])
+                tokens.append(tok)
+    finally:
+        sampler.n_samples, sampler.global_first = keep
+    return torch.cat(images), torch.cat(tokens)
+
+
+@torch.no_grad()
+def temperature_sweep(model, sampler, temps, n_per_temp, sample_steps=None, batch=256, T=16):
+    """R/main.py's temperature sweep (:379-443: for every temperature, calls of ``abdiff.sample(temp=tem)`` at 16 images, each
+    decoded to uint8) as ONE job of ``len(temps) * n_per_temp`` images: image ``g * n_per_temp + j`` has temperature
+    ``temps[g]``.  Returns (uint8 images [len(temps), n_per_temp, C, H, W] -- main.py's ``all_images_list`` --, tokens int64
+    [len(temps), n_per_temp, h, w]) on the device.  The job runs in calls of at most ``batch`` images whatever the group
+    boundaries (``batch=None``: one call), see ``temperature_sweep_range``; one captured graph per call size serves every
+    temperature, where the scalar protocol captures one per temperature.  Image (g, j) is the image ``sample(temps[g])`` gives at
+    global index ``g * n_per_temp + j`` under the sweep's key."""
+    G, n = len(temps), int(n_per_temp)
+    u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T)
+    return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
+
+
+def token_nll_eval(model, sampler, batches, temp=1.0, sample_steps=None, orders=1, T=16, temps=None):
     """How well the denoiser models the VQ-VAE's codes, without a sample: every batch is encoded (``model.encode_images``) and its
     codes scored under the sampler's reverse process (``AbsorbingDiffusion.score``: a lower bound on log p(codes), ``orders``
     reveal orders per image -- DESIGN.md §4.10).  ``batches`` as for ``reconstruction_eval`` (images in [0, 1]; the last batch
     may be smaller).  The per-batch sums stay on the device and ONE copy at the end brings the total to the host.  Returns
     {"bits_per_dim": -mean(log_prob) / (ln 2 * h * w) -- the unit of the reference's training loss, lower is better --,
-    "nats_per_image": -mean(log_prob), "n_images", "orders"}; the mean runs over images and orders."""
+    "nats_per_image": -mean(log_prob), "n_images", "orders"}; the mean runs over images and orders.
+
+    ``temps = [t_0, ...]`` (then ``temp`` is not read): the NLL-versus-temperature curve from one pass -- every batch is repeated
+    ``len(temps)`` times and scored in ONE ``score()`` call with a per-image temperature (replica r of image i sits at index
+    r * B + i of the call and has temperature temps[r]); "bits_per_dim" and "nats_per_image" are then lists with one figure per
+    temperature and "temps" repeats the list.  The replicas of an image sit at different global image indices, so they see
+    different reveal orders: each figure is an unbiased estimate of its own temperature's bound, not the same orders at another
+    temperature."""
     device = next(model.parameters()).device
     if device.type != "cuda":
         raise RuntimeError("spkdiff: token_nll_eval runs the encoder and the denoiser on a ROCm device; there is no CPU path")
-    total = torch.zeros((), dtype=torch.float64, device=device)
+    G = None
+    if temps is not None:
+        tv = _sweep_temps(temps, 1).to(device)
+        G = int(tv.numel())
+    total = torch.zeros(() if G is None else (G,), dtype=torch.float64, device=device)
     n_images = 0
     # (no_grad, not inference_mode: the sampler keeps the buffers of a graph it captures here and writes them in later calls,
     #  which inference tensors would refuse outside this block)
@@ -83,10 +156,21 @@ def token_nll_eval(model, sampler, batches, temp=1.0, sample_steps=None, orders=
         for batch in batches:
             images = batch[0] if isinstance(batch, (tuple, list)) else batch
             codes = model.encode_images((images - 0.5).to(device).float().contiguous(), T)
-            total += sampler.score(codes, temp=temp, sample_steps=sample_steps, orders=orders).log_prob.sum()
+            if G is None:
+                total += sampler.score(codes, temp=temp, sample_steps=sample_steps, orders=orders).log_prob.sum()
+            else:
+                B = int(codes.shape[0])
+                lp = sampler.score(codes.repeat(G, 1, 1), temp=tv.repeat_interleave(B), sample_steps=sample_steps,
+                                   orders=orders).log_prob                       # [orders, G * B]
+                total += lp.reshape(int(orders), G, B).sum(dim=(0, 2))
             n_images += int(images.shape[0])
         if not n_images:
             raise ValueError("token_nll_eval: no batches")
-        nats = -float(total.item()) / (n_images * int(orders))
+        host = total.cpu()
     h, w = sampler.shape
+    if G is not None:
+        nats = [-float(v) / (n_images * int(orders)) for v in host.tolist()]
+        return {"bits_per_dim": [v / (math.log(2) * h * w) for v in nats], "nats_per_image": nats, "n_images": n_images,
+                "orders": int(orders), "temps": [float(v) for v in tv.tolist()]}
+    nats = -float(host.item()) / (n_images * int(orders))
     return {"bits_per_dim": nats / (math.log(2) * h * w), "nats_per_image": nats, "n_images": n_images, "orders": int(orders)}

@@ -1906,13 +1906,28 @@ def den_build_input(x, t, out=None):
     return out
 
 
+def _temp_arg(temp, B, what):
+    """The temperature of a token update: (fp32 device tensor [B], None) for a per-image vector -- the ``_temps`` entry point --
+    or (None, float) for anything ``float()`` takes (a number, a 0-dim or one-element tensor): the scalar entry point, unchanged.
+    A vector is taken as given: contiguous fp32 on the device, one entry per image of the call (index = image, also inside an
+    ``active_set`` scope); its values are the caller's (the kernels divide by whatever is there)."""
+    if not (isinstance(temp, torch.Tensor) and temp.numel() > 1):
+        return None, float(temp)
+    if temp.dtype != torch.float32 or not temp.is_cuda or not temp.is_contiguous() or temp.dim() != 1 or temp.numel() != int(B):
+        raise ValueError(f"{what}: a per-image temp must be a contiguous fp32 device tensor of B = {int(B)} entries, got "
+                         f"{temp.dtype} {tuple(temp.shape)} on '{temp.device}'")
+    return temp, None
+
+
 def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, philox_state=None,
                  next_input=None):
     """In-place update of x_t (int64) and unmasked (bool/u8) from logits [B,K,h,w].  next_input (dense form only): fp32
-    [B,2,h,w] that receives the denoiser input of the next reverse step, cat(x_t, t - 1)."""
+    [B,2,h,w] that receives the denoiser input of the next reverse step, cat(x_t, t - 1).  ``temp``: a number, or a contiguous
+    fp32 device tensor with one temperature per image (spk_psample_step_temps)."""
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
+    temp_b, temp = _temp_arg(temp, x_t.numel() // HW, "psample_step")
     if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
         raise ValueError("x_t must be a contiguous int64 device tensor (updated in place)")
     if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_contiguous():
@@ -1932,7 +1947,12 @@ def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, off
         next_input = _dev(next_input, "next_input", torch.float32)
         if next_input.numel() != B * 2 * HW or not next_input.is_contiguous():
             raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
-    check(lib.spk_psample_step(_p(logits), _p(x_t), _p(unmasked), int(t), float(temp), _p(u), _p(q), int(seed),
+    if temp_b is not None:
+        check(lib.spk_psample_step_temps(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), _p(q), int(seed),
+                                         int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
+                                         _stream(logits)), "spk_psample_step_temps")
+        return x_t, unmasked
+    check(lib.spk_psample_step(_p(logits), _p(x_t), _p(unmasked), int(t), temp, _p(u), _p(q), int(seed),
                                int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
                                _stream(logits)), "spk_psample_step")
     return x_t, unmasked
@@ -1944,11 +1964,12 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
     arguments, the same test -- take the GIVEN token ``x0`` (int64, one per position) instead of a sampled one, and its
     log-probability under softmax(logits / temp) goes to ``logp`` (fp64, nats) and ``t`` to ``step`` (int32, optional); the other
     positions of ``logp`` / ``step`` are not written.  x_t / unmasked in place; ``next_input`` and the ``active_set`` scope as
-    for psample_step."""
+    for psample_step; ``temp`` a number or a per-image fp32 device tensor (spk_pscore_step_temps)."""
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
     n = B * HW
+    temp_b, temp = _temp_arg(temp, B, "pscore_step")
     x0 = _dev(x0, "x0", torch.int64)
     if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
         raise ValueError("x_t must be a contiguous int64 device tensor (updated in place)")
@@ -1971,7 +1992,12 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
         next_input = _dev(next_input, "next_input", torch.float32)
         if next_input.numel() != 2 * n or not next_input.is_contiguous():
             raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
-    check(lib.spk_pscore_step(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), float(temp), _p(u), int(seed), int(offset),
+    if temp_b is not None:
+        check(lib.spk_pscore_step_temps(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), int(seed), int(offset),
+                                        _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact), _p(next_input),
+                                        _stream(logits)), "spk_pscore_step_temps")
+        return logp, step
+    check(lib.spk_pscore_step(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), temp, _p(u), int(seed), int(offset),
                               _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact), _p(next_input),
                               _stream(logits)), "spk_pscore_step")
     return logp, step
@@ -1984,10 +2010,11 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     bn_a, bn_b)`` -- the first denoiser layer of the next step.  Returns (x1 S32 [B,2,h,w,16,16], cnt1 u8 [B,2,h,w,32]) or None,
     and the logits fp32 [B,K,h,w] when asked for.  Inside an ``active_set`` scope (the untouched-image elimination) cnt5 / cnt1 / logits
     are per SLOT of the active list and x_t / unmasked / the noise per image; ``conv1`` must be None there (the next step's first layer
-    belongs to the next step's active set)."""
+    belongs to the next step's active set).  ``temp``: a number or a per-image fp32 device tensor (spk_den_step_tail_temps)."""
     cnt5 = _dev(cnt5, "cnt5", torch.uint8)
     cnt1 = _dev(cnt1, "cnt1", torch.uint8)
     B, nch5, H, W, _ = cnt5.shape
+    temp_b, temp = _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
     wq, scale, bias_d = packed6
     if x_t.dtype != torch.int64 or not x_t.is_contiguous() or x_t.numel() != B * H * W:
         raise ValueError("x_t must be a contiguous int64 device tensor [B,1,h,w]")
@@ -2011,8 +2038,14 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
         w1, b1, a1, bb1 = conv1
         x1 = torch.empty((B, 2, H, W, T, 16), dtype=C4_DTYPE, device=cnt5.device)
         c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
+    if temp_b is not None:
+        check(lib.spk_den_step_tail_temps(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d),
+                                          _p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), _p(q), int(seed), int(offset),
+                                          _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W, int(K),
+                                          _p(act), _p(nact), _stream(cnt5)), "spk_den_step_tail_temps")
+        return (None if x1 is None else (x1, c1o)), logits
     check(lib.spk_den_step_tail(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
-                                _p(x_t), _p(unmasked), int(t), float(temp), _p(u), _p(q), int(seed), int(offset),
+                                _p(x_t), _p(unmasked), int(t), temp, _p(u), _p(q), int(seed), int(offset),
                                 _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W, int(K),
                                 _p(act), _p(nact), _stream(cnt5)), "spk_den_step_tail")
     return (None if x1 is None else (x1, c1o)), logits
