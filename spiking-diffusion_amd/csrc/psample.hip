@@ -38,13 +38,11 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
                                                       long long* __restrict__ x0_hat_out,
                                                       const int* __restrict__ active, const int* __restrict__ n_active,
                                                       int B, int HW, int K, float* __restrict__ next_input, float t_next) {
-  // a captured (hipGraph) launch bakes its arguments: the per-call part of the Philox counter then comes from a
-  // 2-word device buffer {seed, base offset} the host updates before each replay
-  if (philox_state) { seed = philox_state[0]; offset += philox_state[1]; }
+  philox_base(philox_state, seed, offset);
   const int lane = threadIdx.x & 63;
   // active-set form (spk_select_active): logits hold one slot per ACTIVE image (slot s = image active[s]); noise, x_t
   // and unmasked stay indexed by image, so the draws are those of the dense form
-  const int Bn = active ? (*n_active < B ? *n_active : B) : B;
+  const int Bn = spk_active_count(active, n_active, B);
   const long long npos = (long long)Bn * HW;
   const float inv_t = 1.0f / (float)t;
   for (long long ps = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); ps < npos; ps += (long long)gridDim.x * 4) {
@@ -55,16 +53,11 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       // the noise is counter-based / injected per position, so skipping a draw does not move any other)
       const float u = reveal_u(u_in, seed, offset, p, K);
       if (!((u < inv_t) && !unmasked[p])) {
-        // (dense form) the denoiser input of the next reverse step, cat(x_t, t - 1): this position keeps its token
-        if (next_input && lane == 0) {
-          next_input[((long long)b * 2 + 0) * HW + hw] = (float)x_t[p];
-          next_input[((long long)b * 2 + 1) * HW + hw] = t_next;
-        }
+        if (next_input && lane == 0) write_next_input(next_input, b, hw, HW, (float)x_t[p], t_next);   // keeps its token
         continue;
       }
     }
     float l[KPL];
-    float mx = -INFINITY;
     const float tp = spk_temp_of<PT>(temp, active ? active[b] : b);
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
@@ -72,59 +65,14 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       // (unconditional load from a clamped index + select: hipcc waits for a conditional load on its own)
       const float lg = logits[((long long)b * K + (k < K ? k : K - 1)) * HW + hw];
       l[j] = k < K ? lg / tp : -INFINITY;
-      mx = fmaxf(mx, l[j]);
     }
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) se += (lane + 64 * j < K) ? expf(l[j] - mx) : 0.f;
-    se = wave_sum(se);
-    const float lse = mx + logf(se);
-    // Categorical normalises logits, then .probs = softmax(normalised logits)
-    float e[KPL];
-    float mx2 = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) { l[j] = l[j] - lse; mx2 = fmaxf(mx2, l[j]); }
-    mx2 = wave_max(mx2);
-    float se2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) { e[j] = (lane + 64 * j < K) ? expf(l[j] - mx2) : 0.f; se2 += e[j]; }
-    se2 = wave_sum(se2);
-    float best = -INFINITY;
-    // a position without a single comparable ratio (a NaN logit, or every logit -inf: all ratios NaN) gets token 0 --
-    // torch.argmax's answer for an all-NaN row; a valid ratio is >= 0 and always beats this start
-    int besti = 0;
-#pragma unroll
-    for (int j = 0; j < KPL; ++j) {
-      const int k = lane + 64 * j;
-      if (k < K) {
-        float q;
-        if (q_in) {
-          q = q_in[p * K + k];
-        } else {
-          uint32_t r[4];
-          philox4x32(seed, offset + (unsigned long long)(p * K + k), 1u, r);
-          q = -logf(u01_open_left(r[0]));
-        }
-        const float ratio = (e[j] / se2) / q;
-        if (ratio > best) { best = ratio; besti = k; }
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      float ob = __shfl_xor(best, off);
-      int oi = __shfl_xor(besti, off);
-      if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-    }
+    const int besti = categorical_race<KPL>(l, lane, K, q_in, seed, offset, p);
     if (lane == 0) {
       const float u = reveal_u(u_in, seed, offset, p, K);
       bool ch = (u < inv_t) && !unmasked[p];
       if (ch) { unmasked[p] = 1; x_t[p] = (long long)besti; }
       if (x0_hat_out) x0_hat_out[p] = (long long)besti;
-      if (next_input && lane == 0) {
-        next_input[((long long)b * 2 + 0) * HW + hw] = ch ? (float)besti : (float)x_t[p];
-        next_input[((long long)b * 2 + 1) * HW + hw] = t_next;
-      }
+      if (next_input) write_next_input(next_input, b, hw, HW, ch ? (float)besti : (float)x_t[p], t_next);
     }
   }
 }
@@ -134,15 +82,14 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
 __global__ void den_input_kernel(const float* __restrict__ xf, const long long* __restrict__ xi,
                                  const long long* __restrict__ t_vec, long long t_scalar, float* __restrict__ out,
                                  const int* __restrict__ active, const int* __restrict__ n_active, int B, int HW) {
-  const int Bn = active ? (*n_active < B ? *n_active : B) : B;
+  const int Bn = spk_active_count(active, n_active, B);
   const int total = Bn * HW;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int b = i / HW, hw = i % HW;                            // output slot
     const int src = active ? active[b] * HW + hw : i;             // active-set form: slot b holds image active[b]
     const float x = xf ? xf[src] : (float)xi[src];
     const float tv = (float)(t_vec ? t_vec[active ? active[b] : b] : t_scalar);
-    out[((long long)b * 2 + 0) * HW + hw] = x;
-    out[((long long)b * 2 + 1) * HW + hw] = 1.0f * tv;
+    write_next_input(out, b, hw, HW, x, 1.0f * tv);
   }
 }
 
@@ -162,7 +109,7 @@ __global__ __launch_bounds__(64) void select_active_kernel(const uint8_t* __rest
                                                            unsigned long long offset,
                                                            const unsigned long long* __restrict__ philox_state,
                                                            int* __restrict__ active, int* __restrict__ n_active, int B, int HW, int K) {
-  if (philox_state) { seed = philox_state[0]; offset += philox_state[1]; }
+  philox_base(philox_state, seed, offset);
   const float inv_t = 1.0f / (float)t;
   const int lane = threadIdx.x;
   const int gid = blockIdx.x * 64 + lane;
@@ -228,9 +175,9 @@ __global__ __launch_bounds__(256) void select_needed_kernel(const uint8_t* __res
                                                             uint8_t* __restrict__ need, int B, int H, int W, int R, int K) {
   __shared__ int s_cnt[8][8];
   __shared__ int s_last;
-  if (philox_state) { seed = philox_state[0]; offset += philox_state[1]; }
+  philox_base(philox_state, seed, offset);
   const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int Bn = *n_active < B ? *n_active : B;
+  const int Bn = spk_active_count(active, n_active, B);
   const int HW = H * W;
   if (slot < Bn) {
     const int b = active[slot];
@@ -297,13 +244,12 @@ __global__ __launch_bounds__(256) void philox_noise_kernel(unsigned long long se
                                                            const unsigned long long* __restrict__ philox_state,
                                                            float* __restrict__ u_out, float* __restrict__ q_out,
                                                            long long npos, int K) {
-  if (philox_state) { seed = philox_state[0]; offset += philox_state[1]; }
+  philox_base(philox_state, seed, offset);
   const long long nq = q_out ? npos * K : 0;
   const long long total = nq > npos ? nq : npos;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    uint32_t r[4];
     if (u_out && i < npos) u_out[i] = reveal_u(nullptr, seed, offset, i, K);
-    if (i < nq) { philox4x32(seed, offset + (unsigned long long)i, 1u, r); q_out[i] = -logf(u01_open_left(r[0])); }
+    if (i < nq) q_out[i] = race_q(nullptr, seed, offset, i, 1, 0);     // (q_out is flat: i = p * K + k)
   }
 }
 

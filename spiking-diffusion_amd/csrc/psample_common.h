@@ -1,7 +1,7 @@
-// Noise and wave-reduction helpers shared by the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10 counter
-// scheme of spk_psample_step (u: stream 0, counter offset + position * K; q: stream 1, counter offset + position * K + class) and
-// the 64-lane max / sum by lane shuffles.  Every kernel that draws noise goes through these, so that the dense loop, the
-// active-set forms, the fused step tail and spk_philox_noise see the same draws.
+// The token update of a reverse step, defined once for the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10
+// counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
+// offset + position * K + class), the categorical draw categorical_race, the 64-lane max / sum and the prologues every kernel shares.
+// Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
 #include <math.h>
@@ -38,13 +38,37 @@ __device__ __forceinline__ float u01_open_right(uint32_t r) {  // [0, 1)
 
 // The uniform of the `changes` test of a reverse step at image position p (R/snn_model/vq_diffusion.py:116): injected, or stream 0
 // at counter offset + p * K.  changes = (u < 1.0f / (float)t) & ~unmasked in fp32; the sampling kernel, the scoring kernel
-// (pscore.hip) and the two select kernels all take their u from here.
+// (pscore.hip), the fused step tail and the two select kernels all take their u from here.
 __device__ __forceinline__ float reveal_u(const float* __restrict__ u_in, unsigned long long seed, unsigned long long offset,
                                           long long p, int K) {
   if (u_in) return u_in[p];
   uint32_t r[4];
   philox4x32(seed, offset + (unsigned long long)p * (unsigned long long)K, 0u, r);
   return u01_open_right(r[0]);
+}
+
+// The exponential of the race for class k at image position p: injected, or -log of a (0, 1] uniform, stream 1 at offset + p * K + k.
+__device__ __forceinline__ float race_q(const float* __restrict__ q_in, unsigned long long seed, unsigned long long offset,
+                                        long long p, int K, int k) {
+  if (q_in) return q_in[p * K + k];
+  uint32_t r[4];
+  philox4x32(seed, offset + (unsigned long long)(p * K + k), 1u, r);
+  return -logf(u01_open_left(r[0]));
+}
+
+// A captured (hipGraph) launch bakes its arguments: its Philox key / base come from {seed, base offset} the host updates per replay.
+__device__ __forceinline__ void philox_base(const unsigned long long* __restrict__ state, unsigned long long& seed, unsigned long long& offset) {
+  if (state) { seed = state[0]; offset += state[1]; }
+}
+// Active-set form (spk_select_active): how many slots of the list a launch sized for B images works on; B without a list.
+__device__ __forceinline__ int spk_active_count(const int* __restrict__ active, const int* __restrict__ n_active, int B) {
+  return active ? (*n_active < B ? *n_active : B) : B;
+}
+// (dense form) the denoiser input of the next reverse step, cat(x_t, t - 1), at position hw of logits slot b
+__device__ __forceinline__ void write_next_input(float* __restrict__ next_input, int b, int hw, int HW, float token, float t_next) {
+  float* dst = next_input + (long long)b * 2 * HW + hw;         // [B][2][HW]: plane 0 the token, plane 1 the step
+  dst[0] = token;
+  dst[HW] = t_next;
 }
 
 // The temperature argument of the token-update kernels (psample.hip, pscore.hip, step_tail.hip): one fp32 value for the call, or --
@@ -75,6 +99,51 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
+}
+
+// x0_hat = Categorical(logits = l).sample() of one position, by one wave: l[j] is the temperature-scaled logit of class lane + 64 * j
+// (-inf for a class >= K; overwritten).  probs = softmax(l - logsumexp l), the draw argmax_k probs_k / q_k (torch.multinomial's one-draw
+// path), ties to the lower class; every lane returns it.  These fp32 operations in this order are the definition (-ffp-contract=off).
+template <int NJ>
+__device__ __forceinline__ int categorical_race(float (&l)[NJ], int lane, int K, const float* __restrict__ q_in,
+                                                unsigned long long seed, unsigned long long offset, long long p) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) mx = fmaxf(mx, l[j]);
+  mx = wave_max(mx);
+  float se = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) se += (lane + 64 * j < K) ? expf(l[j] - mx) : 0.f;
+  se = wave_sum(se);
+  const float lse = mx + logf(se);
+  float e[NJ];
+  float mx2 = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) { l[j] = l[j] - lse; mx2 = fmaxf(mx2, l[j]); }
+  mx2 = wave_max(mx2);
+  float se2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) { e[j] = (lane + 64 * j < K) ? expf(l[j] - mx2) : 0.f; se2 += e[j]; }
+  se2 = wave_sum(se2);
+  float best = -INFINITY;
+  // a position without a single comparable ratio (a NaN logit, or every logit -inf: all ratios NaN) gets token 0 --
+  // torch.argmax's answer for an all-NaN row; a valid ratio is >= 0 and always beats this start
+  int besti = 0;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K) {
+      const float ratio = (e[j] / se2) / race_q(q_in, seed, offset, p, K, k);
+      if (ratio > best) { best = ratio; besti = k; }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ob = __shfl_xor(best, off);
+    const int oi = __shfl_xor(besti, off);
+    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+  }
+  return besti;
 }
 
 }  // namespace

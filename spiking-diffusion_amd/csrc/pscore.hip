@@ -34,10 +34,10 @@ __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ l
                                                      double* __restrict__ logp_out, int* __restrict__ step_out,
                                                      const int* __restrict__ active, const int* __restrict__ n_active, int B,
                                                      int HW, int K, float* __restrict__ next_input, float t_next) {
-  if (philox_state) { seed = philox_state[0]; offset += philox_state[1]; }     // (a captured launch: see psample_kernel)
+  philox_base(philox_state, seed, offset);
   const int lane = threadIdx.x & 63;
   // active-set form: logits hold one slot per ACTIVE image; noise, x0, x_t, unmasked and the outputs stay indexed by image
-  const int Bn = active ? (*n_active < B ? *n_active : B) : B;
+  const int Bn = spk_active_count(active, n_active, B);
   const long long npos = (long long)Bn * HW;
   const float inv_t = 1.0f / (float)t;
   for (long long ps = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); ps < npos; ps += (long long)gridDim.x * 4) {
@@ -45,10 +45,7 @@ __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ l
     const long long p = active ? (long long)active[b] * HW + hw : ps;
     const float u = reveal_u(u_in, seed, offset, p, K);
     if (!((u < inv_t) && !unmasked[p])) {                           // (wave-uniform)
-      if (next_input && lane == 0) {                                // the next step's denoiser input: this position keeps its token
-        next_input[((long long)b * 2 + 0) * HW + hw] = (float)x_t[p];
-        next_input[((long long)b * 2 + 1) * HW + hw] = t_next;
-      }
+      if (next_input && lane == 0) write_next_input(next_input, b, hw, HW, (float)x_t[p], t_next);   // keeps its token
       continue;
     }
     const float temp = spk_temp_of<PT>(temp_arg, active ? active[b] : b);
@@ -67,10 +64,7 @@ __global__ __launch_bounds__(256) void pscore_kernel(const float* __restrict__ l
       if (step_out) step_out[p] = t;
       x_t[p] = tok;
       unmasked[p] = 1;
-      if (next_input) {
-        next_input[((long long)b * 2 + 0) * HW + hw] = (float)tok;
-        next_input[((long long)b * 2 + 1) * HW + hw] = t_next;
-      }
+      if (next_input) write_next_input(next_input, b, hw, HW, (float)tok, t_next);
     }
   }
 }

@@ -1,7 +1,7 @@
 // The tail of one reverse-diffusion step of the dense sampler as ONE launch per image:
 //
 //   conv6 + mean over T   R/snn_model/vq_diffusion.py:185-187,205-206   (time-collapsed on spike counts, as den_mfma.hip)
-//   p_sample              R/snn_model/vq_diffusion.py:113-124,134-140   (the arithmetic of psample.hip, same noise draws)
+//   p_sample              R/snn_model/vq_diffusion.py:113-124,134-140   (the arithmetic of categorical_race, same noise draws)
 //   conv1 + BN + LIF of the NEXT step's input cat(x_t, t - 1)   :161-165,195-201   (the arithmetic of tinv_lif_kernel)
 //
 // One workgroup = one image, eight waves; wave w owns the 16-channel groups w, w + 8, ... of the logits (the reference's default
@@ -15,8 +15,8 @@
 // spk_common.h) and writes its S32 spikes and spike counts.  Replaces three launches of the dense reverse step
 // (conv3x3_counts_mfma_shared_kernel 33 us + psample_kernel 9 us + tinv_lif_kernel 13 us at B = 256) and the logits round trip.
 //
-// Bit-for-bit the results of those three kernels: same digit planes and fp64 recombination (one rounding), same softmax /
-// exponential-race arithmetic and Philox counters, same fp64 dot product and look-up table.
+// Bit-for-bit the results of those three kernels: same digit planes and fp64 recombination (one rounding), the softmax / exponential
+// race of categorical_race and the Philox counters of reveal_u / race_q (psample_common.h), same fp64 dot product and look-up table.
 #include "den_common.h"
 #include "psample_common.h"
 #include "../../include/spkdiff.h"
@@ -69,8 +69,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT> a) {
   const int b = blockIdx.x;                       // slot: index of the count records and of the logits
   int bi = b;                                     // image: index of tokens, unmasked and noise
   if (a.active) {
-    const int n = *a.n_active < a.B ? *a.n_active : a.B;
-    if (b >= n) return;                           // (uniform over the workgroup)
+    if (b >= spk_active_count(a.active, a.n_active, a.B)) return;   // (uniform over the workgroup)
     bi = a.active[b];
   }
   const int K = a.K, ng = a.ng;
@@ -104,16 +103,14 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT> a) {
   // ---- which positions change at this step, and the tokens as they are: one thread per position, up front (fetched row by row
   //      in the sampling loop these were seven dependent memory round trips per wave)
   unsigned long long seed = a.seed, offset = a.offset;
-  if (a.philox_state) { seed = a.philox_state[0]; offset += a.philox_state[1]; }
+  philox_base(a.philox_state, seed, offset);
   const float inv_t = 1.0f / (float)a.t;
   const float temp = spk_temp_of<PT>(a.temp, bi);  // (per image: requested here, read by the sampling after the K loop)
   if (tid < HW) {
     const long long pi = (long long)bi * HW + tid;
     const uint8_t um = a.unmasked[pi];
     const long long tk = a.x_t[pi];
-    float u;
-    if (a.u_in) u = a.u_in[pi];
-    else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)pi * (unsigned long long)K, 0u, r); u = u01_open_right(r[0]); }
+    const float u = reveal_u(a.u_in, seed, offset, pi, K);
     s_chg[tid] = ((u < inv_t) && !um) ? 1 : 0;
     s_tok[tid] = (float)tk;
   }
@@ -228,6 +225,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT> a) {
     if (!s_chg[p]) continue;                                            // (wave-uniform; s_tok[p] holds the token it keeps)
     // (classes k >= K -- the zero-padded output channels of conv6 and the lanes beyond them -- are masked exactly as
     //  psample_kernel masks them: -inf logits, zero terms)
+    // (categorical_race<NJ> of psample_common.h, the definition, written out: the call made this launch slower, profiles/token_update_once_ab.txt)
     float l[NJ], e[NJ];
     float mx = -INFINITY;
 #pragma unroll
@@ -251,15 +249,12 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT> a) {
     for (int j = 0; j < NJ; ++j) { e[j] = (lane + 64 * j < K) ? expf(l[j] - mx2) : 0.f; se2 += e[j]; }
     se2 = wave_sum(se2);
     float best = -INFINITY;
-    int besti = 0;                                 // (no comparable ratio -- NaN logit, all -inf: token 0, as psample_kernel)
+    int besti = 0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int k = lane + 64 * j;
       if (k < K) {
-        float q;
-        if (a.q_in) q = a.q_in[pi * K + k];
-        else { uint32_t r[4]; philox4x32(seed, offset + (unsigned long long)(pi * K + k), 1u, r); q = -logf(u01_open_left(r[0])); }
-        const float ratio = (e[j] / se2) / q;
+        const float ratio = (e[j] / se2) / race_q(a.q_in, seed, offset, pi, K, k);
         if (ratio > best) { best = ratio; besti = k; }
       }
     }

@@ -1919,6 +1919,47 @@ def _temp_arg(temp, B, what):
     return temp, None
 
 
+def _token_state(x_t, unmasked, n, what):
+    """The state a token update writes in place: contiguous device tensors of ``n`` entries (``what``: the messages' description)."""
+    if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
+        raise ValueError(f"x_t must be a contiguous int64 device tensor {what}")
+    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_cuda or not unmasked.is_contiguous():
+        raise ValueError(f"unmasked must be a contiguous bool/uint8 device tensor {what}")
+    if x_t.numel() != n or unmasked.numel() != n:
+        raise ValueError("x_t / unmasked size mismatch")
+
+
+def _step_noise(u, q, philox_state, n, K):
+    """The noise arguments of a token update, each optional: u fp32 [n], q fp32 [n * K] (device), philox_state int64 [2] -> (u, q)."""
+    if u is not None:
+        u = _dev(u, "u", torch.float32)
+        if u.numel() != n:
+            raise ValueError("u must have B*HW entries")
+    if q is not None:
+        q = _dev(q, "q", torch.float32)
+        if q.numel() != n * K:
+            raise ValueError("q must have B*HW*K entries")
+    if philox_state is not None and (philox_state.dtype != torch.int64 or philox_state.numel() != 2):
+        raise ValueError("philox_state must be an int64 device tensor {seed, base offset}")
+    return u, q
+
+
+def _next_input_arg(next_input, n):
+    """The optional buffer for the next reverse step's denoiser input cat(x_t, t - 1): fp32 [B,2,h,w], contiguous."""
+    if next_input is not None:
+        next_input = _dev(next_input, "next_input", torch.float32)
+        if next_input.numel() != 2 * n or not next_input.is_contiguous():
+            raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
+    return next_input
+
+
+def _launch_by_temp(name, temp_b, temp, head, tail):
+    """Launch ``name(*head, temp, *tail)`` or, ``temp_b`` given, its ``_temps`` sibling with the vector (looked up per call)."""
+    if temp_b is not None:
+        name, temp = name + "_temps", _p(temp_b)
+    check(getattr(lib, name)(*head, temp, *tail), name)
+
+
 def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, philox_state=None,
                  next_input=None):
     """In-place update of x_t (int64) and unmasked (bool/u8) from logits [B,K,h,w].  next_input (dense form only): fp32
@@ -1927,34 +1968,15 @@ def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, off
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
+    n = B * HW
     temp_b, temp = _temp_arg(temp, x_t.numel() // HW, "psample_step")
-    if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
-        raise ValueError("x_t must be a contiguous int64 device tensor (updated in place)")
-    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_contiguous():
-        raise ValueError("unmasked must be a contiguous bool/uint8 device tensor (updated in place)")
-    if x_t.numel() != B * HW or unmasked.numel() != B * HW:
-        raise ValueError("x_t / unmasked size mismatch")
-    if u is not None:
-        u = _dev(u, "u", torch.float32)
-    if q is not None:
-        q = _dev(q, "q", torch.float32)
-        if q.numel() != B * HW * K:
-            raise ValueError("q must have B*HW*K entries")
-    if philox_state is not None and (philox_state.dtype != torch.int64 or philox_state.numel() != 2):
-        raise ValueError("philox_state must be an int64 device tensor {seed, base offset}")
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
     act, nact = (None, None) if ACTIVE is None else ACTIVE
-    if next_input is not None:
-        next_input = _dev(next_input, "next_input", torch.float32)
-        if next_input.numel() != B * 2 * HW or not next_input.is_contiguous():
-            raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
-    if temp_b is not None:
-        check(lib.spk_psample_step_temps(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), _p(q), int(seed),
-                                         int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
-                                         _stream(logits)), "spk_psample_step_temps")
-        return x_t, unmasked
-    check(lib.spk_psample_step(_p(logits), _p(x_t), _p(unmasked), int(t), temp, _p(u), _p(q), int(seed),
-                               int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
-                               _stream(logits)), "spk_psample_step")
+    next_input = _next_input_arg(next_input, n)
+    _launch_by_temp("spk_psample_step", temp_b, temp, (_p(logits), _p(x_t), _p(unmasked), int(t)),
+                    (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
+                     _stream(logits)))
     return x_t, unmasked
 
 
@@ -1971,35 +1993,19 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
     n = B * HW
     temp_b, temp = _temp_arg(temp, B, "pscore_step")
     x0 = _dev(x0, "x0", torch.int64)
-    if x_t.dtype != torch.int64 or not x_t.is_cuda or not x_t.is_contiguous():
-        raise ValueError("x_t must be a contiguous int64 device tensor (updated in place)")
-    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_cuda or not unmasked.is_contiguous():
-        raise ValueError("unmasked must be a contiguous bool/uint8 device tensor (updated in place)")
+    _token_state(x_t, unmasked, n, "(updated in place)")
     if not isinstance(logp, torch.Tensor) or logp.dtype != torch.float64 or not logp.is_cuda or not logp.is_contiguous():
         raise ValueError("logp must be a contiguous fp64 device tensor (written where a position is revealed)")
     if step is not None and (step.dtype != torch.int32 or not step.is_cuda or not step.is_contiguous()):
         raise ValueError("step must be a contiguous int32 device tensor (written where a position is revealed)")
-    if x0.numel() != n or x_t.numel() != n or unmasked.numel() != n or logp.numel() != n or (step is not None and step.numel() != n):
+    if x0.numel() != n or logp.numel() != n or (step is not None and step.numel() != n):
         raise ValueError("x0 / x_t / unmasked / logp / step size mismatch: one entry per position of the logits' batch")
-    if u is not None:
-        u = _dev(u, "u", torch.float32)
-        if u.numel() != n:
-            raise ValueError("u must have B*HW entries")
-    if philox_state is not None and (philox_state.dtype != torch.int64 or philox_state.numel() != 2):
-        raise ValueError("philox_state must be an int64 device tensor {seed, base offset}")
+    u, _ = _step_noise(u, None, philox_state, n, K)
     act, nact = (None, None) if ACTIVE is None else ACTIVE
-    if next_input is not None:
-        next_input = _dev(next_input, "next_input", torch.float32)
-        if next_input.numel() != 2 * n or not next_input.is_contiguous():
-            raise ValueError("next_input must be a contiguous fp32 [B,2,h,w] tensor")
-    if temp_b is not None:
-        check(lib.spk_pscore_step_temps(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), int(seed), int(offset),
-                                        _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact), _p(next_input),
-                                        _stream(logits)), "spk_pscore_step_temps")
-        return logp, step
-    check(lib.spk_pscore_step(_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t), temp, _p(u), int(seed), int(offset),
-                              _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact), _p(next_input),
-                              _stream(logits)), "spk_pscore_step")
+    next_input = _next_input_arg(next_input, n)
+    _launch_by_temp("spk_pscore_step", temp_b, temp, (_p(logits), _p(x0), _p(x_t), _p(unmasked), int(t)),
+                    (_p(u), int(seed), int(offset), _p(philox_state), _p(logp), _p(step), B, HW, K, _p(act), _p(nact),
+                     _p(next_input), _stream(logits)))
     return logp, step
 
 
@@ -2014,18 +2020,11 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     cnt5 = _dev(cnt5, "cnt5", torch.uint8)
     cnt1 = _dev(cnt1, "cnt1", torch.uint8)
     B, nch5, H, W, _ = cnt5.shape
+    n = B * H * W
     temp_b, temp = _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
     wq, scale, bias_d = packed6
-    if x_t.dtype != torch.int64 or not x_t.is_contiguous() or x_t.numel() != B * H * W:
-        raise ValueError("x_t must be a contiguous int64 device tensor [B,1,h,w]")
-    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_contiguous() or unmasked.numel() != B * H * W:
-        raise ValueError("unmasked must be a contiguous bool/uint8 device tensor [B,1,h,w]")
-    if u is not None:
-        u = _dev(u, "u", torch.float32)
-    if q is not None:
-        q = _dev(q, "q", torch.float32)
-        if q.numel() != B * H * W * K:
-            raise ValueError("q must have B*HW*K entries")
+    _token_state(x_t, unmasked, n, "[B,1,h,w]")
+    u, q = _step_noise(u, q, philox_state, n, int(K))
     logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
     act, nact = (None, None) if ACTIVE is None else ACTIVE
     if act is not None and conv1 is not None:
@@ -2038,16 +2037,10 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
         w1, b1, a1, bb1 = conv1
         x1 = torch.empty((B, 2, H, W, T, 16), dtype=C4_DTYPE, device=cnt5.device)
         c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
-    if temp_b is not None:
-        check(lib.spk_den_step_tail_temps(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d),
-                                          _p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(u), _p(q), int(seed), int(offset),
-                                          _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W, int(K),
-                                          _p(act), _p(nact), _stream(cnt5)), "spk_den_step_tail_temps")
-        return (None if x1 is None else (x1, c1o)), logits
-    check(lib.spk_den_step_tail(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
-                                _p(x_t), _p(unmasked), int(t), temp, _p(u), _p(q), int(seed), int(offset),
-                                _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W, int(K),
-                                _p(act), _p(nact), _stream(cnt5)), "spk_den_step_tail")
+    _launch_by_temp("spk_den_step_tail", temp_b, temp, (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale),
+                                                        _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t)),
+                    (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T),
+                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)))
     return (None if x1 is None else (x1, c1o)), logits
 
 

@@ -823,3 +823,66 @@ def test_step_tail_rows_without_a_comparable_ratio(dev, K, L, what):
     ops.psample_step(lg, xb, unb, 1, 1.0, seed=5, offset=STEP)
     assert torch.equal(xb, xa) and torch.equal(unb, una)
     parity(f"degenerate_rows_step_tail_{what}_K{K}", tokens_out_of_range=0, positions_changed=int((~un0).sum()))
+
+
+# =============================================================================================== i. what the wrappers refuse
+@pytest.mark.parametrize("wrapper", ["psample_step", "pscore_step", "den_step_tail"])
+def test_token_update_wrappers_refuse_the_same_bad_arguments(dev, wrapper):
+    """ops.psample_step, ops.pscore_step and ops.den_step_tail check the token state, the noise and next_input through the same
+    helpers: a wrong dtype, a non-contiguous or host tensor, a short u / q / next_input, a philox_state that is not two int64
+    words -- each raises ValueError before any launch (x_t / unmasked as they were; t = 1 on an all-masked state, so a launch
+    would reveal every position).  Every short tensor is a slice of a full-size buffer and the host mask is pinned, so a wrapper
+    that let one through would still read inside an allocation."""
+    B, L, K = 2, 7, 17
+    HW = L * L
+    n = B * HW
+    g = torch.Generator().manual_seed(17)
+
+    def zeros(count, dtype):
+        return torch.zeros(count, dtype=dtype, device=dev)
+    good = dict(x_t=torch.full((B, 1, L, L), K, dtype=torch.int64, device=dev), unmasked=zeros(n, torch.bool).reshape(B, 1, L, L),
+                u=torch.rand(n, generator=g).to(dev), q=(torch.rand(n * K, generator=g) + 0.1).to(dev),
+                philox_state=zeros(2, torch.int64), next_input=zeros(2 * n, torch.float32).reshape(B, 2, L, L))
+    bad = {
+        "x_t int32": dict(x_t=torch.full((2 * n,), K, dtype=torch.int32, device=dev)[:n].reshape(B, 1, L, L)),
+        "x_t non-contiguous": dict(x_t=torch.full((B, 1, L, 2 * L), K, dtype=torch.int64, device=dev)[..., ::2]),
+        "unmasked float32": dict(unmasked=zeros(n, torch.float32).reshape(B, 1, L, L)),
+        "unmasked on the CPU": dict(unmasked=torch.zeros((B, 1, L, L), dtype=torch.bool).pin_memory()),
+        "u short": dict(u=good["u"][:n - 1]),
+        "q short": dict(q=good["q"][:n * K - 1]),
+        "philox_state int32": dict(philox_state=zeros(4, torch.int32)[:2]),
+        "philox_state three words": dict(philox_state=zeros(3, torch.int64)),
+        "next_input short": dict(next_input=zeros(2 * n, torch.float32)[:2 * n - 1]),
+    }
+    takes = {"psample_step": {"q", "next_input"}, "pscore_step": {"next_input"}, "den_step_tail": {"q"}}[wrapper]
+    logits = torch.randn(B, K, L, L, generator=g).to(dev)
+    x0, logp = zeros(n, torch.int64), zeros(n, torch.float64)
+    # (den_step_tail: count records and packed conv6 weights of the right sizes -- two 16-channel groups -- and nothing else)
+    cnt5, cnt1 = zeros(B * 8 * HW * 32, torch.uint8).reshape(B, 8, L, L, 32), zeros(B * 2 * HW * 32, torch.uint8).reshape(B, 2, L, L, 32)
+    packed6 = (zeros(2 * 10 * 18432, torch.int8), zeros(32, torch.float64), zeros(32, torch.float64))
+
+    def call(a):
+        opt = {k: a[k] for k in ("q", "next_input") if k in takes}
+        if wrapper == "psample_step":
+            return ops.psample_step(logits, a["x_t"], a["unmasked"], 1, 1.0, u=a["u"], philox_state=a["philox_state"], **opt)
+        if wrapper == "pscore_step":
+            return ops.pscore_step(logits, x0, a["x_t"], a["unmasked"], 1, 1.0, logp, u=a["u"], philox_state=a["philox_state"], **opt)
+        return ops.den_step_tail(cnt5, cnt1, packed6, a["x_t"], a["unmasked"], 1, 1.0, T=16, K=K, u=a["u"],
+                                 philox_state=a["philox_state"], **opt)
+    wrong = []
+    for name, change in bad.items():
+        if (name.startswith("q ") and "q" not in takes) or (name.startswith("next_input") and "next_input" not in takes):
+            continue
+        a = dict(good, **change)
+        before = a["x_t"].clone(), a["unmasked"].clone()
+        try:
+            call(a)
+            wrong.append(f"{name}: accepted")
+        except ValueError:
+            pass
+        except Exception as e:  # noqa: BLE001  (the wrong exception type is what is reported)
+            wrong.append(f"{name}: {type(e).__name__} instead of ValueError")
+        torch.cuda.synchronize()
+        if not (torch.equal(a["x_t"], before[0]) and torch.equal(a["unmasked"], before[1])):
+            wrong.append(f"{name}: x_t / unmasked written")
+    assert not wrong, f"{wrapper}: {wrong}"
