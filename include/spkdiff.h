@@ -149,15 +149,10 @@ int spk_bn_lif_train_fwd_c4(const float* y, const float* gamma, const float* bet
  * for conv2..conv5 of DummyModel, R/snn_model/vq_diffusion.py:166-184): the exact fp6 x fp4 MFMA convolution of
  * spk_den_conv3x3_mfma_fp6 with the pre-activations (conv + bias, correctly rounded fp32 of the exact dot product) written
  * out instead of the fused BN + LIF -- batch-statistics BN needs all of them first.  in_c4 as for the inference kernel;
- * pre_nhwc fp32 channels-last [T][B][H*W][Cout].  spk_spikes_nhwc_to_fp4 packs channels-last fp32 spikes [T][B][HW][C]
- * (the output of spk_bn_lif_train_fwd) into the C4 input layout. */
+ * pre_nhwc fp32 channels-last [T][B][H*W][Cout].  spk_spikes_nhwc_to_fp4 (spike layouts, below) packs the output of
+ * spk_bn_lif_train_fwd into the C4 input layout. */
 int spk_den_conv3x3_fp6_raw(const uint8_t* in_c4, int nch, const uint8_t* wq, const double* scale, const double* bias_d,
                             float* pre_nhwc, int T, int B, int H, int W, int Cout, spk_stream_t stream);
-int spk_spikes_nhwc_to_fp4(const float* spikes_nhwc, uint8_t* out_c4, int T, int B, int C, int HW, spk_stream_t stream);
-/* The same conversion with the per-neuron spike counts over T as a by-product: counts_nhwc fp32 [B][HW][C] (channels-last) -- what
- * the last layer's weight gradient is convolved with in the training step (its time mean hands every step the same gradient). */
-int spk_spikes_nhwc_to_fp4_counts(const float* spikes_nhwc, uint8_t* out_c4, float* counts_nhwc, int T, int B, int C, int HW,
-                                  spk_stream_t stream);
 
 /* Masked cross-entropy of AbsorbingDiffusion._train_loss (R/snn_model/vq_diffusion.py:85-88: F.cross_entropy with
  * ignore_index=-1, reduction='none') and its gradient in one pass.  logits / dlogits [B,K,HW] fp32; target [B,HW] fp32
@@ -171,13 +166,37 @@ int spk_masked_ce(const float* logits, const float* target, const float* coef, f
  * backward != 0 runs the adjoint instead (in = dL/dsyn, out = dL/dx). */
 int spk_psp(const float* in, float* out, int T, long long N, float tau_s, int backward, spk_stream_t stream);
 
-/* ---- layout converters --------------------------------------------------------------------------------------- */
-/* chunk = C gives plain PTC [B,HW,T,C]; chunk = 32 gives the channel-chunked "CPTC" [B,C/32,HW,T,32] the MFMA
- * kernel reads (one contiguous slab per image and 32-channel K chunk). */
+/* ---- spike layouts (csrc/layouts.hip) ------------------------------------------------------------------------ */
+/* The interface tensor is fp32 [T,B,C,HW] (1.0 = spike).  Between layers a spike tensor is stored in one of four record forms, a
+ * record being the channels of one (position, step) that lie together in memory:
+ *   PTC   u8           [B][HW][T][C]               one byte per channel (0 / 1), all C channels in one record
+ *   CPTC  u8           [B][C/chunk][HW][T][chunk]  the same bytes in records of `chunk` channels (32: the K chunk of the int8 MFMA
+ *                                                  kernel, one contiguous slab per image and chunk)
+ *   C4    e2m1 nibbles [B][C/64][HW][T][32 B]      64 channels per record
+ *   S32   e2m1 nibbles [B][C/32][HW][T][16 B]      32 channels per record
+ * In a nibble record channel k lies in nibble k (even channel = low nibble); a spike is 0x2, the e2m1 code of 1.0, silence 0x0.
+ * C4 is read by spk_den_conv3x3_mfma_fp6 / spk_den_conv3x3_fp6_raw, S32 by spk_den_conv3x3_mfma_fp6v2 and spk_vae_fp6_fwd; the fused
+ * kernels write all four themselves (chunk_out of spk_conv_fused_fwd: 0, a chunk, SPK_CHUNK_C4, SPK_CHUNK_S32).  The entry points
+ * below convert at module boundaries and in tests.
+ * fp32 <-> PTC (chunk = C) / CPTC (chunk < C); SPK_ERR_ARG unless C % chunk == 0: */
 int spk_spikes_to_ptc(const float* spikes_tbchw, uint8_t* out_bhwtc, int T, int B, int C, int HW, int chunk,
                       spk_stream_t stream);
 int spk_ptc_to_spikes(const uint8_t* in_bhwtc, float* spikes_tbchw, int T, int B, int C, int HW, int chunk,
                       spk_stream_t stream);
+/* fp32 <-> C4 (C % 64 == 0) and S32 (C % 32 == 0; SPK_ERR_UNSUPPORTED otherwise): */
+int spk_spikes_to_fp4(const float* spikes, uint8_t* out_c4, int T, int B, int C, int HW, spk_stream_t stream);
+int spk_fp4_to_spikes(const uint8_t* in_c4, float* spikes, int T, int B, int C, int HW, spk_stream_t stream);
+int spk_spikes_to_s32(const float* spikes, uint8_t* out_s32, int T, int B, int C, int HW, spk_stream_t stream);
+int spk_s32_to_spikes(const uint8_t* in_s32, float* spikes, int T, int B, int C, int HW, spk_stream_t stream);
+/* channels-last fp32 spikes [T][B][HW][C] (the output of spk_bn_lif_train_fwd) -> C4 (C % 64 == 0), the training forward's
+ * conversion; _counts: with the per-neuron spike counts over T as a by-product, counts_nhwc fp32 [B][HW][C] (channels-last) -- what
+ * the last layer's weight gradient is convolved with in the training step (its time mean hands every step the same gradient). */
+int spk_spikes_nhwc_to_fp4(const float* spikes_nhwc, uint8_t* out_c4, int T, int B, int C, int HW, spk_stream_t stream);
+int spk_spikes_nhwc_to_fp4_counts(const float* spikes_nhwc, uint8_t* out_c4, float* counts_nhwc, int T, int B, int C, int HW,
+                                  spk_stream_t stream);
+/* u8 PTC -> S32 [B][ceil(C/32)][HW][16][16 B], zero nibbles in the channels beyond C (any C; T = 16 only: SPK_ERR_UNSUPPORTED
+ * otherwise): what the decoder's spike generator hands spk_vae_fp6_fwd. */
+int spk_ptc_to_s32(const uint8_t* in_ptc, uint8_t* out_s32, int T, int B, int HW, int C, spk_stream_t stream);
 
 /* ---- fused (Conv|ConvT) [+BN+LIF] --------------------------------------------------------------------------- */
 int spk_conv_out_size(int in, int k, int stride, int pad, int transposed, int out_pad);
@@ -313,12 +332,6 @@ int spk_den_conv3x3_mfma_fp6v2_listed(const uint8_t* in_s32, int nch, const uint
                                       const float* bn_b, uint8_t* out_s32, uint8_t* out_counts, unsigned* flag_words, int T,
                                       int B, int H, int W, int Cout, const int* n_dyn, const uint8_t* need, int need_radii,
                                       int radius, int flag_cap, spk_stream_t stream);
-/* fp32 spikes [T,B,C,HW] <-> S32 (C % 32 == 0): module boundaries and tests. */
-int spk_spikes_to_s32(const float* spikes, uint8_t* out_s32, int T, int B, int C, int HW, spk_stream_t stream);
-int spk_s32_to_spikes(const uint8_t* in_s32, float* spikes, int T, int B, int C, int HW, spk_stream_t stream);
-/* fp32 spikes [T,B,C,HW] <-> C4 (C % 64 == 0): module boundaries and tests. */
-int spk_spikes_to_fp4(const float* spikes, uint8_t* out_c4, int T, int B, int C, int HW, spk_stream_t stream);
-int spk_fp4_to_spikes(const uint8_t* in_c4, float* spikes, int T, int B, int C, int HW, spk_stream_t stream);
 
 /* ---- spiking VQ-VAE layers on the matrix cores ------------------------------------------------------------------- */
 /* Bytes of the packed int8 digit planes of a k x k (transposed) conv: [ceil(Cout/16)][ceil(Cin/32)][k*k][2][32][32]. */
@@ -373,7 +386,6 @@ long long spk_vae_fp6_packed_bytes(int Cout, int Cin);
 int spk_vae_fp6_pack(const float* w, const float* bias, uint8_t* wq, double* scale, double* bias_d, int* qtab, int Cout, int Cin,
                      int transposed, spk_stream_t stream);
 long long spk_vae_fp6_flag_words(int B, int Cout, int Ho, int Wo);
-int spk_ptc_to_s32(const uint8_t* in_ptc, uint8_t* out_s32, int T, int B, int HW, int C, spk_stream_t stream);
 /* The decoder's front end by token (R/main.py:388-392, R/snn_model/vae_model.py:54-56,66-71: embedding look-up, repeat(T), the 'poisson'
  * spike generator = 1x1 Conv2d + BN + LIF from the reset state): the generator's input at a position is one of the K codebook rows, so
  * its spike train is one of K patterns per output channel.  One call = a K-row pattern table (the arithmetic of spk_conv_fused_fwd's

@@ -545,11 +545,7 @@ __global__ __launch_bounds__(256) void spikegen_expand_kernel(const long long* _
   }
 }
 
-inline int grid_for(long long work_items) {
-  long long g = (work_items + 255) / 256;
-  const long long cap = 256 * 8 * 8;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int GRID_CAP = 256 * 8 * 8;
 
 // RAW output of a spike-input layer with few output channels, one thread per (output position, STEP): the module-API form of the
 // decoder's read-out layer (R/main.py:397: `pred = model.decoder(quantized)` returns the per-step convolution [T,B,C,28,28], memout and
@@ -620,7 +616,7 @@ __global__ __launch_bounds__(256) void conv_raw_steps_kernel(FusedArgs a) {
 template <int INKIND, bool TR>
 int launch_mode(const FusedArgs& a, int mode, hipStream_t stream) {
   const long long total = (long long)a.B * a.Ho * a.Wo * a.Cout;
-  dim3 g(grid_for(total)), blk(256);
+  dim3 g(spk_grid(total, GRID_CAP)), blk(256);
   switch (mode) {
     case SPK_MODE_LIF: hipLaunchKernelGGL((conv_fused_kernel<INKIND, TR, SPK_MODE_LIF>), g, blk, 0, stream, a); break;
     case SPK_MODE_RAW: hipLaunchKernelGGL((conv_fused_kernel<INKIND, TR, SPK_MODE_RAW>), g, blk, 0, stream, a); break;
@@ -661,7 +657,7 @@ extern "C" int spk_conv2d_fwd(const float* x, const float* w, const float* bias,
   if (!x || !w || !y || M <= 0 || Cin <= 0 || Cout <= 0 || k <= 0 || stride <= 0 || pad < 0) return SPK_ERR_ARG;
   int Ho = spk_conv_out_size(H, k, stride, pad, 0, 0), Wo = spk_conv_out_size(W, k, stride, pad, 0, 0);
   if (Ho <= 0 || Wo <= 0) return SPK_ERR_ARG;
-  hipLaunchKernelGGL(conv_nchw_kernel<false>, dim3(grid_for(M * Cout * Ho * Wo)), dim3(256), 0, stream, x, w, bias, y,
+  hipLaunchKernelGGL(conv_nchw_kernel<false>, dim3(spk_grid(M * Cout * Ho * Wo, GRID_CAP)), dim3(256), 0, stream, x, w, bias, y,
                      M, Cin, H, W, Cout, Ho, Wo, k, stride, pad);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
@@ -674,7 +670,7 @@ extern "C" int spk_conv_transpose2d_fwd(const float* x, const float* w, const fl
     return SPK_ERR_ARG;
   int Ho = spk_conv_out_size(H, k, stride, pad, 1, out_pad), Wo = spk_conv_out_size(W, k, stride, pad, 1, out_pad);
   if (Ho <= 0 || Wo <= 0) return SPK_ERR_ARG;
-  hipLaunchKernelGGL(conv_nchw_kernel<true>, dim3(grid_for(M * Cout * Ho * Wo)), dim3(256), 0, stream, x, w, bias, y,
+  hipLaunchKernelGGL(conv_nchw_kernel<true>, dim3(spk_grid(M * Cout * Ho * Wo, GRID_CAP)), dim3(256), 0, stream, x, w, bias, y,
                      M, Cin, H, W, Cout, Ho, Wo, k, stride, pad);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
@@ -742,7 +738,7 @@ extern "C" int spk_conv_fused_fwd(const void* in0, const uint8_t* in1, int C0, i
   if (in_kind == SPK_IN_PTC && mode == SPK_MODE_RAW && Cout <= 4 && Cout != 2 && C1 == 0 && chunk0 == C0 && (C0 % 16) == 0 && !n_dyn_or_null) {
     // few output channels, per-step output (the decoder's read-out layer through the module API): one thread per (position, step)
     const long long total = (long long)B * a.Ho * a.Wo * T;
-    const dim3 g(grid_for(total)), blk(256);
+    const dim3 g(spk_grid(total, GRID_CAP)), blk(256);
 #define SPK_RAW_STEPS(TR_, CO_) hipLaunchKernelGGL((conv_raw_steps_kernel<TR_, CO_>), g, blk, 0, stream, a)
     if (transposed) { if (Cout == 1) SPK_RAW_STEPS(true, 1); else if (Cout == 3) SPK_RAW_STEPS(true, 3); else SPK_RAW_STEPS(true, 4); }
     else            { if (Cout == 1) SPK_RAW_STEPS(false, 1); else if (Cout == 3) SPK_RAW_STEPS(false, 3); else SPK_RAW_STEPS(false, 4); }

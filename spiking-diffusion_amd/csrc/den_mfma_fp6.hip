@@ -556,34 +556,6 @@ __device__ __forceinline__ void pack_fp6_channel(const float* __restrict__ w, co
   }
 }
 
-// fp32 spikes [T,B,C,HW] <-> nibble-packed C4 [B][C/64][HW][T][32] (tests, module boundaries)
-__global__ void spikes_to_fp4_kernel(const float* __restrict__ s, uint8_t* __restrict__ o, int T, int B, int C, int HW) {
-  const long long total = (long long)B * (C / 64) * HW * T * 32;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int byte = (int)(i & 31);
-    long long r = i >> 5;
-    const int t = (int)(r % T); r /= T;
-    const int p = (int)(r % HW); r /= HW;
-    const int cc = (int)(r % (C / 64));
-    const int b = (int)(r / (C / 64));
-    const int c0 = cc * 64 + 2 * byte;
-    const float s0 = s[(((long long)t * B + b) * C + c0) * HW + p], s1 = s[(((long long)t * B + b) * C + c0 + 1) * HW + p];
-    o[i] = (uint8_t)((s0 != 0.f ? 0x02 : 0) | (s1 != 0.f ? 0x20 : 0));
-  }
-}
-__global__ void fp4_to_spikes_kernel(const uint8_t* __restrict__ q, float* __restrict__ s, int T, int B, int C, int HW) {
-  const long long total = (long long)T * B * C * HW;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int p = (int)(i % HW);
-    long long r = i / HW;
-    const int c = (int)(r % C); r /= C;
-    const int b = (int)(r % B);
-    const int t = (int)(r / B);
-    const uint8_t by = q[((((long long)b * (C / 64) + c / 64) * HW + p) * T + t) * 32 + (c % 64) / 2];
-    s[i] = ((by >> (4 * (c & 1))) & 0xf) ? 1.0f : 0.0f;
-  }
-}
-
 __global__ __launch_bounds__(256) void pack_fp6_kernel(const float* __restrict__ w, const float* __restrict__ bias,
                                                        uint8_t* __restrict__ wq, double* __restrict__ scale,
                                                        double* __restrict__ bias_d, int Cout, int Cin, int w_cl) {
@@ -745,93 +717,4 @@ extern "C" int spk_den_conv3x3_fp6_raw(const uint8_t* in_c4, int nch, const uint
     return SPK_ERR_ARG;
   return launch_fp6<true>(in_c4, nch, wq, scale, bias_d, nullptr, nullptr, nullptr, nullptr, nullptr, pre_nhwc, nullptr, T, B,
                           H, W, Cout, stream);
-}
-
-namespace {
-// channels-last fp32 spikes [T][B][HW][C] -> C4: one thread = 4 consecutive channels of one (t, b, hw) = one 16-bit word
-__global__ void spikes_nhwc_to_fp4_kernel(const float* __restrict__ s, uint8_t* __restrict__ o, int T, int B, int C, int HW) {
-  const long long total = (long long)T * B * HW * (C / 4);
-  const int Q = C / 4;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int q = (int)(i % Q);
-    const long long row = i / Q;                       // (t * B + b) * HW + hw
-    const int hw = (int)(row % HW);
-    const long long tb = row / HW;
-    const int b = (int)(tb % B), t = (int)(tb / B);
-    const float4 v = reinterpret_cast<const float4*>(s)[i];
-    const unsigned w = spk_e2m1_nibbles4(v.x, v.y, v.z, v.w);
-    const int c = q * 4;
-    uint8_t* dst = o + ((((long long)b * (C >> 6) + (c >> 6)) * HW + hw) * T + t) * 32 + ((c & 63) >> 1);
-    *reinterpret_cast<uint16_t*>(dst) = (uint16_t)w;
-  }
-}
-}  // namespace
-
-namespace {
-// the same conversion with the per-neuron spike COUNTS over T as a by-product (fp32 [B][HW][C], channels-last): one thread = 4
-// consecutive channels of one (b, hw) for all T steps.  The training step's last layer convolves its weight gradient with these
-// counts (ops.SpikeConvMeanTrainFunction); they were a separate reduction over the [T,B,320,7,7] spike tensor (32 us at B = 32).
-__global__ void spikes_nhwc_to_fp4_counts_kernel(const float* __restrict__ s, uint8_t* __restrict__ o, float* __restrict__ cnt,
-                                                 int T, int B, int C, int HW) {
-  const int Q = C / 4;
-  const long long total = (long long)B * HW * Q, plane = (long long)B * HW * Q;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int q = (int)(i % Q);
-    const long long row = i / Q;                       // b * HW + hw
-    const int hw = (int)(row % HW), b = (int)(row / HW);
-    const int c = q * 4;
-    uint8_t* dst = o + (((long long)b * (C >> 6) + (c >> 6)) * HW + hw) * T * 32 + ((c & 63) >> 1);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = 0; t < T; ++t) {
-      const float4 v = reinterpret_cast<const float4*>(s)[t * plane + i];
-      const unsigned w = spk_e2m1_nibbles4(v.x, v.y, v.z, v.w);
-      acc.x += v.x != 0.f ? 1.f : 0.f; acc.y += v.y != 0.f ? 1.f : 0.f;
-      acc.z += v.z != 0.f ? 1.f : 0.f; acc.w += v.w != 0.f ? 1.f : 0.f;
-      *reinterpret_cast<uint16_t*>(dst + t * 32) = (uint16_t)w;
-    }
-    reinterpret_cast<float4*>(cnt)[i] = acc;
-  }
-}
-}  // namespace
-
-extern "C" int spk_spikes_nhwc_to_fp4_counts(const float* spikes_nhwc, uint8_t* out_c4, float* counts_nhwc, int T, int B, int C,
-                                             int HW, hipStream_t stream) {
-  if (!spikes_nhwc || !out_c4 || !counts_nhwc || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 64) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)B * HW * (C / 4);
-  hipLaunchKernelGGL(spikes_nhwc_to_fp4_counts_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)),
-                     dim3(256), 0, stream, spikes_nhwc, out_c4, counts_nhwc, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_spikes_nhwc_to_fp4(const float* spikes_nhwc, uint8_t* out_c4, int T, int B, int C, int HW,
-                                      hipStream_t stream) {
-  if (!spikes_nhwc || !out_c4 || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 64) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)T * B * HW * (C / 4);
-  hipLaunchKernelGGL(spikes_nhwc_to_fp4_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)),
-                     dim3(256), 0, stream, spikes_nhwc, out_c4, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_spikes_to_fp4(const float* spikes, uint8_t* out_c4, int T, int B, int C, int HW, hipStream_t stream) {
-  if (!spikes || !out_c4 || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 64) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)B * (C / 64) * HW * T * 32;
-  hipLaunchKernelGGL(spikes_to_fp4_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)), dim3(256),
-                     0, stream, spikes, out_c4, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_fp4_to_spikes(const uint8_t* in_c4, float* spikes, int T, int B, int C, int HW, hipStream_t stream) {
-  if (!spikes || !in_c4 || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 64) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)T * B * C * HW;
-  hipLaunchKernelGGL(fp4_to_spikes_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)), dim3(256),
-                     0, stream, in_c4, spikes, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
 }

@@ -1336,34 +1336,6 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
   }
 }
 
-// fp32 spikes [T,B,C,HW] <-> nibble-packed S32 [B][C/32][HW][T][16] (tests, module boundaries)
-__global__ void spikes_to_s32_kernel(const float* __restrict__ s, uint8_t* __restrict__ o, int T, int B, int C, int HW) {
-  const long long total = (long long)B * (C / 32) * HW * T * 16;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int byte = (int)(i & 15);
-    long long r = i >> 4;
-    const int t = (int)(r % T); r /= T;
-    const int p = (int)(r % HW); r /= HW;
-    const int cc = (int)(r % (C / 32));
-    const int b = (int)(r / (C / 32));
-    const int c0 = cc * 32 + 2 * byte;
-    const float s0 = s[(((long long)t * B + b) * C + c0) * HW + p], s1 = s[(((long long)t * B + b) * C + c0 + 1) * HW + p];
-    o[i] = (uint8_t)((s0 != 0.f ? 0x02 : 0) | (s1 != 0.f ? 0x20 : 0));
-  }
-}
-__global__ void s32_to_spikes_kernel(const uint8_t* __restrict__ q, float* __restrict__ s, int T, int B, int C, int HW) {
-  const long long total = (long long)T * B * C * HW;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int p = (int)(i % HW);
-    long long r = i / HW;
-    const int c = (int)(r % C); r /= C;
-    const int b = (int)(r % B);
-    const int t = (int)(r / B);
-    const uint8_t by = q[((((long long)b * (C / 32) + c / 32) * HW + p) * T + t) * 16 + (c % 32) / 2];
-    s[i] = ((by >> (4 * (c & 1))) & 0xf) ? 1.0f : 0.0f;
-  }
-}
-
 }  // namespace
 
 extern "C" long long spk_den_packed_weight_fp6v2_bytes(int Cout, int Cin) {
@@ -1523,24 +1495,4 @@ extern "C" int spk_den_conv3x3_mfma_fp6v2_listed(const uint8_t* in_s32, int nch,
   if (!need || !n_dyn || need_radii <= 0 || need_radii > 8 || radius < 1 || radius > need_radii) return SPK_ERR_ARG;
   return fp6v2_launch(in_s32, nch, wq, scale, bias_d, wl1, qtab, bn_a, bn_b, out_s32, out_counts, flag_words, T, B, H, W, Cout,
                       n_dyn, need, need_radii, radius - 1, flag_cap, 1, stream);
-}
-
-extern "C" int spk_spikes_to_s32(const float* spikes, uint8_t* out_s32, int T, int B, int C, int HW, hipStream_t stream) {
-  if (!spikes || !out_s32 || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 32) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)B * (C / 32) * HW * T * 16;
-  hipLaunchKernelGGL(spikes_to_s32_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)), dim3(256),
-                     0, stream, spikes, out_s32, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_s32_to_spikes(const uint8_t* in_s32, float* spikes, int T, int B, int C, int HW, hipStream_t stream) {
-  if (!spikes || !in_s32 || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SPK_ERR_ARG;
-  if (C % 32) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)T * B * C * HW;
-  hipLaunchKernelGGL(s32_to_spikes_kernel, dim3(spk_blocks(total, 256) > 65536 ? 65536 : spk_blocks(total, 256)), dim3(256),
-                     0, stream, in_s32, spikes, T, B, C, HW);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
 }

@@ -223,47 +223,7 @@ __global__ __launch_bounds__(256) void memout_kernel(const float* __restrict__ x
   }
 }
 
-// ------------------------------------------------------------------------------------------ layout
-// fp32 spikes [T,B,C,H,W]  ->  u8 [B,H,W,T,C]   (one thread per (b, hw, t, c); reads strided, writes coalesced)
-__global__ __launch_bounds__(256) void spikes_to_ptc_kernel(const float* __restrict__ s, uint8_t* __restrict__ o,
-                                                            int T, int B, int C, int HW, int chunk) {
-  // output memory order: [B][C/chunk][HW][T][chunk]  (chunk == C: plain PTC [B][HW][T][C])
-  long long total = (long long)T * B * C * HW;
-  const int nch = C / chunk;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    int cc = (int)(i % chunk);
-    long long r = i / chunk;
-    int t = (int)(r % T); r /= T;
-    int hw = (int)(r % HW); r /= HW;
-    int c = (int)(r % nch) * chunk + cc;
-    int b = (int)(r / nch);
-    float f = s[(((long long)t * B + b) * C + c) * HW + hw];
-    o[i] = f != 0.0f ? 1 : 0;
-  }
-}
-
-// u8 [B,H,W,T,C] -> fp32 [T,B,C,H,W]   (one thread per output element)
-__global__ __launch_bounds__(256) void ptc_to_spikes_kernel(const uint8_t* __restrict__ s, float* __restrict__ o,
-                                                            int T, int B, int C, int HW, int chunk) {
-  long long total = (long long)T * B * C * HW;
-  const int nch = C / chunk;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    int hw = (int)(i % HW);
-    long long r = i / HW;
-    int c = (int)(r % C); r /= C;
-    int b = (int)(r % B);
-    int t = (int)(r / B);
-    o[i] = (float)s[((((long long)b * nch + c / chunk) * HW + hw) * T + t) * chunk + c % chunk];
-  }
-}
-
-inline int grid_for(long long work_items) {
-  long long g = (work_items + 255) / 256;
-  const long long cap = 256 * 8 * 4;    // 256 CUs x 8 blocks, x4 for tail balance; grid-stride the rest
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int LIF_GRID_CAP = 256 * 8 * 4;    // 256 CUs x 8 blocks, x4 for tail balance; grid-stride the rest
 
 inline int lif_grid(long long work_items) {
   long long g = (work_items + SPK_LIF_BLOCK - 1) / SPK_LIF_BLOCK;
@@ -282,7 +242,7 @@ extern "C" int spk_lif_fwd(const float* x_seq, float* v_inout, void* spike_out, 
   const float inv_tau = 1.0f / tau;
   if (spike_dtype == SPK_SPIKE_BITS) {
     long long words = (N + 63) / 64;
-    int grid = grid_for(words * 64);
+    int grid = spk_grid(words * 64, LIF_GRID_CAP);
     if (pow2)
       hipLaunchKernelGGL(lif_fwd_bits_kernel<false>, dim3(grid), dim3(256), 0, stream, x_seq, v_inout,
                          (unsigned long long*)spike_out, T, N, tau, inv_tau, v_threshold, v_reset);
@@ -319,7 +279,7 @@ extern "C" int spk_lif_fwd_ex(const float* x_seq, float* v_inout, float* spike_o
   int ex;
   const bool pow2 = frexpf(tau, &ex) == 0.5f;
   const float inv_tau = 1.0f / tau, keep = (float)(1.0 - 1.0 / (double)tau);
-  const int grid = grid_for(N);
+  const int grid = spk_grid(N, LIF_GRID_CAP);
 #define SPK_LIFX(SOFT, DECAY, DIV)                                                                                   \
   hipLaunchKernelGGL((lif_fwd_ex_kernel<SOFT, DECAY, DIV>), dim3(grid), dim3(256), 0, stream, x_seq, v_inout,        \
                      spike_out_f32, v_seq_out_or_null, T, N, tau, inv_tau, keep, v_threshold, v_reset)
@@ -351,9 +311,10 @@ extern "C" int spk_bn_eval_fwd(const float* x, const float* a, const float* b, f
   long long total = M * C * HW;
   const bool vec = (HW % 4 == 0) && ((((uintptr_t)x | (uintptr_t)y) % 16) == 0);
   if (vec)
-    hipLaunchKernelGGL(bn_eval_kernel<4>, dim3(grid_for(total / 4)), dim3(256), 0, stream, x, a, b, y, total, C, HW);
+    hipLaunchKernelGGL(bn_eval_kernel<4>, dim3(spk_grid(total / 4, LIF_GRID_CAP)), dim3(256), 0, stream, x, a, b, y, total, C,
+                       HW);
   else
-    hipLaunchKernelGGL(bn_eval_kernel<1>, dim3(grid_for(total)), dim3(256), 0, stream, x, a, b, y, total, C, HW);
+    hipLaunchKernelGGL(bn_eval_kernel<1>, dim3(spk_grid(total, LIF_GRID_CAP)), dim3(256), 0, stream, x, a, b, y, total, C, HW);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }
@@ -363,29 +324,9 @@ extern "C" int spk_memout_fwd(const float* x_seq, const float* coef, float* out,
   if (!x_seq || !coef || !out || T <= 0 || T > 64 || N <= 0) return SPK_ERR_ARG;
   const bool vec = (N % 4 == 0) && ((((uintptr_t)x_seq | (uintptr_t)out) % 16) == 0);
   if (vec)
-    hipLaunchKernelGGL(memout_kernel<4>, dim3(grid_for(N / 4)), dim3(256), 0, stream, x_seq, coef, out, T, N);
+    hipLaunchKernelGGL(memout_kernel<4>, dim3(spk_grid(N / 4, LIF_GRID_CAP)), dim3(256), 0, stream, x_seq, coef, out, T, N);
   else
-    hipLaunchKernelGGL(memout_kernel<1>, dim3(grid_for(N)), dim3(256), 0, stream, x_seq, coef, out, T, N);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_spikes_to_ptc(const float* spikes_tbchw, uint8_t* out_bhwtc, int T, int B, int C, int HW,
-                                 int chunk, hipStream_t stream) {
-  if (!spikes_tbchw || !out_bhwtc || T <= 0 || B <= 0 || C <= 0 || HW <= 0 || chunk <= 0 || C % chunk)
-    return SPK_ERR_ARG;
-  hipLaunchKernelGGL(spikes_to_ptc_kernel, dim3(grid_for((long long)T * B * C * HW)), dim3(256), 0, stream,
-                     spikes_tbchw, out_bhwtc, T, B, C, HW, chunk);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-
-extern "C" int spk_ptc_to_spikes(const uint8_t* in_bhwtc, float* spikes_tbchw, int T, int B, int C, int HW,
-                                 int chunk, hipStream_t stream) {
-  if (!in_bhwtc || !spikes_tbchw || T <= 0 || B <= 0 || C <= 0 || HW <= 0 || chunk <= 0 || C % chunk)
-    return SPK_ERR_ARG;
-  hipLaunchKernelGGL(ptc_to_spikes_kernel, dim3(grid_for((long long)T * B * C * HW)), dim3(256), 0, stream,
-                     in_bhwtc, spikes_tbchw, T, B, C, HW, chunk);
+    hipLaunchKernelGGL(memout_kernel<1>, dim3(spk_grid(N, LIF_GRID_CAP)), dim3(256), 0, stream, x_seq, coef, out, T, N);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }

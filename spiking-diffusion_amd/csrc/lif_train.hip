@@ -21,11 +21,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline int grid_for(long long work_items) {
-  long long g = (work_items + 255) / 256;
-  const long long cap = 256 * 8 * 8;
-  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+constexpr int GRID_CAP = 256 * 8 * 8;
 
 template <int VEC>
 __global__ __launch_bounds__(256) void lif_train_fwd_kernel(const float* __restrict__ x, const float* __restrict__ v_init,
@@ -110,11 +106,11 @@ extern "C" int spk_lif_train_fwd(const float* x_seq, const float* v_init, float*
   if (!x_seq || !v_init || !h_seq || !spike_seq || !v_out || T <= 0 || N <= 0 || !(tau > 0.f)) return SPK_ERR_ARG;
   const uintptr_t al = (uintptr_t)x_seq | (uintptr_t)v_init | (uintptr_t)h_seq | (uintptr_t)spike_seq | (uintptr_t)v_out;
   if ((N % 4 == 0) && (al % 16 == 0))
-    hipLaunchKernelGGL(lif_train_fwd_kernel<4>, dim3(grid_for(N / 4)), dim3(256), 0, stream, x_seq, v_init, h_seq, spike_seq,
-                       v_out, T, N, tau, v_threshold, v_reset);
+    hipLaunchKernelGGL(lif_train_fwd_kernel<4>, dim3(spk_grid(N / 4, GRID_CAP)), dim3(256), 0, stream, x_seq, v_init, h_seq,
+                       spike_seq, v_out, T, N, tau, v_threshold, v_reset);
   else
-    hipLaunchKernelGGL(lif_train_fwd_kernel<1>, dim3(grid_for(N)), dim3(256), 0, stream, x_seq, v_init, h_seq, spike_seq,
-                       v_out, T, N, tau, v_threshold, v_reset);
+    hipLaunchKernelGGL(lif_train_fwd_kernel<1>, dim3(spk_grid(N, GRID_CAP)), dim3(256), 0, stream, x_seq, v_init, h_seq,
+                       spike_seq, v_out, T, N, tau, v_threshold, v_reset);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }
@@ -127,7 +123,7 @@ extern "C" int spk_lif_train_bwd(const float* grad_spike_seq, const float* grad_
                        (uintptr_t)grad_v_init;
   const bool vec = (N % 4 == 0) && (al % 16 == 0);
 #define SPK_BWD(VEC, DET)                                                                                               \
-  hipLaunchKernelGGL((lif_train_bwd_kernel<VEC, DET>), dim3(grid_for((N + VEC - 1) / VEC)), dim3(256), 0, stream,         \
+  hipLaunchKernelGGL((lif_train_bwd_kernel<VEC, DET>), dim3(spk_grid((N + VEC - 1) / VEC, GRID_CAP)), dim3(256), 0, stream, \
                      grad_spike_seq, grad_v_last, h_seq, grad_x_seq, grad_v_init, T, N, tau, v_threshold, v_reset, alpha)
   if (vec) { if (detach_reset) SPK_BWD(4, true); else SPK_BWD(4, false); }
   else     { if (detach_reset) SPK_BWD(1, true); else SPK_BWD(1, false); }
@@ -185,10 +181,11 @@ __global__ __launch_bounds__(256) void psp_kernel(const float* __restrict__ in, 
 extern "C" int spk_psp(const float* in, float* out, int T, long long N, float tau_s, int backward, hipStream_t stream) {
   if (!in || !out || T <= 0 || N <= 0 || !(tau_s > 0.f)) return SPK_ERR_ARG;
   const bool vec = (N % 4 == 0) && ((((uintptr_t)in | (uintptr_t)out) % 16) == 0);
-  if (vec && backward) hipLaunchKernelGGL((psp_kernel<4, true>), dim3(grid_for(N / 4)), dim3(256), 0, stream, in, out, T, N, tau_s);
-  else if (vec) hipLaunchKernelGGL((psp_kernel<4, false>), dim3(grid_for(N / 4)), dim3(256), 0, stream, in, out, T, N, tau_s);
-  else if (backward) hipLaunchKernelGGL((psp_kernel<1, true>), dim3(grid_for(N)), dim3(256), 0, stream, in, out, T, N, tau_s);
-  else hipLaunchKernelGGL((psp_kernel<1, false>), dim3(grid_for(N)), dim3(256), 0, stream, in, out, T, N, tau_s);
+  const dim3 g(spk_grid(vec ? N / 4 : N, GRID_CAP)), blk(256);
+  if (vec && backward) hipLaunchKernelGGL((psp_kernel<4, true>), g, blk, 0, stream, in, out, T, N, tau_s);
+  else if (vec) hipLaunchKernelGGL((psp_kernel<4, false>), g, blk, 0, stream, in, out, T, N, tau_s);
+  else if (backward) hipLaunchKernelGGL((psp_kernel<1, true>), g, blk, 0, stream, in, out, T, N, tau_s);
+  else hipLaunchKernelGGL((psp_kernel<1, false>), g, blk, 0, stream, in, out, T, N, tau_s);
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }

@@ -22,6 +22,12 @@
   } while (0)
 
 static inline int spk_blocks(long long n, int threads) { return (int)((n + threads - 1) / threads); }
+// Blocks of 256 threads of a grid-stride launch over `work_items`: ceil(work_items / 256), at least 1, at most `cap` (the loop
+// covers the rest).  The cap is the call site's: how many blocks keep its kernel's memory pipeline full.
+static inline int spk_grid(long long work_items, int cap) {
+  const long long g = (work_items + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
 
 // One LIF step, exactly the arithmetic of
 // SJ/activation_based/neuron.py:799-811 with v_reset as a parameter:

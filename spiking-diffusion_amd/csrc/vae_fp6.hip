@@ -635,41 +635,6 @@ __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restri
   }
 }
 
-// u8 PTC [B][HW][16][C] -> S32 [B][ceil(C/32)][HW][16][16 B] (channels beyond C: zero nibbles); one thread per 16-byte record
-__global__ void ptc_to_s32_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int B, int HW, int C) {
-  const int nch = (C + 31) / 32;
-  const long long total = (long long)B * nch * HW * T16;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    long long r = i;
-    const int t = (int)(r % T16); r /= T16;
-    const int p = (int)(r % HW); r /= HW;
-    const int cc = (int)(r % nch);
-    const int b = (int)(r / nch);
-    const uint8_t* src = in + (((long long)b * HW + p) * T16 + t) * C + cc * 32;
-    const int nc = C - cc * 32 < 32 ? C - cc * 32 : 32;
-    unsigned w[4] = {0, 0, 0, 0};
-    if ((C & 15) == 0) {                                    // 16 or 32 channels: vector loads
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (16 * h < nc) {
-          const uint4 v = *reinterpret_cast<const uint4*>(src + 16 * h);
-          const unsigned q[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {                     // four bytes (0 / 1) -> four nibbles (0 / 2)
-            const unsigned x = q[k] & 0x01010101u;
-            const unsigned n4 = ((x | (x >> 4)) & 0x00ff00ffu);
-            const unsigned n16 = (n4 | (n4 >> 8)) & 0xffffu;
-            w[2 * h + (k >> 1)] |= (n16 << 1) << (16 * (k & 1));
-          }
-        }
-      }
-    } else {
-      for (int c = 0; c < nc; ++c) w[c >> 3] |= (src[c] ? 2u : 0u) << (4 * (c & 7));
-    }
-    *reinterpret_cast<uint4*>(out + i * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
 template <int GEO, int H, int W, int NCH, int OUT, int SPLIT, bool DB>
 int launch_vae(const TArgs& a, long long n_words, hipStream_t stream) {
   constexpr int TPT = tiles_per_tap(NCH), TPL = TPT - 1;
@@ -708,17 +673,6 @@ extern "C" int spk_vae_fp6_pack(const float* w, const float* bias, uint8_t* wq, 
 extern "C" long long spk_vae_fp6_flag_words(int B, int Cout, int Ho, int Wo) {
   if (B <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return -1;
   return 2 + (long long)FLAG_CAP + ((long long)B * Cout * Ho * Wo + 31) / 32 + 1;
-}
-
-extern "C" int spk_ptc_to_s32(const uint8_t* in_ptc, uint8_t* out_s32, int T, int B, int HW, int C, hipStream_t stream) {
-  if (!in_ptc || !out_s32 || B <= 0 || HW <= 0 || C <= 0) return SPK_ERR_ARG;
-  if (T != T16) return SPK_ERR_UNSUPPORTED;
-  const long long total = (long long)B * ((C + 31) / 32) * HW * T16;
-  const long long blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(ptc_to_s32_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, stream, in_ptc, out_s32,
-                     B, HW, C);
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
 }
 
 extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const double* scale, const double* bias_d,

@@ -741,15 +741,15 @@ class DummyModel(nn.Module):
         """conv1 .. conv5 on the input map [B,2,h,w] (``pre1 = (spikes, counts)``: the first layer's output is already there --
         the previous reverse step's tail launch produced it).  Returns (x5, cnt5, x1, cnt1, which, impl, collapse)."""
         T = self.n_steps
-        # spikes travel channel-chunked: CPTC (32 u8 channels per chunk) for the int8 kernel, C4 (64 fp4 nibbles per
-        # chunk) for the fp6 kernel -- the layout each stages per K chunk
+        # spikes travel in the records each kernel family stages per K chunk (ops.LAYOUTS): S32 for fp6v2, C4 for the first fp6
+        # kernel, CPTC of 32 u8 channels for the int8 and the direct kernels
         hw = (int(inp_b2hw.shape[-2]), int(inp_b2hw.shape[-1])) if pre1 is None else (int(pre1[0].shape[2]), int(pre1[0].shape[3]))
         self._latent_hw = hw
         self._last_stateful = bool(stateful)
         which = self.conv_impl
         impl = 'direct' if which == 'direct-f64' else 'auto'
         collapse = which != 'direct-f64' and self.collapse_conv6
-        chunk = ops.CHUNK_S32 if which == 'mfma-fp6v2' else (ops.CHUNK_C4 if which == 'mfma-fp6x6' else 32)
+        chunk = {'mfma-fp6v2': ops.S32, 'mfma-fp6x6': ops.C4}.get(which, ops.cptc(32)).chunk
         if pre1 is None:
             with ops.timed('den.conv1'):
                 r1 = self.conv1.run(inp_b2hw, IN_TINV, final='ptc', T=T, stateful=stateful, chunk_out=chunk,

@@ -105,9 +105,10 @@ def exact_spike_conv(conv, T, H, W):
 
 
 def _in_hw(x, kind):
-    """H x W of the map an input of layout ``kind`` holds (PTC [B,H,W,T,C]; chunked records [B,C/c,H,W,T,c]; fp32 [...,H,W])."""
+    """H x W of the map an input of layout ``kind`` holds (stored spikes: ops.layout_of; fp32 [...,H,W])."""
     if kind == IN_PTC:
-        return (x.shape[2], x.shape[3]) if x.dim() == 6 else (x.shape[1], x.shape[2])
+        _, (_, _, H, W, _) = ops.layout_of(x)
+        return H, W
     return x.shape[-2], x.shape[-1]
 
 
@@ -389,16 +390,17 @@ class FusedSequential(nn.Sequential):
         for bi, (conv, _, _) in enumerate(blocks):
             with ops.timed(getattr(conv, '_spk_tag', None)):          # bench.py tags layers it wants timed in situ
                 geo = conv_geometry(conv)
-                if kind == IN_PTC and cur.dim() == 6 and cur.dtype == ops.C4_DTYPE:
-                    if cur.shape[-1] == 16:
-                        nxt = self._vae_fp6(ctx, bi, geo, cur) or self._fp6v2(ctx, bi, geo, cur)
-                    else:
-                        nxt = self._fp6(ctx, bi, geo, cur)
-                elif self._i8_fits(ctx, bi, geo, cur, kind):
+                lay = ops.layout_of(cur)[0] if kind == IN_PTC else None
+                name = lay.name if lay is not None else None              # (layouts are told apart by name, here and below)
+                if name == 'S32':
+                    nxt = self._vae_fp6(ctx, bi, geo, cur) or self._fp6v2(ctx, bi, geo, cur)
+                elif name == 'C4':
+                    nxt = self._fp6(ctx, bi, geo, cur)
+                elif name == 'CPTC' and lay.rec_channels == 32 and self._i8_fits(ctx, bi, geo, cur):
                     nxt = self._i8(ctx, bi, cur)
                 elif kind == 'collapsed':
                     nxt = self._readout(ctx, bi, geo, cur)
-                elif self._gather_fits(ctx, bi, cur, kind):
+                elif name == 'PTC' and self._gather_fits(ctx, bi, cur):
                     nxt = self._gather(ctx, bi, geo, cur)
                 else:
                     nxt = self._direct(ctx, bi, geo, cur, kind)
@@ -476,12 +478,13 @@ class FusedSequential(nn.Sequential):
         return self._spikes_out(ctx, bi, o)
 
     @staticmethod
-    def _i8_fits(ctx, bi, geo, cur, kind):
+    def _i8_fits(ctx, bi, geo, cur):
+        """(cur: CPTC records of 32 channels)"""
         conv, _, lif = ctx.blocks[bi]
         last = bi == len(ctx.blocks) - 1
         src1 = ctx.in1 if last else None
-        return (ctx.impl != 'direct' and kind == IN_PTC and cur.dim() == 6 and cur.shape[-1] == 32 and
-                (src1 is None or src1.dim() == 6) and not geo['transposed'] and not ctx.want_pre and
+        return (ctx.impl != 'direct' and (src1 is None or ops.layout_of(src1)[0].name == 'CPTC') and
+                not geo['transposed'] and not ctx.want_pre and
                 (lif is not None or ctx.final == 'mean') and
                 ops.den_mfma_supported(conv.out_channels, conv.in_channels, geo['k'], geo['stride'], geo['pad'], ctx.T,
                                        cur.shape[2], cur.shape[3]) and
@@ -512,11 +515,12 @@ class FusedSequential(nn.Sequential):
         ctx.out['f32'], ctx.out['u8'] = r['f32'], r['u8']
 
     @staticmethod
-    def _gather_fits(ctx, bi, cur, kind):
+    def _gather_fits(ctx, bi, cur):
+        """(cur: plain PTC)"""
         conv, _, lif = ctx.blocks[bi]
         last = bi == len(ctx.blocks) - 1
         mode = MODE_LIF if lif is not None else (MODE_MEMOUT if ctx.final == 'memout' else None)
-        return (ctx.impl != 'direct' and kind == IN_PTC and cur.dim() == 5 and not (last and ctx.in1 is not None) and
+        return (ctx.impl != 'direct' and not (last and ctx.in1 is not None) and
                 mode is not None and not ctx.want_pre and not ctx.want_counts and not (last and ctx.chunk_out) and
                 ops.conv_mfma_supported(conv.in_channels, conv.out_channels, ctx.T, mode))
 

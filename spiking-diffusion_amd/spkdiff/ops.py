@@ -274,7 +274,7 @@ class BNLIFTrainFunction(torch.autograd.Function):
         c4 = None
         if want_c4 and C % 64 == 0 and C // 4 <= 256 and 256 % (C // 4) == 0 and all(
                 t is None or t.data_ptr() % 16 == 0 for t in (y, s, v0, v_last)):
-            c4 = torch.empty((B, C // 64, int(y.shape[3]), int(y.shape[4]), T, 32), dtype=C4_DTYPE, device=y.device)
+            c4 = empty_spikes(C4, B, C, int(y.shape[3]), int(y.shape[4]), T, y.device)
         with timed("train.bn_lif_fwd"):
             check(lib.spk_bn_lif_train_fwd_c4(_p(y), _p(g), _p(b), _p(running_mean), _p(running_var), float(momentum),
                                               float(eps), _p(v0), _p(s), _p(v_last), _p(mean), _p(invstd), _p(c4), _p(ws),
@@ -662,32 +662,122 @@ class PSPFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------------------------- layouts
-def spikes_to_ptc(s, chunk=None):
-    """fp32 [T,B,C,H,W] -> u8 [B,H,W,T,C] (plain PTC) or, with ``chunk``, CPTC [B,C/chunk,H,W,T,chunk]."""
+# The storage forms of a spike tensor between layers (the kernels' side of the same table: csrc/layouts.hip).  A record
+# is the channels of one (position, step) that lie together in memory:
+#   PTC   u8 [B,H,W,T,C]                  one byte per channel, all C of them in one record
+#   CPTC  u8 [B,C/chunk,H,W,T,chunk]      the same bytes in records of `chunk` channels (32: the int8 MFMA kernel's K chunk)
+#   C4    int8 [B,C/64,H,W,T,32]          e2m1 nibbles (a spike = 0x2, even channel = low nibble), 64 channels per 32-byte record
+#   S32   int8 [B,C/32,H,W,T,16]          the same nibbles, 32 channels per 16-byte record (fp6v2 and the VQ-VAE's fp6 kernel)
+# The nibble records carry dtype int8 so that they cannot be mistaken for the u8 CPTC of the same shape.
+C4_DTYPE = torch.int8
+CHUNK_C4, CHUNK_S32 = -64, -32      # include/spkdiff.h SPK_CHUNK_C4 / SPK_CHUNK_S32: chunk_out values of spk_conv_fused_fwd
+
+
+class SpikeLayout(NamedTuple):
+    name: str
+    dtype: torch.dtype
+    rec_channels: int        # channels per record (PTC: 0 = all C of the tensor)
+    rec_bytes: int           # bytes per record (PTC: 0 = C)
+    chunk: int               # the C-ABI's `chunk` / `chunk_out` argument that names this layout
+
+
+PTC = SpikeLayout("PTC", torch.uint8, 0, 0, 0)
+C4 = SpikeLayout("C4", C4_DTYPE, 64, 32, CHUNK_C4)
+S32 = SpikeLayout("S32", C4_DTYPE, 32, 16, CHUNK_S32)
+
+
+def cptc(chunk):
+    """The CPTC layout with records of ``chunk`` channels."""
+    return SpikeLayout("CPTC", torch.uint8, int(chunk), int(chunk), int(chunk))
+
+
+LAYOUTS = (PTC, cptc(32), C4, S32)      # (CPTC at the int8 MFMA kernel's chunk; cptc(n) for another)
+
+
+def layout_of(t):
+    """(layout, (B, C, H, W, T)) of a stored spike tensor: the place that tells the four layouts apart, by dtype, rank and record
+    size (PTC, cptc(chunk), C4 or S32; compare by ``.name``).  Any device."""
+    if t.dtype == torch.uint8 and t.dim() == 5:
+        B, H, W, T, C = (int(v) for v in t.shape)
+        return PTC, (B, C, H, W, T)
+    if t.dtype == torch.uint8 and t.dim() == 6:
+        B, nrec, H, W, T, chunk = (int(v) for v in t.shape)
+        return cptc(chunk), (B, nrec * chunk, H, W, T)
+    if t.dtype == C4_DTYPE and t.dim() == 6:
+        B, nrec, H, W, T, rb = (int(v) for v in t.shape)
+        for lay in (S32, C4):
+            if rb == lay.rec_bytes:
+                return lay, (B, nrec * lay.rec_channels, H, W, T)
+    if t.dtype not in (torch.uint8, C4_DTYPE):
+        raise NotImplementedError(f"spkdiff: stored spikes are torch.uint8 (PTC / CPTC) or int8-tagged C4 / S32 records, got {t.dtype}")
+    raise ValueError(f"spkdiff: a {t.dtype} tensor of shape {tuple(t.shape)} is none of the spike layouts (PTC [B,H,W,T,C], CPTC "
+                     "[B,C/chunk,H,W,T,chunk], C4 [B,C/64,H,W,T,32], S32 [B,C/32,H,W,T,16])")
+
+
+def empty_spikes(layout, B, C, H, W, T, device):
+    """Uninitialised spike tensor of C channels in ``layout`` (PTC, cptc(chunk), C4, S32): the one place that spells a record shape.
+    ceil(C / record) records: the channels of a partly filled last record belong to whoever writes the tensor."""
+    if layout.name == "PTC":
+        shape = (B, H, W, T, C)
+    else:
+        shape = (B, (C + layout.rec_channels - 1) // layout.rec_channels, H, W, T, layout.rec_bytes)
+    return torch.empty(shape, dtype=layout.dtype, device=device)
+
+
+def spikes_to_layout(s, layout):
+    """fp32 [T,B,C,H,W] -> the same spikes stored in ``layout`` (PTC, cptc(chunk), C4, S32)."""
     s = _dev(s, "spikes", torch.float32)
     T, B, C, H, W = s.shape
-    if chunk is None:
-        o = torch.empty((B, H, W, T, C), dtype=torch.uint8, device=s.device)
+    o = empty_spikes(layout, B, C, H, W, T, s.device)
+    if layout.dtype == torch.uint8:
+        check(lib.spk_spikes_to_ptc(_p(s), _p(o), T, B, C, H * W, layout.rec_channels or C, _stream(s)), "spk_spikes_to_ptc")
+    elif layout.name == "C4":
+        check(lib.spk_spikes_to_fp4(_p(s), _p(o), T, B, C, H * W, _stream(s)), "spk_spikes_to_fp4")
     else:
-        o = torch.empty((B, C // chunk, H, W, T, chunk), dtype=torch.uint8, device=s.device)
-    check(lib.spk_spikes_to_ptc(_p(s), _p(o), T, B, C, H * W, chunk or C, _stream(s)), "spk_spikes_to_ptc")
+        check(lib.spk_spikes_to_s32(_p(s), _p(o), T, B, C, H * W, _stream(s)), "spk_spikes_to_s32")
     return o
+
+
+def layout_to_spikes(q, expect=None):
+    """A stored spike tensor of any of the four layouts (``expect``: of that one) -> fp32 [T,B,C,H,W]."""
+    q = _dev(q, "stored spikes" if expect is None else expect.name)
+    lay, (B, C, H, W, T) = layout_of(q)
+    if expect is not None and lay.name != expect.name:
+        raise NotImplementedError(f"spkdiff: {expect.name} spikes expected, got {lay.name} ({q.dtype} {tuple(q.shape)})")
+    o = torch.empty((T, B, C, H, W), dtype=torch.float32, device=q.device)
+    if lay.dtype == torch.uint8:
+        check(lib.spk_ptc_to_spikes(_p(q), _p(o), T, B, C, H * W, lay.rec_channels or C, _stream(q)), "spk_ptc_to_spikes")
+    elif lay.name == "C4":
+        check(lib.spk_fp4_to_spikes(_p(q), _p(o), T, B, C, H * W, _stream(q)), "spk_fp4_to_spikes")
+    else:
+        check(lib.spk_s32_to_spikes(_p(q), _p(o), T, B, C, H * W, _stream(q)), "spk_s32_to_spikes")
+    return o
+
+
+# The names the layers, tests and tools call: fp32 [T,B,C,H,W] <-> u8 [B,H,W,T,C] (plain PTC) or, with ``chunk``, CPTC
+# [B,C/chunk,H,W,T,chunk]; <-> C4 [B,C/64,H,W,T,32]; <-> S32 [B,C/32,H,W,T,16].  ptc_to_spikes decodes any of the four.
+def spikes_to_ptc(s, chunk=None):
+    return spikes_to_layout(s, PTC if chunk is None else cptc(chunk))
 
 
 def ptc_to_spikes(p):
-    """u8 [B,H,W,T,C] or CPTC [B,C/chunk,H,W,T,chunk] (or int8-tagged C4) -> fp32 [T,B,C,H,W]."""
-    if p.dtype == C4_DTYPE:
-        return s32_to_spikes(p) if p.shape[-1] == 16 else c4_to_spikes(p)
-    p = _dev(p, "ptc", torch.uint8)
-    if p.dim() == 6:
-        B, nch, H, W, T, chunk = p.shape
-        C = nch * chunk
-    else:
-        B, H, W, T, C = p.shape
-        chunk = C
-    o = torch.empty((T, B, C, H, W), dtype=torch.float32, device=p.device)
-    check(lib.spk_ptc_to_spikes(_p(p), _p(o), T, B, C, H * W, chunk, _stream(p)), "spk_ptc_to_spikes")
-    return o
+    return layout_to_spikes(p)
+
+
+def spikes_to_c4(s):
+    return spikes_to_layout(s, C4)
+
+
+def c4_to_spikes(q):
+    return layout_to_spikes(q, C4)
+
+
+def spikes_to_s32(s):
+    return spikes_to_layout(s, S32)
+
+
+def s32_to_spikes(q):
+    return layout_to_spikes(q, S32)
 
 
 def count_spikes(t: torch.Tensor):
@@ -702,16 +792,13 @@ def count_spikes(t: torch.Tensor):
         T = int(t.shape[0])
         n = t.numel()
         inner, kind, numel = n // T, 2, n
-    elif t.dtype == torch.uint8:
-        T, rec = int(t.shape[-2]), int(t.shape[-1])
+    else:
+        lay, (_, C, _, _, T) = layout_of(t)
+        rec = lay.rec_bytes or C
         if rec % 4:
             raise NotImplementedError("count_spikes: PTC records must be a multiple of 4 bytes")
-        n, inner, kind, numel = t.numel() // 4, rec // 4, 0, t.numel()
-    elif t.dtype == C4_DTYPE:
-        T, rec = int(t.shape[-2]), int(t.shape[-1])
-        n, inner, kind, numel = t.numel() // 4, rec // 4, 1, t.numel() * 2
-    else:
-        raise NotImplementedError(t.dtype)
+        nibbles = lay.dtype == C4_DTYPE                          # spk_count_spikes' kind 1: two channels per byte
+        n, inner, kind, numel = t.numel() // 4, rec // 4, int(nibbles), t.numel() * (2 if nibbles else 1)
     check(lib.spk_count_spikes(_p(t), n, inner, T, kind, _p(out), _stream(t)), "spk_count_spikes")
     tot, t0, ones = (int(v) for v in out.tolist())
     return {"total": tot, "t0": t0, "numel": numel, "numel_t0": numel // T, "binary": kind != 2 or tot == ones}
@@ -732,13 +819,8 @@ def pack_conv_weight(w, transposed):
 
 
 IN_PTC, IN_TINV, IN_SEQ = 0, 1, 2
-# "C4" spike tensors (fp4 e2m1 nibbles, 64 channels per 32-byte record: [B, C/64, H, W, 16, 32]) carry dtype int8 so that
-# they cannot be mistaken for the u8 CPTC layout of the same shape
-CHUNK_C4 = -64
 STEP_TAIL_MAX_K = 512        # csrc/step_tail.hip TK_MAX: classes the fused reverse-step tail takes (four 16-channel groups per wave)
 VQ_TRAIN_MAX_D = 64          # csrc/vq_train.hip VT_MAX_D: the fused VQ training operators keep one code vector per thread
-CHUNK_S32 = -32          # "S32": the same nibbles in 32-channel records [B, C/32, H, W, 16, 16] (fp6v2 kernel)
-C4_DTYPE = torch.int8
 
 
 def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transposed=False, out_pad=0, in1=None,
@@ -752,11 +834,8 @@ def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transpo
     chunk0 = chunk1 = 0
     if in_kind == IN_PTC:
         in0 = _dev(in0, "in0", torch.uint8)
-        if in0.dim() == 6:                                   # CPTC [B, C/chunk, H, W, T, chunk]
-            B, nch, H, W, T_in, chunk0 = in0.shape
-            C0 = nch * chunk0
-        else:
-            B, H, W, T_in, C0 = in0.shape
+        lay0, (B, C0, H, W, T_in) = layout_of(in0)
+        chunk0 = lay0.chunk
         if T_in != T:
             raise ValueError("T mismatch")
     elif in_kind == IN_TINV:
@@ -772,11 +851,8 @@ def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transpo
     C1 = 0
     if in1 is not None:
         in1 = _dev(in1, "in1", torch.uint8)
-        if in1.dim() == 6:
-            chunk1 = in1.shape[-1]
-            C1 = in1.shape[1] * chunk1
-        else:
-            C1 = in1.shape[-1]
+        lay1, (_, C1, _, _, _) = layout_of(in1)
+        chunk1 = lay1.chunk
     kk, Cin, Cout = w_packed.shape
     if Cin != C0 + C1 or kk != k * k:
         raise ValueError(f"packed weight {tuple(w_packed.shape)} does not match Cin={C0 + C1}, k={k}")
@@ -786,13 +862,9 @@ def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transpo
         if want_counts:
             res["cnt"] = torch.empty((B, Cout // 32, Ho, Wo, 32), dtype=torch.uint8, device=dev)
         if want_ptc:
-            if chunk_out == CHUNK_C4:                        # nibble-packed fp4 spikes, tagged by dtype int8
-                res["ptc"] = torch.empty((B, Cout // 64, Ho, Wo, T, 32), dtype=C4_DTYPE, device=dev)
-            elif chunk_out == CHUNK_S32:
-                res["ptc"] = torch.empty((B, Cout // 32, Ho, Wo, T, 16), dtype=C4_DTYPE, device=dev)
-            else:
-                shape = (B, Ho, Wo, T, Cout) if not chunk_out else (B, Cout // chunk_out, Ho, Wo, T, chunk_out)
-                res["ptc"] = out_ptc if out_ptc is not None else torch.empty(shape, dtype=torch.uint8, device=dev)
+            lay = C4 if chunk_out == C4.chunk else S32 if chunk_out == S32.chunk else cptc(chunk_out) if chunk_out else PTC
+            given = out_ptc if lay.dtype == torch.uint8 else None
+            res["ptc"] = given if given is not None else empty_spikes(lay, B, Cout, Ho, Wo, T, dev)
         if want_f32:
             res["f32"] = out_f32 if out_f32 is not None else torch.empty((T, B, Cout, Ho, Wo), dtype=torch.float32, device=dev)
         if want_pre:
@@ -870,7 +942,7 @@ def den_conv3x3_mfma(in0, packed, Cout, *, mode, in1=None, bn_a=None, bn_b=None,
     wq, scale, bias_d = packed
     out_c = out_f = None
     if mode == MODE_LIF:
-        out_c = out if out is not None else torch.empty((B, Cout // 32, H, W, T, 32), dtype=torch.uint8, device=in0.device)
+        out_c = out if out is not None else empty_spikes(cptc(32), B, Cout, H, W, T, in0.device)
     else:
         out_f = out if out is not None else torch.empty((B, Cout, H, W), dtype=torch.float32, device=in0.device)
     cnt = None
@@ -933,7 +1005,7 @@ def den_conv3x3_mfma_fp6(in0, packed, Cout, *, bn_a, bn_b, v=None, want_counts=F
     if rec != 32:
         raise ValueError("C4 spike records are 32 bytes (64 channels)")
     wq, scale, bias_d = packed
-    out = torch.empty((B, Cout // 64, H, W, T, 32), dtype=C4_DTYPE, device=in0.device)
+    out = empty_spikes(C4, B, Cout, H, W, T, in0.device)
     cnt = torch.empty((B, Cout // 32, H, W, 32), dtype=torch.uint8, device=in0.device) if want_counts else None
     check(lib.spk_den_conv3x3_mfma_fp6(_p(in0), nch, _p(wq), _p(scale), _p(bias_d), _p(bn_a), _p(bn_b), _p(v), _p(out),
                                        _p(cnt), T, B, H, W, Cout, _n_dyn(), _stream(in0)), "spk_den_conv3x3_mfma_fp6")
@@ -944,7 +1016,7 @@ def spikes_cl_to_c4(s):
     """fp32 spikes [T,B,C,H,W] with channels-last memory -> C4 [B, C/64, H, W, T, 32]."""
     s = _cl5(s, "spikes")
     T, B, C, H, W = s.shape
-    o = torch.empty((B, C // 64, H, W, T, 32), dtype=C4_DTYPE, device=s.device)
+    o = empty_spikes(C4, B, C, H, W, T, s.device)
     check(lib.spk_spikes_nhwc_to_fp4(_p(s), _p(o), T, B, C, H * W, _stream(s)), "spk_spikes_nhwc_to_fp4")
     return o
 
@@ -953,7 +1025,7 @@ def spikes_cl_to_c4_counts(s):
     """spikes_cl_to_c4 + the spike counts over T, fp32 [B,C,H,W] (channels-last memory), from the same pass."""
     s = _cl5(s, "spikes")
     T, B, C, H, W = s.shape
-    o = torch.empty((B, C // 64, H, W, T, 32), dtype=C4_DTYPE, device=s.device)
+    o = empty_spikes(C4, B, C, H, W, T, s.device)
     cnt = _empty_cl((B, C, H, W), s.device)
     check(lib.spk_spikes_nhwc_to_fp4_counts(_p(s), _p(o), _p(cnt), T, B, C, H * W, _stream(s)), "spk_spikes_nhwc_to_fp4_counts")
     return o, cnt
@@ -1116,7 +1188,10 @@ class SpikeConvTrainFunction(torch.autograd.Function):
         if prep is not None and not prep.matches(weight):
             prep = None
         T, B, C, H, W = (int(v) for v in s.shape)
-        if c4 is not None and (tuple(c4.shape) != (B, C // 64, H, W, T, 32) or c4.dtype != C4_DTYPE or c4.device != s.device):
+        try:
+            if c4 is not None and (c4.device != s.device or layout_of(c4) != (C4, (B, C, H, W, T))):
+                c4 = None
+        except (ValueError, NotImplementedError):               # (no spike tensor at all: dropped like any other mismatch)
             c4 = None
         with timed("train.conv_fwd_fp6"):
             y = den_conv3x3_fp6_raw(c4 if c4 is not None else spikes_cl_to_c4(s),
@@ -1234,24 +1309,6 @@ class SpikeConvMeanTrainFunction(torch.autograd.Function):
         return gi, gw, gb, None
 
 
-def spikes_to_c4(s):
-    """fp32 [T,B,C,H,W] -> C4 [B, C/64, H, W, T, 32]."""
-    s = _dev(s, "spikes", torch.float32)
-    T, B, C, H, W = s.shape
-    o = torch.empty((B, C // 64, H, W, T, 32), dtype=C4_DTYPE, device=s.device)
-    check(lib.spk_spikes_to_fp4(_p(s), _p(o), T, B, C, H * W, _stream(s)), "spk_spikes_to_fp4")
-    return o
-
-
-def c4_to_spikes(q):
-    """C4 [B, C/64, H, W, T, 32] -> fp32 [T,B,C,H,W]."""
-    q = _dev(q, "c4", C4_DTYPE)
-    B, nch, H, W, T, _ = q.shape
-    o = torch.empty((T, B, nch * 64, H, W), dtype=torch.float32, device=q.device)
-    check(lib.spk_fp4_to_spikes(_p(q), _p(o), T, B, nch * 64, H * W, _stream(q)), "spk_fp4_to_spikes")
-    return o
-
-
 # ------------------------------------------------------------------------------- fp6v2: the sampler's denoiser convolutions
 def den_fp6v2_supported(Cout, Cin, k, stride, pad, T, H, W):
     return bool(lib.spk_den_conv3x3_mfma_fp6v2_supported(Cout, Cin, k, stride, pad, T, H, W))
@@ -1340,7 +1397,7 @@ def den_conv3x3_mfma_fp6v2(in0, packed, Cout, *, bn_a, bn_b, want_counts=False, 
     if rec != 16:
         raise ValueError("S32 spike records are 16 bytes (32 channels)")
     wq, scale, bias_d, wl1, qtab = packed
-    out = torch.empty((B, Cout // 32, H, W, T, 16), dtype=C4_DTYPE, device=in0.device)
+    out = empty_spikes(S32, B, Cout, H, W, T, in0.device)
     cnt = torch.empty((B, Cout // 32, H, W, 32), dtype=torch.uint8, device=in0.device) if want_counts else None
     flags = _flag_bitmap(in0.device, lib.spk_den_fp6v2_flag_words(B, Cout, H, W))
     if (need_radius is not None and NEED is not None and ACTIVE is not None and (H, W) == (7, 7) and
@@ -1390,24 +1447,6 @@ def _fp6v2_stats(in0, packed, Cout, bn_a, bn_b, out, cnt, flags):
                         "neurons": int(B * Cout * H * W), "repair_ms": ms[2], "last_position_ms": ms[4]})
 
 
-def spikes_to_s32(s):
-    """fp32 [T,B,C,H,W] -> S32 [B, C/32, H, W, T, 16]."""
-    s = _dev(s, "spikes", torch.float32)
-    T, B, C, H, W = s.shape
-    o = torch.empty((B, C // 32, H, W, T, 16), dtype=C4_DTYPE, device=s.device)
-    check(lib.spk_spikes_to_s32(_p(s), _p(o), T, B, C, H * W, _stream(s)), "spk_spikes_to_s32")
-    return o
-
-
-def s32_to_spikes(q):
-    """S32 [B, C/32, H, W, T, 16] -> fp32 [T,B,C,H,W]."""
-    q = _dev(q, "s32", C4_DTYPE)
-    B, nch, H, W, T, _ = q.shape
-    o = torch.empty((T, B, nch * 32, H, W), dtype=torch.float32, device=q.device)
-    check(lib.spk_s32_to_spikes(_p(q), _p(o), T, B, nch * 32, H * W, _stream(q)), "spk_s32_to_spikes")
-    return o
-
-
 # ---------------------------------------------------------------------------------------------- MFMA VQ-VAE layers
 def conv_mfma_supported(Cin, Cout, T, mode):
     # policy: a spiking layer goes there only with whole 16-channel groups of output (the kernel itself pads any Cout)
@@ -1440,7 +1479,7 @@ def conv_mfma_fused(in_ptc, packed, Cout, *, mode, k, stride, pad, transposed=Fa
     out_p = out_f = out_u = None
     if mode == MODE_LIF and out_s32:
         # nibble-packed "S32" spikes [B, Cout/32, Ho, Wo, 16, 16]: the input layout of the fp6 kernels
-        o = torch.empty((B, Cout // 32, Ho, Wo, T, 16), dtype=C4_DTYPE, device=in_ptc.device)
+        o = empty_spikes(S32, B, Cout, Ho, Wo, T, in_ptc.device)
         check(lib.spk_conv_mfma_fused_lif_s32(_p(in_ptc), _p(wq), _p(scale), _p(bias_d), _p(bn_a), _p(bn_b), _p(v), _p(o), T, B,
                                               H, W, Cin, Cout, k, stride, pad, int(transposed), out_pad, _stream(in_ptc)),
               "spk_conv_mfma_fused_lif_s32")
@@ -1452,7 +1491,7 @@ def conv_mfma_fused(in_ptc, packed, Cout, *, mode, k, stride, pad, transposed=Fa
         out_f = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=in_ptc.device)
     elif mode == MODE_LIF:
         coef = None
-        out_p = torch.empty((B, Ho, Wo, T, Cout), dtype=torch.uint8, device=in_ptc.device)
+        out_p = empty_spikes(PTC, B, Cout, Ho, Wo, T, in_ptc.device)
     else:
         out_f = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=in_ptc.device)
         if want_u8:
@@ -1496,7 +1535,7 @@ def ptc_to_s32(ptc):
     """u8 PTC spikes [B,H,W,16,C] -> S32 [B, ceil(C/32), H, W, 16, 16] (zero nibbles beyond C)."""
     ptc = _dev(ptc, "ptc", torch.uint8)
     B, H, W, T, C = ptc.shape
-    o = torch.empty((B, (C + 31) // 32, H, W, T, 16), dtype=C4_DTYPE, device=ptc.device)
+    o = empty_spikes(S32, B, C, H, W, T, ptc.device)
     check(lib.spk_ptc_to_s32(_p(ptc), _p(o), T, B, H * W, C, _stream(ptc)), "spk_ptc_to_s32")
     return o
 
@@ -1515,9 +1554,9 @@ def vae_fp6_fwd(in_s32, packed, Cout, *, bn_a, bn_b, transposed, out_kind, coef=
         coef = _dev(coef, "coef", torch.float32)
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=in_s32.device)
     elif out_kind == VAE_OUT_S32:
-        out = torch.empty((B, Cout // 32, Ho, Wo, T, 16), dtype=C4_DTYPE, device=in_s32.device)
+        out = empty_spikes(S32, B, Cout, Ho, Wo, T, in_s32.device)
     else:
-        out = torch.empty((B, Ho, Wo, T, Cout), dtype=torch.uint8, device=in_s32.device)
+        out = empty_spikes(PTC, B, Cout, Ho, Wo, T, in_s32.device)
     flags = _flag_ws("vae", in_s32.device, lib.spk_vae_fp6_flag_words(B, Cout, Ho, Wo))
     check(lib.spk_vae_fp6_fwd(_p(in_s32), _p(wq), _p(scale), _p(bias_d), _p(qtab), _p(bn_a), _p(bn_b), _p(coef), _p(out),
                               int(out_kind), _p(flags), T, B, H, W, Cin, Cout, int(transposed), int(FLAG_CAP), _stream(in_s32)),
@@ -1874,7 +1913,7 @@ def spikegen_tokens_s32(tokens, codebook, w_packed, bias, bn_a, bn_b, T=16, tabl
         build = table_key is None or ent[1] != table_key or ent[2] != stream
         ent[1], ent[2] = (None, None) if table_key is None else (table_key, stream)
     B, h, w = tokens.shape
-    out = torch.empty((B, 1, h, w, T, 16), dtype=C4_DTYPE, device=tokens.device)
+    out = empty_spikes(S32, B, Cout, h, w, T, tokens.device)
     check(lib.spk_spikegen_tokens_s32(_p(tokens), _p(codebook), _p(w_packed), _p(bias), _p(bn_a), _p(bn_b), _p(ws), int(build), _p(out),
                                       T, tokens.numel(), K, D, Cout, stream), "spk_spikegen_tokens_s32")
     return out
@@ -2035,7 +2074,7 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
                                   "v_reset=0) form; run conv1 as its own launch for other step counts")
     if conv1 is not None:
         w1, b1, a1, bb1 = conv1
-        x1 = torch.empty((B, 2, H, W, T, 16), dtype=C4_DTYPE, device=cnt5.device)
+        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
         c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
     _launch_by_temp("spk_den_step_tail", temp_b, temp, (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale),
                                                         _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t)),
@@ -2303,7 +2342,7 @@ def linear_lif(x: torch.Tensor, weight: torch.Tensor, bias, v: torch.Tensor, out
         if C * H * W != n_out:
             raise ValueError(f"out_ptc {tuple(out_ptc)} does not hold {n_out} outputs")
         out_kind, pc = LIN_OUT_PTC, (C, H, W)
-        out = torch.empty((B, H, W, T, C), dtype=torch.uint8, device=x.device)
+        out = empty_spikes(PTC, B, C, H, W, T, x.device)
     else:
         out_kind = LIN_OUT_U8
         if want_out:
