@@ -98,6 +98,16 @@ def _dev(t: torch.Tensor, name: str, dtype=None):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _state(t: torch.Tensor, name: str):
+    """A tensor the kernel updates in place.  ``_dev`` would hand the kernel a contiguous COPY of a non-contiguous one and the
+    caller's tensor would silently keep its old values, so such a tensor is refused."""
+    if isinstance(t, torch.Tensor) and not t.is_contiguous():
+        raise ValueError(f"spkdiff: {name} is updated in place and must be contiguous (shape {tuple(t.shape)}, strides "
+                         f"{tuple(t.stride())}); a copy would take the update and {name} itself would not advance. "
+                         f"Pass {name}.contiguous() and keep that tensor as the state.")
+    return _dev(t, name, torch.float32)
+
+
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -122,10 +132,10 @@ def clock_probe(device, target_ms: float = 4.0):
 
 # ---------------------------------------------------------------------------------------------- neuron
 def lif_fwd(x_seq: torch.Tensor, v: torch.Tensor, tau=2.0, v_threshold=1.0, v_reset=0.0, spike_dtype=SPIKE_F32):
-    """x_seq [T, ...] fp32, v [...] fp32 (updated in place) -> spikes. Mirrors the cupy-plugin contract
+    """x_seq [T, ...] fp32, v [...] fp32 contiguous (updated in place; a non-contiguous v is a ValueError) -> spikes. Mirrors the cupy-plugin contract
     SJ/activation_based/neuron.py:954-966 (x_seq.flatten(1), v.flatten(0))."""
+    v = _state(v, "v")
     x_seq = _dev(x_seq, "x_seq", torch.float32)
-    v = _dev(v, "v", torch.float32)
     T = x_seq.shape[0]
     N = x_seq[0].numel()
     if v.numel() != N:
@@ -146,9 +156,9 @@ def lif_fwd(x_seq: torch.Tensor, v: torch.Tensor, tau=2.0, v_threshold=1.0, v_re
 def lif_fwd_ex(x_seq: torch.Tensor, v: torch.Tensor, tau=2.0, v_threshold=1.0, v_reset=0.0, soft_reset=False, decay_input=True,
                want_v_seq=False):
     """The reference neuron's other eval forms (spk_lif_fwd_ex): soft reset, decay_input=False, v_seq.  Returns
-    (spikes fp32 like x_seq, v_seq or None); v updated in place."""
+    (spikes fp32 like x_seq, v_seq or None); v (contiguous, else ValueError) updated in place."""
+    v = _state(v, "v")
     x_seq = _dev(x_seq, "x_seq", torch.float32)
-    v = _dev(v, "v", torch.float32)
     T, N = x_seq.shape[0], x_seq[0].numel()
     if v.numel() != N:
         raise ValueError(f"v has {v.numel()} elements, x_seq[0] has {N}")

@@ -1284,7 +1284,7 @@ def test_lif_train_kernels_vs_live_oracle(dev, ops, N, tau, vr):
     s, h, vl = ops.lif_train_fwd(xs.to(dev), v0.to(dev), tau, 1.0, vr)
     gx, gv0 = ops.lif_train_bwd(gs.to(dev), gv.to(dev), h, tau, 1.0, vr, 2.0, False)
     assert torch.equal(s.cpu(), so.detach())
-    assert float((vl.cpu() - vlast.detach()).abs().max()) <= 1e-6
+    assert torch.equal(vl.cpu(), vlast.detach())                  # (IEEE fp32 operation by operation: the oracle's bits)
     for got, want in ((gx.cpu(), xo.grad), (gv0.cpu(), vo.grad)):
         err = (got - want).abs()
         assert float((err / (1e-6 + 1e-5 * want.abs())).max()) <= 1.0, float(err.max())
