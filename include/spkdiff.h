@@ -594,6 +594,26 @@ int spk_psample_step_temps(const float* logits_bkhw, long long* x_t_inout, uint8
                            unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                            long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
                            const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
+/* Top-k truncated sampling: spk_psample_step_topk and spk_den_step_tail_topk take the arguments, checks and
+ * properties of spk_psample_step_temps / spk_den_step_tail_temps plus `const int* topk_b`, a device array of B int32 values placed
+ * after temp_b and indexed by IMAGE like it (slot s of an active list reads topk_b[active[s]]).  For a position of image i let
+ * z_c = logits_c / temp_b[i] (the one fp32 division, classes c < K) and k = topk_b[i]:
+ *   - k <= 0 or k >= K: the image is not truncated -- every output is bit for bit the `_temps` entry point's;
+ *   - otherwise tau = the k-th largest of the row's non-NaN z_c, counting multiplicity, and every class with z_c < tau (IEEE
+ *     comparison) is replaced by -inf before the unchanged race (same operations, same order, same noise counters: the host form is
+ *     z.masked_fill(z < z.topk(k).values[..., -1:], -inf)).  Classes equal to tau all stay, so more than k classes may remain;
+ *     -0.0 and +0.0 compare equal; a row with fewer than k entries above -inf loses nothing; a NaN is never replaced, so a row
+ *     that holds one still gets token 0.  With k = 1 and a unique maximum the token is the arg max whatever the noise.
+ * Only positions whose token is drawn are truncated (the changing ones; all of them with x0_hat_out).  The noise of a dropped
+ * class is simply not used: no other draw moves, so split independence, philox_state and hipGraph capture hold as before.  tau is
+ * an exact order statistic (a bit-wise select over order-preserving keys, csrc/psample_common.h): deterministic, no sort.  The only
+ * check on temp_b / topk_b is for NULL (SPK_ERR_ARG before any launch).  There is no truncating score entry point: a token
+ * outside the kept set would score -inf. */
+int spk_psample_step_topk(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                          const int* topk_b, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                          unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                          long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
+                          const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -653,6 +673,16 @@ int spk_den_step_tail_temps(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, 
                             const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                             uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                             const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
+/* spk_den_step_tail with top-k truncation (1 <= K <= 512; workgroup s of the active-set form reads temp_b[active[s]] and
+ * topk_b[active[s]]): see spk_psample_step_topk. */
+int spk_den_step_tail_topk(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                           const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                           int t, const float* temp_b, const int* topk_b, const float* u_or_null, const float* q_or_null,
+                           unsigned long long philox_seed, unsigned long long philox_offset,
+                           const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                           const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                           uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                           const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
 /* q_sample of the diffusion training step, R/snn_model/vq_diffusion.py:61-75: mask = u < t[b] / num_timesteps (fp32, as there);
  * x_t = mask ? mask_id : x_0;  x_0_ignore = mask ? x_0 : -1 (the loss's ignore index).  x0 / u / outputs fp32 [B*HW], t int64 [B],
  * mask_out optional u8.  u is the caller's draw (torch.rand_like in the reference's order). */

@@ -29,9 +29,11 @@ __device__ __forceinline__ bool __any_sync_quad(bool v) {      // OR over the 4 
 // PT = per-image temperature (spk_psample_step_temps): `temp` is then a device array indexed by IMAGE (active[slot] in the
 // active-set form, like x_t / unmasked / the noise), read once per position; the division below is the same fp32 division.  A
 // separate instantiation: the scalar kernel's code does not change.
-template <int KPL, bool PT = false>
+// TK = top-k truncation (spk_psample_step_topk; always with PT): `temp` is then the pair of per-image arrays {temperatures, k}, and
+// a position whose token is drawn has its scaled logits truncated (truncate_top_k, psample_common.h) ahead of the unchanged race.
+template <int KPL, bool PT = false, bool TK = false>
 __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
-                                                      uint8_t* __restrict__ unmasked, int t, spk_temp_arg_t<PT> temp,
+                                                      uint8_t* __restrict__ unmasked, int t, spk_temp_arg_t<PT, TK> temp,
                                                       const float* __restrict__ u_in, const float* __restrict__ q_in,
                                                       unsigned long long seed, unsigned long long offset,
                                                       const unsigned long long* __restrict__ philox_state,
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       }
     }
     float l[KPL];
-    const float tp = spk_temp_of<PT>(temp, active ? active[b] : b);
+    const float tp = spk_temp_of<PT, TK>(temp, active ? active[b] : b);
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
       const int k = lane + 64 * j;
@@ -66,6 +68,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       const float lg = logits[((long long)b * K + (k < K ? k : K - 1)) * HW + hw];
       l[j] = k < K ? lg / tp : -INFINITY;
     }
+    if constexpr (TK) truncate_top_k<KPL>(l, lane, K, temp.topk[active ? active[b] : b]);
     const int besti = categorical_race<KPL>(l, lane, K, q_in, seed, offset, p);
     if (lane == 0) {
       const float u = reveal_u(u_in, seed, offset, p, K);
@@ -336,13 +339,13 @@ extern "C" int spk_den_build_input(const float* x_float_or_null, const long long
 }
 
 namespace {
-template <bool PT>
-int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_arg_t<PT> temp,
+template <bool PT, bool TK = false>
+int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_arg_t<PT, TK> temp,
                    const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
                    unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                    long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null, const int* n_active_or_null,
                    float* next_input_b2hw_or_null, hipStream_t stream) {
-  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT>(temp) || B <= 0 || HW <= 0 || K <= 0)
+  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK>(temp) || B <= 0 || HW <= 0 || K <= 0)
     return SPK_ERR_ARG;
   if (next_input_b2hw_or_null && active_or_null) return SPK_ERR_ARG;      // (the active-set form gathers its input by slot)
   if ((active_or_null == nullptr) != (n_active_or_null == nullptr) || (active_or_null && x0_hat_out_or_null))
@@ -352,7 +355,7 @@ int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unma
   int grid = (int)((npos + 3) / 4);
   if (grid > 4096) grid = 4096;
 #define SPK_PSAMPLE_LAUNCH(KPL)                                                                                          \
-  hipLaunchKernelGGL((psample_kernel<KPL, PT>), dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, \
+  hipLaunchKernelGGL((psample_kernel<KPL, PT, TK>), dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, \
                      t, temp, u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, \
                      active_or_null, n_active_or_null, B, HW, K, next_input_b2hw_or_null, (float)(t - 1))
   if (K <= 256) SPK_PSAMPLE_LAUNCH(4);
@@ -386,4 +389,17 @@ extern "C" int spk_psample_step_temps(const float* logits_bkhw, long long* x_t_i
   return psample_launch<true>(logits_bkhw, x_t_inout, unmasked_inout, t, temp_b, u_or_null, q_or_null, philox_seed, philox_offset,
                               philox_state_or_null, x0_hat_out_or_null, B, HW, K, active_or_null, n_active_or_null,
                               next_input_b2hw_or_null, stream);
+}
+
+// The same step with top-k truncation: per IMAGE a temperature (temp_b fp32 [B]) and a k (topk_b int32 [B]; k <= 0 or k >= K: that
+// image is not truncated) on the device (include/spkdiff.h).
+extern "C" int spk_psample_step_topk(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                     const float* temp_b, const int* topk_b, const float* u_or_null, const float* q_or_null,
+                                     unsigned long long philox_seed, unsigned long long philox_offset,
+                                     const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B,
+                                     int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                                     float* next_input_b2hw_or_null, hipStream_t stream) {
+  return psample_launch<true, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topk{temp_b, topk_b}, u_or_null, q_or_null,
+                                    philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, B, HW, K, active_or_null,
+                                    n_active_or_null, next_input_b2hw_or_null, stream);
 }

@@ -1,6 +1,7 @@
 // The token update of a reverse step, defined once for the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10
 // counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
-// offset + position * K + class), the categorical draw categorical_race, the 64-lane max / sum and the prologues every kernel shares.
+// offset + position * K + class), the categorical draw categorical_race, the top-k truncation truncate_top_k that may precede it, the
+// 64-lane max / sum and the prologues every kernel shares.
 // Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
@@ -75,18 +76,25 @@ __device__ __forceinline__ void write_next_input(float* __restrict__ next_input,
 // PT, the `_temps` entry points -- a device array fp32 [B] indexed by IMAGE (the index of x_t / unmasked / the noise, not the slot of
 // an active list).  Both forms divide the logit by the value in the same fp32 division, so an image whose entry equals the scalar
 // gets the scalar call's results bit for bit.  The host can check a value (> 0), of an array only the pointer.
-template <bool PT> struct spk_temp_arg { using type = float; };
-template <> struct spk_temp_arg<true> { using type = const float*; };
-template <bool PT> using spk_temp_arg_t = typename spk_temp_arg<PT>::type;
+// TK, the `_topk` entry points (top-k truncation, below): the argument is the pair of per-image arrays, temperatures fp32 [B] and k
+// int32 [B], both indexed by IMAGE.  The scalar and `_temps` kernels keep the argument they always had.
+struct spk_temp_topk { const float* temp; const int* topk; };
+template <bool PT, bool TK = false> struct spk_temp_arg { using type = float; };
+template <> struct spk_temp_arg<true, false> { using type = const float*; };
+template <> struct spk_temp_arg<true, true> { using type = spk_temp_topk; };
+template <bool PT, bool TK = false> using spk_temp_arg_t = typename spk_temp_arg<PT, TK>::type;
 
-template <bool PT>
-__device__ __forceinline__ float spk_temp_of(spk_temp_arg_t<PT> temp, int image) {
-  if constexpr (PT) return temp[image];
+template <bool PT, bool TK = false>
+__device__ __forceinline__ float spk_temp_of(spk_temp_arg_t<PT, TK> temp, int image) {
+  static_assert(PT || !TK, "the truncating kernels take per-image arrays");
+  if constexpr (TK) return temp.temp[image];
+  else if constexpr (PT) return temp[image];
   else return temp;
 }
-template <bool PT>
-inline bool spk_temp_arg_ok(spk_temp_arg_t<PT> temp) {
-  if constexpr (PT) return temp != nullptr;
+template <bool PT, bool TK = false>
+inline bool spk_temp_arg_ok(spk_temp_arg_t<PT, TK> temp) {
+  if constexpr (TK) return temp.temp != nullptr && temp.topk != nullptr;
+  else if constexpr (PT) return temp != nullptr;
   else return temp > 0.f;
 }
 
@@ -144,6 +152,39 @@ __device__ __forceinline__ int categorical_race(float (&l)[NJ], int lane, int K,
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
   }
   return besti;
+}
+
+// Top-k truncation of one position's temperature-scaled logits, ahead of categorical_race: tau = the k-th
+// largest of the row's non-NaN l (classes < K, counting multiplicity), every class with l < tau becomes -inf; classes equal to
+// tau all stay, a NaN is never replaced, and k <= 0 or k >= K leaves the row as it is.  An exact order statistic, no sort and no
+// LDS: every fp32 maps to a 32-bit key that orders as the floats do (sign bit flipped for v >= 0, all bits for v < 0), and tau's
+// key is built from its top bit down -- the largest key T with at least k candidates >= T, counted over the wave by ballot.  Key 0
+// is the bit pattern of a NaN, so it marks what does not count (a NaN, a class >= K); fewer than k candidates leave T = 0, whose
+// float is a NaN: nothing is below it.  The keep test is the float comparison (-0.0 and +0.0 are equal), not a key comparison.
+// Wave-uniform arguments K, k; every lane ends with the same tau.
+template <int NJ>
+__device__ __forceinline__ void truncate_top_k(float (&l)[NJ], int lane, int K, int k) {
+  if (k <= 0 || k >= K) return;
+  uint32_t key[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const uint32_t b = __float_as_uint(l[j]);
+    const bool counts = (lane + 64 * j < K) && !(l[j] != l[j]);
+    key[j] = counts ? ((b & 0x80000000u) ? ~b : (b | 0x80000000u)) : 0u;
+  }
+  uint32_t T = 0u;
+#pragma unroll 1
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t trial = T | (1u << bit);
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) n += __popcll(__ballot(key[j] >= trial));
+    if (n >= k) T = trial;
+  }
+  const float tau = __uint_as_float((T & 0x80000000u) ? (T & 0x7FFFFFFFu) : ~T);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (l[j] < tau) l[j] = -INFINITY;
 }
 
 }  // namespace

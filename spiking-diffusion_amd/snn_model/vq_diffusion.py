@@ -94,17 +94,19 @@ class Score(NamedTuple):
 
 class _SamplerGraph:
     """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
-    conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
+    conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``topk`` = int32 [B] of a truncating graph (which always has ``temps`` too); ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
     score graph: ``target[1:]`` = (logp, step), zeroed inside the graph), and every other buffer the captured launches address by raw pointer: freed earlier,
     its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
     (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
-    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False):
+    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False):
         self.graph = self.derived = None                            # set by the capture
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         # per-image temperatures are one more INPUT: the captured token updates read this buffer, filled before each replay
-        self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp else None
+        self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp or top_k else None
+        # ... and so is the per-image k of a truncating graph (DESIGN.md §4.12)
+        self.topk = torch.zeros(b, dtype=torch.int32, device=dev) if top_k else None
         self.x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         self.unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self.start_in = (torch.empty((b, h, w), dtype=torch.int64, device=dev),
@@ -253,15 +255,38 @@ class AbsorbingDiffusion(Sampler):
         ``n_samples = B`` under the same seed, and a shard (``set_shard``) gives the tokens the whole job gives.
         ``temp``: a number, or one temperature per image of the call's batch (``_temp_arg``): image i is
         sampled as ``sample(temp[i])`` samples it -- the same tokens under the same key and global image index, in every launch
-        form, and one captured graph serves every vector."""
+        form, and one captured graph serves every vector.  Top-k truncation: ``sample_top_k``."""
+        return self._sample_call(temp, sample_steps, noise, record, x_init, known, None)
+
+    @torch.no_grad()
+    def sample_top_k(self, top_k, temp=1.0, sample_steps=None, noise=None, record=None, x_init=None, known=None):
+        """``sample()`` with top-k truncation: every token is drawn from its position's ``k`` likeliest codes,
+        renormalised -- the classes below the k-th largest temperature-scaled logit are dropped ahead of the unchanged draw
+        (classes that tie with the k-th all stay).  ``top_k``: None (``sample()`` itself: the same calls with the same arguments),
+        an int >= 1 for every image, or one entry per image of the call (``_topk_arg``): integers >= 0, where 0 -- like any k >=
+        num_classes -- leaves that image untruncated; a device tensor is int32 [B] and taken as given.  Every other argument is
+        sample()'s; same noise contract (a dropped class's draw is simply not used: no other draw moves), so the tokens do not
+        depend on the launch form, on the split (``set_shard``) or on eager / captured, and with k = 1 an image gets its arg max
+        at every position.  In a captured graph ``top_k`` and the temperatures are inputs: one graph per (batch, steps, form,
+        conditional) serves every k and every temperature.  ``score()`` takes no ``top_k``: a given token outside the kept set
+        would score -inf, which bounds nothing."""
+        return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k)
+
+    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         temp = self._temp_arg(temp, b)
+        top_k = self._topk_arg(top_k, b)
         dn = self._denoise_fn
         dev = next(dn.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
         temp = self._temp_on(temp, dev)
+        if top_k is not None:
+            # a truncating call takes both per image: the `_topk` kernels read two arrays, and its graph two inputs
+            top_k = self._topk_on(top_k, dev, b)
+            if not isinstance(temp, torch.Tensor):
+                temp = torch.full((b,), temp, dtype=torch.float32, device=dev)
         h, w = self.shape
         if start is not None and (start[0].device != dev or start[1].device != dev):
             raise ValueError(f'spkdiff: x_init / known must be on the denoiser\'s device {dev}')
@@ -273,7 +298,46 @@ class AbsorbingDiffusion(Sampler):
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
         form = self._form(b, h, w, record is not None)
-        return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record)
+        return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k)
+
+    def _topk_arg(self, top_k, b):
+        """The ``top_k`` of sample_top_k() for a batch of ``b``, checked before anything is drawn or launched.  None: no
+        truncation.  An int >= 1 (a Python or numpy integer, a 0-dim integer tensor or array; not a bool): that k for every image
+        -- returns the int.  Otherwise one entry per image: host data (a list / tuple, a numpy array, a CPU tensor) must be ``b``
+        integers >= 0 (0: that image is not truncated; ValueError for a wrong length, a negative entry, a non-integer or a bool)
+        and comes back as a CPU int32 tensor [b]; a device tensor is taken as given -- int32 [b], its values are not read."""
+        if top_k is None:
+            return None
+        bad = ValueError(f'spkdiff: top_k must be None, an int >= 1 or one integer >= 0 per image of the call ({b}), got {top_k!r}')
+        if isinstance(top_k, bool):
+            raise bad
+        if isinstance(top_k, torch.Tensor) and top_k.is_cuda:
+            if top_k.dim() != 1 or int(top_k.numel()) != b or top_k.dtype != torch.int32:
+                raise ValueError(f'spkdiff: a per-image top_k on the device must be int32 [{b}] (one entry per image of the call), '
+                                 f'got {top_k.dtype} {tuple(top_k.shape)}')
+            return top_k.contiguous()
+        try:
+            v = top_k.detach() if isinstance(top_k, torch.Tensor) else torch.as_tensor(top_k)
+        except (TypeError, ValueError, RuntimeError):
+            raise bad from None
+        if v.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise bad                          # (floats, bools, complex: not a count)
+        if v.dim() == 0:
+            if int(v) < 1:
+                raise bad
+            return int(v)
+        if v.dim() != 1 or int(v.numel()) != b or bool((v < 0).any()) or bool((v > 0x7FFFFFFF).any()):
+            raise bad
+        return v.to(torch.int32)
+
+    @staticmethod
+    def _topk_on(top_k, dev, b):
+        """``_topk_arg``'s result for the kernels: int32 [b] on the denoiser's device (an int: broadcast; host data: its one copy)."""
+        if not isinstance(top_k, torch.Tensor):
+            return torch.full((b,), int(top_k), dtype=torch.int32, device=dev)
+        if top_k.is_cuda and top_k.device != dev:
+            raise ValueError(f'spkdiff: a per-image top_k must be on the denoiser\'s device {dev}, got {top_k.device}')
+        return top_k.to(dev)
 
     def _temp_arg(self, temp, b):
         """The ``temp`` of sample() / score() for a batch of ``b``, checked before anything is drawn or launched.  Anything
@@ -329,7 +393,8 @@ class AbsorbingDiffusion(Sampler):
         (only u is read); ``noise_source = 'host'`` draws u only.  ``record`` receives (t, x_t, unmasked, logits) per step as in
         sample() (dense form).  With ``use_graph`` and neither ``noise`` nor ``record`` an order is one replay of a captured graph
         that takes x_0 and ``known`` as inputs (a key of its own; sample()'s graphs and keys are untouched).
-        ``temp``: a number or one temperature per image, as in sample() (every order scores image i at ``temp[i]``)."""
+        ``temp``: a number or one temperature per image, as in sample() (every order scores image i at ``temp[i]``).  There is no
+        ``top_k`` here (sample_top_k): under truncation a given token outside the kept set scores -inf, not a useful bound."""
         if isinstance(x_0, torch.Tensor) and x_0.dim() in (3, 4):      # (host checks of a per-image temp: before the device is looked at)
             temp = self._temp_arg(temp, int(x_0.shape[0]))
         start = self._start_state_args(x_0, known, what='x_0', call='score()', alone=True)
@@ -362,12 +427,12 @@ class AbsorbingDiffusion(Sampler):
                                   None if known is None else start, record, target=(x0, logp[o], step[o]))
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
-    def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None):
+    def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
-                return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target)
+                return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k)
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -385,9 +450,10 @@ class AbsorbingDiffusion(Sampler):
                 torch.cuda.synchronize(dev)
             finally:
                 self._capturing = False
-        return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target)
+        return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k)
 
-    def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None):
+    def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
+                      top_k=None):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
@@ -402,7 +468,8 @@ class AbsorbingDiffusion(Sampler):
             else:
                 noise = lambda t: (torch.rand(b, 1, h, w).to(dev), None)      # noqa: E731
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
-        self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target)
+        self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
+                            top_k=top_k)
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -413,7 +480,8 @@ class AbsorbingDiffusion(Sampler):
         else:
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
-    def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None):
+    def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
+                       top_k=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -421,8 +489,10 @@ class AbsorbingDiffusion(Sampler):
         every spk_psample_step (one launch less per step; None: every step builds its own); ``record``: see sample();
         ``target = (x0, logp, step)``: teacher-forced (score()) -- the token update of every step is spk_pscore_step, which writes
         the given token x0 where spk_psample_step writes a sampled one and leaves its log-probability in logp, t in step (never a
-        fused-tail form: ``form.tail`` / ``form.tail_act`` are off there)."""
+        fused-tail form: ``form.tail`` / ``form.tail_act`` are off there); ``top_k``: int32 device tensor [B] -- handed to every token
+        update of sample_top_k() and to nothing else (None: the calls carry no such keyword)."""
         dn = self._denoise_fn
+        trunc = {} if top_k is None else {'top_k': top_k}
         b, _, h, w = x_t.shape
         K = self.num_classes
         seed, state = src.seed, src.state
@@ -441,12 +511,12 @@ class AbsorbingDiffusion(Sampler):
                     # conv6 on the counts + the token update as ONE launch -- dense: with the next step's first layer (pre1);
                     # elimination: per active slot, without it (that layer belongs to the next step's active set)
                     pre1, logits = dn.sample_step(x_t, unmasked, t, temp, u, q, seed, off, philox_state=state, pre1=pre1,
-                                                  want_next=form.tail and t > 1, want_logits=record is not None)
+                                                  want_next=form.tail and t > 1, want_logits=record is not None, **trunc)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
                     if target is None:
                         ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
-                                         next_input=inp if t > 1 else None)
+                                         next_input=inp if t > 1 else None, **trunc)
                     else:
                         ops.pscore_step(logits, target[0], x_t, unmasked, t, temp, target[1], target[2], u, seed, off,
                                         philox_state=state, next_input=inp if t > 1 else None)
@@ -586,7 +656,7 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
-    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False):
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -597,7 +667,7 @@ class AbsorbingDiffusion(Sampler):
             temp, first = 'per-image', 'any-shard'
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
-                conditional) + (('score',) if score else ())
+                conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ())
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
@@ -607,9 +677,9 @@ class AbsorbingDiffusion(Sampler):
             g.target[1].zero_()
             g.target[2].zero_()
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
-                            act=g.act, need=g.need, inp=g.inp, target=g.target)
+                            act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk)
 
-    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None):
+    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -618,15 +688,16 @@ class AbsorbingDiffusion(Sampler):
         takes the shard's counter base ``global_first * h * w * K`` through the second word of ``state`` (the kernels add it to
         every step's offset: the same counters), so the calls of a sharded job share it; scalar calls keep the shard in the key.
         ``target = (x0, logp, step)``: a score graph (again a key of its own) -- x0 is one more input (with ``start`` it IS the
-        codes input), logp / step receive the graph's outputs."""
+        codes input), logp / step receive the graph's outputs.  ``top_k`` (int32 device tensor [B]; ``temp`` is then a vector too):
+        a truncating graph -- a marker in the key, the vector copied into the graph's ``topk`` buffer before each replay."""
         dn = self._denoise_fn
-        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None)
+        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k)
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
             g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
-                              per_image_temp=isinstance(temp, torch.Tensor))
+                              per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None)
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -651,6 +722,8 @@ class AbsorbingDiffusion(Sampler):
         g.state.copy_(torch.tensor([seed, base], dtype=torch.int64), non_blocking=False)
         if g.temps is not None:
             g.temps.copy_(temp)
+        if g.topk is not None:
+            g.topk.copy_(top_k)
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
@@ -803,11 +876,11 @@ class DummyModel(nn.Module):
 
     @torch.no_grad()
     def sample_step(self, x_t, unmasked, t, temp, u=None, q=None, seed=0, offset=0, philox_state=None, pre1=None,
-                    want_next=True, want_logits=False):
+                    want_next=True, want_logits=False, top_k=None):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor.  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation).  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -817,10 +890,11 @@ class DummyModel(nn.Module):
         if want_next:
             a1, b1 = bn1.affine_terms()
             nxt = (conv1._spk_params.get(conv1), None if conv1.bias is None else conv1.bias.detach(), a1, b1)
+        trunc = {} if top_k is None else {'top_k': top_k}
         with ops.timed('den.tail'):
             return ops.den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
                                      K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,
-                                     conv1=nxt, want_logits=want_logits)
+                                     conv1=nxt, want_logits=want_logits, **trunc)
 
     def _run_train(self, x, t):
         """train() mode (R/snn_model/vq_diffusion.py:189-208 with batch-statistics BN and surrogate-gradient LIF): the

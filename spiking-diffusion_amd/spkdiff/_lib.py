@@ -140,6 +140,11 @@ _SIGS = {
                                       P, P, P, P]),
     "spk_den_step_tail_temps": (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, P, P, P, c_ulonglong, c_ulonglong, P, P, P,
                                         P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    # top-k truncation: the `_temps` signatures with a device array int32 [B] after the temperatures
+    "spk_psample_step_topk": (c_int, [P, P, P, c_int, P, P, P, P, c_ulonglong, c_ulonglong, P, P, c_int, c_int, c_int,
+                                      P, P, P, P]),
+    "spk_den_step_tail_topk": (c_int, [P, c_int, P, c_int, P, P, P, P, P, P, c_int, P, P, P, P, c_ulonglong, c_ulonglong, P, P, P,
+                                       P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "spk_philox_noise": (c_int, [c_ulonglong, c_ulonglong, P, P, P, c_int, c_int, c_int, P]),
     "spk_completion_state": (c_int, [P, P, P, P, P] + [c_int] * 8 + [c_longlong, P]),
     "spk_completion_compose": (c_int, [P, P, P, P] + [c_int] * 4 + [P]),

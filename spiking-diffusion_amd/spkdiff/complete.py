@@ -54,7 +54,19 @@ def complete_images(model, sampler, images, keep, temp=1.0, sample_steps=None, T
     Returns a ``Completion`` of device tensors.  ``paste``: the given pixels of ``images_u8`` are the input's
     (uint8(clip(image + 0.5, 0, 1) * 255), R/main.py:401), the rest the decoder's; False: the decoder's image everywhere.
     ``temp``: a number or one temperature per image, as ``sample()`` takes it.
-    One key draw from torch's global CPU generator, as every ``sample()`` call."""
+    One key draw from torch's global CPU generator, as every ``sample()`` call.  Top-k truncation: ``complete_images_top_k``."""
+    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, None)
+
+
+@torch.no_grad()
+def complete_images_top_k(model, sampler, images, keep, top_k, temp=1.0, sample_steps=None, T=16, paste=True):
+    """``complete_images`` with the unknown tokens drawn under top-k truncation: ``top_k`` is None, an int >= 1
+    or one k per image (0: that image is not truncated), as ``AbsorbingDiffusion.sample_top_k`` takes it.  The known tokens are
+    never drawn, so they come back unchanged whatever k is."""
+    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k)
+
+
+def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k):
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)
     h, w = H // 4, W // 4
@@ -63,7 +75,11 @@ def complete_images(model, sampler, images, keep, temp=1.0, sample_steps=None, T
     codes = model.encode_images(images, T)
     x_init, known, n_known = ops.completion_state(codes, keep, int(sampler.num_classes), int(sampler.mask_id), ENC_STRIDE,
                                                   ENC_RADIUS, want_counts=True)
-    tokens = sampler.sample(temp=temp, sample_steps=sample_steps, x_init=x_init, known=known).reshape(B, h, w)
+    if top_k is None:
+        tokens = sampler.sample(temp=temp, sample_steps=sample_steps, x_init=x_init, known=known)
+    else:
+        tokens = sampler.sample_top_k(top_k, temp=temp, sample_steps=sample_steps, x_init=x_init, known=known)
+    tokens = tokens.reshape(B, h, w)
     _, u8 = model.decode_tokens(tokens, T)
     if paste:
         u8 = ops.completion_compose(images, keep, u8)

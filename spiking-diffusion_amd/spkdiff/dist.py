@@ -82,32 +82,42 @@ def sample_images_sharded(generate_local, total: int, sampler=None):
     return gather_images(generate_local(lo, hi), total)
 
 
-def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True):
+def _per_image(v):
+    """Is ``v`` one entry per image of a job (to be sliced by shard), not one value for all of them?"""
+    return isinstance(v, (list, tuple)) or (getattr(v, 'ndim', 0) == 1 and len(v) > 1)
+
+
+def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None):
     """``spkdiff.complete.complete_images`` of one job over the ranks: every rank holds the whole job's ``images`` / ``keep``,
     completes its ``shard_range`` of them as a shard of the job (``set_shard``: shared key, counters on the global image index,
     so the images do not depend on the split) and one gather returns all uint8 images [total, C, H, W] on every rank.
     ``temp``: a number, or one temperature per image of the whole job (every rank passes the whole vector; a rank uses its
-    shard's slice)."""
-    from .complete import complete_images
-    per_image = isinstance(temp, (list, tuple)) or (getattr(temp, 'ndim', 0) == 1 and len(temp) > 1)
+    shard's slice).  ``top_k``: None, an int >= 1 or one k per image of the whole job, sliced in the same way
+    (``spkdiff.complete.complete_images_top_k``)."""
+    from .complete import complete_images, complete_images_top_k
+    per_image, per_image_k = _per_image(temp), _per_image(top_k)
 
     def generate_local(lo, hi):
-        return complete_images(model, sampler, images[lo:hi], keep[lo:hi], temp=temp[lo:hi] if per_image else temp,
-                               sample_steps=sample_steps, T=T, paste=paste).images_u8
+        tl = temp[lo:hi] if per_image else temp
+        if top_k is None:
+            return complete_images(model, sampler, images[lo:hi], keep[lo:hi], temp=tl, sample_steps=sample_steps, T=T,
+                                   paste=paste).images_u8
+        return complete_images_top_k(model, sampler, images[lo:hi], keep[lo:hi], top_k[lo:hi] if per_image_k else top_k, temp=tl,
+                                     sample_steps=sample_steps, T=T, paste=paste).images_u8
     return sample_images_sharded(generate_local, int(images.shape[0]), sampler=sampler)
 
 
-def temperature_sweep_sharded(model, sampler, temps, n_per_temp, sample_steps=None, batch=256, T=16):
+def temperature_sweep_sharded(model, sampler, temps, n_per_temp, sample_steps=None, batch=256, T=16, top_k=None):
     """``spkdiff.evaluate.temperature_sweep`` of one job over the ranks: every rank runs its ``shard_range`` of the job's
     ``len(temps) * n_per_temp`` images (``temperature_sweep_range``: calls of at most ``batch`` images, one key for the whole
     job, broadcast from rank 0) and one gather returns the uint8 images [len(temps), n_per_temp, C, H, W] on every rank -- the
-    images of the one-rank sweep under the same key."""
+    images of the one-rank sweep under the same key.  ``top_k``: None, an int or one k per temperature (``temperature_sweep_top_k``)."""
     from .evaluate import temperature_sweep_range
     G, n = len(temps), int(n_per_temp)
     keep = (sampler.n_samples, sampler.global_first)
 
     def generate_local(lo, hi):
-        return temperature_sweep_range(model, sampler, temps, n, lo, hi, sample_steps=sample_steps, batch=batch, T=T)[0]
+        return temperature_sweep_range(model, sampler, temps, n, lo, hi, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k)[0]
     try:
         u8 = sample_images_sharded(generate_local, G * n, sampler=sampler)
     finally:

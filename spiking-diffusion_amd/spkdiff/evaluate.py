@@ -79,14 +79,38 @@ def _sweep_temps(temps, n_per_temp):
     return tv.to(torch.float32).repeat_interleave(n_per_temp)
 
 
+def _sweep_top_k(top_k, n_temps, n_per_temp):
+    """The ``top_k`` of a sweep, per image of the job as ``_sweep_temps`` expands the temperatures: None, or int32 [n_temps *
+    n_per_temp] on the host from an int >= 0 (every image) or one k per temperature (image g * n_per_temp + j has top_k[g];
+    0: that group is not truncated)."""
+    if top_k is None:
+        return None
+    bad = ValueError(f"temperature_sweep: top_k must be None, an integer >= 0 or one per temperature ({n_temps}), got {top_k!r}")
+    if isinstance(top_k, bool):
+        raise bad
+    try:
+        kv = torch.as_tensor(top_k).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise bad from None
+    if kv.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) or kv.dim() > 1:
+        raise bad
+    kv = kv.reshape(-1).expand(n_temps) if kv.numel() == 1 else kv
+    if kv.numel() != n_temps or bool((kv < 0).any()) or bool((kv > 0x7FFFFFFF).any()):
+        raise bad
+    return kv.to(torch.int32).repeat_interleave(int(n_per_temp))
+
+
 @torch.no_grad()
-def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_steps=None, batch=256, T=16):
+def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_steps=None, batch=256, T=16, top_k=None):
     """Images [lo, hi) of the job ``temperature_sweep`` describes -- what one rank of ``spkdiff.dist.temperature_sweep_sharded``
     runs: (uint8 [hi - lo, C, H, W], tokens int64 [hi - lo, h, w]).  Calls of at most ``batch`` images (None: one call), each a
     shard of the job (``set_shard(first, count)``) with its slice of the per-image temperature vector, all under ONE noise key
     (``AbsorbingDiffusion._one_key``: one draw from torch's CPU generator, broadcast from rank 0 inside a process group), so the
-    images depend on neither ``batch`` nor the range.  ``n_samples`` / ``global_first`` of the sampler are restored."""
+    images depend on neither ``batch`` nor the range.  ``n_samples`` / ``global_first`` of the sampler are restored.
+    ``top_k``: None, an int or one k per temperature (``temperature_sweep_top_k``); every call takes its slice of the per-image
+    vector through ``sample_top_k``."""
     tv = _sweep_temps(temps, n_per_temp)
+    kv = _sweep_top_k(top_k, len(temps), n_per_temp)
     lo, hi = int(lo), int(hi)
     if not 0 <= lo < hi <= tv.numel():
         raise ValueError(f"temperature_sweep: the range [{lo}, {hi}) is not inside the job's {tv.numel()} images")
@@ -96,6 +120,7 @@ def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_st
     if step < 1:
         raise ValueError("temperature_sweep: batch must be >= 1 or None")
     tv = tv.to(next(model.parameters()).device)        # one copy: every call takes a slice
+    kv = None if kv is None else kv.to(tv.device)
     keep = (sampler.n_samples, sampler.global_first)
     images, tokens = [], []
     try:
@@ -104,7 +129,10 @@ def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_st
             for first in range(lo, hi, step):
                 count = min(step, hi - first)
                 sampler.set_shard(first, count)
-                tok = sampler.sample(temp=tv[first:first + count], sample_steps=sample_steps)
+                if kv is None:
+                    tok = sampler.sample(temp=tv[first:first + count], sample_steps=sample_steps)
+                else:
+                    tok = sampler.sample_top_k(kv[first:first + count], temp=tv[first:first + count], sample_steps=sample_steps)
                 tok = tok.reshape(count, tok.shape[-2], tok.shape[-1])
                 images.append(model.decode_tokens(tok, T, want_u8=True)[1])
                 tokens.append(tok)
@@ -122,8 +150,17 @@ def temperature_sweep(model, sampler, temps, n_per_temp, sample_steps=None, batc
     boundaries (``batch=None``: one call), see ``temperature_sweep_range``; one captured graph per call size serves every
     temperature, where the scalar protocol captures one per temperature.  Image (g, j) is the image ``sample(temps[g])`` gives at
     global index ``g * n_per_temp + j`` under the sweep's key."""
+    return temperature_sweep_top_k(model, sampler, temps, n_per_temp, None, sample_steps=sample_steps, batch=batch, T=T)
+
+
+@torch.no_grad()
+def temperature_sweep_top_k(model, sampler, temps, n_per_temp, top_k, sample_steps=None, batch=256, T=16):
+    """``temperature_sweep`` with top-k truncation: ``top_k`` is None (the plain sweep), an int for every image
+    or one k per temperature -- image (g, j) is drawn at temperature ``temps[g]`` from its positions' ``top_k[g]`` likeliest codes
+    (0: group g is not truncated).  Same job, same key rule, same result shapes; the images depend on neither ``batch`` nor the
+    split, and one captured graph per call size serves every temperature and every k."""
     G, n = len(temps), int(n_per_temp)
-    u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T)
+    u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k)
     return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
 
 

@@ -2002,30 +2002,55 @@ def _next_input_arg(next_input, n):
     return next_input
 
 
-def _launch_by_temp(name, temp_b, temp, head, tail):
-    """Launch ``name(*head, temp, *tail)`` or, ``temp_b`` given, its ``_temps`` sibling with the vector (looked up per call)."""
+def _topk_arg(top_k, temp, B, what, device):
+    """``top_k`` of a token update: None -- the call as it always was, (None, temp) -- or an int32 device tensor
+    [B], one k per image of the call (index = image, also inside an ``active_set`` scope; k <= 0 or k >= K: that image is not
+    truncated), taken as given: returns (top_k, temp_b).  The ``_topk`` entry points take their temperatures per image too: a
+    vector goes through as it is (fp32 [B] on the device), a number is broadcast."""
+    if top_k is None:
+        return None, temp
+    B = int(B)
+    if (not isinstance(top_k, torch.Tensor) or top_k.dtype != torch.int32 or not top_k.is_cuda or not top_k.is_contiguous() or
+            top_k.dim() != 1 or top_k.numel() != B):
+        got = f"{top_k.dtype} {tuple(top_k.shape)} on '{top_k.device}'" if isinstance(top_k, torch.Tensor) else repr(type(top_k))
+        raise ValueError(f"{what}: top_k must be a contiguous int32 device tensor of B = {B} entries, got {got}")
+    if isinstance(temp, torch.Tensor) and temp.is_cuda and temp.dtype == torch.float32 and temp.dim() == 1 and temp.numel() == B:
+        return top_k, temp.contiguous()
+    temp_b, temp = _temp_arg(temp, B, what)
+    return top_k, temp_b if temp_b is not None else torch.full((B,), temp, dtype=torch.float32, device=device)
+
+
+def _launch_by_temp(name, temp_b, temp, head, tail, top_k=None):
+    """Launch ``name(*head, temp, *tail)`` or, ``temp_b`` given, its ``_temps`` sibling with the vector (looked up per call);
+    ``top_k`` given (then with ``temp_b``): its ``_topk`` sibling with both vectors."""
+    if top_k is not None:
+        name = name + "_topk"
+        check(getattr(lib, name)(*head, _p(temp_b), _p(top_k), *tail), name)
+        return
     if temp_b is not None:
         name, temp = name + "_temps", _p(temp_b)
     check(getattr(lib, name)(*head, temp, *tail), name)
 
 
 def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, philox_state=None,
-                 next_input=None):
+                 next_input=None, top_k=None):
     """In-place update of x_t (int64) and unmasked (bool/u8) from logits [B,K,h,w].  next_input (dense form only): fp32
     [B,2,h,w] that receives the denoiser input of the next reverse step, cat(x_t, t - 1).  ``temp``: a number, or a contiguous
-    fp32 device tensor with one temperature per image (spk_psample_step_temps)."""
+    fp32 device tensor with one temperature per image (spk_psample_step_temps).  ``top_k``: int32 device tensor with one k per
+    image -- every drawn token comes from its position's k likeliest classes (spk_psample_step_topk; 0: not truncated)."""
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
     n = B * HW
-    temp_b, temp = _temp_arg(temp, x_t.numel() // HW, "psample_step")
+    top_k, temp = _topk_arg(top_k, temp, x_t.numel() // HW, "psample_step", logits.device)
+    temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, x_t.numel() // HW, "psample_step")
     _token_state(x_t, unmasked, n, "(updated in place)")
     u, q = _step_noise(u, q, philox_state, n, K)
     act, nact = (None, None) if ACTIVE is None else ACTIVE
     next_input = _next_input_arg(next_input, n)
     _launch_by_temp("spk_psample_step", temp_b, temp, (_p(logits), _p(x_t), _p(unmasked), int(t)),
                     (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
-                     _stream(logits)))
+                     _stream(logits)), top_k=top_k)
     return x_t, unmasked
 
 
@@ -2059,18 +2084,20 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
 
 
 def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
-                  conv1=None, want_logits=False):
+                  conv1=None, want_logits=False, top_k=None):
     """The tail of one dense reverse step as one launch (spk_den_step_tail): conv6 on the spike counts + time mean, the token
     update of ``psample_step`` (x_t / unmasked in place, same noise arguments) and -- with ``conv1 = (w_packed [9,2,64], bias,
     bn_a, bn_b)`` -- the first denoiser layer of the next step.  Returns (x1 S32 [B,2,h,w,16,16], cnt1 u8 [B,2,h,w,32]) or None,
     and the logits fp32 [B,K,h,w] when asked for.  Inside an ``active_set`` scope (the untouched-image elimination) cnt5 / cnt1 / logits
     are per SLOT of the active list and x_t / unmasked / the noise per image; ``conv1`` must be None there (the next step's first layer
-    belongs to the next step's active set).  ``temp``: a number or a per-image fp32 device tensor (spk_den_step_tail_temps)."""
+    belongs to the next step's active set).  ``temp``: a number or a per-image fp32 device tensor (spk_den_step_tail_temps);
+    ``top_k``: int32 device tensor, one k per image, as for psample_step (spk_den_step_tail_topk)."""
     cnt5 = _dev(cnt5, "cnt5", torch.uint8)
     cnt1 = _dev(cnt1, "cnt1", torch.uint8)
     B, nch5, H, W, _ = cnt5.shape
     n = B * H * W
-    temp_b, temp = _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
+    top_k, temp = _topk_arg(top_k, temp, x_t.numel() // (H * W), "den_step_tail", cnt5.device)
+    temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
     wq, scale, bias_d = packed6
     _token_state(x_t, unmasked, n, "[B,1,h,w]")
     u, q = _step_noise(u, q, philox_state, n, int(K))
@@ -2089,7 +2116,7 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     _launch_by_temp("spk_den_step_tail", temp_b, temp, (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale),
                                                         _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t)),
                     (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T),
-                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)))
+                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)), top_k=top_k)
     return (None if x1 is None else (x1, c1o)), logits
 
 
