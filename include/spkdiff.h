@@ -34,10 +34,19 @@ typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
                            * training branch and the training convolutions: 102, the token-table spike generator: 103; round 6: `int flag_cap` (and `int form` for spk_den_conv3x3_mfma_fp6v2) in front of the
                            * stream of the four certified-kernel entry points, spk_set_option / spk_get_option left the shipped library: 104;
                            * `active` / `n_active` of spk_den_step_tail: 105; the host-side shape
-                           * predicates spk_*_supported / spk_vae_fp6_kind: 106); spkdiff/_lib.py refuses a library whose
-                           * spk_version() differs from the signatures it declares.  Purely additive entry points (the SNN_VAE
+                           * predicates spk_*_supported / spk_vae_fp6_kind: 106); spkdiff/_lib.py reads its signatures from this header and
+                           * refuses a library whose spk_version() differs.  Purely additive entry points (the SNN_VAE
                            * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
                            * symbol at import, so a library that lacks one fails there */
+
+/* return codes below zero (0: success; above zero: a hipError_t) */
+#define SPK_ERR_ARG (-1)         /* bad argument: null pointer, non-positive size, contradictory combination */
+#define SPK_ERR_UNSUPPORTED (-2) /* a shape or option this entry point has no kernel for; nothing was launched */
+
+/* spike storage dtypes (spk_lif_fwd) */
+#define SPK_SPIKE_F32 0
+#define SPK_SPIKE_U8 1
+#define SPK_SPIKE_BITS 2 /* one bit per neuron-step, 64 neurons per u64 word (wave ballot) */
 
 /* fused-kernel epilogue modes (spk_conv_fused_fwd) */
 #define SPK_CHUNK_C4 (-64) /* chunk_out value: fp4 nibble-packed output, 64 channels per chunk */
@@ -62,7 +71,8 @@ const char* spk_error_string(int code);
 /* Multi-step eval LIF (hard reset, decay_input): replaces LIFNode.multi_step_forward eval branch
  * SJ/activation_based/neuron.py:971-1011 -> jit_eval_multi_step_forward_hard_reset_decay_input :799-811, and mirrors the
  * cupy plugin contract :954-966.  x_seq [T,N] fp32; v_inout [N] fp32 (state before / after); spike_out [T,N] as
- * spike_dtype 0 = fp32, 1 = u8, 2 = bit-packed u64 words [T, ceil(N/64)] (bit l of word w = neuron 64w+l). */
+ * spike_dtype SPK_SPIKE_F32 = fp32, SPK_SPIKE_U8 = u8, SPK_SPIKE_BITS = bit-packed u64 words [T, ceil(N/64)] (bit l of word w =
+ * neuron 64w+l). */
 int spk_lif_fwd(const float* x_seq, float* v_inout, void* spike_out, int T, long long N, float tau, float v_threshold,
                 float v_reset, int spike_dtype, spk_stream_t stream);
 /* The other eval forms of the reference neuron, SJ/activation_based/neuron.py:827-900 (dispatch :971-1011): soft reset
@@ -371,16 +381,19 @@ int spk_conv_mfma_fused_lif_s32(const uint8_t* in_ptc, const int8_t* wq, const d
 /* The spike-input 3x3 stride-2 layers of the spiking VQ-VAE from the reset state on the block-scaled fp6 x fp4 MFMA
  * (csrc/vae_fp6.hip): the same spikes as spk_conv_mfma_fused_fwd -- five digit planes on the matrix cores, certified decisions,
  * exact recomputation of the flagged neurons.  spk_vae_fp6_kind answers which instance exists for a layer -- its out_kind, or -1:
- *   out_kind 0: Decoder convT2 (R/snn_model/vae_model.py:146-150) -> out = fp32 [B][4*H*W][Cout] = sum_t coef[t] * spike[t], the input
+ *   SPK_VAE_OUT_COLLAPSED: Decoder convT2 (R/snn_model/vae_model.py:146-150) -> out = fp32 [B][4*H*W][Cout] = sum_t coef[t] * spike[t], the input
  *       of spk_readout_collapsed_fwd (the spike frames are not stored);
- *   out_kind 1: Decoder convT1 (:139-144) -> out = S32 spikes [B][Cout/32][4*H*W][16][16 B];
- *   out_kind 2: Encoder conv2 (:115-118) -> out = u8 PTC [B][H*W/4][16][Cout].
+ *   SPK_VAE_OUT_S32: Decoder convT1 (:139-144) -> out = S32 spikes [B][Cout/32][4*H*W][16][16 B];
+ *   SPK_VAE_OUT_PTC: Encoder conv2 (:115-118) -> out = u8 PTC [B][H*W/4][16][Cout].
  * spk_vae_fp6_fwd takes the out_kind that spk_vae_fp6_kind names for its layer (k 3, stride 2, pad 1; out_pad 1 if transposed).
  * in_s32: S32 spikes [B][ceil(Cin/32)][H*W][16][16 B] with zero nibbles in the channels beyond Cin (spk_ptc_to_s32 converts u8
  * PTC spikes).  spk_vae_fp6_pack: fp32 weight (Conv2d [Cout][Cin][3][3] / ConvTranspose2d [Cin][Cout][3][3]) (+bias) -> digit
  * tiles (spk_vae_fp6_packed_bytes), fp64 scale / bias [Cout], qtab int32 [Cout][9][Cin].  flag_words: zero-initialised u32
  * workspace of spk_vae_fp6_flag_words(B, Cout, Ho, Wo) words, clean again after the call; flag_cap as for
  * spk_den_conv3x3_mfma_fp6v2 (< 0: the whole id list). */
+#define SPK_VAE_OUT_COLLAPSED 0
+#define SPK_VAE_OUT_S32 1
+#define SPK_VAE_OUT_PTC 2
 int spk_vae_fp6_kind(int Cin, int Cout, int k, int stride, int pad, int out_pad, int transposed, int T, int H, int W);
 long long spk_vae_fp6_packed_bytes(int Cout, int Cin);
 int spk_vae_fp6_pack(const float* w, const float* bias, uint8_t* wq, double* scale, double* bias_d, int* qtab, int Cout, int Cin,
@@ -423,7 +436,8 @@ int spk_embedding_fwd(const long long* tokens, const float* codebook, float* out
  * spk_vq_train_quant: out_bdhw fp32 [B,D,HW] = xm + (E[idx] - xm) (the straight-through value) and loss_out[0] =
  *   mse(q, xm) + beta * mse(xm, q).  ws: spk_vq_train_ws_bytes() bytes, zero-initialised once, clean again after every call.
  * spk_vq_train_bwd: gout_bdhw = dL/d out, gloss_or_null [1] = dL/d loss (device) -> gx_seq [T,B,D,HW], galpha_out [1],
- *   gcodebook_out [K,D] (one workgroup per code, fixed summation order).  SPK_ERR_UNSUPPORTED for D > 64. */
+ *   gcodebook_out [K,D] (one workgroup per code, fixed summation order).  SPK_ERR_UNSUPPORTED for D > SPK_VQ_TRAIN_MAX_D. */
+#define SPK_VQ_TRAIN_MAX_D 64
 long long spk_vq_train_ws_bytes(void);
 int spk_vq_train_readout(const float* x_seq, const float* coef, const float* alpha, float* xm_out, float* dxa_out, int T, int B,
                          int D, int HW, spk_stream_t stream);
@@ -656,6 +670,7 @@ int spk_pscore_step_temps(const float* logits_bkhw, const long long* x0, long lo
  * serves slot s of the list: cnt5 / cnt1 / logits_out are indexed by slot (what the active-set denoiser launches produced), x_t / unmasked /
  * the noise by image active[s], so the draws are those of the dense form; x1_s32_out must be NULL there (the next step's first layer is
  * the next step's active set's). */
+#define SPK_STEP_TAIL_MAX_K 512 /* the largest K spk_den_step_tail and its _temps / _topk forms take */
 int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                       const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                       float temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
@@ -812,8 +827,9 @@ int spk_svae_latent_loss_bwd(const float* q_z, const float* p_z_or_null, const i
  * FID_loss is fp32, stored as its bit pattern in the low 32 bits of stats_out[2]: 0.001f * sum_{k != max_index}
  * ((float)hist[k] - (float)N / K)^2 / (K - 1), fp32 arithmetic, fixed summation order (K = 1: NaN, as mse_loss of empty
  * tensors).  Integer results are exact; the whole result is deterministic.  ws: at least 8 * (K + 1) bytes, zeroed by the call
- * (one hipMemsetAsync ahead of the launch); capturable in a hipGraph.  SPK_ERR_UNSUPPORTED for K > 4096 (the LDS histogram) or
+ * (one hipMemsetAsync ahead of the launch); capturable in a hipGraph.  SPK_ERR_UNSUPPORTED for K > SPK_VQ_USAGE_MAX_K (the LDS histogram) or
  * N > 2^31 - 1. */
+#define SPK_VQ_USAGE_MAX_K 4096
 int spk_vq_code_usage(const long long* idx, long long N, int K, long long* hist_out, long long* stats_out, void* ws,
                       spk_stream_t stream);
 
@@ -832,7 +848,8 @@ long long spk_ssim_mse_ws_bytes(int N, int C, int H, int W, int window_size);
  * A NaN in an image makes that image's two sums NaN and no other's.  Fixed-order reductions, no floating-point atomics: two
  * calls give bit-equal results.  ws_buf: spk_ssim_mse_ws_bytes bytes, 8-byte aligned, this call's alone while it is in flight;
  * nothing is expected of its contents (the per-tile partials are written before the second launch reads them); capturable in a
- * hipGraph.  SPK_ERR_UNSUPPORTED for window_size > 31 or 2^31 tiles and more. */
+ * hipGraph.  SPK_ERR_UNSUPPORTED for window_size > SPK_SSIM_MAX_WINDOW or 2^31 tiles and more. */
+#define SPK_SSIM_MAX_WINDOW 31
 int spk_ssim_mse(const float* img1, const float* img2, const float* window2d, double* ssim_sum_out, double* sq_sum_out,
                  void* ws_buf, int N, int C, int H, int W, int window_size, spk_stream_t stream);
 

@@ -4,16 +4,9 @@
 #include <stdint.h>
 #include <utility>
 
-#define SPK_OK 0
-#define SPK_ERR_ARG (-1)      // bad argument (null pointer, non-positive size, unsupported combination)
-#define SPK_ERR_UNSUPPORTED (-2)
+#define SPK_OK 0              // the negative return codes SPK_ERR_* and the spike dtypes SPK_SPIKE_*: include/spkdiff.h
 
 #define SPK_MAX_T 16          // time steps kept in registers by the fused kernels
-
-// spike storage dtypes (spk_lif_fwd)
-#define SPK_SPIKE_F32 0
-#define SPK_SPIKE_U8 1
-#define SPK_SPIKE_BITS 2      // one bit per neuron-step, 64 neurons per u64 word (wave ballot)
 
 #define SPK_LAUNCH_CHECK()                                   \
   do {                                                       \

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int SS_THREADS = 256, SS_TILE = 32, SS_MAX_WS = 31;
+constexpr int SS_THREADS = 256, SS_TILE = 32, SS_MAX_WS = SPK_SSIM_MAX_WINDOW;
 constexpr int SS_SPAN = SS_TILE + SS_MAX_WS - 1;                 // 62: tile + halo, per side
 constexpr int SS_W_DOUBLES = SS_MAX_WS * SS_MAX_WS;              // 961 window values (fp64)
 constexpr int SS_TILE_FLOATS = SS_SPAN * SS_SPAN;                // 3844 per image

@@ -27,7 +27,7 @@ namespace {
 constexpr int TCK = 32;                           // channels per K chunk
 constexpr int TW_CHUNK = 9 * 2 * 32 * TCK;        // 18432 B of packed weights per (channel group, chunk)
 constexpr int TNCH = 10;                          // 8 chunks of conv5 counts + 2 of conv1 counts (256 + 64 channels)
-constexpr int TK_MAX = 512;                       // classes = conv6 output channels (KG = groups per wave = ceil(K / 128) <= 4)
+constexpr int TK_MAX = SPK_STEP_TAIL_MAX_K;                      // classes = conv6 output channels (KG = groups per wave = ceil(K / 128) <= 4)
 constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested this many taps ahead of their MFMAs
 
 // PT = per-image temperature (spk_den_step_tail_temps): `temp` is a device array fp32 [B] indexed by IMAGE (psample_common.h); the

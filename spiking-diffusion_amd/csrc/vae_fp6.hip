@@ -42,7 +42,6 @@ constexpr int T16 = 16;
 constexpr int POSB = 256;                    // bytes per position and 32-channel chunk: 16 steps x 16 B
 constexpr int WT = 1536;                     // one B tile: 64 lanes x 32 six-bit codes
 constexpr unsigned FLAG_CAP = 1u << 20;
-constexpr int OUT_COLLAPSED = 0, OUT_S32 = 1, OUT_PTC = 2;
 
 __host__ __device__ constexpr int tiles_per_tap(int nch) { return nch == 2 ? 5 : 3; }
 // tile (tap, j): NCH = 2: j = 0..3: chunk j / 2, digit pair j % 2; j = 4: fifth digit, K half 0 = chunk 0, half 1 = chunk 1.
@@ -159,7 +158,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
   const float Ac4 = 1024.0f * scale_f * bna;
   float coef[16];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) coef[r] = OUT == OUT_COLLAPSED ? a.coef[r] : 0.f;
+  for (int r = 0; r < 16; ++r) coef[r] = OUT == SPK_VAE_OUT_COLLAPSED ? a.coef[r] : 0.f;
 
   const int row = lane & 31, half = lane >> 5;
   const int hsel = (row >> 2) & 1, tt = (row & 3) + 4 * (row >> 3);
@@ -357,7 +356,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             const float h = fmaf(z - v, 0.5f, v);            // == v + (z - v) * 0.5f: the product is exact
             const float hm = h - 1.0f;
             dmin = fminf(dmin, fabsf(hm));
-            if constexpr (OUT == OUT_COLLAPSED) {
+            if constexpr (OUT == SPK_VAE_OUT_COLLAPSED) {
               // spike = h >= 1: reset v and add the step's coefficient UNDER THE SPIKE MASK (v_cmpx narrows exec, two plain
               // instructions, exec restored): three vector instructions instead of compare + two selects + add (convT2 -5 %;
               // the spike-bit outputs measured slower in this form -- hipcc keeps their sixteen masks in SGPRs -- and keep the C form)
@@ -373,7 +372,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             }
           }
         }
-        if constexpr (OUT != OUT_COLLAPSED) mybits = ~(__builtin_bitreverse32(mybits) >> 16) & 0xffffu;   // bit r = NOT sign(h_r - 1)
+        if constexpr (OUT != SPK_VAE_OUT_COLLAPSED) mybits = ~(__builtin_bitreverse32(mybits) >> 16) & 0xffffu;   // bit r = NOT sign(h_r - 1)
         const int p = 2 * tl[i] + half;                       // accumulator lane half == position within the tile
         const bool ok = tv[i] && p < NPOS;
         const int pc = p < NPOS ? p : NPOS - 1;
@@ -389,18 +388,18 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
           if (idx < a.flag_cap) a.flags[2 + idx] = (unsigned)nid_f;
           else atomicOr(a.flags + 2 + FLAG_CAP + (nid_f >> 5), 1u << (nid_f & 31));
         }
-        if (OUT == OUT_COLLAPSED) {
+        if (OUT == SPK_VAE_OUT_COLLAPSED) {
           if (ok) reinterpret_cast<float*>(a.out)[pos * a.Cout + co] = m;
         } else {
           // a 16x16 bit transpose per 16-lane row gives lane t the 16 channel bits of step t (den_mfma_fp6v2.hip)
           const unsigned bitsv = spk_transpose16_rows(mybits, lane);
           const int t = lane & 15, hi = (lane >> 4) & 1;
-          if (ok && OUT == OUT_S32) {
+          if (ok && OUT == SPK_VAE_OUT_S32) {
             const uint2 o = spk_e2m1_record(bitsv);
             uint8_t* rec = reinterpret_cast<uint8_t*>(a.out) + ((((long long)b * G + g) * Ho * Wo + oy * Wo + ox) * T16 + t) * 16;
             *reinterpret_cast<uint2*>(rec + 8 * hi) = o;
           }
-          if (ok && OUT == OUT_PTC) {
+          if (ok && OUT == SPK_VAE_OUT_PTC) {
             uint4 o;
             o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
             o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
@@ -531,12 +530,12 @@ __device__ __forceinline__ void vae_fix_neuron(const TArgs& a, long long nid, in
     const long long S = (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
     const float y = (float)fma((double)S, sc, bi);
     const bool s = spk_lif_step_default(v, fmaf(y, bna, bnb));
-    if (OUT == OUT_COLLAPSED) m = m + (s ? a.coef[r] : 0.f);
+    if (OUT == SPK_VAE_OUT_COLLAPSED) m = m + (s ? a.coef[r] : 0.f);
     bits |= s ? (1u << r) : 0u;
   }
-  if (OUT == OUT_COLLAPSED) {
+  if (OUT == SPK_VAE_OUT_COLLAPSED) {
     if (lane == 0) reinterpret_cast<float*>(a.out)[nid] = m;
-  } else if (OUT == OUT_S32) {
+  } else if (OUT == SPK_VAE_OUT_S32) {
     if (lane < 16) {                                          // lane = time step: one nibble of the (position, t) record
       const int g = co >> 5, G = a.Cout >> 5, byte = (co & 31) >> 1;
       uint8_t* rec = reinterpret_cast<uint8_t*>(a.out) + ((((long long)b * G + g) * Ho * Wo + oy * Wo + ox) * T16 + lane) * 16;
@@ -680,7 +679,7 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
                                int out_kind, unsigned* flag_words, int T, int B, int H, int W, int Cin, int Cout, int transposed,
                                int flag_cap, hipStream_t stream) {
   if (!in_s32 || !wq || !scale || !bias_d || !qtab || !bn_a || !bn_b || !out || !flag_words || B <= 0) return SPK_ERR_ARG;
-  if (out_kind == OUT_COLLAPSED && !coef_or_null) return SPK_ERR_ARG;
+  if (out_kind == SPK_VAE_OUT_COLLAPSED && !coef_or_null) return SPK_ERR_ARG;
   const int kind = spk_vae_fp6_kind(Cin, Cout, 3, 2, 1, transposed ? 1 : 0, transposed, T, H, W);
   if (kind < 0 || kind != out_kind) return SPK_ERR_UNSUPPORTED;
   if (B > (1 << 22)) return SPK_ERR_UNSUPPORTED;             // (not in the predicate: the batch is no part of the layer's shape)
@@ -694,26 +693,26 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
   const long long n_words = (neurons + 31) / 32;
   a.ticket_idx = 2 + (long long)FLAG_CAP + n_words;
   // one instance per (kind, H): spk_vae_fp6_kind has checked that this one exists
-  if (kind == OUT_COLLAPSED) {                                                               // decoder convT2
+  if (kind == SPK_VAE_OUT_COLLAPSED) {                                                        // decoder convT2
     // half images per item, one input slab (two do not fit beside the weights); two class rows per item with two slabs measured
     // 231 against 195 us (profiles/r5_ab_kernel_variants.txt (7))
-    return H == 14 ? launch_vae<0, 14, 14, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream)
-                   : launch_vae<0, 16, 16, 2, OUT_COLLAPSED, 2, false>(a, n_words, stream);
+    return H == 14 ? launch_vae<0, 14, 14, 2, SPK_VAE_OUT_COLLAPSED, 2, false>(a, n_words, stream)
+                   : launch_vae<0, 16, 16, 2, SPK_VAE_OUT_COLLAPSED, 2, false>(a, n_words, stream);
   }
-  if (kind == OUT_S32) {                                                                     // decoder convT1
-    return H == 7 ? launch_vae<0, 7, 7, 1, OUT_S32, 1, true>(a, n_words, stream)
-                  : launch_vae<0, 8, 8, 1, OUT_S32, 1, true>(a, n_words, stream);
+  if (kind == SPK_VAE_OUT_S32) {                                                              // decoder convT1
+    return H == 7 ? launch_vae<0, 7, 7, 1, SPK_VAE_OUT_S32, 1, true>(a, n_words, stream)
+                  : launch_vae<0, 8, 8, 1, SPK_VAE_OUT_S32, 1, true>(a, n_words, stream);
   }
-  return H == 14 ? launch_vae<1, 14, 14, 1, OUT_PTC, 1, true>(a, n_words, stream)           // encoder conv2
-                 : launch_vae<1, 16, 16, 1, OUT_PTC, 1, false>(a, n_words, stream);         // (two slabs do not fit)
+  return H == 14 ? launch_vae<1, 14, 14, 1, SPK_VAE_OUT_PTC, 1, true>(a, n_words, stream)     // encoder conv2
+                 : launch_vae<1, 16, 16, 1, SPK_VAE_OUT_PTC, 1, false>(a, n_words, stream);   // (two slabs do not fit)
 }
 
 // Which instance exists for a layer: its output form, or -1.  The whole dispatch table of spk_vae_fp6_fwd.
 extern "C" int spk_vae_fp6_kind(int Cin, int Cout, int k, int stride, int pad, int out_pad, int transposed, int T, int H, int W) {
   if (k != 3 || stride != 2 || pad != 1 || T != T16 || Cout <= 0 || (Cout % 32) || H != W) return -1;
   const bool mid = H == 14 || H == 16, small = H == 7 || H == 8;
-  if (transposed && out_pad == 1 && Cin == 64 && mid) return OUT_COLLAPSED;     // decoder convT2
-  if (transposed && out_pad == 1 && Cin == 16 && small) return OUT_S32;         // decoder convT1
-  if (!transposed && Cin == 32 && mid) return OUT_PTC;                          // encoder conv2
+  if (transposed && out_pad == 1 && Cin == 64 && mid) return SPK_VAE_OUT_COLLAPSED;   // decoder convT2
+  if (transposed && out_pad == 1 && Cin == 16 && small) return SPK_VAE_OUT_S32;       // decoder convT1
+  if (!transposed && Cin == 32 && mid) return SPK_VAE_OUT_PTC;                        // encoder conv2
   return -1;
 }

@@ -16,7 +16,7 @@
 
 namespace {
 
-constexpr int VT_MAX_D = 64, VT_MAX_BLOCKS = 256;
+constexpr int VT_MAX_D = SPK_VQ_TRAIN_MAX_D, VT_MAX_BLOCKS = 256;
 
 __global__ __launch_bounds__(256) void vq_train_readout_kernel(const float* __restrict__ x, const float* __restrict__ coef,
                                                                const float* __restrict__ alpha, float* __restrict__ xm,

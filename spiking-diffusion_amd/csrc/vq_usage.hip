@@ -16,7 +16,7 @@
 
 namespace {
 
-constexpr int VU_MAX_K = 4096, VU_THREADS = 256, VU_MAX_BLOCKS = 128, VU_PER_BLOCK = 4096;
+constexpr int VU_MAX_K = SPK_VQ_USAGE_MAX_K, VU_THREADS = 256, VU_MAX_BLOCKS = 128, VU_PER_BLOCK = 4096;
 
 __global__ __launch_bounds__(VU_THREADS) void vq_usage_kernel(const long long* __restrict__ idx, long long N, int K,
                                                               long long per_block, unsigned* ticket,

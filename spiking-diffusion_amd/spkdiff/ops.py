@@ -13,8 +13,10 @@ import torch.nn.functional as F
 from . import _lib
 from ._lib import check, lib
 
-MODE_LIF, MODE_RAW, MODE_MEMOUT, MODE_MEAN = 0, 1, 2, 3
-SPIKE_F32, SPIKE_U8, SPIKE_BITS = 0, 1, 2
+# The C-ABI's enumerations and limits keep their Python names here; include/spkdiff.h defines each one (SPK_<name>).
+_C = _lib.CONSTANTS
+MODE_LIF, MODE_RAW, MODE_MEMOUT, MODE_MEAN = (_C["SPK_MODE_" + n] for n in ("LIF", "RAW", "MEMOUT", "MEAN"))
+SPIKE_F32, SPIKE_U8, SPIKE_BITS = (_C["SPK_SPIKE_" + n] for n in ("F32", "U8", "BITS"))
 MAX_T = 16
 
 
@@ -680,7 +682,7 @@ class PSPFunction(torch.autograd.Function):
 #   S32   int8 [B,C/32,H,W,T,16]          the same nibbles, 32 channels per 16-byte record (fp6v2 and the VQ-VAE's fp6 kernel)
 # The nibble records carry dtype int8 so that they cannot be mistaken for the u8 CPTC of the same shape.
 C4_DTYPE = torch.int8
-CHUNK_C4, CHUNK_S32 = -64, -32      # include/spkdiff.h SPK_CHUNK_C4 / SPK_CHUNK_S32: chunk_out values of spk_conv_fused_fwd
+CHUNK_C4, CHUNK_S32 = _C["SPK_CHUNK_C4"], _C["SPK_CHUNK_S32"]      # chunk_out values of spk_conv_fused_fwd
 
 
 class SpikeLayout(NamedTuple):
@@ -828,9 +830,9 @@ def pack_conv_weight(w, transposed):
     return out
 
 
-IN_PTC, IN_TINV, IN_SEQ = 0, 1, 2
-STEP_TAIL_MAX_K = 512        # csrc/step_tail.hip TK_MAX: classes the fused reverse-step tail takes (four 16-channel groups per wave)
-VQ_TRAIN_MAX_D = 64          # csrc/vq_train.hip VT_MAX_D: the fused VQ training operators keep one code vector per thread
+IN_PTC, IN_TINV, IN_SEQ = (_C["SPK_IN_" + n] for n in ("PTC", "TINV", "SEQ"))
+STEP_TAIL_MAX_K = _C["SPK_STEP_TAIL_MAX_K"]   # classes the fused reverse-step tail takes (four 16-channel groups per wave)
+VQ_TRAIN_MAX_D = _C["SPK_VQ_TRAIN_MAX_D"]     # the fused VQ training operators keep one code vector per thread
 
 
 def conv_fused(in0, w_packed, bias, *, in_kind, T, mode, k, stride, pad, transposed=False, out_pad=0, in1=None,
@@ -1415,7 +1417,7 @@ def den_conv3x3_mfma_fp6v2(in0, packed, Cout, *, bn_a, bn_b, want_counts=False, 
         rc = lib.spk_den_conv3x3_mfma_fp6v2_listed(_p(in0), nch, _p(wq), _p(scale), _p(bias_d), _p(wl1), _p(qtab), _p(bn_a),
                                                    _p(bn_b), _p(out), _p(cnt), _p(flags), T, B, H, W, Cout, _n_dyn(),
                                                    _p(NEED.buf), NEED.radii, int(need_radius), int(FLAG_CAP), _stream(in0))
-        if rc != -2:
+        if rc != _C["SPK_ERR_UNSUPPORTED"]:
             check(rc, "spk_den_conv3x3_mfma_fp6v2_listed")
             return (out, cnt) if want_counts else out
         # SPK_ERR_UNSUPPORTED: this device / partition has too few CUs for the per-class division of the listed launch (e.g.
@@ -1514,7 +1516,7 @@ def conv_mfma_fused(in_ptc, packed, Cout, *, mode, k, stride, pad, transposed=Fa
     return {"f32": out_f, "u8": out_u}
 
 
-VAE_OUT_COLLAPSED, VAE_OUT_S32, VAE_OUT_PTC = 0, 1, 2
+VAE_OUT_COLLAPSED, VAE_OUT_S32, VAE_OUT_PTC = (_C["SPK_VAE_OUT_" + n] for n in ("COLLAPSED", "S32", "PTC"))
 
 
 def vae_fp6_kind(Cin, Cout, k, stride, pad, out_pad, transposed, T, H, W):
@@ -1643,7 +1645,7 @@ def vq_argmin(flat_x, codebook):
     return idx
 
 
-VQ_USAGE_MAX_K = 4096        # spk_vq_code_usage keeps the histogram in LDS: larger codebooks take the torch ops below
+VQ_USAGE_MAX_K = _C["SPK_VQ_USAGE_MAX_K"]     # spk_vq_code_usage keeps the histogram in LDS: larger codebooks take the torch ops below
 
 
 class CodeUsage(NamedTuple):
@@ -1695,13 +1697,13 @@ def vq_code_usage(idx, K):
     packed = torch.empty(K + 3, dtype=torch.int64, device=idx.device)
     ws = torch.empty(K + 1, dtype=torch.int64, device=idx.device)
     rc = lib.spk_vq_code_usage(_p(idx), idx.numel(), K, _p(packed), _p(packed[K:]), _p(ws), _stream(idx))
-    if rc == -2 and K > VQ_USAGE_MAX_K:
+    if rc == _C["SPK_ERR_UNSUPPORTED"] and K > VQ_USAGE_MAX_K:
         return vq_code_usage_torch(idx, K)
     check(rc, "spk_vq_code_usage")
     return _code_usage_views(packed, K)
 
 
-SSIM_MAX_WINDOW = 31         # spk_ssim_mse stages a 32x32 tile plus the window's halo in LDS
+SSIM_MAX_WINDOW = _C["SPK_SSIM_MAX_WINDOW"]   # spk_ssim_mse stages a 32x32 tile plus the window's halo in LDS
 
 
 def ssim_mse_out_size(n, window_size):
@@ -2317,8 +2319,8 @@ def select_active(unmasked, t, u=None, seed=0, offset=0, philox_state=None, out=
 
 
 # ---------------------------------------------------------------------------------------------- SNN_VAE spiking MLP
-LIN_IN_F32, LIN_IN_U8, LIN_IN_PTC = 0, 1, 2
-LIN_OUT_F32, LIN_OUT_U8, LIN_OUT_PTC = 0, 1, 2
+LIN_IN_F32, LIN_IN_U8, LIN_IN_PTC = (_C["SPK_LIN_IN_" + n] for n in ("F32", "U8", "PTC"))
+LIN_OUT_F32, LIN_OUT_U8, LIN_OUT_PTC = (_C["SPK_LIN_OUT_" + n] for n in ("F32", "U8", "PTC"))
 
 
 def _linear_params(weight, bias, n_in):
