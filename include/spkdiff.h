@@ -853,6 +853,37 @@ long long spk_ssim_mse_ws_bytes(int N, int C, int H, int W, int window_size);
 int spk_ssim_mse(const float* img1, const float* img2, const float* window2d, double* ssim_sum_out, double* sq_sum_out,
                  void* ws_buf, int N, int C, int H, int W, int window_size, spk_stream_t stream);
 
+/* ---- the plain-CNN VQVAE baseline, eval path (csrc/ann_vqvae.hip) ---------------------------------------------------- */
+/* R/snn_model/vae_model.py:548-672 (main.py --model vq-vae).  fp32 products and accumulation (fmaf, one fixed order per
+ * output), deterministic, image i's result independent of B; no allocation, no synchronisation, capturable in a hipGraph.
+ * Weights in the reference modules' layouts: Conv2d [Cout,Cin,k,k], ConvTranspose2d [Cin,Cout,k,k]; codebook [K,D].
+ * spk_ann_vqvae_supported: 1 for C in {1, 3}, H == W in {28, 32}, D == SPK_ANN_VQVAE_D and 2 <= K <= SPK_ANN_VQVAE_MAX_K, else
+ * 0; the two entry points return SPK_ERR_UNSUPPORTED for every other shape.  A workgroup takes one image; a launch has at most
+ * SPK_ANN_VQVAE_GRID_CAP workgroups, which loop over the images beyond that. */
+#define SPK_ANN_VQVAE_D 16
+#define SPK_ANN_VQVAE_MAX_K 1024
+#define SPK_ANN_VQVAE_GRID_CAP 256
+int spk_ann_vqvae_supported(int C, int H, int W, int D, int K);
+/* CNN_Encoder + CNN_VectorQuantizer.get_code_indices (+ quantize) in ONE launch: images fp32 [B,C,H,W] -> idx_out int64
+ * [B*h*w] (h = H / 4), z_out fp32 [B,D,h,w] (the encoder's output) or NULL, e_out fp32 [B,D,h,w] (the chosen codebook rows) or
+ * NULL.  Conv 3x3 s2 p1 C->32 + ReLU (w1, b1), Conv 3x3 s2 p1 32->64 + ReLU (w2, b2), Conv 1x1 64->D (w3, b3); the
+ * distances are fp64 on the fp32 z and the arg min is spk_vq_argmin's (first index on ties, a NaN row gives torch.argmin's
+ * index, always in [0, K)). */
+int spk_ann_vqvae_encode(const float* images, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, const float* b3, const float* codebook, long long* idx_out, float* z_out_or_null,
+                         float* e_out_or_null, int B, int C, int H, int W, int D, int K, spk_stream_t stream);
+/* CNN_Decoder in two launches from tokens int64 [B,h,w] (the embedding gather folded in; a token outside [0, K) embeds as
+ * NaN, as in spk_embedding_fwd, and reads nothing) or from e fp32 [B,D,h,w] -- exactly one of the two is non-NULL:
+ * ConvT 3x3 s2 p1 op1 D->64 + ReLU (wt1, bt1), ConvT 3x3 s2 p1 op1 64->32 + ReLU (wt2, bt2), ConvT 3x3 s1 p1 32->C (wt3, bt3)
+ * -> x_recon_out fp32 [B,C,H,W] and, unless NULL, u8_out = uint8(clip(x_recon + 0.5, 0, 1) * 255), truncated (R/main.py:400; a
+ * NaN pixel gives 0).  ws: spk_ann_vqvae_decode_ws_bytes(B, H, W) bytes, 8-byte aligned, this call's alone while it is in
+ * flight (the second layer's output; nothing is expected of its contents).  B <= 65535. */
+long long spk_ann_vqvae_decode_ws_bytes(int B, int H, int W);
+int spk_ann_vqvae_decode(const long long* tokens_or_null, const float* e_or_null, const float* codebook, const float* wt1,
+                         const float* bt1, const float* wt2, const float* bt2, const float* wt3, const float* bt3, void* ws,
+                         long long ws_bytes, float* x_recon_out, uint8_t* u8_out_or_null, int B, int C, int H, int W, int D,
+                         int K, spk_stream_t stream);
+
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every
  * matrix-core number: devices of one pool differ by ~10 %).  nblocks workgroups of 256 threads issue 4*iters MFMAs per

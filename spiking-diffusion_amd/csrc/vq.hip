@@ -9,23 +9,12 @@
 // lowest index, and the index is always in [0, K) -- also for rows of NaN or inf.  Code indices are int64 like the
 // reference's.
 #include "spk_common.h"
+#include "vq_argmin.h"
 #include "../../include/spkdiff.h"
 
 namespace {
 
 constexpr int VQ_MAX_D = 64;
-constexpr int VQ_NONE = 0x7fffffff;                                // "no candidate yet": loses to every real code
-
-// The argmin in three parts.  A lane sees its codes in ascending order and starts from (+inf, VQ_NONE): it keeps a candidate
-// while its best is not NaN and the candidate is NaN or strictly smaller (vq_lane_takes), so it holds its first NaN, else its
-// first minimum, else -- every distance +inf -- nothing.  The lanes are combined in torch.argmin's order (vq_better: NaN first,
-// then ascending distance, then ascending index), and a row left with VQ_NONE had only +inf distances: code 0 (vq_index).
-__device__ __forceinline__ bool vq_lane_takes(double d, double b) { return b == b && !(d >= b); }
-__device__ __forceinline__ bool vq_better(double d, int k, double b, int i) {
-  if (b != b) return d != d && k < i;
-  return d != d || d < b || (d == b && k < i);
-}
-__device__ __forceinline__ int vq_index(int besti) { return besti == VQ_NONE ? 0 : besti; }
 
 // block = 256 threads = 4 waves; one wave per latent position; the codebook and its squared norms are staged in LDS once
 // per block; a position's read-out vector lives in registers (16 lane broadcasts), so the position loop has no barrier.
@@ -105,12 +94,7 @@ __global__ __launch_bounds__(256) void vq_kernel(const uint8_t* __restrict__ z, 
         if (k < K && vq_lane_takes(dist, best)) { best = dist; besti = k; }
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      double ob = __shfl_xor(best, off);
-      int oi = __shfl_xor(besti, off);
-      if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
-    }
+    vq_wave_combine(best, besti);
     besti = vq_index(besti);
     if (lane == 0) idx_out[p] = (long long)besti;
     if (zq_out && lane < D) {
@@ -179,12 +163,7 @@ __global__ __launch_bounds__(256) void vq16_kernel(const uint8_t* __restrict__ z
         const double dist = x2 + s_e2[kc] - 2.0 * dot;
         if (k < K && vq_lane_takes(dist, best)) { best = dist; besti = k; }
       }
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const double ob = __shfl_xor(best, off);
-        const int oi = __shfl_xor(besti, off);
-        if (vq_better(ob, oi, best, besti)) { best = ob; besti = oi; }
-      }
+      vq_wave_combine(best, besti);
       besti = vq_index(besti);
       if (lane == 0) idx_out[p] = (long long)besti;
       if (zq_out && lane < D) {

@@ -18,6 +18,10 @@ decoder take SNN_VQVAE's training path.
 ``SNN_VQVAE_uni`` (R/snn_model/vae_model.py:674-801) is SNN_VQVAE with ``VectorQuantizer_uni``: the same kernels, plus the
 codebook-usage statistic the quantizer computes and prints on every call, one launch of ``csrc/vq_usage.hip``.
 
+``VQVAE`` (R/snn_model/vae_model.py:548-672, the plain-CNN baseline) runs its eval forward, ``encode_images`` and
+``decode_tokens`` on ``csrc/ann_vqvae.hip``: encoder and code search one launch, decoder two.  Its modules are the reference's
+torch operators; they serve CPU tensors, hooks and the training branch.
+
 Re-exported names match what ``from snn_model.vae_model import *`` gives R/main.py (``functional`` in particular,
 R/main.py:101-107,317).
 """
@@ -658,13 +662,195 @@ class SNN_VQVAE_uni(SNN_VQVAE):
         return e, x_recon, encoding_indices
 
 
-def _not_in_scope(name):
-    class _Stub(nn.Module):
-        def __init__(self, *a, **k):
-            raise NotImplementedError(f'spkdiff: {name} is a baseline model outside the named hot path '
-                                      '(SURVEY.md §2.1 #3); only SNN_VQVAE, SNN_VQVAE_uni and SNN_VAE are implemented')
-    _Stub.__name__ = name
-    return _Stub
+# ---- VQVAE: the plain-CNN baseline (R/snn_model/vae_model.py:548-672, main.py --model vq-vae) --------------------------------
+# The ANN the paper's tables set the spiking model against.  The modules, children and state_dict keys are the reference's.  In
+# eval() on a ROCm device the forward is three launches of csrc/ann_vqvae.hip (encoder + code search: one; decoder: two); CPU
+# tensors, other dtypes, unsupported shapes and modules with hooks take the modules below, which are the reference's operators
+# in the reference's order.  train() runs those operators under autograd (mse + commitment cost + straight-through).
+
+class CNN_VectorQuantizer(nn.Module):
+    """VQ-VAE layer of the ANN baseline (R/snn_model/vae_model.py:548-605)."""
+
+    def __init__(self, embedding_dim, num_embeddings, commitment_cost):
+        super().__init__()
+        self.embedding_dim = embedding_dim
+        self.num_embeddings = num_embeddings
+        self.commitment_cost = commitment_cost
+        self.embeddings = nn.Embedding(self.num_embeddings, self.embedding_dim)
+
+    def forward(self, x):
+        x = x.permute(0, 2, 3, 1).contiguous()                      # [B, C, H, W] -> [B, H, W, C]
+        flat_x = x.reshape(-1, self.embedding_dim)
+        encoding_indices = self.get_code_indices(flat_x)
+        quantized = self.quantize(encoding_indices)
+        quantized = quantized.view_as(x)
+        if not self.training:
+            quantized = quantized.permute(0, 3, 1, 2).contiguous()
+            return quantized, encoding_indices
+        q_latent_loss = F.mse_loss(quantized, x.detach())           # moves the embeddings towards the encoder's output
+        e_latent_loss = F.mse_loss(x, quantized.detach())           # commitment loss
+        loss = q_latent_loss + self.commitment_cost * e_latent_loss
+        quantized = x + (quantized - x).detach()                    # straight-through estimator
+        quantized = quantized.permute(0, 3, 1, 2).contiguous()
+        return quantized, loss
+
+    def get_code_indices(self, flat_x):
+        distances = (
+            torch.sum(flat_x ** 2, dim=1, keepdim=True) +
+            torch.sum(self.embeddings.weight ** 2, dim=1) -
+            2. * torch.matmul(flat_x, self.embeddings.weight.t())
+        )
+        return torch.argmin(distances, dim=1)
+
+    def quantize(self, encoding_indices):
+        """Returns embedding tensor for a batch of indices."""
+        return self.embeddings(encoding_indices)
 
 
-VQVAE = _not_in_scope('VQVAE')
+class CNN_Encoder(nn.Module):
+    """Encoder of VQ-VAE"""
+
+    def __init__(self, in_dim=3, latent_dim=16):
+        super().__init__()
+        self.in_dim = in_dim
+        self.latent_dim = latent_dim
+        self.convs = nn.Sequential(
+            nn.Conv2d(in_dim, 32, 3, stride=2, padding=1),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(32, 64, 3, stride=2, padding=1),
+            nn.ReLU(inplace=True),
+            nn.Conv2d(64, latent_dim, 1),
+        )
+
+    def forward(self, x):
+        return self.convs(x)
+
+
+class CNN_Decoder(nn.Module):
+    """Decoder of VQ-VAE"""
+
+    def __init__(self, out_dim=1, latent_dim=16):
+        super().__init__()
+        self.out_dim = out_dim
+        self.latent_dim = latent_dim
+        self.convs = nn.Sequential(
+            nn.ConvTranspose2d(latent_dim, 64, 3, stride=2, padding=1, output_padding=1),
+            nn.ReLU(inplace=True),
+            nn.ConvTranspose2d(64, 32, 3, stride=2, padding=1, output_padding=1),
+            nn.ReLU(inplace=True),
+            nn.ConvTranspose2d(32, out_dim, 3, padding=1),
+        )
+
+    def forward(self, x):
+        return self.convs(x)
+
+
+def _ann_conv_is(m, cls, cin, cout, k, stride, pad, out_pad=None):
+    return (type(m) is cls and (m.in_channels, m.out_channels) == (cin, cout) and m.kernel_size == (k, k)
+            and m.stride == (stride, stride) and m.padding == (pad, pad) and m.dilation == (1, 1) and m.groups == 1
+            and m.bias is not None and (out_pad is None or m.output_padding == (out_pad, out_pad))
+            and m.padding_mode == 'zeros')
+
+
+class VQVAEConstructorError(TypeError, NotImplementedError):
+    """``VQVAE(in_dim, embedding_dim, num_embeddings)`` without ``data_variance``.  The reference's constructor raises TypeError for
+    that call (a missing positional argument), and so does this one; while the class was a stub the same call raised
+    NotImplementedError, which callers written against it catch, so the error is both."""
+
+
+_REQUIRED = object()
+
+
+class VQVAE(nn.Module):
+    """VQ-VAE"""
+
+    def __init__(self, in_dim, embedding_dim, num_embeddings, data_variance=_REQUIRED, commitment_cost=0.25):
+        if data_variance is _REQUIRED:
+            raise VQVAEConstructorError("VQVAE.__init__() missing 1 required positional argument: 'data_variance' -- it takes the "
+                                        "four arguments of SNN_VQVAE and SNN_VQVAE_uni (R/main.py:107: in_dim, embedding_dim, "
+                                        "num_embeddings, train_data_variance)")
+        super().__init__()
+        self.in_dim = in_dim
+        self.embedding_dim = embedding_dim
+        self.num_embeddings = num_embeddings
+        self.data_variance = data_variance
+
+        self.encoder = CNN_Encoder(in_dim, embedding_dim)
+        self.vq_layer = CNN_VectorQuantizer(embedding_dim, num_embeddings, commitment_cost)
+        self.decoder = CNN_Decoder(in_dim, embedding_dim)
+
+    # -- the fused path -------------------------------------------------------------------------------------------
+    def _is_reference_net(self):
+        """Are the children the reference's layers (what csrc/ann_vqvae.hip implements)?"""
+        enc, dec, D = self.encoder.convs, self.decoder.convs, self.embedding_dim
+        return (len(enc) == 5 and len(dec) == 5 and all(type(m) is nn.ReLU for m in (enc[1], enc[3], dec[1], dec[3]))
+                and _ann_conv_is(enc[0], nn.Conv2d, self.in_dim, 32, 3, 2, 1) and _ann_conv_is(enc[2], nn.Conv2d, 32, 64, 3, 2, 1)
+                and _ann_conv_is(enc[4], nn.Conv2d, 64, D, 1, 1, 0)
+                and _ann_conv_is(dec[0], nn.ConvTranspose2d, D, 64, 3, 2, 1, 1)
+                and _ann_conv_is(dec[2], nn.ConvTranspose2d, 64, 32, 3, 2, 1, 1)
+                and _ann_conv_is(dec[4], nn.ConvTranspose2d, 32, self.in_dim, 3, 1, 1, 0)
+                and type(self.vq_layer.embeddings) is nn.Embedding
+                and tuple(self.vq_layer.embeddings.weight.shape) == (self.num_embeddings, D))
+
+    def _fused(self, t, hw):
+        """Does a call on tensor ``t`` for images of size ``hw`` take csrc/ann_vqvae.hip?  ROCm device, the library supports
+        the shape, fp32 parameters on that device, the reference's layers, no hooks anywhere below (syops, monitors)."""
+        cb = self.vq_layer.embeddings.weight
+        return (t.is_cuda and cb.device == t.device and all(p.dtype == torch.float32 and p.device == t.device
+                                                            for p in self.parameters())
+                and ops.ann_vqvae_supported(self.in_dim, hw[0], hw[1], self.embedding_dim, self.num_embeddings)
+                and not has_hooks(self) and self._is_reference_net())
+
+    def _images_fused(self, x):
+        return (x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == self.in_dim
+                and self._fused(x, x.shape[2:]))
+
+    def _enc_params(self):
+        c = self.encoder.convs
+        return (c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[4].weight, c[4].bias)
+
+    def _dec_params(self):
+        c = self.decoder.convs
+        return (c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[4].weight, c[4].bias)
+
+    def forward(self, x):
+        if not self.training and self._images_fused(x):
+            B, _, H, W = x.shape
+            cb = self.vq_layer.embeddings.weight
+            enco, _, e = ops.ann_vqvae_encode(x, self._enc_params(), cb, want_e=True)
+            x_recon, _ = ops.ann_vqvae_decode(enco.view(B, H // 4, W // 4), self._dec_params(), cb)
+            return e, x_recon, enco
+        z = self.encoder(x)
+        if not self.training:
+            e, enco = self.vq_layer(z)
+            x_recon = self.decoder(e)
+            return e, x_recon, enco
+
+        e, e_q_loss = self.vq_layer(z)
+        x_recon = self.decoder(e)
+        recon_loss = F.mse_loss(x_recon, x) / self.data_variance
+        return e_q_loss, recon_loss, F.mse_loss(x_recon, x)
+
+    # ---- convenience entry points of the MI355X build (not in the reference), SNN_VQVAE's call shapes ----------------
+    @torch.no_grad()
+    def encode_images(self, images, T=16):
+        """images [B,C,H,W] already normalised (images - 0.5) -> code indices [B,h,w].  ``T`` is accepted and ignored (the
+        spiking models' callers pass it)."""
+        B, _, H, W = images.shape
+        if self._images_fused(images):
+            idx, _, _ = ops.ann_vqvae_encode(images, self._enc_params(), self.vq_layer.embeddings.weight)
+        else:
+            z = self.encoder(images).permute(0, 2, 3, 1).contiguous()
+            idx = self.vq_layer.get_code_indices(z.reshape(-1, self.embedding_dim))
+        return idx.reshape(B, H // 4, W // 4)
+
+    @torch.no_grad()
+    def decode_tokens(self, tokens, T=16, want_u8=True):
+        """tokens int64 [B,h,w] -> (pred fp32 [B,C,H,W], uint8 image = clip(pred + 0.5, 0, 1) * 255 truncated, R/main.py:400,
+        or None).  ``T`` is accepted and ignored."""
+        B, h, w = tokens.shape
+        if tokens.dtype == torch.int64 and self._fused(tokens, (4 * h, 4 * w)):
+            return ops.ann_vqvae_decode(tokens, self._dec_params(), self.vq_layer.embeddings.weight, want_u8=want_u8)
+        pred = self.decoder(self.vq_layer.quantize(tokens).permute(0, 3, 1, 2).contiguous())
+        u8 = ((pred + 0.5).clamp(0, 1) * 255).to(torch.uint8) if want_u8 else None
+        return pred, u8

@@ -37,15 +37,19 @@ def get_data_for_diff(train_loader, model, T: int = 16, carry_state: bool = True
     batch, R/load_dataset_snn.py:65-66).  ``carry_state=True`` (default) is that call sequence on the fused module path
     -- same indices as the reference (fixture F12), same module state afterwards; a batch of another size raises, as it
     does there.  ``carry_state=False`` encodes every batch from the reset state with the encoder alone (time-invariant
-    input folded into the first kernel; nothing of the module state is read or written)."""
+    input folded into the first kernel; nothing of the module state is read or written).
+
+    The plain-CNN ``VQVAE`` (main.py --model vq-vae) has no state to carry and takes one argument -- the reference's
+    two-argument call raises TypeError for it --: it is encoded with ``encode_images`` whatever ``carry_state`` says."""
     print('prepare data for train diffusion...')
     model.eval()
     train_indices = []
     dev = next(model.parameters()).device
+    stateless = isinstance(model, VQVAE)
     for images, labels in train_loader:
         images = (images - 0.5).to(dev).float().contiguous()  # normalize to [-0.5, 0.5]
         with torch.inference_mode():
-            if carry_state:
+            if carry_state and not stateless:
                 images_spike = images.unsqueeze(0).repeat(T, 1, 1, 1, 1)
                 _, _, encoding_indices = model(images_spike, images)
                 L = images.shape[-1] // 4

@@ -34,9 +34,11 @@ def aggregate(per_batch_ssim_loss, per_batch_mse):
 
 def reconstruction_eval(model, batches, T=16, window_size=11):
     """``batches`` yields ``images`` in [0, 1] ([B,C,H,W]) or ``(images, labels)``; ``model`` is an eval-mode SNN_VQVAE,
-    SNN_VQVAE_uni (three outputs) or SNN_VAE (two outputs) on a ROCm device.  Returns {"loss_ssim", "loss_mse" (unrounded
+    SNN_VQVAE_uni (three outputs), SNN_VAE (two outputs) or the plain-CNN VQVAE (called with the images alone, R/main.py:311)
+    on a ROCm device.  Returns {"loss_ssim", "loss_mse" (unrounded
     means), "loss_ssim_rounded", "loss_mse_rounded" (what main.py prints), "n_batches"}.  The last batch may be smaller."""
     from metric.pytorch_ssim import create_window
+    from snn_model.vae_model import VQVAE
     from spikingjelly.activation_based import functional
 
     device = next(model.parameters()).device
@@ -48,9 +50,12 @@ def reconstruction_eval(model, batches, T=16, window_size=11):
         for batch in batches:
             images = batch[0] if isinstance(batch, (tuple, list)) else batch
             norm_images = (images - 0.5).to(device)
-            images_spike = norm_images.unsqueeze(0).repeat(T, 1, 1, 1, 1)
-            recon_images = model(images_spike, norm_images)[1]
-            functional.reset_net(model)
+            if isinstance(model, VQVAE):                # (the ANN baseline: one argument, no neuron state to reset)
+                recon_images = model(norm_images)[1]
+            else:
+                images_spike = norm_images.unsqueeze(0).repeat(T, 1, 1, 1, 1)
+                recon_images = model(images_spike, norm_images)[1]
+                functional.reset_net(model)
             N, C, H, W = norm_images.shape
             i = len(denoms)
             if i % 64 == 0:

@@ -2659,3 +2659,90 @@ class LatentLossFunction(torch.autograd.Function):
             check(lib.spk_svae_latent_loss_bwd(_p(q), _p(p), _p(idx), _p(gl), _p(gs), _p(gq), _p(gp), T, B, cz, k, ctx.tau_s,
                                                _stream(q)), "spk_svae_latent_loss_bwd")
         return gq, gp, None, None
+
+
+# ---------------------------------------------------------------------------------------------- the plain-CNN VQVAE baseline
+# csrc/ann_vqvae.hip: the encoder + code search in one launch, the decoder in two.  A workgroup takes one image and a launch has
+# at most ANN_VQVAE_GRID_CAP workgroups, which loop over the images beyond that (the batch sizes the tests make special).
+ANN_VQVAE_D = _C["SPK_ANN_VQVAE_D"]
+ANN_VQVAE_MAX_K = _C["SPK_ANN_VQVAE_MAX_K"]
+ANN_VQVAE_GRID_CAP = _C["SPK_ANN_VQVAE_GRID_CAP"]
+ANN_VQVAE_GROUP = 1                # images a workgroup works on at a time
+
+
+def ann_vqvae_supported(C, H, W, D, K):
+    """Do spk_ann_vqvae_encode / _decode take images [*,C,H,W], embedding_dim D and K codes?  Host-only: no device needed."""
+    return bool(lib.spk_ann_vqvae_supported(int(C), int(H), int(W), int(D), int(K)))
+
+
+def _ann_params(params, n, what):
+    if len(params) != n:
+        raise ValueError(f"{what}: expected {n} weight / bias tensors, got {len(params)}")
+    return [_dev(p.detach(), f"{what} parameter {i}", torch.float32) for i, p in enumerate(params)]
+
+
+def ann_vqvae_encode(images, enc_params, codebook, want_z=False, want_e=False):
+    """images fp32 [B,C,H,W]; enc_params = (w1, b1, w2, b2, w3, b3) of CNN_Encoder.convs.{0,2,4}; codebook [K,D] ->
+    (indices int64 [B*h*w], z fp32 [B,D,h,w] or None, e fp32 [B,D,h,w] or None), h = H / 4.  One launch."""
+    images = _dev(images, "images", torch.float32)
+    if images.dim() != 4:
+        raise ValueError(f"ann_vqvae_encode: images must be [B,C,H,W], got {tuple(images.shape)}")
+    w1, b1, w2, b2, w3, b3 = _ann_params(enc_params, 6, "ann_vqvae_encode")
+    codebook = _dev(codebook.detach(), "codebook", torch.float32)
+    B, C, H, W = images.shape
+    K, D = codebook.shape
+    if (tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)) != ((32, C, 3, 3), (64, 32, 3, 3), (D, 64, 1, 1)):
+        raise ValueError("ann_vqvae_encode: the weights are not CNN_Encoder's for these images and this codebook")
+    h, w = H // 4, W // 4
+    idx = torch.empty(B * h * w, dtype=torch.int64, device=images.device)
+    z = torch.empty((B, D, h, w), dtype=torch.float32, device=images.device) if want_z else None
+    e = torch.empty((B, D, h, w), dtype=torch.float32, device=images.device) if want_e else None
+    check(lib.spk_ann_vqvae_encode(_p(images), _p(w1), _p(b1), _p(w2), _p(b2), _p(w3), _p(b3), _p(codebook), _p(idx), _p(z),
+                                   _p(e), B, C, H, W, D, K, _stream(images)), "spk_ann_vqvae_encode")
+    return idx, z, e
+
+
+def ann_vqvae_decode_ws(B, H, W, device):
+    """A workspace for ann_vqvae_decode calls of this shape (the second layer's output)."""
+    nbytes = int(lib.spk_ann_vqvae_decode_ws_bytes(int(B), int(H), int(W)))
+    if nbytes < 0:
+        check(nbytes, "spk_ann_vqvae_decode_ws_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def ann_vqvae_decode(code, dec_params, codebook, want_u8=False, ws=None):
+    """code: tokens int64 [B,h,w] (the embedding gather folded in; a token outside [0, K) gives NaN pixels where it reaches)
+    or e fp32 [B,D,h,w]; dec_params = (wt1, bt1, wt2, bt2, wt3, bt3) of CNN_Decoder.convs.{0,2,4}; codebook [K,D] ->
+    (x_recon fp32 [B,C,H,W], uint8(clip(x_recon + 0.5, 0, 1) * 255) or None).  Two launches.  ``ws``: a workspace of
+    ``ann_vqvae_decode_ws`` to reuse (this call's alone while it is in flight)."""
+    wt1, bt1, wt2, bt2, wt3, bt3 = _ann_params(dec_params, 6, "ann_vqvae_decode")
+    codebook = _dev(codebook.detach(), "codebook", torch.float32)
+    K, D = codebook.shape
+    C = wt3.shape[1]
+    if (tuple(wt1.shape), tuple(wt2.shape), tuple(wt3.shape)) != ((D, 64, 3, 3), (64, 32, 3, 3), (32, C, 3, 3)):
+        raise ValueError("ann_vqvae_decode: the weights are not CNN_Decoder's for this codebook")
+    if code.dtype == torch.int64:
+        code = _dev(code, "tokens", torch.int64)
+        if code.dim() != 3:
+            raise ValueError(f"ann_vqvae_decode: tokens must be [B,h,w], got {tuple(code.shape)}")
+        tokens, e = code, None
+        B, h, w = code.shape
+    else:
+        code = _dev(code, "e", torch.float32)
+        if code.dim() != 4 or code.shape[1] != D:
+            raise ValueError(f"ann_vqvae_decode: e must be [B,{D},h,w], got {tuple(code.shape)}")
+        tokens, e = None, code
+        B, _, h, w = code.shape
+    H, W = 4 * h, 4 * w
+    nbytes = int(lib.spk_ann_vqvae_decode_ws_bytes(B, H, W))
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=code.device)
+    elif not (ws.is_cuda and ws.device == code.device and ws.is_contiguous() and ws.data_ptr() % 8 == 0
+              and ws.numel() * ws.element_size() >= nbytes):
+        raise ValueError(f"ann_vqvae_decode: ws must be a contiguous 8-byte aligned device buffer of at least {nbytes} bytes")
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=code.device)
+    u8 = torch.empty((B, C, H, W), dtype=torch.uint8, device=code.device) if want_u8 else None
+    check(lib.spk_ann_vqvae_decode(_p(tokens), _p(e), _p(codebook), _p(wt1), _p(bt1), _p(wt2), _p(bt2), _p(wt3), _p(bt3), _p(ws),
+                                   ws.numel() * ws.element_size(), _p(out), _p(u8), B, C, H, W, D, K, _stream(code)),
+          "spk_ann_vqvae_decode")
+    return out, u8

@@ -185,6 +185,46 @@ def synth_denoiser_state(cfg: PathConfig = MNIST, seed: int = 4321, calib_batch:
     return {k: v.contiguous() for k, v in sd.items()}
 
 
+def synth_ann_vqvae_state(cfg: PathConfig = MNIST, seed: int = 2468, K: int = 128, calib_batch: int = 64) -> dict:
+    """Synthetic ``VQVAE`` state_dict (the plain-CNN baseline, R/snn_model/vae_model.py:548-672; keys ``encoder.convs.{0,2,4}.*``,
+    ``vq_layer.embeddings.weight``, ``decoder.convs.{0,2,4}.*``).  The codebook is K encoder outputs of a calibration batch of
+    ``stroke_images`` (another seed than any test's images) plus a small jitter: default-initialised N(0, 1) rows are all far
+    from the encoder's outputs and one code would win everywhere.  The last decoder layer is rescaled so that the reconstruction
+    of the calibration batch spans [-0.55, 0.55]: the uint8 image uses its whole range and clips at both ends."""
+    sd: dict = {}
+    D = cfg.latent_dim
+    _conv_params(sd, "encoder.convs.0", 32, cfg.in_dim, 3, seed)
+    _conv_params(sd, "encoder.convs.2", 64, 32, 3, seed)
+    _conv_params(sd, "encoder.convs.4", D, 64, 1, seed)
+    sd["vq_layer.embeddings.weight"] = torch.zeros(K, D)
+    _conv_params(sd, "decoder.convs.0", 64, D, 3, seed, transposed=True)
+    _conv_params(sd, "decoder.convs.2", 32, 64, 3, seed, transposed=True)
+    _conv_params(sd, "decoder.convs.4", cfg.in_dim, 32, 3, seed, transposed=True)
+
+    cal = stroke_images(calib_batch, seed=seed + 1, img=cfg.img, channels=cfg.in_dim) - 0.5
+    p = "encoder.convs."
+    z = F.relu(F.conv2d(cal, sd[p + "0.weight"], sd[p + "0.bias"], 2, 1))
+    z = F.relu(F.conv2d(z, sd[p + "2.weight"], sd[p + "2.bias"], 2, 1))
+    z = F.conv2d(z, sd[p + "4.weight"], sd[p + "4.bias"])
+    flat = z.permute(0, 2, 3, 1).reshape(-1, D)
+    if flat.shape[0] < K:
+        raise ValueError(f"synth_ann_vqvae_state: {calib_batch} calibration images give {flat.shape[0]} latent rows, fewer than K = {K}")
+    pick = torch.randperm(flat.shape[0], generator=_gen(seed, "ann.codebook.pick"))[:K]
+    cb = (flat[pick] + 0.01 * torch.randn(K, D, generator=_gen(seed, "ann.codebook.jitter"))).contiguous()
+    sd["vq_layer.embeddings.weight"] = cb
+    d = (flat ** 2).sum(1, keepdim=True) + (cb ** 2).sum(1) - 2.0 * flat @ cb.t()
+    q = cb[d.argmin(1)].view(calib_batch, cfg.latent, cfg.latent, D).permute(0, 3, 1, 2)
+    p = "decoder.convs."
+    y = F.relu(F.conv_transpose2d(q, sd[p + "0.weight"], sd[p + "0.bias"], 2, 1, 1))
+    y = F.relu(F.conv_transpose2d(y, sd[p + "2.weight"], sd[p + "2.bias"], 2, 1, 1))
+    y = F.conv_transpose2d(y, sd[p + "4.weight"], sd[p + "4.bias"], 1, 1)
+    lo, hi = float(y.min()), float(y.max())
+    a = 1.1 / (hi - lo)
+    sd[p + "4.weight"] = sd[p + "4.weight"] * a
+    sd[p + "4.bias"] = sd[p + "4.bias"] * a + (-0.55 - a * lo)
+    return {k: v.contiguous() for k, v in sd.items()}
+
+
 SVAE_LATENT, SVAE_K = 56, 20          # R/snn_model/vae_model.py:203-208 (latent_dim = 28*2, k = 20)
 
 
