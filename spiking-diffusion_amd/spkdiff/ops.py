@@ -795,7 +795,11 @@ def s32_to_spikes(q):
 def count_spikes(t: torch.Tensor):
     """Spike statistics of a tensor in any storage format of this library, counted on the device (spk_count_spikes):
     dict(total, t0, numel, numel_t0, binary).  fp32 [T, ...] (the reference interface; ``binary`` = every nonzero entry is
-    exactly 1.0), u8 PTC [B,H,W,T,C] / CPTC [B,C/ch,H,W,T,ch], int8-tagged C4 / S32 [B,C/rec_ch,H,W,T,rec]."""
+    exactly 1.0), u8 PTC [B,H,W,T,C] / CPTC [B,C/ch,H,W,T,ch], int8-tagged C4 / S32 [B,C/rec_ch,H,W,T,rec].
+    ``numel`` is the tensor's CAPACITY: for C4 / S32 it counts record slots (64 / 32 per record), not channels that a layer
+    drives -- the S32 spikes of a 16-channel spike generator report 32 slots per (position, step), half of them never set, so
+    ``total / numel`` there is half the generator's firing rate.  Divide by the channel count you know, not by ``numel``, when
+    a record is partly filled.  -0.0 is no spike in an fp32 tensor; NaN and denormals are (and make ``binary`` False)."""
     if not t.is_cuda:
         raise RuntimeError(f"spkdiff: tensor on '{t.device}'; there is no CPU path")
     t = t if t.is_contiguous() else t.contiguous()
