@@ -73,6 +73,18 @@ __device__ __forceinline__ void spk_dma16s_masked(const void* sbase, unsigned vo
 __device__ __forceinline__ void spk_dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ unsigned spk_lds_addr(const void* p) { return (unsigned)(size_t)SPK_LDS(p); }
 
+// The block-scaled fp4 x fp6 MFMA of den_mfma_fp6.hip and den_mfma_fp6v2.hip as inline assembly (explicit register classes):
+// D = A(32 x 64 fp4) * B(64 x 32 fp6) + C, accumulator in AGPRs ("a") or VGPRs ("v"); *_Z: C = 0 (first MFMA of an item).
+// s_nop 1: the two wait states between a VALU write of an operand register (the B fragment hand-over is v_mov) and
+// the MFMA that reads it, which hipcc's hazard recognizer cannot insert around inline assembly.
+#define SPK_FP6_PRE "s_nop 1\n\t"
+#define SPK_MFMA_FP6(CLS, acc, av, bv, sa, sb)                                                                       \
+  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"  \
+               : "+" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
+#define SPK_MFMA_FP6_Z(CLS, acc, av, bv, sa, sb)                                                                     \
+  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"   \
+               : "=&" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
+
 // Layout of the position-list buffer written by spk_select_needed (psample.hip) and read by the listed form of the fp6v2
 // kernel, for B image slots and R radii.  Bytes: [0, 64) header (u32 ticket of the list-building pass); per radius 16 int32
 // (slots per tile-count class 1..6); per radius 6 x B int32 (the slots of each class); per radius B 64-byte records.

@@ -52,17 +52,6 @@ struct Fp6Args {
   int gx;      // > 0: XCD-aware item walk with gx channel groups per XCD (see the kernel); 0: image-major
 };
 
-// D = A(32 x 64 fp4) * B(64 x 32 fp6) + C, accumulator in AGPRs ("a") or VGPRs ("v"); *_Z: C = 0 (first MFMA of an item).
-// s_nop 1: the two wait states between a VALU write of an operand register (the B fragment hand-over is v_mov) and
-// the MFMA that reads it, which hipcc's hazard recognizer cannot insert around inline assembly.
-#define SPK_FP6_PRE "s_nop 1\n\t"
-#define SPK_MFMA_FP6(CLS, acc, av, bv, sa, sb)                                                                       \
-  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"  \
-               : "+" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
-#define SPK_MFMA_FP6_Z(CLS, acc, av, bv, sa, sb)                                                                     \
-  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"   \
-               : "=&" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
-
 constexpr int SPK_FP6_PF = 4;         // A fragments in flight ahead of the MFMA that consumes them
 constexpr int SPK_FP6_DMA_EVERY = 2;  // one piece every second step: all 18 are issued in the first 60 % of a chunk and land before its end
 // NT = row tiles per wave: 6 when H*W is odd and H*W / 2 <= 24 (7x7: 24 tiles of 2 positions, no padding rows; the last

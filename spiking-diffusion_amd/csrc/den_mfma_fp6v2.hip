@@ -19,6 +19,8 @@
 //    membrane potential ever comes within D_t of the threshold (1 - 6e-4 of the neurons at the denoiser's firing rates of
 //    3 - 7 %).  The fixup launch recomputes the flagged neurons EXACTLY (all six digits as the pack kernel's int32 quantised
 //    weights, 64-bit sums, fp64 recombination, one rounding: the arithmetic of den_mfma_fp6.hip) and patches their spikes.
+//    The flag workspace with its protocol (flag, hand-over, scan), the pieces of that recomputation and the weight tile format are
+//    shared with vae_fp6.hip: cert_common.h.
 //    Unflagged neurons provably emit the spikes the exact arithmetic would; flagged ones are the exact arithmetic.  Membrane
 //    potentials are not an output here (fresh state in, nothing written back): callers that carry LIF state, and the
 //    training forward, use den_mfma_fp6.hip.  (The earlier form, five digits on the matrix cores -- 23 MFMAs, the fifth
@@ -31,23 +33,15 @@
 // Spike layout "S32": [B][C/32][H*W][T = 16][16 B], channel c of a group in byte (c % 32) / 2, low nibble first, e2m1 codes
 // 0x0 / 0x2.  The last position of a 7x7 latent (the 49th: 24 full 32-row tiles + 1) is computed exactly by the tail
 // launch from the same packed weights plus two sixth-digit tiles stored for its four taps.
-#include "den_common.h"
+#include "cert_common.h"
 #include "../../include/spkdiff.h"
-#include <math.h>
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-typedef int v6i __attribute__((ext_vector_type(6)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int T16 = 16;
-constexpr int CK = 32;                                   // input channels per K chunk
-constexpr int POSB = T16 * CK / 2;                       // 256 B per latent position per chunk
-constexpr int WT = 64 * 24;                              // one B tile: 64 lanes x 32 six-bit codes
+constexpr int CK = 32;                                   // input channels per K chunk: POSB = T16 * CK / 2 bytes per latent position
 constexpr int N_PAIR = 18;                               // tiles 0..17: (tap, digit pair 01 | 23)
 constexpr int N_D4 = 5;                                  // tiles 18..22: fifth digit, taps (0,1) (2,3) (4,5) (6,7) (8,-)
 constexpr int N_MAIN = N_PAIR + N_D4;
@@ -57,21 +51,12 @@ constexpr int W_PIECES = (N_PAIR * WT + 1023) / 1024;    // one-KiB DMA pieces p
 constexpr int W_LDS = W_PIECES * 1024;
 constexpr int W_SLAB = ((N_MAIN + N_L5) * WT + 1023) / 1024 * 1024;   // bytes per (channel group, chunk) in memory
 
-// Workspace layout (spk_den_fp6v2_flag_words): ws[0] live count of flagged neurons, ws[1] the count published for the tail launch,
-// ws[2 .. 2 + FLAG_CAP) their ids, then the overflow bitmap (one bit per neuron of the layer), then the hand-over ticket.  The id list
-// holds the first `flag_cap` <= FLAG_CAP flagged neurons of a launch (a per-call argument: the parity suite runs the overflow path with
-// 64 and 0); every further one sets its bit in the bitmap, which the tail launch scans and clears.  The LAYOUT never depends on flag_cap.
-constexpr unsigned FLAG_CAP = 1u << 20;
-
 struct V2Args {
   const uint8_t* in0; int nch;               // S32 spikes, nch = Cin / 32
   const uint8_t* wq; const double* scale; const double* bias; const float* wl1;
   const float* bn_a; const float* bn_b;
   uint8_t* out; uint8_t* out_cnt;
-  unsigned* flags;                           // ws[0]: number of flagged neurons (live), ws[1]: the count of the last finished
-                                             //  launch (published by the hand-over or the re-arming), ws[2..2+cap): their ids,
-  unsigned flag_cap;                         //  then the overflow bitmap (one bit per neuron; used only beyond cap), then the
-  long long ticket_idx;                      //  ticket of the hand-over (ws[1] = the count published for the tail launch)
+  CertWs ws;                                 // the flag workspace (cert_common.h, spk_den_fp6v2_flag_words)
   int handover;                              // 1: the main launch publishes the count (fp6v2_handover); 0: the tail launches read
                                              //    ws[0] and the last-position launch, which follows the repair launch, re-arms it
   const int* qtab;                           // quantised weights int32 [Cout][9][Cin] (exact recomputation)
@@ -82,14 +67,6 @@ struct V2Args {
   int B, Cout, Cin;
   int gx, nsets;                             // XCD-aware walk (gx > 0) or flat walk (gx == 0)
 };
-
-#define SPK_FP6_PRE "s_nop 1\n\t"
-#define SPK_MFMA2(CLS, acc, av, bv, sa, sb)                                                                          \
-  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"  \
-               : "+" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
-#define SPK_MFMA2_Z(CLS, acc, av, bv, sa, sb)                                                                        \
-  asm volatile(SPK_FP6_PRE "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:2"   \
-               : "=&" CLS(acc) : "v"(av), "v"(bv), "v"(sa), "v"(sb))
 
 constexpr int SPK_V2_KMIN = 2;          // listed positions: an item of fewer tiles per wave still costs about this many (operand copies)
 constexpr float SPK_V2_SPARE = 1.0f;    // factor on the certification bound (2.0f = the first builds' spare factor)
@@ -132,8 +109,7 @@ constexpr int SPK_V2_PF = 6;            // four-wave items: A fragments requeste
 // The epilogue uses the closed form of the same recursion, dh_t <= max c + 8 eps max |z| (|v| <= max |z|), WITHOUT the spare factor --
 // the digit term of c_t is exact (528 is the largest residue there is), eps already holds every rounding 2.5-4 times over, and
 // the number of flagged neurons (the repair launch: 7 % of a dense reverse step) is proportional to the bound.  Every
-// unflagged neuron provably emits the exact path's spikes; flagged ones are recomputed exactly.
-constexpr float CERT_4EPS = 4.0f * 2.38418579e-07f;
+// unflagged neuron provably emits the exact path's spikes; flagged ones are recomputed exactly.  (CERT_4EPS = 4 eps: cert_common.h)
 
 // Store the spikes of one 32-row tile: every lane holds the 16 step bits of its neuron (channel = lane & 31 of the group,
 // position = its lane half); a 16x16 bit transpose per 16-lane row gives lane t the 16 channel bits of step t = 8 bytes of
@@ -578,11 +554,11 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
 #define V2_PAIR_MFMA(J)                                                                                      \
 do {                                                                                                        \
   if constexpr (FIRST && blk == 0) {                                                                        \
-    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA2_Z("a", acc[i][J], av, bp[0][J], sc_a, sc_p);              \
-    else SPK_MFMA2_Z("v", acc[i][J], av, bp[0][J], sc_a, sc_p);                                             \
+    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA_FP6_Z("a", acc[i][J], av, bp[0][J], sc_a, sc_p);              \
+    else SPK_MFMA_FP6_Z("v", acc[i][J], av, bp[0][J], sc_a, sc_p);                                             \
   } else {                                                                                                  \
-    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA2("a", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);          \
-    else SPK_MFMA2("v", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);                                         \
+    if constexpr (NACC * i + (J) < N_AGPR) SPK_MFMA_FP6("a", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);          \
+    else SPK_MFMA_FP6("v", acc[i][J], av, bp[blk & 1][J], sc_a, sc_p);                                         \
   }                                                                                                         \
 } while (0)
           V2_PAIR_MFMA(0);
@@ -674,7 +650,6 @@ do {                                                                            
       // digits move z_t by at most c_t = cE + cT n_t (n_t active inputs of the row).  D_t = D_{t-1} / 2 + c_t + 4 eps (|z_t| +
       // |v_{t-1}|) and |v| <= max |z| give D_t <= 2 (cE + cT max_t n_t) + 16 eps max_t |z_t| for every t: track max |z|,
       // max n and min |h - 1| (three instructions per step instead of eight) and compare once, against dh = D / 2
-      typedef float v2f __attribute__((ext_vector_type(2)));
       float zmax = 0.f, dmin = 3.0e38f;
       int nmax = nmax_rec;
 #pragma unroll
@@ -736,12 +711,7 @@ do {                                                                            
       // position there: computed and dropped
       const int p = (PRUNE || BSKIP) ? p_out[i] : 2 * ti + half + band * HWb;
       const bool listed = !PRUNE || 2 * ti + half < n_list;
-      if (flg && listed) {
-        const long long n = ((long long)b * a.Cout + co) * HW + p;
-        const unsigned idx = atomicAdd(a.flags, 1u);
-        if (idx < a.flag_cap) a.flags[2 + idx] = (unsigned)n;
-        else atomicOr(a.flags + 2 + FLAG_CAP + (n >> 5), 1u << (n & 31));
-      }
+      if (flg && listed) spk_cert_flag(a.ws, ((long long)b * a.Cout + co) * HW + p);
       const long long rec = (((long long)b * G + g) * HW + p) * POSB;
       store_tile_spikes(a.out, a.out_cnt, mybits, lane, rec, (((long long)b * G + g) * HW + p) * 32, listed);
       __builtin_amdgcn_sched_barrier(0);
@@ -768,24 +738,13 @@ __device__ __forceinline__ void fp6v2_wg_map(const V2Args& a, int& g, int& il, i
   }
 }
 
-// Hand-over to the tail launch: the workgroup that finishes last publishes the number of flagged neurons (ws[1]) and re-arms
-// the live counter (ws[0]) for the next layer's main launch.  The workgroups of a main launch finish at different times, so
-// this ticket costs nothing -- and the tail launch then needs no ordering between its repair part (which reads the count)
-// and anything that resets it: repair and last position run as ONE launch.
+// Hand-over to the tail launch (spk_cert_handover): the tail launch then needs no ordering between its repair part (which reads the
+// count) and anything that resets it: repair and last position run as ONE launch.
 __device__ __forceinline__ void fp6v2_handover(const V2Args& a) {
   if (!a.handover) return;
-  // (no fence: every atomicAdd on the counter has RETURNED before its wave reaches the barrier, the count is read back with
-  //  an atomic, and list entries are plain stores read by the next launch -- a __threadfence here cost 4.5 us per launch)
   __syncthreads();
-  if (threadIdx.x == 0) {
-    if (atomicAdd(a.flags + a.ticket_idx, 1u) == gridDim.x - 1) {
-      a.flags[1] = atomicAdd(a.flags, 0u);
-      a.flags[0] = 0u;
-      a.flags[a.ticket_idx] = 0u;
-    }
-  }
+  if (threadIdx.x == 0) spk_cert_handover(a.ws);
 }
-
 
 template <int H, int W, int NWV, bool SPLIT = false>
 __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_kernel(V2Args a) {
@@ -876,7 +835,6 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_listed_kernel(V2Arg
 //     halves are the images), its waves splitting the K chunks; the four taps that reach position (H-1, W-1) from inside
 //     the image; operands straight from L2; all six digits (the two sixth-digit tiles of the slab), fp64 recombination.
 // (2) the flagged neurons of the main launch, exactly (fixup_neuron / fp6v2_fixup_kernel below).
-__device__ __forceinline__ float exact_preact(double s, double sc, double bi) { return (float)fma(s, sc, bi); }
 
 // red: ONE [3][16][64] buffer (the partial sums of waves 1 .. 3 pass through it one after the other: the merged tail launch
 // keeps eight workgroups on a CU) or, WIDE, three of them (one barrier: the stand-alone launch of full batches)
@@ -887,7 +845,7 @@ __device__ __forceinline__ void fp6v2_lastpos_body(const V2Args& a, const int bi
   const int nch = a.nch, G = a.Cout >> 5;
   const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
   // (without the hand-over this launch follows the repair launch on the stream and re-arms the flag counter)
-  if (!a.handover && bid == 0 && threadIdx.x == 0) { a.flags[1] = a.flags[0]; a.flags[0] = 0u; }
+  if (!a.handover && bid == 0 && threadIdx.x == 0) { a.ws.flags[1] = a.ws.flags[0]; a.ws.flags[0] = 0u; }
   // one unit = NP 32-row tiles = NP image pairs (the lane halves of a tile are the two images) x one channel group: the
   // weight tiles of a chunk are read ONCE for all of them (with one pair per unit the launch moved 327 MB of weight tiles
   // through L2 for the 256 -> 512 layer at B = 256: bound by that).  The four waves of a workgroup split the K chunks
@@ -1055,22 +1013,10 @@ __device__ __forceinline__ void fixup_neuron(const V2Args& a, long long n, unsig
     const int4* qp = reinterpret_cast<const int4*>(a.qtab + ((long long)co * 9 + tap) * Cin + cc * 32);
     const unsigned w4[4] = {sp.x, sp.y, sp.z, sp.w};
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int4 q = qp[j];
-      const unsigned nib = w4[j >> 1] >> (16 * (j & 1));     // four nibbles: channels 4j .. 4j + 3
-      part += (nib & 0x000fu) ? (long long)q.x : 0ll;
-      part += (nib & 0x00f0u) ? (long long)q.y : 0ll;
-      part += (nib & 0x0f00u) ? (long long)q.z : 0ll;
-      part += (nib & 0xf000u) ? (long long)q.w : 0ll;
-    }
+    for (int j = 0; j < 4; ++j) spk_cert_add_active8(part, w4[j], qp[2 * j], qp[2 * j + 1]);     // channels 8j .. 8j + 7
   }
   // lanes l, l + 16, l + 32, l + 48 of a wave hold the same time step (t = u & 15; the block size is a multiple of 64)
-#pragma unroll
-  for (int off = 16; off <= 32; off <<= 1) {
-    const int lo = __shfl_xor((int)(unsigned)(part & 0xffffffffll), off);
-    const int hi = __shfl_xor((int)(part >> 32), off);
-    part += (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-  }
+  part = spk_cert_sum_quarters(part);
   if (lane < 16 && part != 0) atomicAdd(&sS[lane], (unsigned long long)part);
   __syncthreads();
   if (tid < 64) {
@@ -1086,11 +1032,7 @@ __device__ __forceinline__ void fixup_neuron(const V2Args& a, long long n, unsig
     const int g = co >> 5;
     if (lane < 16) {
       uint8_t* rec = a.out + ((((long long)b * (a.Cout >> 5) + g) * HW + p) * POSB);
-      const int byte = (co & 31) >> 1;
-      const unsigned shw = 8u * (byte & 3) + 4u * (co & 1);
-      unsigned* wp = reinterpret_cast<unsigned*>(rec + lane * 16 + (byte & ~3));
-      atomicAnd(wp, ~(0xFu << shw));
-      if ((bits >> lane) & 1u) atomicOr(wp, 0x2u << shw);
+      spk_cert_patch_nibble(rec + lane * 16, co, (bits >> lane) & 1u);
     }
     if (a.out_cnt && lane == 0) a.out_cnt[(((long long)b * (a.Cout >> 5) + g) * HW + p) * 32 + (co & 31)] = (uint8_t)__popc(bits);
   }
@@ -1101,26 +1043,9 @@ template <int H, int W>
 __device__ __forceinline__ void fp6v2_fixup_body(const V2Args& a, long long n_words, const unsigned bid, const unsigned nb,
                                                  unsigned long long* sS) {
   const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
-  const unsigned count = a.flags[a.handover ? 1 : 0];       // published by the main launch (fp6v2_handover), or live
-  const unsigned nlist = count < a.flag_cap ? count : a.flag_cap;
-  for (unsigned e = bid; e < nlist; e += nb) fixup_neuron<H, W>(a, (long long)a.flags[2 + e], sS, Bn);
-  if (count > a.flag_cap) {
-    // overflow path (more than flag_cap flagged neurons): the rest sit in the bitmap; scan a share of it, clear as we go
-    unsigned* bm = a.flags + 2 + FLAG_CAP;
-    const long long per = (n_words + nb - 1) / nb;
-    const long long w0 = (long long)bid * per;
-    const long long w1 = w0 + per < n_words ? w0 + per : n_words;
-    for (long long wi = w0; wi < w1; ++wi) {
-      unsigned wv = bm[wi];                                // (uniform over the workgroup)
-      __syncthreads();
-      if (threadIdx.x == 0 && wv) bm[wi] = 0u;
-      while (wv) {
-        const int bit = __ffs((int)wv) - 1;
-        wv &= wv - 1;
-        fixup_neuron<H, W>(a, wi * 32 + bit, sS, Bn);
-      }
-    }
-  }
+  const unsigned count = a.ws.flags[a.handover ? 1 : 0];       // published by the main launch (fp6v2_handover), or live
+  spk_cert_scan<true>(a.ws, count, bid, nb, n_words, threadIdx.x == 0,
+                      [&](long long n) __attribute__((always_inline)) { fixup_neuron<H, W>(a, n, sS, Bn); });
 }
 
 // (1b) Round 5: the last position with the weight tiles SHARED through LDS.  fp6v2_lastpos_body reads the thirteen tiles of every
@@ -1195,7 +1120,7 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
       const v2i by = *reinterpret_cast<const v2i*>(wt + 1024 + lane * 8);
       return v6i{bx[0], bx[1], bx[2], bx[3], by[0], by[1]};
     };
-    auto mm = [&](v16f& d, const v4i& av, const v6i& bv, int sb) { SPK_MFMA2("v", d, av, bv, sc_a, sb); };
+    auto mm = [&](v16f& d, const v4i& av, const v6i& bv, int sb) { SPK_MFMA_FP6("v", d, av, bv, sc_a, sb); };
     // (fences: at most four tiles in flight -- left alone hipcc requests all thirteen first: 188 registers, two workgroups per CU)
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -1267,10 +1192,9 @@ __global__ __launch_bounds__(256, PART == 3 ? 4 : 1) void fp6v2_tail_kernel(V2Ar
 
 // ------------------------------------------------------------------------------------------------ weight packing
 // one block per output channel: channel maximum -> shift s, every weight -> six balanced radix-32 digits, written as the
-// per-lane 24-byte B fragments (lane = K half * 32 + channel within the group of 32; 32 six-bit codes, little-endian;
-// bytes 0..15 in the ds_read_b128 part of the tile, 16..23 in its ds_read_b64 part).  Tile order per (group, 32-channel
-// chunk): (tap, pair) x 18 [K half 0: even digit, half 1: odd digit, same 32 input channels], fifth digit x 5 [K half 0:
-// tap 2q, half 1: tap 2q + 1], sixth digit x 2 [taps (0, 1) and (3, 4)].  Also the L1 norm of the quantised weights.
+// per-lane 24-byte B fragments (spk_cert_emit_fragment: lane = K half * 32 + channel within the group of 32).  Tile order per
+// (group, 32-channel chunk): (tap, pair) x 18 [K half 0: even digit, half 1: odd digit, same 32 input channels], fifth digit
+// x 5 [K half 0: tap 2q, half 1: tap 2q + 1], sixth digit x 2 [taps (0, 1) and (3, 4)].  Also the L1 norm of the quantised weights.
 __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict__ w, const float* __restrict__ bias,
                                                          uint8_t* __restrict__ wq, double* __restrict__ scale,
                                                          double* __restrict__ bias_d, float* __restrict__ wl1,
@@ -1284,7 +1208,7 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
   const int sh = 29 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^29 <= 16.5 * 32^5
   double l1 = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
-    const double q = rint(ldexp((double)wc[i], sh));
+    const double q = spk_cert_quantise(wc[i], sh);
     l1 += fabs(q);
     const int ci = i / 9, tap = i - 9 * ci;
     qtab[((long long)co * 9 + tap) * Cin + ci] = (int)q;          // |q| < 2^29
@@ -1296,8 +1220,7 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    scale[co] = ldexp(1.0, -sh);
-    bias_d[co] = bias ? (double)bias[co] : 0.0;
+    spk_cert_scale_bias(scale, bias_d, bias, co, sh);
     wl1[co] = (float)(ldexp(ssum[0], -sh) * 1.000001);      // rounded up: it feeds an upper bound
   }
   const int nchunks = Cin / CK, g = co >> 5, col = co & 31;
@@ -1309,30 +1232,8 @@ __global__ __launch_bounds__(256) void pack_fp6v2_kernel(const float* __restrict
     if (tau < N_PAIR) { tap = tau >> 1; digit = 2 * (tau & 1) + kh; }
     else if (tau < N_MAIN) { tap = 2 * (tau - N_PAIR) + kh; digit = 4; valid = tap < 9; }
     else { tap = (tau == N_MAIN ? 0 : 3) + kh; digit = 5; }
-    unsigned bits[6] = {0, 0, 0, 0, 0, 0};
-    if (valid) {
-      for (int j = 0; j < 32; ++j) {
-        const int ci = c * CK + j;
-        int dg[6];
-        spk_balanced_digits<5>((long long)rint(ldexp((double)wc[ci * 9 + tap], sh)), dg);
-        int d = 0;
-#pragma unroll
-        for (int p = 0; p < 6; ++p) d = (p == digit) ? dg[p] : d;
-        const unsigned code = spk_e2m3_code(d);
-        const int bit = 6 * j, wd = bit >> 5, sft = bit & 31;
-#pragma unroll
-        for (int q2 = 0; q2 < 6; ++q2) {         // static register indexing
-          if (q2 == wd) bits[q2] |= code << sft;
-          if (q2 == wd + 1 && sft > 26) bits[q2] |= code >> (32 - sft);
-        }
-      }
-    }
-    uint8_t* tile = wq + (long long)(g * nchunks + c) * W_SLAB + tau * WT;
-    const int ln = kh * 32 + col;
-    unsigned* d16 = reinterpret_cast<unsigned*>(tile + ln * 16);
-    unsigned* d8 = reinterpret_cast<unsigned*>(tile + 1024 + ln * 8);
-    d16[0] = bits[0]; d16[1] = bits[1]; d16[2] = bits[2]; d16[3] = bits[3];
-    d8[0] = bits[4]; d8[1] = bits[5];
+    spk_cert_emit_fragment(wq + (long long)(g * nchunks + c) * W_SLAB + tau * WT, kh * 32 + col, digit, valid,
+                           [&](int j) { return (long long)spk_cert_quantise(wc[(c * CK + j) * 9 + tap], sh); });
   }
 }
 
@@ -1354,8 +1255,7 @@ extern "C" int spk_den_pack_weight_fp6v2(const float* w, const float* bias, uint
 
 extern "C" long long spk_den_fp6v2_flag_words(int B, int Cout, int H, int W) {
   if (B <= 0 || Cout <= 0 || H <= 0 || W <= 0) return -1;
-  long long words = 2 + (long long)FLAG_CAP + ((long long)B * Cout * H * W + 31) / 32 + 1;   // (+ ticket)
-  return words;
+  return spk_cert_flag_words((long long)B * Cout * H * W);
 }
 
 extern "C" int spk_den_conv3x3_mfma_fp6v2_supported(int Cout, int Cin, int k, int stride, int pad, int T, int H, int W) {
@@ -1377,8 +1277,8 @@ static int fp6v2_launch(const uint8_t* in_s32, int nch, const uint8_t* wq, const
   if (need && (bands || !n_dyn_or_null)) return SPK_ERR_UNSUPPORTED;   // (not in the predicate: a property of the call's lists, not of the shape)
   V2Args a;
   a.in0 = in_s32; a.nch = nch; a.wq = wq; a.scale = scale; a.bias = bias_d; a.wl1 = wl1; a.qtab = qtab;
-  a.bn_a = bn_a; a.bn_b = bn_b; a.out = out_s32; a.out_cnt = out_counts; a.flags = flag_words;
-  a.flag_cap = flag_cap < 0 || (unsigned)flag_cap > FLAG_CAP ? FLAG_CAP : (unsigned)flag_cap;   // (< 0: the whole list)
+  a.bn_a = bn_a; a.bn_b = bn_b; a.out = out_s32; a.out_cnt = out_counts;
+  a.ws = spk_cert_ws(flag_words, flag_cap, (long long)B * Cout * H * W);
   a.n_dyn = n_dyn_or_null;
   a.need = nullptr; a.cls_cnt = nullptr; a.cls_list = nullptr;
   if (need) {
@@ -1413,8 +1313,7 @@ static int fp6v2_launch(const uint8_t* in_s32, int nch, const uint8_t* wq, const
   const int a_bytes = bands ? ((8 / 2 + 1 + 2) * 9 + 1) * POSB : ((7 + 2) * 8 + 1) * POSB;
   // (+ the active-input counters of the four-digit form: s_cin [cells][16], s_row [positions + 1][16])
   const size_t lds = 2 * ((size_t)a_bytes + W_LDS) + (size_t)((a_bytes / POSB) + (bands ? 32 : 49) + 1) * 64 + 256;   // (+ s_nmax)
-  const long long n_words = ((long long)B * Cout * H * W + 31) / 32;
-  a.ticket_idx = 2 + (long long)FLAG_CAP + n_words;
+  const long long n_words = spk_cert_bitmap_words((long long)B * Cout * H * W);
   // every main launch publishes the count for a merged tail launch (repair + last position as ONE launch: 1.6 % faster than two)
   a.handover = 1;
   if (parts != 7) {

@@ -3,7 +3,8 @@
 // contract as den_mfma_fp6v2.hip: 29-bit per-channel fixed-point weights as radix-32 digits, adjacent digits sharing an fp32
 // accumulator through the per-block scales, every spike decision certified against an error bound, the few neurons that come
 // within the bound of the threshold recomputed exactly (all six digits, 64-bit sums, fp64 recombination, one rounding) by a
-// tail launch.  Unflagged neurons provably emit the exact path's spikes; the result is the one spk_conv_mfma_fused_fwd (int8
+// tail launch (the flag workspace and its protocol, the pieces of the exact repair and the weight tile format: cert_common.h, shared
+// with that kernel).  Unflagged neurons provably emit the exact path's spikes; the result is the one spk_conv_mfma_fused_fwd (int8
 // gather kernel) produces for the same layer.  Round 4: FOUR digits on the matrix cores (two accumulators per tile,
 // 4 / 2 instead of 5 / 3 MFMAs and weight-tile reads per tap and chunk) behind the COUNTED bound of den_mfma_fp6v2.hip -- the
 // active inputs of every input record are popcounted once per item, then per class and output position the maximum over the
@@ -25,23 +26,12 @@
 // Spikes in: "S32" [B][Cin/32 (rounded up)][H*W][16][16 B] (fp4 nibbles; channels beyond Cin must be zero).  Out: S32, plain u8
 // PTC [B][Ho*Wo][16][Cout], or -- for the layer in front of the linear read-out -- the time-collapsed tensor
 // m = sum_t coef[t] * s_t (fp32 [B][Ho*Wo][Cout], spk_readout_collapsed_fwd): the spike frames are then never stored.
-#include "den_common.h"
+#include "cert_common.h"
 #include "../../include/spkdiff.h"
-#include <math.h>
 #include <type_traits>
 #include <utility>
 
 namespace {
-
-typedef int v6i __attribute__((ext_vector_type(6)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-constexpr int T16 = 16;
-constexpr int POSB = 256;                    // bytes per position and 32-channel chunk: 16 steps x 16 B
-constexpr int WT = 1536;                     // one B tile: 64 lanes x 32 six-bit codes
-constexpr unsigned FLAG_CAP = 1u << 20;
 
 __host__ __device__ constexpr int tiles_per_tap(int nch) { return nch == 2 ? 5 : 3; }
 // tile (tap, j): NCH = 2: j = 0..3: chunk j / 2, digit pair j % 2; j = 4: fifth digit, K half 0 = chunk 0, half 1 = chunk 1.
@@ -51,13 +41,11 @@ struct TArgs {
   const uint8_t* in;                         // S32 [B][NCH][H*W][16][16 B]
   const uint8_t* wq; const double* scale; const double* bias; const float* bn_a; const float* bn_b; const float* coef;
   void* out;
-  // flags[0]: live count of flagged neurons (zero between calls), flags[1]: the count published by the main launch's last
-  // workgroup for the repair launch, flags[2 .. 2 + cap): their ids, then the overflow bitmap, then the ticket of that hand-over
-  unsigned* flags; unsigned flag_cap; long long ticket_idx; const int* qtab;       // qtab int32 [Cout][9][Cin]
+  CertWs ws;                                 // the flag workspace (cert_common.h)
+  const int* qtab;                           // int32 [Cout][9][Cin]
   int B, Cout, Cin;
 };
 
-constexpr float CERT_4EPS = 4.0f * 2.38418579e-07f;
 constexpr int SPK_VT_NWV = 16;          // waves per workgroup.  Round 4: SIXTEEN (four per SIMD) with one tile per pass: the four-digit form needs ~100
                                         // registers at one tile per pass, four waves issue vector instructions at 2.0 instead of 3.1 cycles each
                                         // (tools/coexec_probe.hip) and overlap one another's multiply phases: encode -> decode at B = 1024
@@ -383,11 +371,7 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
         const int oy = GEO == 0 ? 2 * (part * RQ + ry) + PY : ry, ox = GEO == 0 ? 2 * rx + PX : rx;
         const long long pos = ((long long)b * Ho + oy) * Wo + ox;
         const long long nid_f = pos * a.Cout + co;
-        if (flg && ok) {
-          const unsigned idx = atomicAdd(a.flags, 1u);            // (the count of flagged neurons: statistics, tests)
-          if (idx < a.flag_cap) a.flags[2 + idx] = (unsigned)nid_f;
-          else atomicOr(a.flags + 2 + FLAG_CAP + (nid_f >> 5), 1u << (nid_f & 31));
-        }
+        spk_cert_flag(a.ws, nid_f, flg && ok);
         if (OUT == SPK_VAE_OUT_COLLAPSED) {
           if (ok) reinterpret_cast<float*>(a.out)[pos * a.Cout + co] = m;
         } else {
@@ -450,24 +434,13 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
     if (!DB) __syncthreads();                                  // everyone is done with the slab before the next copy lands
   }
   spk_dma_wait_all();
-  // hand-over to the repair launch: the workgroup that finishes last publishes the count and re-arms the live counter (the
-  // workgroups finish at different times, so this ticket costs nothing; a ticket in the repair launch, whose workgroups all
-  // arrive at once, cost 16 us, a separate reset launch 5)
-  // (no fence needed: every atomicAdd on the counter has returned before its wave reaches the barrier, and the count is read
-  //  back with an atomic)
   __syncthreads();
-  if (tid == 0) {
-    if (atomicAdd(a.flags + a.ticket_idx, 1u) == gridDim.x - 1) {
-      a.flags[1] = atomicAdd(a.flags, 0u);
-      a.flags[0] = 0u;
-      a.flags[a.ticket_idx] = 0u;
-    }
-  }
+  if (tid == 0) spk_cert_handover(a.ws);   // to the repair launch
 }
 
 // One flagged neuron, exactly, by one wave: lane = (time step t, quarter of a 32-channel chunk); every contributing tap and
-// chunk costs one 4-byte read of the spike record and eight quantised weights; 64-bit sums meet through two shuffles, then
-// the reference's BN and LIF steps run on the correctly rounded pre-activations and the neuron's output is rewritten.
+// chunk costs one 4-byte read of the spike record and eight quantised weights (spk_cert_add_active8); 64-bit sums meet through two
+// shuffles, then the reference's BN and LIF steps run on the correctly rounded pre-activations and the neuron's output is rewritten.
 template <int GEO, int H, int W, int NCH, int OUT>
 __device__ __forceinline__ void vae_fix_neuron(const TArgs& a, long long nid, int lane) {
   constexpr int Ho = Geo<GEO, H, W>::Ho, Wo = Geo<GEO, H, W>::Wo;
@@ -501,34 +474,18 @@ __device__ __forceinline__ void vae_fix_neuron(const TArgs& a, long long nid, in
         if (c * 32 + 8 * q >= a.Cin) continue;                // (padding channels of the last chunk carry no weights)
         const unsigned nib = *reinterpret_cast<const unsigned*>(a.in + ((((long long)b * NCH + c) * H * W + iy * W + ix) * T16 + t) * 16 + 4 * q);
         const int4* qp = reinterpret_cast<const int4*>(a.qtab + ((long long)co * 9 + tap) * a.Cin + c * 32 + 8 * q);
-        const int4 q0 = qp[0], q1 = qp[1];
-        part += (nib & 0x0000000fu) ? (long long)q0.x : 0ll;
-        part += (nib & 0x000000f0u) ? (long long)q0.y : 0ll;
-        part += (nib & 0x00000f00u) ? (long long)q0.z : 0ll;
-        part += (nib & 0x0000f000u) ? (long long)q0.w : 0ll;
-        part += (nib & 0x000f0000u) ? (long long)q1.x : 0ll;
-        part += (nib & 0x00f00000u) ? (long long)q1.y : 0ll;
-        part += (nib & 0x0f000000u) ? (long long)q1.z : 0ll;
-        part += (nib & 0xf0000000u) ? (long long)q1.w : 0ll;
+        spk_cert_add_active8(part, nib, qp[0], qp[1]);
       }
     }
   }
-#pragma unroll
-  for (int off = 16; off <= 32; off <<= 1) {
-    const int lo = __shfl_xor((int)(unsigned)(part & 0xffffffffll), off);
-    const int hi = __shfl_xor((int)(part >> 32), off);
-    part += (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-  }
+  part = spk_cert_sum_quarters(part);
   const double sc = a.scale[co], bi = a.bias[co];
   const float bna = a.bn_a[co], bnb = a.bn_b[co];
   float v = 0.f, m = 0.f;
   unsigned bits = 0;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int lo = __shfl((int)(unsigned)(part & 0xffffffffll), r);
-    const int hi = __shfl((int)(part >> 32), r);
-    const long long S = (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-    const float y = (float)fma((double)S, sc, bi);
+    const float y = exact_preact((double)spk_shfl64(part, r), sc, bi);
     const bool s = spk_lif_step_default(v, fmaf(y, bna, bnb));
     if (OUT == SPK_VAE_OUT_COLLAPSED) m = m + (s ? a.coef[r] : 0.f);
     bits |= s ? (1u << r) : 0u;
@@ -537,12 +494,9 @@ __device__ __forceinline__ void vae_fix_neuron(const TArgs& a, long long nid, in
     if (lane == 0) reinterpret_cast<float*>(a.out)[nid] = m;
   } else if (OUT == SPK_VAE_OUT_S32) {
     if (lane < 16) {                                          // lane = time step: one nibble of the (position, t) record
-      const int g = co >> 5, G = a.Cout >> 5, byte = (co & 31) >> 1;
+      const int g = co >> 5, G = a.Cout >> 5;
       uint8_t* rec = reinterpret_cast<uint8_t*>(a.out) + ((((long long)b * G + g) * Ho * Wo + oy * Wo + ox) * T16 + lane) * 16;
-      unsigned* wp = reinterpret_cast<unsigned*>(rec + (byte & ~3));
-      const unsigned shw = 8u * (byte & 3) + 4u * (co & 1);
-      atomicAnd(wp, ~(0xFu << shw));
-      if ((bits >> lane) & 1u) atomicOr(wp, 0x2u << shw);
+      spk_cert_patch_nibble(rec, co, (bits >> lane) & 1u);
     }
   } else {
     if (lane < 16) reinterpret_cast<uint8_t*>(a.out)[(pos * T16 + lane) * a.Cout + co] = (uint8_t)((bits >> lane) & 1u);
@@ -550,40 +504,16 @@ __device__ __forceinline__ void vae_fix_neuron(const TArgs& a, long long nid, in
 }
 
 template <int GEO, int H, int W, int NCH, int OUT>
-__device__ __attribute__((noinline)) void vae_fix_neuron_call(const uint8_t* in, const int* qtab, const double* scale, const double* bias,
-                                                              const float* bn_a, const float* bn_b, const float* coef, void* out,
-                                                              int Cin, int Cout, long long nid, int lane) {
-  TArgs a;
-  a.in = in; a.qtab = qtab; a.scale = scale; a.bias = bias; a.bn_a = bn_a; a.bn_b = bn_b; a.coef = coef; a.out = out;
-  a.Cin = Cin; a.Cout = Cout;
-  a.wq = nullptr; a.flags = nullptr; a.flag_cap = 0; a.ticket_idx = 0; a.B = 0;
-  vae_fix_neuron<GEO, H, W, NCH, OUT>(a, nid, lane);
-}
-
-template <int GEO, int H, int W, int NCH, int OUT>
 __global__ __launch_bounds__(256) void vae_fp6_fixup_kernel(TArgs a, long long n_words) {
   const int lane = threadIdx.x & 63;
   const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6), nwv = (long long)gridDim.x * 4;
-  const unsigned count = a.flags[1];
-  const unsigned nlist = count < a.flag_cap ? count : a.flag_cap;
-  for (long long e = wv; e < nlist; e += nwv) vae_fix_neuron<GEO, H, W, NCH, OUT>(a, (long long)a.flags[2 + e], lane);
-  if (count > a.flag_cap) {                  // overflow: the rest sit in the bitmap; every wave scans a share, clearing as it goes
-    unsigned* bm = a.flags + 2 + FLAG_CAP;
-    for (long long wi = wv; wi < n_words; wi += nwv) {
-      unsigned wd = bm[wi];
-      if (wd && lane == 0) bm[wi] = 0u;
-      while (wd) {
-        const int bit = __ffs((int)wd) - 1;
-        wd &= wd - 1;
-        vae_fix_neuron<GEO, H, W, NCH, OUT>(a, wi * 32 + bit, lane);
-      }
-    }
-  }
+  spk_cert_scan<false>(a.ws, a.ws.flags[1], wv, nwv, n_words, lane == 0,
+                       [&](long long nid) __attribute__((always_inline)) { vae_fix_neuron<GEO, H, W, NCH, OUT>(a, nid, lane); });
 }
 
 // one block per output channel: channel maximum -> shift s, every weight -> six balanced radix-32 digits, written as the
-// per-lane 24-byte B fragments of the tiles listed at tiles_per_tap; also the quantised weights themselves (int32
-// [Cout][9][Cin]) for the exact recomputation.  w: Conv2d [Cout][Cin][3][3] or ConvTranspose2d [Cin][Cout][3][3].
+// per-lane 24-byte B fragments (spk_cert_emit_fragment) of the tiles listed at tiles_per_tap; also the quantised weights
+// themselves (int32 [Cout][9][Cin]) for the exact recomputation.  w: Conv2d [Cout][Cin][3][3] or ConvTranspose2d [Cin][Cout][3][3].
 __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restrict__ w, const float* __restrict__ bias,
                                                            uint8_t* __restrict__ wq, double* __restrict__ scale,
                                                            double* __restrict__ bias_d, int* __restrict__ qtab, int Cout,
@@ -599,9 +529,9 @@ __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restri
   const int sh = 29 - spk_channel_exponent(smax, m);     // |w| * 2^sh < 2^29 <= 16.5 * 32^5
   for (int i = threadIdx.x; i < n; i += 256) {
     const int ci = i / 9, tap = i - 9 * ci;
-    qtab[((long long)co * 9 + tap) * Cin + ci] = (int)rint(ldexp((double)wat(ci, tap), sh));
+    qtab[((long long)co * 9 + tap) * Cin + ci] = (int)spk_cert_quantise(wat(ci, tap), sh);
   }
-  if (threadIdx.x == 0) { scale[co] = ldexp(1.0, -sh); bias_d[co] = bias ? (double)bias[co] : 0.0; }
+  if (threadIdx.x == 0) spk_cert_scale_bias(scale, bias_d, bias, co, sh);
   const int g = co >> 5, col = co & 31;
   for (int rec = threadIdx.x; rec < 9 * TPT * 2; rec += 256) {
     const int kh = rec & 1, tau = rec >> 1, tap = tau / TPT, j = tau % TPT;
@@ -609,28 +539,10 @@ __global__ __launch_bounds__(256) void pack_vae_fp6_kernel(const float* __restri
     bool live = true;
     if (NCH == 2) { chunk = j < 4 ? (j >> 1) : kh; digit = j < 4 ? 2 * (j & 1) + kh : 4; }
     else { chunk = 0; digit = j < 2 ? 2 * j + kh : 4; live = j < 2 || kh == 0; }
-    unsigned bits[6] = {0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < 32 && live; ++k) {
+    spk_cert_emit_fragment(wq + ((long long)g * 9 * TPT + tau) * WT, kh * 32 + col, digit, live, [&](int k) {
       const int ci = chunk * 32 + k;
-      int dg[6];
-      spk_balanced_digits<5>(ci < Cin ? (long long)rint(ldexp((double)wat(ci, tap), sh)) : 0ll, dg);
-      int d = 0;
-#pragma unroll
-      for (int p = 0; p < 6; ++p) d = (p == digit) ? dg[p] : d;
-      const unsigned code = spk_e2m3_code(d);
-      const int bit = 6 * k, wd = bit >> 5, sft = bit & 31;
-#pragma unroll
-      for (int q2 = 0; q2 < 6; ++q2) {
-        if (q2 == wd) bits[q2] |= code << sft;
-        if (q2 == wd + 1 && sft > 26) bits[q2] |= code >> (32 - sft);
-      }
-    }
-    uint8_t* tile = wq + ((long long)g * 9 * TPT + tau) * WT;
-    const int ln = kh * 32 + col;
-    unsigned* d16 = reinterpret_cast<unsigned*>(tile + ln * 16);
-    unsigned* d8 = reinterpret_cast<unsigned*>(tile + 1024 + ln * 8);
-    d16[0] = bits[0]; d16[1] = bits[1]; d16[2] = bits[2]; d16[3] = bits[3];
-    d8[0] = bits[4]; d8[1] = bits[5];
+      return ci < Cin ? (long long)spk_cert_quantise(wat(ci, tap), sh) : 0ll;
+    });
   }
 }
 
@@ -671,7 +583,7 @@ extern "C" int spk_vae_fp6_pack(const float* w, const float* bias, uint8_t* wq, 
 
 extern "C" long long spk_vae_fp6_flag_words(int B, int Cout, int Ho, int Wo) {
   if (B <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return -1;
-  return 2 + (long long)FLAG_CAP + ((long long)B * Cout * Ho * Wo + 31) / 32 + 1;
+  return spk_cert_flag_words((long long)B * Cout * Ho * Wo);
 }
 
 extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const double* scale, const double* bias_d,
@@ -685,13 +597,12 @@ extern "C" int spk_vae_fp6_fwd(const uint8_t* in_s32, const uint8_t* wq, const d
   if (B > (1 << 22)) return SPK_ERR_UNSUPPORTED;             // (not in the predicate: the batch is no part of the layer's shape)
   TArgs a;
   a.in = in_s32; a.wq = wq; a.scale = scale; a.bias = bias_d; a.bn_a = bn_a; a.bn_b = bn_b; a.coef = coef_or_null; a.out = out;
-  a.flags = flag_words; a.qtab = qtab; a.B = B; a.Cout = Cout; a.Cin = Cin;
-  a.flag_cap = flag_cap < 0 || (unsigned)flag_cap > FLAG_CAP ? FLAG_CAP : (unsigned)flag_cap;   // id-list entries used (< 0: all); layout fixed
+  a.qtab = qtab; a.B = B; a.Cout = Cout; a.Cin = Cin;
   const int Ho = transposed ? 2 * H : H / 2, Wo = transposed ? 2 * W : W / 2;
   const long long neurons = (long long)B * Cout * Ho * Wo;
   if (neurons >= (1ll << 32)) return SPK_ERR_UNSUPPORTED;          // neuron ids are 32-bit (not in the predicate: grows with the batch)
-  const long long n_words = (neurons + 31) / 32;
-  a.ticket_idx = 2 + (long long)FLAG_CAP + n_words;
+  const long long n_words = spk_cert_bitmap_words(neurons);
+  a.ws = spk_cert_ws(flag_words, flag_cap, neurons);
   // one instance per (kind, H): spk_vae_fp6_kind has checked that this one exists
   if (kind == SPK_VAE_OUT_COLLAPSED) {                                                        // decoder convT2
     // half images per item, one input slab (two do not fit beside the weights); two class rows per item with two slabs measured
