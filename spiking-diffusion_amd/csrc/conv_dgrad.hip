@@ -425,7 +425,7 @@ __global__ __launch_bounds__(NTHR, 1) void dgrad3x3_kernel(DgArgs a) {
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int rr = (r & 3) + 8 * (r >> 2) + 4 * half, y = 4 * mt + (rr >> 3), x = rr & 7;
+        const int rr = spk_acc_row(r, half), y = 4 * mt + (rr >> 3), x = rr & 7;
         const int p = y * HH + x;
         if (x < HH && y < HH) {
 #pragma unroll

@@ -111,7 +111,7 @@ template <int INKIND, bool TRANSPOSED, int MODE>
 __global__ __launch_bounds__(256) void conv_fused_kernel(FusedArgs a) {
   constexpr bool TINV = INKIND == SPK_IN_TINV;
   const int Cin = a.C0 + a.C1;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;     // buffers and strides stay sized by a.B
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const long long total = (long long)Bn * a.Ho * a.Wo * a.Cout;
   const int T = a.T;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -299,19 +299,14 @@ __device__ __forceinline__ void tinv_store(const TinvArgs& a, unsigned mybits, i
                    ((co16 % a.out_c4) >> 1);
     *reinterpret_cast<uint2*>(dst) = o;
   } else {
-    uint4 o;
-    o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
-    o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
-    o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
-    o.w = (((bitsv >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
-    *reinterpret_cast<uint4*>(a.out + (((long long)b * plane + op) * 16 + tl) * a.Cout + co16) = o;
+    *reinterpret_cast<uint4*>(a.out + (((long long)b * plane + op) * 16 + tl) * a.Cout + co16) = spk_u8_record(bitsv);
   }
 }
 
 // KC > 0: k = KS and Cin = KC are compile-time and the thread's KS * KS * KC weights live in registers
 template <int KS, int KC>
 __global__ __launch_bounds__(256) void tinv_lif_kernel(TinvArgs a) {
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const int co = threadIdx.x % a.Cout, pl = threadIdx.x / a.Cout, ppb = 256 / a.Cout;     // positions per block step
   const int plane = a.Ho * a.Wo;
   const int npos = Bn * plane;
@@ -419,7 +414,7 @@ __global__ __launch_bounds__(256) void tinv_lif_staged_kernel(TinvArgs a) {
   __shared__ int sB[PB], sOp[PB];
   __shared__ float s_th[16];
   __shared__ unsigned s_pat[18];
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const int co = threadIdx.x % a.Cout, pl = threadIdx.x / a.Cout, ppb = 256 / a.Cout;
   const int plane = a.Ho * a.Wo;
   const int npos = Bn * plane;

@@ -12,14 +12,10 @@
 //
 // Layouts: input / output spikes plain PTC u8 [B][H*W][T=16][C]; packed weights [ceil(Cout/16)][ceil(Cin/32)][k*k]
 // [2 column tiles][32 cols][32 k] int8 (spk_pack_conv_weight_i8; Cin / Cout are zero-padded to 32 / 16).
-#include "spk_common.h"
+#include "den_common.h"
 #include "../../include/spkdiff.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
 constexpr int T16 = 16;
 
@@ -141,16 +137,12 @@ __global__ __launch_bounds__(256) void conv_mfma_gather_kernel(GArgs a) {
   const int co = g * 16 + ch;
   const bool co_ok = co < a.Cout;
   const double sc = a.scale[g * 16 + ch], bi = a.bias[g * 16 + ch];     // padded to 16 per group by the packer
-  // Pairwise exchange (den_mfma_fp6.hip): v_permlane16_swap(acc[0][ct][r], acc[1][ct][r]) leaves the even lane with both
-  // digits of column tile ct of row tile 0 and the odd lane with those of row tile 1 -- 32 swaps give every lane all four
-  // digits of ONE neuron for all 16 steps; both lane parities recombine and scan their own tile.
+  // Pairwise exchange: spk_digits_recombine (den_common.h) on the words of row tiles 0 and 1 gives the even lane all four digits
+  // of ONE neuron of tile 0 and the odd lane those of tile 1, for all 16 steps; both lane parities scan their own tile.
   float xs[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[0][0][r], (unsigned)acc[1][0][r], false, false);
-    const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[0][1][r], (unsigned)acc[1][1][r], false, false);
-    const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
-    const double s = fma((double)hi, 65536.0, (double)lo);
+    const double s = spk_digits_recombine<int>(acc[0][0][r], acc[1][0][r], acc[0][1][r], acc[1][1][r]);
     xs[r] = (float)fma(s, sc, bi);
   }
   // even lanes own tile 0, odd lanes tile 1; accumulator lane-half = position within the tile
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(256) void conv_mfma_gather_kernel(GArgs a) {
                                 8 * (g & 1)) = spk_e2m1_record(bitsv);
     }
     if (pos_ok && a.out_ptc) {
-      uint4 o;
+      uint4 o;                                  // spk_u8_record(bitsv) of spk_common.h, written out: the call reorders the products
       o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
       o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
       o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
@@ -307,21 +299,16 @@ __device__ __forceinline__ void gather2_body(const GArgs& a, int b, int g, int p
       }
     }
   }
-  // ---- epilogue (identical to the generic kernel)
+  // ---- epilogue (that of conv_mfma_gather_kernel, the definition, written out: as a shared function every instance compiles
+  //      differently; here q is decoded without a division and v_io is indexed at a clamped position)
   const int col = lane & 31, ch = col & 15, odd = col >> 4;
   const int co = g * 16 + ch;
   const bool co_ok = co < a.Cout;
   const double sc = a.scale[g * 16 + ch], bi = a.bias[g * 16 + ch];
-  // Pairwise exchange (den_mfma_fp6.hip): v_permlane16_swap(acc[0][ct][r], acc[1][ct][r]) leaves the even lane with both
-  // digits of column tile ct of row tile 0 and the odd lane with those of row tile 1 -- 32 swaps give every lane all four
-  // digits of ONE neuron for all 16 steps; both lane parities recombine and scan their own tile.
   float xs[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[0][0][r], (unsigned)acc[1][0][r], false, false);
-    const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[0][1][r], (unsigned)acc[1][1][r], false, false);
-    const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
-    const double s = fma((double)hi, 65536.0, (double)lo);
+    const double s = spk_digits_recombine<int>(acc[0][0][r], acc[1][0][r], acc[0][1][r], acc[1][1][r]);
     xs[r] = (float)fma(s, sc, bi);
   }
   const int q = pg * 4 + 2 * odd + half;
@@ -353,7 +340,7 @@ __device__ __forceinline__ void gather2_body(const GArgs& a, int b, int g, int p
                                 8 * (g & 1)) = spk_e2m1_record(bitsv);
     }
     if (pos_ok && a.out_ptc) {
-      uint4 o;
+      uint4 o;                                  // spk_u8_record(bitsv) of spk_common.h, written out: the call reorders the products
       o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
       o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
       o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;

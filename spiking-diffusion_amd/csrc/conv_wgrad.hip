@@ -233,7 +233,7 @@ __global__ __launch_bounds__(NTHR, 1) void wgrad3x3_bf16_kernel(WgArgs a) {
   for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int co = co0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;     // spk_acc_row(r, half) of den_common.h, written out
       out[((long long)co * 9 + tap) * a.Cin + ci0 + ct * 32 + row] = acc[tap][r];
     }
 }

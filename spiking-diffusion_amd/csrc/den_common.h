@@ -73,6 +73,27 @@ __device__ __forceinline__ void spk_dma16s_masked(const void* sbase, unsigned vo
 __device__ __forceinline__ void spk_dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ unsigned spk_lds_addr(const void* p) { return (unsigned)(size_t)SPK_LDS(p); }
 
+// ------------------------------------------------------------------------------------------------ int8 digit planes
+// The exact value of one output of the int8 digit-plane kernels (den_mfma.hip, conv_mfma_gather.hip, step_tail.hip) from its
+// four base-256 digit sums.  Lane contract: a 32-wide column tile is 16 channels x 2 digit planes, digit parity = lane bit 4,
+// so partner lanes col and col ^ 16 hold planes {0, 2} and {1, 3} of one channel (column tiles 0 and 1).  The caller passes
+// two accumulator words A, B per column tile; v_permlane16_swap(A, B) returns {even row: A.even, odd row: B.even} and
+// {even row: A.odd, odd row: B.odd}, so the even lane of a pair gets all four digits of word A and the odd lane those of
+// word B, and each returns (((d0 256 + d1) 256 + d2) 256 + d3) of ITS word.  WIDE is the integer the digit pairs are joined
+// in: a digit sum over K 0/1 spikes is at most 128 K, so `int` holds 257 x that for any layer (K < 65 000); the counts forms
+// multiply spike COUNTS of up to 127 and need `long long`.  The fp64 fma is exact (|value| < 2^53).
+template <typename WIDE>
+__device__ __forceinline__ double spk_digits_recombine(int a01, int b01, int a23, int b23) {
+  const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)a01, (unsigned)b01, false, false);
+  const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)a23, (unsigned)b23, false, false);
+  const WIDE hi = (WIDE)(int)p01[0] * 256 + (int)p01[1], lo = (WIDE)(int)p23[0] * 256 + (int)p23[1];
+  return fma((double)hi, 65536.0, (double)lo);
+}
+
+// Row of a 32x32 MFMA accumulator tile that register `reg` (0 .. 15) of a lane in lane-half `half` (lane >> 5) holds.
+constexpr int spk_acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+static_assert(spk_acc_row(0, 1) == 4 && spk_acc_row(4, 0) == 8 && spk_acc_row(15, 1) == 31, "32x32 accumulator layout");
+
 // The block-scaled fp4 x fp6 MFMA of den_mfma_fp6.hip and den_mfma_fp6v2.hip as inline assembly (explicit register classes):
 // D = A(32 x 64 fp4) * B(64 x 32 fp6) + C, accumulator in AGPRs ("a") or VGPRs ("v"); *_Z: C = 0 (first MFMA of an item).
 // s_nop 1: the two wait states between a VALU write of an operand register (the B fragment hand-over is v_mov) and

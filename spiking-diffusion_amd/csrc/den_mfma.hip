@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = a.nch0 + a.nch1;
   const int G = a.Cout >> 4;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const int total = Bn * G;
 
   // zero both A images once: the borders stay zero for the whole kernel, interiors are overwritten by DMA
@@ -210,17 +210,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
 
     }   // chunks
     // ---------------- epilogue: exact recombination, BN, LIF scan over the 16 accumulator registers ----------
-    // Partner lanes (col, col ^ 16) hold digit planes {0,2} and {1,3} of the same channel.  recombine(i, x):
-    // v_permlane16_swap(A, B) gives A' = {even row: A.even, odd row: B.even}, B' = {even row: A.odd, odd row: B.odd};
-    // with A = acc[.][r] (t = r) and B = acc[.][r + 8] every lane ends up with both digits of ITS time step (even
-    // lane t = r, odd lane t = r + 8), recombines it in fp64, and a third swap hands both lanes all 16 fp32 values.
+    // recombine(i, x): spk_digits_recombine (den_common.h) on the words of t = r and t = r + 8 -- the even lane recombines ITS
+    // time step t = r, the odd lane t = r + 8 -- and a third swap hands both lanes all 16 fp32 values.
     auto recombine = [&](int i, float (&x)[16]) {
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][0][r], (unsigned)acc[i][0][r + 8], false, false);
-        const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[i][1][r], (unsigned)acc[i][1][r + 8], false, false);
-        const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
-        const double s = fma((double)hi, 65536.0, (double)lo);        // exact
+        const double s = spk_digits_recombine<int>(acc[i][0][r], acc[i][0][r + 8], acc[i][1][r], acc[i][1][r + 8]);
         const float xm = (float)fma(s, sc, bi);                        // the one rounding to fp32 (s*sc is exact)
         const v2u xx = __builtin_amdgcn_permlane16_swap(__float_as_uint(xm), __float_as_uint(xm), false, false);
         x[r] = __uint_as_float(xx[0]);                                 // t = r     (computed by the even lane)
@@ -233,10 +228,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
       // transpose inside every 16-lane row (= 16 channels of one position) turns them into per-time-step channel masks.
 #pragma unroll
       for (int ip = 0; ip < NT; ip += 2) {
-        // Pairwise exchange (as in den_mfma_fp6.hip): v_permlane16_swap(acc[ip][ct][r], acc[ip + 1][ct][r]) leaves the
-        // even lane with both digits of column tile ct of tile ip and the odd lane with those of tile ip + 1, so 32
-        // swaps give every lane all four digits of ONE neuron for all 16 steps; the odd tile out of an odd NT is
-        // split over the lane parities by time steps (recombine()).
+        // Pairwise exchange: spk_digits_recombine on the words of tiles ip and ip + 1 gives the even lane all four digits
+        // of ONE neuron of tile ip and the odd lane those of tile ip + 1, for all 16 steps; the odd tile out of an odd NT
+        // is split over the lane parities by time steps (recombine()).
         float xa[16];
         const bool paired = ip + 1 < NT;
         // keep this pair's accumulators in their AGPR tuples up to here: hipcc otherwise copies 16-register tuples
@@ -249,11 +243,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
         if (paired) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
+            // spk_digits_recombine<int> of den_common.h, written out: the call reorders this launch's accumulator reads
             const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][0][r], (unsigned)acc[paired ? ip + 1 : ip][0][r], false, false);
             const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[ip][1][r], (unsigned)acc[paired ? ip + 1 : ip][1][r], false, false);
             const int hi = (int)p01[0] * 256 + (int)p01[1], lo = (int)p23[0] * 256 + (int)p23[1];
             const double s = fma((double)hi, 65536.0, (double)lo);        // exact
-            xa[r] = (float)fma(s, sc, bi);                                 // the one rounding to fp32
+            xa[r] = (float)fma(s, sc, bi);                                // the one rounding to fp32
           }
         } else {
           recombine(ip, xa);
@@ -278,11 +273,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_mfma_kernel(MfmaArgs a) {
           a.out_cnt[(((long long)b * (a.Cout >> 5) + (co >> 5)) * HW + p) * CK + (co & 31)] = (uint8_t)cnt;
         // every lane stores one (position, time step): 16 channels = 16 bytes
         if (pos_ok) {
-          uint4 o;
-          o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
-          o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
-          o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
-          o.w = (((bitsv >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
+          const uint4 o = spk_u8_record(bitsv);
           const int co0 = g * 16;
           uint8_t* dst = a.out + ((((long long)b * (a.Cout >> 5) + (co0 >> 5)) * HW + p) * T16 + (lane & 15)) * CK +
                          (co0 & 31);
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(256) void conv3x3_counts_mfma_kernel(CntArgs a) {
   __shared__ int red[2][16][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int HW = a.H * a.W;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const long long nrows = (long long)Bn * HW;
   const bool split = nrows <= 32 * 160;                     // (uniform over the launch)
   const long long tile = split ? (long long)blockIdx.x : (long long)blockIdx.x * 4 + wave;
@@ -384,14 +375,10 @@ __global__ __launch_bounds__(256) void conv3x3_counts_mfma_kernel(CntArgs a) {
   const float invT = 1.0f / (float)a.T;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    // after the swaps the even lane holds all four digits of accumulator row r, the odd lane those of row r + 8
-    const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc0[r], (unsigned)acc0[r + 8], false, false);
-    const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc1[r], (unsigned)acc1[r + 8], false, false);
-    const long long hi = (long long)(int)p01[0] * 256 + (int)p01[1], lo = (long long)(int)p23[0] * 256 + (int)p23[1];
-    const double s = fma((double)hi, 65536.0, (double)lo);
+    const double s = spk_digits_recombine<long long>(acc0[r], acc0[r + 8], acc1[r], acc1[r + 8]);
     const float xsum = (float)fma(s, sc, bT);                       // sum over T of the pre-activations, rounded once
-    const int rr = r + 8 * odd;
-    const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;           // accumulator row of register rr
+    const int rr = r + 8 * odd;                                     // (the even lane recombined register r, the odd lane r + 8)
+    const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;           // spk_acc_row(rr, half) of den_common.h, written out
     const long long Ro = tile * 32 + orow;
     if (Ro < nrows) {
       const int ob = (int)(Ro / HW), op = (int)(Ro % HW);
@@ -415,7 +402,7 @@ __global__ __launch_bounds__(256) void conv3x3_counts_mfma_shared_kernel(CntArgs
   __shared__ v4i s_a[2][4 * MAXP * 2 + 8];                   // the count records of the (up to) four images the 128 rows lie in
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int HW = a.H * a.W;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const long long nrows = (long long)Bn * HW;
   const long long tile = (long long)blockIdx.x * 4 + wave;
   const long long R0 = (long long)blockIdx.x * 128;
@@ -505,19 +492,17 @@ __global__ __launch_bounds__(256) void conv3x3_counts_mfma_shared_kernel(CntArgs
     step(c, P0{});
     if (c + 1 < nchunks) step(c + 1, P1{});
   }
+  // (the epilogue of conv3x3_counts_mfma_kernel, the definition, written out: as a shared function both kernels compile differently)
   const int col = lane & 31, ch = col & 15, odd = col >> 4;
   const int co = g * 16 + ch;
   const double sc = a.scale[co], bT = a.bias[co] * (double)a.T;
   const float invT = 1.0f / (float)a.T;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc0[r], (unsigned)acc0[r + 8], false, false);
-    const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc1[r], (unsigned)acc1[r + 8], false, false);
-    const long long hi = (long long)(int)p01[0] * 256 + (int)p01[1], lo = (long long)(int)p23[0] * 256 + (int)p23[1];
-    const double s = fma((double)hi, 65536.0, (double)lo);
+    const double s = spk_digits_recombine<long long>(acc0[r], acc0[r + 8], acc1[r], acc1[r + 8]);
     const float xsum = (float)fma(s, sc, bT);                       // sum over T of the pre-activations, rounded once
-    const int rr = r + 8 * odd;
-    const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;           // accumulator row of register rr
+    const int rr = r + 8 * odd;                                     // (the even lane recombined register r, the odd lane r + 8)
+    const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;           // spk_acc_row(rr, half) of den_common.h, written out
     const long long Ro = tile * 32 + orow;
     if (Ro < nrows) {
       const int ob = (int)(Ro / HW), op = (int)(Ro % HW);

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_fp6_kernel(Fp6Args a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = a.nch0;
   const int G = a.Cout >> 4;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const int total = Bn * G * (SPLIT ? 2 : 1);
 
   // zero both A images once: the borders stay zero for the whole kernel, interiors are overwritten by DMA
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void conv3x3_fp6_lastpos_kernel(Fp6Args a) {
   const int HW = a.H * a.W, nchunks = a.nch0;
   const int g = blockIdx.y * 4 + wave;                      // Cout % 64 == 0: groups come in fours
   const int b0 = blockIdx.x * 2 * LP_TILES;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   if (b0 >= Bn) return;
   const int row = lane & 31, half = lane >> 5;
   const int hsel = (row >> 2) & 1, tt = (row & 3) + 4 * (row >> 3);       // A row -> (image parity, time step)

@@ -639,7 +639,7 @@ do {                                                                            
         // the count of accumulator row r sits in the A-layout lane (r & 3) + 8 (r >> 2) + 4 half
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rowA = (r & 3) + 8 * (r >> 2);
+          const int rowA = spk_acc_row(r, 0);
           const int c0 = __builtin_amdgcn_readlane(cnt[i], rowA), c1 = __builtin_amdgcn_readlane(cnt[i], rowA + 4);
           cntv[r] = half ? c1 : c0;
         }
@@ -748,7 +748,7 @@ __device__ __forceinline__ void fp6v2_handover(const V2Args& a) {
 
 template <int H, int W, int NWV, bool SPLIT = false>
 __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_kernel(V2Args a) {
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   int g, il, lanes;
   fp6v2_wg_map(a, g, il, lanes);
   if constexpr (NWV == 8 && !SPLIT) {
@@ -771,7 +771,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_kernel(V2Args a) {
 // Small batches: two half-image items per image (fp6v2_body HALF), four waves
 template <int H, int W>
 __global__ __launch_bounds__(256, 1) void conv3x3_fp6v2_half_kernel(V2Args a) {
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   int g, il, lanes;
   fp6v2_wg_map(a, g, il, lanes);
   fp6v2_body<H, W, 4, false, 3, true>(a, g, il, lanes, Bn, nullptr);
@@ -843,7 +843,7 @@ __device__ __forceinline__ void fp6v2_lastpos_body(const V2Args& a, const int bi
   constexpr int HW = H * W, NP = SPK_V2_LP_PAIRS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = a.nch, G = a.Cout >> 5;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   // (without the hand-over this launch follows the repair launch on the stream and re-arms the flag counter)
   if (!a.handover && bid == 0 && threadIdx.x == 0) { a.ws.flags[1] = a.ws.flags[0]; a.ws.flags[0] = 0u; }
   // one unit = NP 32-row tiles = NP image pairs (the lane halves of a tile are the two images) x one channel group: the
@@ -1042,7 +1042,7 @@ __device__ __forceinline__ void fixup_neuron(const V2Args& a, long long n, unsig
 template <int H, int W>
 __device__ __forceinline__ void fp6v2_fixup_body(const V2Args& a, long long n_words, const unsigned bid, const unsigned nb,
                                                  unsigned long long* sS) {
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   const unsigned count = a.ws.flags[a.handover ? 1 : 0];       // published by the main launch (fp6v2_handover), or live
   spk_cert_scan<true>(a.ws, count, bid, nb, n_words, threadIdx.x == 0,
                       [&](long long n) __attribute__((always_inline)) { fixup_neuron<H, W>(a, n, sS, Bn); });
@@ -1062,7 +1062,7 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int nch = a.nch, G = a.Cout >> 5;
-  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;
+  const int Bn = a.n_dyn ? (*a.n_dyn < a.B ? *a.n_dyn : a.B) : a.B;     // spk_batch_count of spk_common.h, written out
   const int g = bid % G, b0 = (bid / G) * 8;
   if (b0 >= Bn) return;                                     // (uniform over the workgroup)
   const int row = lane & 31, half = lane >> 5;

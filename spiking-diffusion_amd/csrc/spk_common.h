@@ -22,6 +22,9 @@ static inline int spk_grid(long long work_items, int cap) {
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+// Images a kernel processes: the optional device-side count, at most B.  Buffers and strides stay sized by B.
+__device__ __forceinline__ int spk_batch_count(const int* n_dyn, int B) { return n_dyn ? (*n_dyn < B ? *n_dyn : B) : B; }
+
 // One LIF step, exactly the arithmetic of
 // SJ/activation_based/neuron.py:799-811 with v_reset as a parameter:
 //   v = v + (x - (v - v_reset)) / tau ; s = v >= v_th ; v = v_reset * s + (1 - s) * v
@@ -162,6 +165,21 @@ __device__ __forceinline__ uint2 spk_e2m1_record(unsigned bits16) {
   uint2 o;
   o.x = spk_spread8(bits16 & 0xffu);
   o.y = spk_spread8((bits16 >> 8) & 0xffu);
+  return o;
+}
+// byte spike records ("PTC" / "CPTC" u8): the same 16 channels as 16 bytes of 0 or 1, channel k in byte k.
+// spk_spread4_u8: bit k -> byte k of four channel bits (the multiply puts a copy of the nibble at bit offsets 0, 7, 14, 21).
+constexpr unsigned spk_spread4_u8(unsigned nib) { return ((nib & 0xfu) * 0x00204081u) & 0x01010101u; }
+static_assert(spk_spread4_u8(0x0u) == 0x00000000u && spk_spread4_u8(0xFu) == 0x01010101u, "byte spike record");
+static_assert(spk_spread4_u8(0xAu) == 0x01000100u && spk_spread4_u8(0x1u) == 0x00000001u, "byte spike record");
+static_assert(spk_spread4_u8(0x38u) == 0x01000000u, "byte spike record: only the low nibble counts");
+// the record of a row of spk_transpose16_rows
+__device__ __forceinline__ uint4 spk_u8_record(unsigned bits16) {
+  uint4 o;
+  o.x = spk_spread4_u8(bits16);
+  o.y = spk_spread4_u8(bits16 >> 4);
+  o.z = spk_spread4_u8(bits16 >> 8);
+  o.w = spk_spread4_u8(bits16 >> 12);
   return o;
 }
 // four fp32 spikes (zero / nonzero) of consecutive channels -> their 16-bit quarter of a record

@@ -205,13 +205,10 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK> a) 
       for (int rt = 0; rt < 2; ++rt) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-          const v2u p01 = __builtin_amdgcn_permlane16_swap((unsigned)acc[rt][0][r], (unsigned)acc[rt][0][r + 8], false, false);
-          const v2u p23 = __builtin_amdgcn_permlane16_swap((unsigned)acc[rt][1][r], (unsigned)acc[rt][1][r + 8], false, false);
-          const long long hi = (long long)(int)p01[0] * 256 + (int)p01[1], lo = (long long)(int)p23[0] * 256 + (int)p23[1];
-          const double s = fma((double)hi, 65536.0, (double)lo);
+          const double s = spk_digits_recombine<long long>(acc[rt][0][r], acc[rt][0][r + 8], acc[rt][1][r], acc[rt][1][r + 8]);
           const float xsum = (float)fma(s, sc, bT);
           const int rr = r + 8 * odd;
-          const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;
+          const int orow = (rr & 3) + 8 * (rr >> 2) + 4 * half;     // spk_acc_row(rr, half) of den_common.h, written out
           const int op = rt * 32 + orow;
           const float lg = xsum * invT;
           s_logit[op][co] = lg;

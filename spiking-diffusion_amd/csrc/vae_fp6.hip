@@ -383,14 +383,8 @@ __global__ __launch_bounds__(SPK_VT_NWV * 64, 1) void vae_fp6_kernel(TArgs a) {
             uint8_t* rec = reinterpret_cast<uint8_t*>(a.out) + ((((long long)b * G + g) * Ho * Wo + oy * Wo + ox) * T16 + t) * 16;
             *reinterpret_cast<uint2*>(rec + 8 * hi) = o;
           }
-          if (ok && OUT == SPK_VAE_OUT_PTC) {
-            uint4 o;
-            o.x = ((bitsv & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.y = (((bitsv >> 4) & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.z = (((bitsv >> 8) & 0xfu) * 0x00204081u) & 0x01010101u;
-            o.w = (((bitsv >> 12) & 0xfu) * 0x00204081u) & 0x01010101u;
-            *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.out) + (pos * T16 + t) * a.Cout + g * 32 + 16 * hi) = o;
-          }
+          if (ok && OUT == SPK_VAE_OUT_PTC)
+            *reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.out) + (pos * T16 + t) * a.Cout + g * 32 + 16 * hi) = spk_u8_record(bitsv);
         }
       }
     };
