@@ -225,8 +225,12 @@ int spk_pack_conv_weight(const float* w, float* packed, int Cout, int Cin, int k
  *                out_ptc is written as nibble-packed fp4 "C4" (see spk_den_conv3x3_mfma_fp6; Cout % 64 == 0);
  *                SPK_CHUNK_S32: as "S32" (see spk_den_conv3x3_mfma_fp6v2; Cout % 32 == 0).
  *   out_counts (mode LIF, optional): per-neuron spike counts over T, u8 [B,Cout/32,Ho*Wo,32].
- *   n_dyn_or_null: optional device-side image count (<= B, see spk_select_active): only images [0, *n_dyn) are computed;
- *                buffers stay sized by B. */
+ *   n_dyn_or_null: optional device-side image count (0 <= *n_dyn <= B: the caller's duty; see spk_select_active): only images
+ *                [0, *n_dyn) are computed; buffers stay sized by B.  For an image at or past the count NOTHING is written: no byte
+ *                of any output (spikes, fp32 values, BN outputs, spike counts) and not its v_inout, which keeps the value it
+ *                came with; a count of 0 writes nothing at all.  The count is read on the device when the kernel runs, so a
+ *                captured graph follows the value its tensor holds at each replay.  The same holds for every n_dyn_or_null /
+ *                n_dyn below (tests/test_gpu_image_count.py). */
 int spk_conv_fused_fwd(const void* in0, const uint8_t* in1, int C0, int C1, int in_kind, const float* w_packed,
                        const float* bias, const float* bn_a, const float* bn_b, float* v_inout, uint8_t* out_ptc,
                        float* out_f32, float* out_pre, uint8_t* out_u8, const float* coef, int apply_tanh, int mode,
@@ -315,6 +319,9 @@ int spk_den_conv3x3_mfma_fp6(const uint8_t* in_c4, int nch, const uint8_t* wq, c
  * form: 0 = automatic (7x7 latents with fewer items -- B x Cout / 32 -- than half the CUs run two half-image items per image on
  * four-wave workgroups: R/main.py's own n_samples = 16 leaves half the chip idle otherwise), 1 = whole-image items always (the
  * reference form for the bit-equality test of the split).  Same spikes bit for bit either way.
+ * n_dyn_or_null as in spk_conv_fused_fwd, in every launch of the call: an image at or past the count gets no record, no spike
+ * count and no flag entry (neither id nor bitmap bit), its last position included; with a count of 0 the workspace still comes back
+ * clean and word 1 is 0.
  * SPK_ERR_UNSUPPORTED unless spk_den_conv3x3_mfma_fp6v2_supported (Cin = 32 * nch). */
 long long spk_den_packed_weight_fp6v2_bytes(int Cout, int Cin);
 int spk_den_pack_weight_fp6v2(const float* w, const float* bias, uint8_t* wq, double* scale, double* bias_d, float* wl1,
@@ -326,8 +333,9 @@ int spk_den_conv3x3_mfma_fp6v2(const uint8_t* in_s32, int nch, const uint8_t* wq
                                const int* n_dyn_or_null, int flag_cap, int form, spk_stream_t stream);
 /* Measurement aid: re-run ONE tail part of the last spk_den_conv3x3_mfma_fp6v2 call on the same arguments and workspace --
  * part 2: the exact recomputation of the neurons that call flagged (flag_words[1] holds their number, the id list is intact;
- * recomputing them again writes the same spikes), part 4: the last position of every image (7x7).  bench.py times these to
- * report `repair_ms` / `last_position_ms` per layer; flag_words[1] / (B * Cout * H * W) is the flagged fraction. */
+ * recomputing them again writes the same spikes), part 4: the last position of every image (7x7) below the count
+ * (n_dyn_or_null as in spk_den_conv3x3_mfma_fp6v2: the last position of an image at or past it is left as it was).  bench.py times
+ * these to report `repair_ms` / `last_position_ms` per layer; flag_words[1] / (B * Cout * H * W) is the flagged fraction. */
 int spk_den_conv3x3_mfma_fp6v2_part(const uint8_t* in_s32, int nch, const uint8_t* wq, const double* scale,
                                     const double* bias_d, const float* wl1, const int* qtab, const float* bn_a,
                                     const float* bn_b, uint8_t* out_s32, uint8_t* out_counts_or_null, unsigned* flag_words,
@@ -336,7 +344,10 @@ int spk_den_conv3x3_mfma_fp6v2_part(const uint8_t* in_s32, int nch, const uint8_
 /* The same layer restricted to the positions the sampler will read (7x7 only): need = the buffer written by
  * spk_select_needed(..., R = need_radii) for the same B; radius (1..need_radii) selects the lists this layer computes --
  * 1 for the layer whose output the logits convolution reads, 2 for the one below it, ...  Listed positions (and the 49th)
- * receive exactly the spikes of the full call; the other positions of out_s32 / out_counts are left as they were. */
+ * receive exactly the spikes of the full call; the other positions of out_s32 / out_counts are left as they were.
+ * n_dyn (required) as n_dyn_or_null of spk_den_conv3x3_mfma_fp6v2.  The lists carry the slot count of the spk_select_needed call
+ * that wrote them; *n_dyn may be lower by the time of this call, and then it decides: a listed slot at or past it is written
+ * nowhere -- no record, count or flag entry. */
 int spk_den_conv3x3_mfma_fp6v2_listed(const uint8_t* in_s32, int nch, const uint8_t* wq, const double* scale,
                                       const double* bias_d, const float* wl1, const int* qtab, const float* bn_a,
                                       const float* bn_b, uint8_t* out_s32, uint8_t* out_counts, unsigned* flag_words, int T,

@@ -275,8 +275,9 @@ static_assert(v2_roles_ok(8, V2_FULL_NCA, V2_FULL_NCWW, 7 * 2, W_PIECES, 7 * 7 *
 // register allocation are its own (one body whose chunk loops alone were per class spilled 109 registers at the joins).
 template <int H, int W, int NWV, bool SPLIT, int NTP, bool HALF = false, int CLS = V2_INT>
 __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const int il, const int lanes, const int n_images,
-                                           const int* __restrict__ slots) {
+                                           const int* __restrict__ slots, const int n_live = 0) {
   constexpr bool PRUNE = NTP > 0;
+  constexpr bool LIVE = PRUNE && !HALF;                // listed slots: one at or past the image count n_live is computed and dropped
   static_assert(!HALF || (PRUNE && !SPLIT && H == 7 && W == 7 && NWV == 4 && NTP == 3), "half-image items: 7x7, four waves x three tiles");
   // how the four-digit form counts the active inputs of a row: REC: once per input record and chunk for the whole workgroup
   // (full items: the per-fragment popcounts were 29 % of the launch's vector issue), else per A fragment in the K loop
@@ -710,7 +711,7 @@ do {                                                                            
       // accumulator lane half == position within the tile; a list that does not fill its last tiles repeats its last
       // position there: computed and dropped
       const int p = (PRUNE || BSKIP) ? p_out[i] : 2 * ti + half + band * HWb;
-      const bool listed = !PRUNE || 2 * ti + half < n_list;
+      const bool listed = (!PRUNE || 2 * ti + half < n_list) && (!LIVE || b < n_live);
       if (flg && listed) spk_cert_flag(a.ws, ((long long)b * a.Cout + co) * HW + p);
       const long long rec = (((long long)b * G + g) * HW + p) * POSB;
       store_tile_spikes(a.out, a.out_cnt, mybits, lane, rec, (((long long)b * G + g) * HW + p) * 32, listed);
@@ -785,6 +786,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_fp6v2_half_kernel(V2Args a) {
 template <int H, int W, int NWV>
 __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_listed_kernel(V2Args a) {
   constexpr int NC = (H * W / 2) / 4;                    // classes: 1 .. NC tiles per wave
+  // (the lists carry the image count of the spk_select_needed call that wrote them; a.n_dyn may have been lowered since: the tail
+  //  launch follows it, and so must every store and flag of this one)
+  const int Bn = spk_batch_count(a.n_dyn, a.B);
   int g, il, lanes;
   fp6v2_wg_map(a, g, il, lanes);
   int cnt[NC], work[NC], u[NC];
@@ -822,9 +826,9 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_listed_kernel(V2Arg
   const int* slots = a.cls_list + (long long)(cls < 0 ? 0 : cls) * a.B;
   static_assert(NWV == 8, "listed positions: two waves per SIMD");
   switch (cls) {
-    case 0: case 1: fp6v2_body<H, W, 8, false, 1>(a, g, il_c, lanes_c, cnt[cls], slots); break;
-    case 2: case 3: fp6v2_body<H, W, 8, false, 2>(a, g, il_c, lanes_c, cnt[cls], slots); break;
-    case 4: case 5: fp6v2_body<H, W, 8, false, 3>(a, g, il_c, lanes_c, cnt[cls], slots); break;
+    case 0: case 1: fp6v2_body<H, W, 8, false, 1>(a, g, il_c, lanes_c, cnt[cls], slots, Bn); break;
+    case 2: case 3: fp6v2_body<H, W, 8, false, 2>(a, g, il_c, lanes_c, cnt[cls], slots, Bn); break;
+    case 4: case 5: fp6v2_body<H, W, 8, false, 3>(a, g, il_c, lanes_c, cnt[cls], slots, Bn); break;
     default: break;
   }
   fp6v2_handover(a);
