@@ -70,7 +70,7 @@ struct V2Args {
 
 constexpr int SPK_V2_KMIN = 2;          // listed positions: an item of fewer tiles per wave still costs about this many (operand copies)
 constexpr float SPK_V2_SPARE = 1.0f;    // factor on the certification bound (2.0f = the first builds' spare factor)
-constexpr int SPK_V2_REC_STEP = 13;     // the K-loop step whose gap takes the record popcounts (the reads are issued at step 1; 7: no gain, 13: +0.4 %)
+constexpr int SPK_V2_REC_STEP = 13;     // the K-loop step (= two MFMAs) whose gap takes the record popcounts (the reads are issued at step 1; 7: no gain, 13: +0.4 %)
 // Accumulators of the two-waves-per-SIMD kernels stay in VGPRs (243 registers, no scratch; the round-2/3 form with eight tiles in AGPRs:
 // dense reverse process 91.2 / 92.4 against 90.6 / 90.2 ms, profiles/r4_ab_kernel_variants.txt).
 // Full 7x7 batches run repair + last position as ONE tail launch (hand-over by the main launch): 1.6 % faster than two launches
@@ -96,6 +96,15 @@ constexpr int SPK_V2_LP_SPLIT_MAX = 512;   // last-position part: up to this man
                                            // (1024 until round 4; same box, dense / elimination / lists, ms per 100-step sample at B = 256:
                                            //  1024: 88.0 / 43.5 / 34.2, 512: 87.4 / 43.3 / 34.1, 256 and 0: 87.4 / 44.3 / 35.2)
 constexpr int SPK_V2_PF = 6;            // four-wave items: A fragments requested this many steps ahead of the MFMA that consumes them
+// Full 7x7 items (tap pairs, v2p_sched): register sets of the A-fragment ring per wave class.  The ring must close over a chunk (the
+// fragment count -- 15 interior, 9 top / right / left, 11 bottom -- a multiple of the ring, or the ring's last owners dead in time):
+// 5 / 3 / 4 sets request a fragment 4-12 / 2 / 2-3 MFMAs ahead of its first use.  The border waves reach the chunk barrier 12-18 MFMAs
+// before the interior waves of their SIMD: their shorter distance costs nothing.  (Interior waves on 3 sets, two MFMAs ahead
+// everywhere: profiles/tap_pair_ab.txt.)
+constexpr int SPK_V2_TP_SLOTS_INT = 5;
+constexpr int v2_tp_slots(int cls) { return cls == 0 ? SPK_V2_TP_SLOTS_INT : (cls == 4 ? 4 : 3); }
+constexpr int SPK_V2_TP_PFD = 12;       // ... and at most this many MFMAs ahead (one pair block)
+constexpr int SPK_V2_TP_TAIL = 6;       // the chunk barrier sits this many MFMAs before the end of the chunk
 
 // Certification.  The approximate path (the leading digits, fp32 recombination, folded constants) and the exact path (six
 // digits, fp64 recombination, the reference's BN / LIF operations) run the same LIF recursion on pre-activations that differ by
@@ -146,30 +155,45 @@ __device__ const uint8_t V2_HALF_REC[2][64] = {
 // an exact integer accumulation.  24 of the 49 positions lie on the border and miss 3 of their 9 taps (5 at a corner).  Position 48 is the
 // tail launch's; the other 23 are gathered by SIDE, one wave per side, so that both positions of a tile miss the same three taps and the
 // whole tap BLOCK -- its MFMAs, its two weight tiles, its fragment reads -- drops out of that wave's K loop:
-//   top    0 1 | 2 3 | 4 5            6 blocks x 3 tiles   (no taps 0 1 2)
-//   right  6 13 | 20 27 | 34 41       6 blocks x 3 tiles   (no taps 2 5 8)
-//   left   7 14 | 21 28 | 35 42       6 blocks x 3 tiles   (no taps 0 3 6)
-//   bottom 43 44 | 45 46 | 47 40      6 blocks x 3 tiles + taps 6 7 8 on the third tile alone (40 is interior)
-//   four interior waves               9 blocks x 3 tiles
+//   top    0 1 | 2 3 | 4 5            6 taps x 3 tiles   (no taps 0 1 2)
+//   right  6 13 | 20 27 | 34 41       6 taps x 3 tiles   (no taps 2 5 8)
+//   left   7 14 | 21 28 | 35 42       6 taps x 3 tiles   (no taps 0 3 6)
+//   bottom 43 44 | 45 46 | 47 40      6 taps x 3 tiles + taps 6 7 8 on the third tile alone (40 is interior)
+//   four interior waves               9 taps x 3 tiles
 // i.e. 11 x 6 + 13 x 9 = 183 (tile, tap) steps per chunk instead of 216: 15.25 MFMAs per row tile and chunk on average instead of 18.
-// A K loop follows its class's block list: blocks in issue order, each one tap on the LAST nt tiles of the wave.  The bottom wave's
-// one-tile blocks come second, not last: behind the chunk barrier (four steps before the end) nothing may read the current buffers,
-// and a block's weight tiles are requested at the first step of the block before it.
+// A K loop follows its class's block list: blocks in issue order, each on the LAST nt tiles of the wave.  The bottom wave's one-tile
+// blocks come second, not last: behind the chunk barrier nothing may read the current buffers.
+//
+// TAP PAIRS (full 7x7 items).  A digit-pair MFMA carries the SAME 32 input channels in both K halves, so lanes r and r + 32 read the
+// same 16 bytes of the spike record: 1 KB of LDS return traffic per A fragment for 512 distinct bytes.  A PAIR block puts two adjacent
+// TAPS (a, a + 1) of ONE digit into the K halves instead: lanes 0-31 read the cell of tap a, lanes 32-63 the cell of tap a + 1, and the
+// block issues four MFMAs per row tile -- digit 0 at 2^8 and digit 1 at 2^3 into acc[i][0], digit 2 at 2^8 and digit 3 at 2^3 into
+// acc[i][1] -- where two single-tap blocks issued 2 x 2.  The scale is uniform over the lanes; the accumulators hold the same exact
+// integers 32 D_even + D_odd (sums of exact products below 2^24: the order is free), so every pre-activation, spike, count and flag is
+// bit for bit what the digit-pair form gives.  One A fragment now feeds four MFMAs: 98 fragment reads per chunk instead of 183.  The
+// packed weights are untouched: a tile (tap, pair) keeps the even digit in the slots of lanes 0-31 and the odd digit in those of lanes
+// 32-63 (16 bytes at lane * 16, 8 bytes at 1024 + lane * 8), so the operand "(tap a | tap a + 1), digit d" is the matching half of tile
+// (a, pair) for lanes 0-31 and of tile (a + 1, pair) for lanes 32-63 -- 2 WT further on, ONE constant: two per-lane base registers
+// (16-byte and 8-byte part; the odd digit is 512 / 256 bytes behind the even one), every 16-lane group still reading 256 contiguous
+// bytes.  A class with an odd number of taps keeps its last tap (8) as a SINGLE block: the two digit-pair MFMAs per tile of every other form.
+// Same box, three alternating passes, B = 256 (profiles/tap_pair_ab.txt): dense reverse process 77.79-77.99 -> 76.14-76.66 ms, den.conv4 /
+// conv5 main + tail 320-323 / 309 -> 311-313 / 301-304 us; SQ_INSTS_MFMA per den.conv4 launch unchanged, SQ_INSTS_LDS 15.3 M -> 12.6 M,
+// SQ_LDS_IDX_ACTIVE 54.2 M -> 43.0 M.
 enum : int { V2_INT = 0, V2_TOP, V2_RIGHT, V2_LEFT, V2_BOTTOM, V2_NCLS };
-struct V2Plan { int nblk; int tap[9]; int nt[9]; };
+struct V2Plan { int nblk; int tap[9]; int nt[9]; int pair[9]; };   // pair[b] = 1: taps (tap[b], tap[b] + 1) in the K halves
 constexpr int V2_FT = 3;                                 // row tiles per wave of a full item
 constexpr V2Plan V2_PLAN[V2_NCLS] = {
-    {9, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {3, 3, 3, 3, 3, 3, 3, 3, 3}},
-    {6, {3, 4, 5, 6, 7, 8}, {3, 3, 3, 3, 3, 3}},
-    {6, {0, 1, 3, 4, 6, 7}, {3, 3, 3, 3, 3, 3}},
-    {6, {1, 2, 4, 5, 7, 8}, {3, 3, 3, 3, 3, 3}},
-    {9, {0, 6, 7, 8, 1, 2, 3, 4, 5}, {3, 1, 1, 1, 3, 3, 3, 3, 3}}};
-constexpr V2Plan v2_uniform_plan(int nt) {               // every other form: all nine taps on all tiles
-  V2Plan p = {9, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {}};
+    {5, {0, 2, 4, 6, 8}, {3, 3, 3, 3, 3}, {1, 1, 1, 1, 0}},
+    {3, {3, 5, 7}, {3, 3, 3}, {1, 1, 1}},
+    {3, {0, 3, 6}, {3, 3, 3}, {1, 1, 1}},
+    {3, {1, 4, 7}, {3, 3, 3}, {1, 1, 1}},
+    {5, {0, 6, 8, 2, 4}, {3, 1, 1, 3, 3}, {1, 1, 0, 1, 1}}};
+constexpr V2Plan v2_uniform_plan(int nt) {               // every other form: all nine taps on all tiles, one tap per block
+  V2Plan p = {9, {0, 1, 2, 3, 4, 5, 6, 7, 8}, {}, {}};
   for (int b = 0; b < 9; ++b) p.nt[b] = nt;
   return p;
 }
-constexpr int v2_plan_start(const V2Plan& p, int blk) {  // first step of a block (blk == nblk: the number of steps)
+constexpr int v2_plan_start(const V2Plan& p, int blk) {  // first step (one A fragment: a block x one of its tiles) of a block (blk == nblk: their number)
   int n = 0;
   for (int b = 0; b < blk; ++b) n += p.nt[b];
   return n;
@@ -178,6 +202,85 @@ constexpr int v2_plan_blk(const V2Plan& p, int s) {      // block of a step
   int b = 0;
   while (s >= p.nt[b]) s -= p.nt[b++];
   return b;
+}
+constexpr bool v2_plan_has(const V2Plan& p, int b, int tap) { return p.tap[b] == tap || (p.pair[b] && p.tap[b] + 1 == tap); }
+// The MFMAs ("ops") of a tap-pair K loop.  A block issues nd = 4 (pair) or 2 (single) B operands on each of its nt tiles, operand
+// outer and tile inner: a B operand serves nt consecutive MFMAs and dies, and nt = 3 MFMAs lie between two that accumulate into the
+// same register.  Operand `sel` of a pair block is digit sel (accumulator sel >> 1, scale 2^8 / 2^3 for even / odd), of a single
+// block the digit-pair tile sel.  A one-tile pair block runs its digits 0 2 1 3 (accumulators 0 1 0 1, as the single blocks do).
+constexpr int v2p_nd(const V2Plan& p, int b) { return p.pair[b] ? 4 : 2; }
+constexpr int v2p_op_start(const V2Plan& p, int blk) {   // first op of a block (blk == nblk: the number of ops)
+  int n = 0;
+  for (int b = 0; b < blk; ++b) n += v2p_nd(p, b) * p.nt[b];
+  return n;
+}
+constexpr int v2p_op_blk(const V2Plan& p, int m) {
+  int b = 0;
+  while (m >= v2p_op_start(p, b + 1)) ++b;
+  return b;
+}
+constexpr int v2p_swap(int q) { return ((q & 1) << 1) | (q >> 1); }   // 0 2 1 3 (its own inverse)
+constexpr int v2p_op_sel(const V2Plan& p, int b, int q) { return p.nt[b] > 1 ? q / p.nt[b] : (p.pair[b] ? v2p_swap(q) : q); }
+constexpr int v2p_op_tile(const V2Plan& p, int b, int q) { return V2_FT - p.nt[b] + (p.nt[b] > 1 ? q % p.nt[b] : 0); }
+constexpr int v2p_b_start(const V2Plan& p, int blk) {    // first B operand of a block (blk == nblk: their number)
+  int n = 0;
+  for (int b = 0; b < blk; ++b) n += v2p_nd(p, b);
+  return n;
+}
+constexpr int v2p_b_blk(const V2Plan& p, int g) {
+  int b = 0;
+  while (g >= v2p_b_start(p, b + 1)) ++b;
+  return b;
+}
+// first and last op that reads A fragment f (= step f) / B operand g
+constexpr int v2p_a_first(const V2Plan& p, int f) { return v2p_op_start(p, v2_plan_blk(p, f)) + f - v2_plan_start(p, v2_plan_blk(p, f)); }
+constexpr int v2p_a_last(const V2Plan& p, int f) { return v2p_a_first(p, f) + (v2p_nd(p, v2_plan_blk(p, f)) - 1) * p.nt[v2_plan_blk(p, f)]; }
+constexpr int v2p_b_first(const V2Plan& p, int g) {
+  const int b = v2p_b_blk(p, g), sel = g - v2p_b_start(p, b);
+  return v2p_op_start(p, b) + (p.nt[b] > 1 ? sel * p.nt[b] : (p.pair[b] ? v2p_swap(sel) : sel));
+}
+constexpr int v2p_b_last(const V2Plan& p, int g) { return v2p_b_first(p, g) + p.nt[v2p_b_blk(p, g)] - 1; }
+// WHEN the reads are issued.  A fragments live in a ring of `nslot` register sets (fragment f in set f % nslot), B operands in four
+// (operand sel of a block in set sel).  A read is issued in front of op `at`: as soon as its set is free (the op after the last use
+// of the set's previous owner, the previous chunk's if need be: the loop is periodic over the chunks of an item), the A reads not
+// more than `pfd` ops ahead of their first use.  at < 0: the read belongs to the previous chunk's tail, at op nm + at, BEHIND that
+// chunk's barrier at op mb = nm - tail (in front of it the next chunk's buffers are still being copied) -- or to the prologue of an
+// item's first chunk.  ok: every read in front of its first use and behind the last use of its set's previous owner, every read of the
+// current buffers in front of the chunk barrier (the reads scheduled AT op mb are issued first, then the barrier).
+struct V2Sched { int nf, nb, nm, mb; int a_at[27]; int b_at[36]; int a_dist, b_dist; bool ok; };   // *_dist: fewest ops between a read and its first use
+constexpr V2Sched v2p_sched(const V2Plan& p, int nslot, int pfd, int tail) {
+  V2Sched s = {};
+  s.nf = v2_plan_start(p, p.nblk); s.nb = v2p_b_start(p, p.nblk); s.nm = v2p_op_start(p, p.nblk); s.mb = s.nm - tail;
+  s.ok = s.nf <= 27 && s.nb <= 36 && s.nf >= nslot && tail > 0 && s.mb > 0;
+  s.a_dist = s.b_dist = s.nm;
+  for (int f = 0; f < s.nf && s.ok; ++f) {
+    int free_at = -s.nm;
+    for (int k = 1; k <= s.nf; ++k) {
+      const int g = f - k, gg = g < 0 ? g + s.nf : g;
+      if (gg % nslot == f % nslot) { free_at = v2p_a_last(p, gg) + 1 - (g < 0 ? s.nm : 0); break; }
+    }
+    const int first = v2p_a_first(p, f);
+    int at = free_at > first - pfd ? free_at : first - pfd;
+    if (at < 0 && at < s.mb - s.nm) at = s.mb - s.nm;
+    s.a_at[f] = at;
+    s.a_dist = first - at < s.a_dist ? first - at : s.a_dist;
+    s.ok = s.ok && at >= free_at && at <= first && (at < 0 ? at + s.nm >= s.mb : at <= s.mb);
+  }
+  for (int g = 0; g < s.nb && s.ok; ++g) {
+    const int sel = g - v2p_b_start(p, v2p_b_blk(p, g));
+    int free_at = -s.nm;
+    for (int k = 1; k <= s.nb; ++k) {
+      const int h = g - k, hh = h < 0 ? h + s.nb : h;
+      if (hh - v2p_b_start(p, v2p_b_blk(p, hh)) == sel) { free_at = v2p_b_last(p, hh) + 1 - (h < 0 ? s.nm : 0); break; }
+    }
+    const int first = v2p_b_first(p, g);
+    int at = free_at;
+    if (at < 0 && at < s.mb - s.nm) at = s.mb - s.nm;
+    s.b_at[g] = at;
+    s.b_dist = first - at < s.b_dist ? first - at : s.b_dist;
+    s.ok = s.ok && at >= free_at && at <= first && (at < 0 ? at + s.nm >= s.mb : at <= s.mb);
+  }
+  return s;
 }
 // [wave][tile][half] -> position; waves w and w + 4 share a SIMD: one border wave beside one interior wave, i.e. 45 / 45 / 45 / 48
 // steps per SIMD and chunk instead of 54.  Same box, three alternating passes, B = 256 (profiles/border_skip_ab.txt): den.conv4 /
@@ -199,20 +302,24 @@ constexpr bool v2_full_map_ok() {
         if (p >= 48 || seen[p]) return false;
         seen[p] = true;
       }
+  int steps = 0;                                         // (tile, tap) steps issued: the 183 the border skip leaves, none of them beside the image
   for (int w = 0; w < 8; ++w) {
     const V2Plan& pl = V2_PLAN[V2_WAVE_CLS[w]];
+    for (int b = 0; b < pl.nblk; ++b)
+      if (pl.tap[b] + pl.pair[b] > 8 || pl.nt[b] < 1 || pl.nt[b] > V2_FT) return false;   // a pair is (a, a + 1)
     for (int i = 0; i < V2_FT; ++i)
       for (int tap = 0; tap < 9; ++tap) {
         int n = 0;
-        for (int b = 0; b < pl.nblk; ++b) n += pl.tap[b] == tap && i >= V2_FT - pl.nt[b];
+        for (int b = 0; b < pl.nblk; ++b) n += v2_plan_has(pl, b, tap) && i >= V2_FT - pl.nt[b];
         if (n > 1) return false;
+        steps += n;
         for (int h = 0; h < 2 && n == 0; ++h) {
           const int y = V2_FULL_POS[w][i][h] / 7 + tap / 3 - 1, x = V2_FULL_POS[w][i][h] % 7 + tap % 3 - 1;
           if (y >= 0 && y < 7 && x >= 0 && x < 7) return false;
         }
       }
   }
-  return true;
+  return steps == 11 * 6 + 13 * 9;
 }
 static_assert(v2_full_map_ok(), "full 7x7 items: position table and block lists");
 
@@ -220,7 +327,7 @@ static_assert(v2_full_map_ok(), "full 7x7 items: position table and block lists"
 // waves of a workgroup: wave w owns A pieces w * npa + j (j < npa = ceil(14 / nca)) and W pieces w + ncww * q.  Every form but the full
 // 7x7 one uses all its waves.  On full 7x7 items the interior waves (27 steps per chunk) set the length of the chunk and the border wave
 // of their SIMD reaches the chunk barrier 9 steps (bottom: 6) before them: the three 18-step waves -- top, right, left -- issue ALL the
-// copies, 14 / 14 / 13 pieces, one per step from the chunk's first; the bottom wave and the interior waves issue none.  A border class
+// copies, 14 / 14 / 13 pieces, one per step (= two MFMAs) from the chunk's first; the bottom wave and the interior waves issue none.  A border class
 // is ONE wave, so its piece table is a compile-time constant (scalar instructions of a den.conv4 launch 20.3 M -> 15.0 M).  Same box,
 // three alternating passes, B = 256 (profiles/copy_roles_ab.txt): dense reverse process 78.55-78.63 -> 77.11-77.35 ms, den.conv4 / conv5
 // main + tail 322-327 / 311-313 -> 317-321 / 306-307 us.  The same file has what paid less or not at all: the four border waves copying
@@ -353,8 +460,12 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
   __syncthreads();         // no wave's first DMA piece may land in a cell another wave has yet to zero
 
   // per-lane LDS byte offsets of this wave's A fragments (tile ti = wave + NWV * i; full 7x7 items: the positions of V2_FULL_POS),
-  // relative to tap (0, 0): the same cell for both K halves (digit-pair instructions)
+  // relative to tap (0, 0): the same cell for both K halves (digit-pair instructions); a tap-pair block adds the second tap's distance,
+  // one cell or PW - 2 cells, in the upper lane half (a_hd1, a_hd2)
   const int row = lane & 31, half = lane >> 5;
+  const int a_hd1 = half * POSB, a_hd2 = half * (PW - 2) * POSB;
+  // tap-pair B operands: lanes 0-31 read their half of tile (a, pair), lanes 32-63 theirs of tile (a + 1, pair), 2 WT further on
+  const int b_o16 = lane * 16 + half * (2 * WT - 512), b_o8 = 1024 + lane * 8 + half * (2 * WT - 256);
   const int hsel = (row >> 2) & 1, tt = (row & 3) + 4 * (row >> 3);
   int a_off[NT];
   int p_out[NT];                                          // output position of this lane's accumulator rows
@@ -405,6 +516,7 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
 
   const int sc_a = 0x7f7f7f7f;                            // e8m0 block scales: spikes x 1
   const int sc_p = half ? (int)0x82828282u : (int)0x87878787u;   // digit pairs: even digit (K half 0) x 2^8, odd digit x 2^3
+  const int sc_hi = (int)0x87878787u, sc_lo = (int)0x82828282u;  // tap pairs: one digit in both K halves
 
   int it = 0;                                             // running chunk counter: LDS buffer = it & 1
   if (il < nitems) {
@@ -447,9 +559,10 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
       rec_ok[k] = r < NREC;
       rec_off[k] = v2_rec_off(r, NREC, W);
     }
-    constexpr int PFX = NWV == 4 ? SPK_V2_PF : 4;
+    constexpr int PFX = BSKIP ? v2_tp_slots(CLS) : (NWV == 4 ? SPK_V2_PF : 4);
     v6i bp[2][2];                                         // digit-pair tiles of block parity [blk & 1][pair]  (AH: carried over the
     v4i af[PFX];                                          //  chunks of an item: a chunk's last steps fill them for the next one)
+                                                          // (tap pairs: B operand sel in bp[sel >> 1][sel & 1], A fragment f in af[f % PFX])
     for (int c = 0; c < nch; ++c, ++it) {
       const int buf = it & 1, buf1 = buf ^ 1;             // this chunk's buffers, the next chunk's (where this chunk's copies go)
       if constexpr (!AH) {
@@ -468,29 +581,129 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
       // steps later, inside the MFMA stream (in front of it they held the chunk's first MFMA back by an LDS round trip at every
       // chunk barrier).
       v4i rvq[NR];
+      // Full 7x7 items: the K loop of the class's tap-pair plan ("TAP PAIRS" above), one op = one MFMA.  Every read is issued in front
+      // of the op its schedule names (v2p_sched), the reads of the NEXT chunk's first operands behind the chunk barrier at op MB.
+      auto compute_tap_pairs = [&](auto first_tag, const uint8_t* A, const uint8_t* Wb) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        constexpr V2Plan P = V2_PLAN[BSKIP ? CLS : V2_INT];
+        constexpr V2Sched S = v2p_sched(P, PFX, SPK_V2_TP_PFD, SPK_V2_TP_TAIL);
+        constexpr int NM = S.nm, MB = S.mb, NF = S.nf, NB = S.nb, NPIECES = NPA + NPW;
+        static_assert(S.ok, "tap pairs: every read in front of its first use, behind its register set's last use, on the right side of the chunk barrier");
+        // (the bottom wave's one-tile blocks take a new B operand with every MFMA: four sets leave one MFMA between read and use there,
+        //  as the digit-pair loop did -- that wave is 12 MFMAs per chunk shorter than the interior wave of its SIMD)
+        static_assert(S.a_dist >= 2 && S.b_dist >= (CLS == V2_BOTTOM ? 1 : 3), "no read right in front of the MFMA that needs it");
+        static_assert(P.pair[0] && P.nt[0] == NT, "the first block writes (not accumulates) every accumulator: digits 0 and 2 of a pair block");
+        // one copy slot per MFMA pair from the chunk's first (a wave's 14 pieces are out by op 26), the record counts at ops 2 and
+        // 2 x SPK_V2_REC_STEP: all in front of the chunk barrier
+        static_assert((NPIECES == 0 || 2 * (NPIECES - 1) < MB) && 2 * SPK_V2_REC_STEP < MB, "copy slots and record-count ops in front of the chunk barrier");
+        auto toff = [](int tap) constexpr -> int { return ((tap / 3) * PW + (tap % 3)) * POSB; };
+        auto lda = [&](const uint8_t* base, auto f_tag) -> v4i {
+          constexpr int f = decltype(f_tag)::value, blk = v2_plan_blk(P, f), i = NT - P.nt[blk] + (f - v2_plan_start(P, blk));
+          constexpr int t0 = toff(P.tap[blk]), dl = P.pair[blk] ? toff(P.tap[blk] + 1) - t0 : 0;
+          static_assert(dl == 0 || dl == POSB || dl == (PW - 2) * POSB, "a pair's second tap: the next cell, or the first of the next row");
+          const int o = dl == 0 ? a_off[i] : a_off[i] + (dl == POSB ? a_hd1 : a_hd2);
+          return *reinterpret_cast<const v4i*>(base + o + t0);
+        };
+        auto ldb = [&](const uint8_t* base, auto g_tag) -> v6i {
+          // 16 + 8 bytes per lane; the 8-byte read is volatile so that hipcc does not pair the tails of two operands
+          constexpr int g = decltype(g_tag)::value, blk = v2p_b_blk(P, g), sel = g - v2p_b_start(P, blk);
+          constexpr int tile = 2 * P.tap[blk] + (P.pair[blk] ? sel >> 1 : sel), odd = P.pair[blk] ? sel & 1 : 0;
+          const uint8_t* p = base + tile * WT;
+          const int o16 = P.pair[blk] ? b_o16 + 512 * odd : lane * 16, o8 = P.pair[blk] ? b_o8 + 256 * odd : 1024 + lane * 8;
+          const v4i x = *reinterpret_cast<const v4i*>(p + o16);
+          typedef const volatile __attribute__((address_space(3))) v2i* lds_v2i_ptr;
+          const v2i y = *(lds_v2i_ptr)SPK_LDS(p + o8);
+          const v6i r = {x[0], x[1], x[2], x[3], y[0], y[1]};
+          return r;
+        };
+        if constexpr (FIRST) {
+          static_for<NB>([&](auto g_tag) {
+            constexpr int g = decltype(g_tag)::value, sel = g - v2p_b_start(P, v2p_b_blk(P, g));
+            if constexpr (S.b_at[g] < 0) bp[sel >> 1][sel & 1] = ldb(Wb, g_tag);
+          });
+          static_for<NF>([&](auto f_tag) {
+            constexpr int f = decltype(f_tag)::value;
+            if constexpr (S.a_at[f] < 0) af[f % PFX] = lda(A, f_tag);
+          });
+        }
+        const uint8_t* An = sA + buf1 * A_BYTES + band_off;
+        const uint8_t* Wn = sW + buf1 * W_LDS;
+        const bool ahead = c + 1 < nch;                     // (the last chunk of an item reads nothing ahead)
+        static_for<NM>([&](auto m_tag) {
+          constexpr int m = decltype(m_tag)::value, blk = v2p_op_blk(P, m), q = m - v2p_op_start(P, blk);
+          constexpr int sel = v2p_op_sel(P, blk, q), i = v2p_op_tile(P, blk, q);
+          constexpr int f = v2_plan_start(P, blk) + i - (NT - P.nt[blk]);
+          // this chunk's reads ...
+          static_for<NB>([&](auto g_tag) {
+            constexpr int g = decltype(g_tag)::value, gs = g - v2p_b_start(P, v2p_b_blk(P, g));
+            if constexpr (S.b_at[g] == m) bp[gs >> 1][gs & 1] = ldb(Wb, g_tag);
+          });
+          static_for<NF>([&](auto f_tag) {
+            if constexpr (S.a_at[decltype(f_tag)::value] == m) af[decltype(f_tag)::value % PFX] = lda(A, f_tag);
+          });
+          if constexpr (m == MB) {
+            // every read of this chunk's buffers is issued; this wave's copies of the next chunk have landed: the chunk barrier
+            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+          }
+          // ... and, behind the barrier, the next chunk's first ones
+          if constexpr (m >= MB) {
+            if (ahead) {
+              static_for<NB>([&](auto g_tag) {
+                constexpr int g = decltype(g_tag)::value, gs = g - v2p_b_start(P, v2p_b_blk(P, g));
+                if constexpr (S.b_at[g] + NM == m) bp[gs >> 1][gs & 1] = ldb(Wn, g_tag);
+              });
+              static_for<NF>([&](auto f_tag) {
+                if constexpr (S.a_at[decltype(f_tag)::value] + NM == m) af[decltype(f_tag)::value % PFX] = lda(An, f_tag);
+              });
+            }
+          }
+          if constexpr (!P.pair[blk]) {
+            SPK_MFMA_FP6("v", acc[i][sel], af[f % PFX], bp[0][sel], sc_a, sc_p);
+          } else if constexpr (FIRST && blk == 0 && (sel & 1) == 0) {
+            SPK_MFMA_FP6_Z("v", acc[i][sel >> 1], af[f % PFX], bp[sel >> 1][0], sc_a, sc_hi);
+          } else if constexpr ((sel & 1) == 0) {
+            SPK_MFMA_FP6("v", acc[i][sel >> 1], af[f % PFX], bp[sel >> 1][0], sc_a, sc_hi);
+          } else {
+            SPK_MFMA_FP6("v", acc[i][sel >> 1], af[f % PFX], bp[sel >> 1][1], sc_a, sc_lo);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if constexpr ((m & 1) == 0 && m / 2 < NPIECES) issue_piece(m / 2, n_aslab, n_wslab, n_dA, n_dW);
+          if constexpr (m == 2) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) rvq[k] = *reinterpret_cast<const v4i*>(sA + buf * A_BYTES + rec_off[k]);
+          }
+          if constexpr (m == 2 * SPK_V2_REC_STEP) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k)
+              creg[k] += __builtin_popcount((unsigned)rvq[k][0]) + __builtin_popcount((unsigned)rvq[k][1]) +
+                         __builtin_popcount((unsigned)rvq[k][2]) + __builtin_popcount((unsigned)rvq[k][3]);
+          }
+        });
+      };
       auto compute = [&](auto first_tag) {
         constexpr bool FIRST = decltype(first_tag)::value;
         const uint8_t* A = sA + buf * A_BYTES + band_off;
         const uint8_t* Wb = sW + buf * W_LDS;
         auto toff = [](int tap) constexpr -> int { return ((tap / 3) * PW + (tap % 3)) * POSB; };
-        // Step order: the blocks of the wave's list (V2Plan), one tap per block, one step per row tile of the block; a step issues
-        // the two digit-pair MFMAs
-        constexpr V2Plan P = BSKIP ? V2_PLAN[CLS] : v2_uniform_plan(NT);
+        if constexpr (BSKIP) {
+          compute_tap_pairs(first_tag, A, Wb);
+          return;
+        }
+        // Step order: nine blocks, one tap per block, one step per row tile of the block; a step issues the two digit-pair MFMAs
+        constexpr V2Plan P = v2_uniform_plan(NT);
         constexpr int NBLK = P.nblk, NSTEP = v2_plan_start(P, NBLK);
         constexpr int PF = PFX;
         constexpr int NPIECES = NPA + NPW;
         // what the schedule below relies on:
         static_assert(P.nt[0] == NT, "the first block writes (not accumulates) every accumulator");
-        // copy slots: two per block (its first step and its middle step), or, where three waves copy for eight (full 7x7 items), one per
-        // step from the chunk's first -- a wave's 14 pieces are out by step 13 of 18, the last step in front of the chunk barrier
-        constexpr bool SLOT1 = BSKIP && (NCA != NWV || NCWW != NWV);
-        static_assert(SLOT1 || 2 * NBLK >= NPIECES, "two copy slots per block: every DMA piece of the wave gets one");
+        // copy slots: two per block (its first step and its middle step)
+        static_assert(2 * NBLK >= NPIECES, "two copy slots per block: every DMA piece of the wave gets one");
         static_assert((!AH || NSTEP >= 2 * PF) && (!REC || NSTEP > SPK_V2_REC_STEP), "look-ahead slots; the record-count steps exist");
         // AH, the chunk barrier at step NSTEP - PF: the copies are issued in front of it (it waits for them), and so is every read of
         // the current buffers -- the last fragment at step NSTEP - PF - 1 by construction, the last weight tiles at the first step of
         // the last block but one (8x8 bands, two tiles per wave: in the step that opens with the barrier; the first copy into these
         // buffers is PF steps behind it)
-        static_assert(!AH || ((SLOT1 ? NPIECES : v2_plan_start(P, (NPIECES + 1) / 2)) <= NSTEP - PF && v2_plan_start(P, NBLK - 2) <= NSTEP - PF),
+        static_assert(!AH || (v2_plan_start(P, (NPIECES + 1) / 2) <= NSTEP - PF && v2_plan_start(P, NBLK - 2) <= NSTEP - PF),
                       "chunk barrier behind the copies and the last weight-tile read");
         auto lda_at = [&](const uint8_t* base, auto s_tag) -> v4i {
           constexpr int s = decltype(s_tag)::value;
@@ -534,9 +747,8 @@ __device__ __forceinline__ void fp6v2_body(const V2Args& a, const int g, const i
           // (two per block: 18 slots for the 11 pieces of a wave of four)
 #define V2_DMA_SLOT()                                                                              \
   do {                                                                                             \
-    if constexpr (SLOT1 && s < NPIECES) issue_piece(s, n_aslab, n_wslab, n_dA, n_dW);                 \
-    if constexpr (!SLOT1 && j == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);     \
-    if constexpr (!SLOT1 && j == (nt > 1 ? nt / 2 : 0) && 2 * blk + 1 < NPIECES)                   \
+    if constexpr (j == 0 && 2 * blk < NPIECES) issue_piece(2 * blk, n_aslab, n_wslab, n_dA, n_dW);                \
+    if constexpr (j == (nt > 1 ? nt / 2 : 0) && 2 * blk + 1 < NPIECES)                             \
       issue_piece(2 * blk + 1, n_aslab, n_wslab, n_dA, n_dW);                                      \
   } while (0)
           // the next block's weight tiles are requested at the first step of this block
@@ -755,7 +967,7 @@ __global__ __launch_bounds__(NWV * 64, 1) void conv3x3_fp6v2_kernel(V2Args a) {
   if constexpr (NWV == 8 && !SPLIT) {
     // full 7x7 items: every wave runs the body of its class (wave-uniform; the eight waves meet at the same barriers whichever
     // body they are in: the zeroing, one per chunk, two per item, the hand-over).  Five bodies are 68 KB of code against 15 KB for
-    // one (216 registers, no scratch, as before).  Top, right and left sharing ONE body whose tap offsets and weight-tile offsets
+    // one (217 registers, no scratch: profiles/tap_pair_resources.txt).  Top, right and left sharing ONE body whose tap offsets and weight-tile offsets
     // sit in SGPRs (one address add per LDS read, 43 KB) measured the same: 77.5-78.1 against 77.5-77.8 ms per dense reverse
     // process (profiles/border_skip_ab.txt) -- the compile-time form is kept, it needs no second addressing path.
     switch (__builtin_amdgcn_readfirstlane((int)V2_WAVE_CLS[(threadIdx.x >> 6) & 7])) {
