@@ -546,6 +546,20 @@ int spk_conv_train_gather_supported(int Cred, int Cout, int k, int stride, int f
 int spk_conv_train_gather(const float* in_cl, const float* w, const float* bias_or_null, float* out_cl, int N, int Hi, int Wi,
                           int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form, long long w_tap,
                           long long w_red, long long w_out, spk_stream_t stream);
+/* spk_conv_train_gather with a fused epilogue, for the plain-CNN VQVAE baseline in training (the ReLU between its layers,
+ * R/snn_model/vae_model.py:607-658): separate instantiations of the same kernels, same arguments, shapes, launch forms and error
+ * codes; spk_conv_train_gather itself is unchanged.  v = acc + bias is spk_conv_train_gather's value, bit for bit.
+ *   _relu:   out = v < 0 ? 0 : v            (a NaN stays NaN, -0.0 stays -0.0: torch.relu's values)
+ *   _masked: out = act <= 0 ? 0 : v         act_cl: a channels-last tensor of the output's shape -- threshold_backward's rule on the
+ *            SAVED post-ReLU activation (nn.ReLU(inplace=True) keeps only its result): the data gradient through a ReLU.
+ * Matrix path and the Cred <= 4 vector kernel; the Cout <= 4 vector kernel (no VQVAE layer needs an epilogue there) returns
+ * SPK_ERR_UNSUPPORTED. */
+int spk_conv_train_gather_relu(const float* in_cl, const float* w, const float* bias_or_null, float* out_cl, int N, int Hi, int Wi,
+                               int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form, long long w_tap,
+                               long long w_red, long long w_out, spk_stream_t stream);
+int spk_conv_train_gather_masked(const float* in_cl, const float* w, const float* bias_or_null, const float* act_cl, float* out_cl,
+                                 int N, int Hi, int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form,
+                                 long long w_tap, long long w_red, long long w_out, spk_stream_t stream);
 /* Weight (and bias) gradient of the same layers: D(tap, cu, cv) = sum over (n, q) of u[n, q * stride - pad + k, cu] * v[n, q, cv],
  * written to gw_out[tap * g_tap + cu * g_u + cv * g_v].  layer.Conv2d: u = the layer's input, v = gy; layer.ConvTranspose2d:
  * u = gy, v = the layer's input (u is the tensor on the finer grid).  bias_from: 0 none, 1: gb_out[cv] = column sums of v, 2:
@@ -894,6 +908,41 @@ int spk_ann_vqvae_decode(const long long* tokens_or_null, const float* e_or_null
                          const float* bt1, const float* wt2, const float* bt2, const float* wt3, const float* bt3, void* ws,
                          long long ws_bytes, float* x_recon_out, uint8_t* u8_out_or_null, int B, int C, int H, int W, int D,
                          int K, spk_stream_t stream);
+
+/* ---- the plain-CNN VQVAE baseline, training (csrc/ann_vqvae_train.hip) -------------------------------------------------- */
+/* Vector quantiser and loss of VQVAE.forward in train() mode (R/snn_model/vae_model.py:575-591, 660-672) on channels-last fp32
+ * tensors; the convolutions are spk_conv_train_gather(_relu / _masked) and spk_conv_train_wgrad.  fp32 element-wise arithmetic in
+ * the reference's order; the two mean squares are fp64 sums of a fixed shape that depends on the sizes only (per row / per
+ * SPK_ANN_VQVAE_TRAIN_CHUNK elements, then one single-workgroup launch in index order): deterministic, independent of the grid.
+ * No atomics, no state: ws is scratch (spk_ann_vqvae_train_ws_bytes(rows, elems) bytes, 8-byte aligned, this call's alone while it is
+ * in flight), nothing is expected of its contents.  Capturable in a hipGraph; nothing is read back to the host.
+ *
+ * spk_ann_vqvae_train_vq_fwd: z fp32 [N,D] (the rows of Conv 1x1's channels-last output), codebook [K,D] -> idx_out int64 [N]
+ *   (spk_vq_argmin's arithmetic and rule: what spk_ann_vqvae_encode chooses for the same z), e_out [N,D] = z + (q - z) with
+ *   q = codebook[idx] (two fp32 roundings, the straight-through value), loss_out [1] = m + beta * m, m = mean((q - z)^2).
+ *   D <= SPK_VQ_TRAIN_MAX_D and the codebook ((D + 1) floats and a double per code) within 64 KB of LDS:
+ *   spk_ann_vqvae_train_supported(D, K); SPK_ERR_UNSUPPORTED beyond.  Two launches.
+ * spk_ann_vqvae_train_vq_bwd: gz_out [N,D] = g_e + g_loss * beta * 2 (z - q) / (N D); gcodebook_out [K,D]: row k = g_loss * 2 / (N D) *
+ *   sum over the rows with idx = k, in ascending row order, of (q - z) (fp64 sum; one workgroup per code; an unused code's row is
+ *   zero).  g_e_or_null NULL = zero, g_loss_or_null [1] (device) NULL = zero.  One launch.
+ * spk_ann_vqvae_train_loss_fwd: x_recon_cl fp32 [B,H,W,C], x_nchw fp32 [B,C,H,W] (the caller's image), data_variance [1] (device) ->
+ *   real_out [1] = mse = mean((x_recon - x)^2), recon_out [1] = mse / data_variance.  Two launches.
+ * spk_ann_vqvae_train_loss_bwd: gx_recon_cl [B,H,W,C] = s * 2 (x_recon - x) / n with s = g_recon / data_variance + g_real (device
+ *   scalars, NULL = zero).  One launch. */
+#define SPK_ANN_VQVAE_TRAIN_CHUNK 2048
+/* 1 where spk_ann_vqvae_train_vq_fwd takes embedding_dim D and K codes (host-only; D = 16: K <= 862), else 0. */
+int spk_ann_vqvae_train_supported(int D, int K);
+long long spk_ann_vqvae_train_ws_bytes(long long rows, long long elems);
+int spk_ann_vqvae_train_vq_fwd(const float* z, const float* codebook, long long* idx_out, float* e_out, float* loss_out, float beta,
+                               void* ws, long long ws_bytes, long long N, int D, int K, spk_stream_t stream);
+int spk_ann_vqvae_train_vq_bwd(const float* g_e_or_null, const float* g_loss_or_null, const float* z, const long long* idx,
+                               const float* codebook, float beta, float* gz_out, float* gcodebook_out, long long N, int D, int K,
+                               spk_stream_t stream);
+int spk_ann_vqvae_train_loss_fwd(const float* x_recon_cl, const float* x_nchw, const float* data_variance, float* recon_out,
+                                 float* real_out, void* ws, long long ws_bytes, int B, int C, int H, int W, spk_stream_t stream);
+int spk_ann_vqvae_train_loss_bwd(const float* x_recon_cl, const float* x_nchw, const float* g_recon_or_null,
+                                 const float* g_real_or_null, const float* data_variance, float* gx_recon_cl, int B, int C, int H,
+                                 int W, spk_stream_t stream);
 
 /* ---- measurement aid ------------------------------------------------------------------------------------------ */
 /* Shader clock this device holds under a block-scaled fp6 x fp4 MFMA load (bench.py records it next to every

@@ -154,8 +154,22 @@ inline void build_class_tab(ClassTab& ct, const GArgs& a, int rows) {
   for (int c = cs * cs; c <= MAX_CLASSES; ++c) ct.first[c] = first;
 }
 
-template <int J, int CN, int RM>
-__global__ __launch_bounds__(512) void conv_train_gather_kernel(GArgs a, ClassTab ct_arg) {
+// EPI: the epilogue on v = acc + bias -- EPI_NONE: v; EPI_RELU: v < 0 ? 0 : v (a NaN stays NaN); EPI_MASK: act <= 0 ? 0 : v with act a
+// channels-last tensor of the output's shape (the data gradient through a ReLU whose result was saved).  The epilogues are
+// instantiations of their own: <..., EPI_NONE, GArgs> is the kernel as it was before they came, instruction for instruction
+// (profiles/ann_train_epilogue_resources.txt).
+constexpr int EPI_NONE = 0, EPI_RELU = 1, EPI_MASK = 2;
+struct GArgsAct : GArgs { const float* act; };      // the arguments of the EPI_MASK kernels
+
+template <int EPI, class A>
+__device__ __forceinline__ float gather_epilogue(const float v, const A& a, const long long o) {
+  if constexpr (EPI == EPI_RELU) return v < 0.f ? 0.f : v;
+  else if constexpr (EPI == EPI_MASK) return a.act[o] <= 0.f ? 0.f : v;
+  else return v;
+}
+
+template <int J, int CN, int RM, int EPI = EPI_NONE, class GA = GArgs>
+__global__ __launch_bounds__(512) void conv_train_gather_kernel(GA a, ClassTab ct_arg) {
   constexpr int NTH = 512, NWV = 8;                 // eight waves share one staged weight image
   extern __shared__ __attribute__((aligned(16))) float4 sB[];       // [tap][J][2][CN * 32]
   __shared__ ClassTab ct;                           // (LDS copy of the host-built table: published by the barrier behind the weight staging)
@@ -256,7 +270,13 @@ __global__ __launch_bounds__(512) void conv_train_gather_kernel(GArgs a, ClassTa
         if (co < a.Cout) {
 #pragma unroll
           for (int i = 0; i < 16; ++i)
-            if (orow[i] >= 0) a.out[(long long)orow[i] * a.Cout + co] = acc[rm][cn][i] + bv;
+            if (orow[i] >= 0) {
+              if constexpr (EPI == EPI_NONE) a.out[(long long)orow[i] * a.Cout + co] = acc[rm][cn][i] + bv;
+              else {
+                const long long o = (long long)orow[i] * a.Cout + co;
+                a.out[o] = gather_epilogue<EPI>(acc[rm][cn][i] + bv, a, o);
+              }
+            }
         }
       }
     }
@@ -324,8 +344,8 @@ __global__ __launch_bounds__(256) void conv_train_c1out_kernel(GArgs a) {
 }
 
 // ---- one to four reduced channels (the 1 -> 32 / 3 -> 32 first layer forward, the read-out layer's data gradient): regular form ----
-template <int CR>
-__global__ __launch_bounds__(256) void conv_train_c1in_kernel(GArgs a) {
+template <int CR, int EPI = EPI_NONE, class GA = GArgs>
+__global__ __launch_bounds__(256) void conv_train_c1in_kernel(GA a) {
   extern __shared__ float sW1[];                    // [tap][ci][Cout]
   const int tid = threadIdx.x, C = a.Cout, CQ = C >> 2;
   const int nt = a.k * a.k;
@@ -359,7 +379,13 @@ __global__ __launch_bounds__(256) void conv_train_c1in_kernel(GArgs a) {
           }
         }
       }
-      *reinterpret_cast<float4*>(a.out + ((long long)row * a.Wo + ox) * C + 4 * cq) = acc;
+      if constexpr (EPI == EPI_NONE) *reinterpret_cast<float4*>(a.out + ((long long)row * a.Wo + ox) * C + 4 * cq) = acc;
+      else {
+        const long long o = ((long long)row * a.Wo + ox) * C + 4 * cq;
+        acc.x = gather_epilogue<EPI>(acc.x, a, o); acc.y = gather_epilogue<EPI>(acc.y, a, o + 1);
+        acc.z = gather_epilogue<EPI>(acc.z, a, o + 2); acc.w = gather_epilogue<EPI>(acc.w, a, o + 3);
+        *reinterpret_cast<float4*>(a.out + o) = acc;
+      }
     }
   }
 }
@@ -952,23 +978,35 @@ int gather_kind(int Cred, int Cout, int k, int stride, int form) {
   return 1;
 }
 
-template <int J, int CN, int RM>
-void launch_gather(const GArgs& a, dim3 grid, size_t lds, hipStream_t s) {
+template <int EPI>
+struct EpiArgs { using type = GArgs; static const GArgs& make(const GArgs& a, const float*) { return a; } };
+template <>
+struct EpiArgs<EPI_MASK> { using type = GArgsAct; static GArgsAct make(const GArgs& a, const float* act) { GArgsAct e; static_cast<GArgs&>(e) = a; e.act = act; return e; } };
+
+template <int J, int CN, int RM, int EPI>
+void launch_gather(const GArgs& a, const float* act, dim3 grid, size_t lds, hipStream_t s) {
+  using A = typename EpiArgs<EPI>::type;
   // (the opt-in to > 64 KB of dynamic LDS: once per instantiation -- thread-safe -- and outside any stream capture: the warm-up
   //  iterations in front of a capture make the first call)
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_train_gather_kernel<J, CN, RM>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_train_gather_kernel<J, CN, RM, EPI, A>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               152 * 1024);
   });
   ClassTab ct;
   build_class_tab(ct, a, RM * 32);
-  hipLaunchKernelGGL((conv_train_gather_kernel<J, CN, RM>), grid, dim3(512), lds, s, a, ct);
+  hipLaunchKernelGGL((conv_train_gather_kernel<J, CN, RM, EPI, A>), grid, dim3(512), lds, s, EpiArgs<EPI>::make(a, act), ct);
 }
-template <int J>
-void launch_gather_j(const GArgs& a, int CN, int RM, dim3 grid, size_t lds, hipStream_t s) {
-  if (CN == 2) launch_gather<J, 2, 1>(a, grid, lds, s);
-  else launch_gather<J, 1, 1>(a, grid, lds, s);
+template <int J, int EPI>
+void launch_gather_j(const GArgs& a, const float* act, int CN, int RM, dim3 grid, size_t lds, hipStream_t s) {
+  if (CN == 2) launch_gather<J, 2, 1, EPI>(a, act, grid, lds, s);
+  else launch_gather<J, 1, 1, EPI>(a, act, grid, lds, s);
+}
+
+template <int CR, int EPI>
+void launch_c1in(const GArgs& a, const float* act, dim3 grid, size_t lds, hipStream_t s) {
+  using A = typename EpiArgs<EPI>::type;
+  hipLaunchKernelGGL((conv_train_c1in_kernel<CR, EPI, A>), grid, dim3(256), lds, s, EpiArgs<EPI>::make(a, act));
 }
 
 }  // namespace
@@ -977,12 +1015,14 @@ extern "C" int spk_conv_train_gather_supported(int Cred, int Cout, int k, int st
   return gather_kind(Cred, Cout, k, stride, form) != 0;
 }
 
-extern "C" int spk_conv_train_gather(const float* in_cl, const float* w, const float* bias_or_null, float* out_cl, int N, int Hi,
-                                     int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form,
-                                     long long w_tap, long long w_red, long long w_out, spk_stream_t stream) {
-  if (!in_cl || !w || !out_cl || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || pad < 0) return SPK_ERR_ARG;
+namespace {
+template <int EPI>
+int conv_train_gather_run(const float* in_cl, const float* w, const float* bias_or_null, const float* act, float* out_cl, int N, int Hi,
+                          int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form, long long w_tap,
+                          long long w_red, long long w_out, spk_stream_t stream) {
+  if (!in_cl || !w || !out_cl || (EPI == EPI_MASK && !act) || N <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || pad < 0) return SPK_ERR_ARG;
   const int kind = gather_kind(Cred, Cout, k, stride, form);
-  if (!kind) return SPK_ERR_UNSUPPORTED;
+  if (!kind || (kind == 2 && EPI != EPI_NONE)) return SPK_ERR_UNSUPPORTED;
   if ((long long)N * Ho * Wo >= (1ll << 31) / 64 * 64 || (long long)N * Hi * Wi * Cred >= (1ll << 31)) return SPK_ERR_UNSUPPORTED;
   GArgs a{in_cl, w, bias_or_null, out_cl, N, Hi, Wi, Cred, Ho, Wo, Cout, k, stride, pad, form, w_tap, w_red, w_out};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -990,10 +1030,10 @@ extern "C" int spk_conv_train_gather(const float* in_cl, const float* w, const f
     const int rows = N * Ho;
     const dim3 gr(rows < CT_C1_ROWS_CAP ? rows : CT_C1_ROWS_CAP);
     const size_t ldsw = (size_t)k * k * Cred * Cout * 4;
-    if (Cred == 1) hipLaunchKernelGGL(conv_train_c1in_kernel<1>, gr, dim3(256), ldsw, s, a);
-    else if (Cred == 2) hipLaunchKernelGGL(conv_train_c1in_kernel<2>, gr, dim3(256), ldsw, s, a);
-    else if (Cred == 3) hipLaunchKernelGGL(conv_train_c1in_kernel<3>, gr, dim3(256), ldsw, s, a);
-    else hipLaunchKernelGGL(conv_train_c1in_kernel<4>, gr, dim3(256), ldsw, s, a);
+    if (Cred == 1) launch_c1in<1, EPI>(a, act, gr, ldsw, s);
+    else if (Cred == 2) launch_c1in<2, EPI>(a, act, gr, ldsw, s);
+    else if (Cred == 3) launch_c1in<3, EPI>(a, act, gr, ldsw, s);
+    else launch_c1in<4, EPI>(a, act, gr, ldsw, s);
   } else if (kind == 2) {
     const int LP = Cred / 4;
     const int blocks = N * Ho < CT_C1_ROWS_CAP ? N * Ho : CT_C1_ROWS_CAP;
@@ -1026,18 +1066,41 @@ extern "C" int spk_conv_train_gather(const float* in_cl, const float* w, const f
     gx = gx < cap ? gx : cap;
     dim3 grid(gx, gy);
     switch (J) {
-      case 1: launch_gather_j<1>(a, CN, RM, grid, lds, s); break;
-      case 2: launch_gather_j<2>(a, CN, RM, grid, lds, s); break;
-      case 3: launch_gather_j<3>(a, CN, RM, grid, lds, s); break;
-      case 4: launch_gather_j<4>(a, CN, RM, grid, lds, s); break;
-      case 5: launch_gather_j<5>(a, CN, RM, grid, lds, s); break;
-      case 6: launch_gather_j<6>(a, CN, RM, grid, lds, s); break;
-      case 7: launch_gather_j<7>(a, CN, RM, grid, lds, s); break;
-      default: launch_gather_j<8>(a, CN, RM, grid, lds, s); break;
+      case 1: launch_gather_j<1, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 2: launch_gather_j<2, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 3: launch_gather_j<3, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 4: launch_gather_j<4, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 5: launch_gather_j<5, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 6: launch_gather_j<6, EPI>(a, act, CN, RM, grid, lds, s); break;
+      case 7: launch_gather_j<7, EPI>(a, act, CN, RM, grid, lds, s); break;
+      default: launch_gather_j<8, EPI>(a, act, CN, RM, grid, lds, s); break;
     }
   }
   SPK_LAUNCH_CHECK();
   return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_conv_train_gather(const float* in_cl, const float* w, const float* bias_or_null, float* out_cl, int N, int Hi,
+                                     int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form,
+                                     long long w_tap, long long w_red, long long w_out, spk_stream_t stream) {
+  return conv_train_gather_run<EPI_NONE>(in_cl, w, bias_or_null, nullptr, out_cl, N, Hi, Wi, Cred, Ho, Wo, Cout, k, stride, pad, form, w_tap,
+                                         w_red, w_out, stream);
+}
+
+extern "C" int spk_conv_train_gather_relu(const float* in_cl, const float* w, const float* bias_or_null, float* out_cl, int N, int Hi,
+                                          int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride, int pad, int form,
+                                          long long w_tap, long long w_red, long long w_out, spk_stream_t stream) {
+  return conv_train_gather_run<EPI_RELU>(in_cl, w, bias_or_null, nullptr, out_cl, N, Hi, Wi, Cred, Ho, Wo, Cout, k, stride, pad, form, w_tap,
+                                         w_red, w_out, stream);
+}
+
+extern "C" int spk_conv_train_gather_masked(const float* in_cl, const float* w, const float* bias_or_null, const float* act_cl,
+                                            float* out_cl, int N, int Hi, int Wi, int Cred, int Ho, int Wo, int Cout, int k, int stride,
+                                            int pad, int form, long long w_tap, long long w_red, long long w_out,
+                                            spk_stream_t stream) {
+  return conv_train_gather_run<EPI_MASK>(in_cl, w, bias_or_null, act_cl, out_cl, N, Hi, Wi, Cred, Ho, Wo, Cout, k, stride, pad, form, w_tap,
+                                         w_red, w_out, stream);
 }
 
 namespace {

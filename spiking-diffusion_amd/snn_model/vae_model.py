@@ -19,8 +19,11 @@ decoder take SNN_VQVAE's training path.
 codebook-usage statistic the quantizer computes and prints on every call, one launch of ``csrc/vq_usage.hip``.
 
 ``VQVAE`` (R/snn_model/vae_model.py:548-672, the plain-CNN baseline) runs its eval forward, ``encode_images`` and
-``decode_tokens`` on ``csrc/ann_vqvae.hip``: encoder and code search one launch, decoder two.  Its modules are the reference's
-torch operators; they serve CPU tensors, hooks and the training branch.
+``decode_tokens`` on ``csrc/ann_vqvae.hip``: encoder and code search one launch, decoder two.  In train() mode the iteration runs
+on ``csrc/conv_train.hip`` (the six convolutions, the ReLU an epilogue of the launches around it) and
+``csrc/ann_vqvae_train.hip`` (quantiser and losses) as one autograd node.  Its modules are the reference's torch operators; they
+serve CPU tensors, hooks, other dtypes and shapes, codebooks beyond the training quantiser's (K > 862), images that want a
+gradient, and ``fused_train = False``.
 
 Re-exported names match what ``from snn_model.vae_model import *`` gives R/main.py (``functional`` in particular,
 R/main.py:101-107,317).
@@ -666,7 +669,9 @@ class SNN_VQVAE_uni(SNN_VQVAE):
 # The ANN the paper's tables set the spiking model against.  The modules, children and state_dict keys are the reference's.  In
 # eval() on a ROCm device the forward is three launches of csrc/ann_vqvae.hip (encoder + code search: one; decoder: two); CPU
 # tensors, other dtypes, unsupported shapes and modules with hooks take the modules below, which are the reference's operators
-# in the reference's order.  train() runs those operators under autograd (mse + commitment cost + straight-through).
+# in the reference's order.  In train() the same test sends the iteration to csrc/conv_train.hip (the six convolutions with the ReLU
+# as an epilogue) and csrc/ann_vqvae_train.hip (quantiser, commitment cost, straight-through value, mse) as one autograd node;
+# ``fused_train = False`` or any of the conditions above runs the modules under autograd.
 
 class CNN_VectorQuantizer(nn.Module):
     """VQ-VAE layer of the ANN baseline (R/snn_model/vae_model.py:548-605)."""
@@ -778,6 +783,8 @@ class VQVAE(nn.Module):
         self.encoder = CNN_Encoder(in_dim, embedding_dim)
         self.vq_layer = CNN_VectorQuantizer(embedding_dim, num_embeddings, commitment_cost)
         self.decoder = CNN_Decoder(in_dim, embedding_dim)
+        # training: ops.ANNVQVAETrainFunction on the HIP training kernels (False: the modules below under autograd)
+        self.fused_train = True
 
     # -- the fused path -------------------------------------------------------------------------------------------
     def _is_reference_net(self):
@@ -813,6 +820,21 @@ class VQVAE(nn.Module):
         c = self.decoder.convs
         return (c[0].weight, c[0].bias, c[2].weight, c[2].bias, c[4].weight, c[4].bias)
 
+    def _train_fused(self, x):
+        """Does a train() call on ``x`` take the HIP training kernels (csrc/conv_train.hip, csrc/ann_vqvae_train.hip)?  Not an
+        image that wants a gradient (the node gives it none), nor a codebook beyond the quantiser kernel's (K > 862 at D = 16)."""
+        return (self.fused_train and not x.requires_grad and self._images_fused(x)
+                and ops.ann_vqvae_train_supported(x.shape, self._enc_params(), self._dec_params(), self.vq_layer.embeddings.weight))
+
+    def _data_variance_on(self, device):
+        """data_variance as the fp32 device scalar the loss kernels read, converted once per value and device (a tensor's in-place
+        update or replacement converts again): an iteration reads nothing back and uploads nothing."""
+        dv = self.data_variance
+        key = ((id(dv), dv._version) if isinstance(dv, torch.Tensor) else float(dv), str(device))
+        if getattr(self, "_dv_key", None) != key:
+            self._dv_dev, self._dv_key = ops.ann_data_variance(dv, device), key
+        return self._dv_dev
+
     def forward(self, x):
         if not self.training and self._images_fused(x):
             B, _, H, W = x.shape
@@ -820,6 +842,12 @@ class VQVAE(nn.Module):
             enco, _, e = ops.ann_vqvae_encode(x, self._enc_params(), cb, want_e=True)
             x_recon, _ = ops.ann_vqvae_decode(enco.view(B, H // 4, W // 4), self._dec_params(), cb)
             return e, x_recon, enco
+        if self.training and self._train_fused(x):
+            params = self._enc_params() + self._dec_params() + (self.vq_layer.embeddings.weight,)
+            beta, dv = self.vq_layer.commitment_cost, self._data_variance_on(x.device)
+            if not torch.is_grad_enabled():               # the three values; nothing is kept
+                return ops.ann_vqvae_train_forward(x, params[:6], params[6:12], params[12], beta, dv)[0]
+            return ops.ANNVQVAETrainFunction.apply(x, beta, dv, *params)
         z = self.encoder(x)
         if not self.training:
             e, enco = self.vq_layer(z)

@@ -515,24 +515,27 @@ def conv_train_supported(xshape, weight, stride, pad, transposed, out_pad, need_
     return lib.spk_conv_train_wgrad_ws_bytes(N, Ho, Wo, Cin, Cout, k) > 0
 
 
-def conv_train_forward(x, weight, bias, stride, pad, transposed, out_pad):
+def conv_train_forward(x, weight, bias, stride, pad, transposed, out_pad, relu=False):
     """y [N,Cout,Ho,Wo] (channels-last memory) = conv2d / conv_transpose2d(x, weight) + bias on the fp32 matrix cores
-    (spk_conv_train_gather)."""
+    (spk_conv_train_gather); ``relu``: relu(y) from the same launch (spk_conv_train_gather_relu)."""
     xin = _cl4(x.detach(), "x")
     w = weight.detach()
     N, Cin, Hi, Wi, Cout, Ho, Wo, k = _conv_train_geometry(xin.shape, w, stride, pad, transposed, out_pad)
     tap, s_ci, s_co = _conv_w_strides(w, transposed)
     y = _empty_cl((N, Cout, Ho, Wo), xin.device)
     b = None if bias is None else _dev(bias.detach(), "bias", torch.float32)
+    name = "spk_conv_train_gather_relu" if relu else "spk_conv_train_gather"
     with timed("train.conv_fwd"):
-        check(lib.spk_conv_train_gather(_p(xin), _p(w), _p(b), _p(y), N, Hi, Wi, Cin, Ho, Wo, Cout, k, stride, pad,
-                                        1 if transposed else 0, tap, s_ci, s_co, _stream(xin)), "spk_conv_train_gather")
+        check(getattr(lib, name)(_p(xin), _p(w), _p(b), _p(y), N, Hi, Wi, Cin, Ho, Wo, Cout, k, stride, pad,
+                                 1 if transposed else 0, tap, s_ci, s_co, _stream(xin)), name)
     return y
 
 
-def conv_train_backward(grad_y, x, weight, stride, pad, transposed, out_pad, needs):
+def conv_train_backward(grad_y, x, weight, stride, pad, transposed, out_pad, needs, relu_input=False):
     """(gi, gw, gb) of a convolution layer from gy (any layout; converted to channels-last if it is not), the saved input and
-    the weight: spk_conv_train_gather in the transposed role + spk_conv_train_wgrad.  gw in the memory format of ``weight``."""
+    the weight: spk_conv_train_gather in the transposed role + spk_conv_train_wgrad.  gw in the memory format of ``weight``.
+    ``relu_input``: ``x`` is the result of a ReLU and gi is the gradient in front of it (zero where x <= 0), from the same launch
+    (spk_conv_train_gather_masked)."""
     gy = _cl4(grad_y, "grad_y")
     xin = _cl4(x.detach(), "x")
     w = weight.detach()
@@ -542,9 +545,12 @@ def conv_train_backward(grad_y, x, weight, stride, pad, transposed, out_pad, nee
     gi = gw = gb = None
     if needs[0]:
         gi = _empty_cl((N, Cin, Hi, Wi), gy.device)
+        geo = (N, Ho, Wo, Cout, Hi, Wi, Cin, k, stride, pad, 0 if transposed else 1, tap, s_co, s_ci, st)
         with timed("train.conv_bwd_data"):
-            check(lib.spk_conv_train_gather(_p(gy), _p(w), None, _p(gi), N, Ho, Wo, Cout, Hi, Wi, Cin, k, stride, pad,
-                                            0 if transposed else 1, tap, s_co, s_ci, st), "spk_conv_train_gather")
+            if relu_input:
+                check(lib.spk_conv_train_gather_masked(_p(gy), _p(w), None, _p(xin), _p(gi), *geo), "spk_conv_train_gather_masked")
+            else:
+                check(lib.spk_conv_train_gather(_p(gy), _p(w), None, _p(gi), *geo), "spk_conv_train_gather")
     if needs[1] or needs[2]:
         gw = torch.empty_like(w)                     # (the memory format of a dense weight is preserved; the kernel takes gw's own strides)
         g_tap, g_ci, g_co = _conv_w_strides(gw, transposed)
@@ -2750,3 +2756,142 @@ def ann_vqvae_decode(code, dec_params, codebook, want_u8=False, ws=None):
                                    ws.numel() * ws.element_size(), _p(out), _p(u8), B, C, H, W, D, K, _stream(code)),
           "spk_ann_vqvae_decode")
     return out, u8
+
+
+# ---------------------------------------------------------------------------------------------- the plain-CNN VQVAE baseline, training
+# VQVAE.forward in train() mode (R/snn_model/vae_model.py:660-672) on csrc/conv_train.hip (the six convolutions, the ReLU as
+# an epilogue of the launch in front of it and of the data-gradient launch behind it) and csrc/ann_vqvae_train.hip (the
+# time-free vector quantiser and the mean-squared-error loss).  Everything between the caller's image and the three loss
+# scalars is channels-last: Conv 1x1's output IS the reference's flat_x [B*h*w, D].
+# (stride, pad, transposed, out_pad, ReLU behind it) of CNN_Encoder.convs.{0,2,4} and CNN_Decoder.convs.{0,2,4}
+ANN_TRAIN_LAYERS = ((2, 1, False, 0, True), (2, 1, False, 0, True), (1, 0, False, 0, False),
+                    (2, 1, True, 1, True), (2, 1, True, 1, True), (1, 1, True, 0, False))
+
+
+def ann_vqvae_train_supported(xshape, enc_params, dec_params, codebook):
+    """Do the training kernels take the quantiser (spk_ann_vqvae_train_supported: D and the codebook's LDS image) and every layer
+    of the network (forward, the data gradients the backward needs, weight gradient) for images of this shape?"""
+    K, D = (int(v) for v in codebook.shape)
+    if not lib.spk_ann_vqvae_train_supported(D, K):
+        return False
+    shape = tuple(int(v) for v in xshape)
+    for i, (w, (stride, pad, tr, op, _)) in enumerate(zip(tuple(enc_params[0::2]) + tuple(dec_params[0::2]), ANN_TRAIN_LAYERS)):
+        if not conv_train_supported(shape, w, stride, pad, tr, op, need_gi=i > 0, forward=True):
+            return False
+        _, _, _, _, Cout, Ho, Wo, _ = _conv_train_geometry(shape, w, stride, pad, tr, op)
+        shape = (shape[0], Cout, Ho, Wo)
+    return True
+
+
+def ann_data_variance(data_variance, device):
+    """data_variance as a float32 device tensor [1]: an fp32 device tensor is taken as it is, anything else (a Python number, a CPU
+    tensor as R/main.py:91-107 passes, another dtype) is converted -- one small launch and no read-back.  VQVAE keeps the
+    result per model, so its iterations convert nothing."""
+    if isinstance(data_variance, torch.Tensor) and data_variance.is_cuda:
+        return _dev(data_variance.detach().reshape(1).to(torch.float32), "data_variance", torch.float32)
+    return torch.full((1,), float(data_variance), dtype=torch.float32, device=device)
+
+
+def _ann_train_ws(rows, elems, device):
+    """Scratch of the two mean-square reductions (the partial sums; no state).  Per (device, stream), or per ops.flag_scope
+    store under capture, like the other loss kernels' workspaces."""
+    return _flag_ws("ann_vqvae_train", device, (int(lib.spk_ann_vqvae_train_ws_bytes(int(rows), int(elems))) + 7) // 8 * 2)
+
+
+def ann_vqvae_train_forward(x, enc_params, dec_params, codebook, beta, data_variance):
+    """images x fp32 [B,C,H,W]; enc_params / dec_params as for ann_vqvae_encode / _decode; codebook [K,D] ->
+    ((e_q_loss, recon_loss, real_loss_rec) fp32 scalars on the device, record): the record holds what the backward needs, all
+    channels-last -- x, a1, a2 (post-ReLU), z [B,D,h,w], idx int64 [B*h*w], e, d1, d2 (post-ReLU), x_recon and data_variance [1].
+    Ten launches (plus one layout copy of an RGB image)."""
+    x = _dev(x.detach(), "x", torch.float32)
+    if x.dim() != 4:
+        raise ValueError(f"ann_vqvae_train_forward: images must be [B,C,H,W], got {tuple(x.shape)}")
+    enc = _ann_params(enc_params, 6, "ann_vqvae_train_forward")
+    dec = _ann_params(dec_params, 6, "ann_vqvae_train_forward")
+    cb = _dev(codebook.detach(), "codebook", torch.float32)
+    B, C, H, W = x.shape
+    K, D = cb.shape
+    if (tuple(tuple(w.shape) for w in enc[0::2] + dec[0::2])
+            != ((32, C, 3, 3), (64, 32, 3, 3), (D, 64, 1, 1), (D, 64, 3, 3), (64, 32, 3, 3), (32, C, 3, 3))):
+        raise ValueError("ann_vqvae_train_forward: the weights are not CNN_Encoder's / CNN_Decoder's for these images and this codebook")
+    dv = ann_data_variance(data_variance, x.device)
+    L = ANN_TRAIN_LAYERS
+    a1 = conv_train_forward(x, enc[0], enc[1], *L[0][:4], relu=True)
+    a2 = conv_train_forward(a1, enc[2], enc[3], *L[1][:4], relu=True)
+    z = conv_train_forward(a2, enc[4], enc[5], *L[2][:4])
+    N = z.shape[0] * z.shape[2] * z.shape[3]
+    idx = torch.empty(N, dtype=torch.int64, device=x.device)
+    e = _empty_cl(tuple(z.shape), x.device)
+    l_eq, l_rec, l_real = (torch.empty((), dtype=torch.float32, device=x.device) for _ in range(3))
+    ws = _ann_train_ws(N, x.numel(), x.device)
+    nb = ws.numel() * ws.element_size()
+    st = _stream(x)
+    with timed("train.ann_vq_fwd"):
+        check(lib.spk_ann_vqvae_train_vq_fwd(_p(z), _p(cb), _p(idx), _p(e), _p(l_eq), float(beta), _p(ws), nb, N, D, K, st),
+              "spk_ann_vqvae_train_vq_fwd")
+    d1 = conv_train_forward(e, dec[0], dec[1], *L[3][:4], relu=True)
+    d2 = conv_train_forward(d1, dec[2], dec[3], *L[4][:4], relu=True)
+    x_recon = conv_train_forward(d2, dec[4], dec[5], *L[5][:4])
+    with timed("train.ann_loss_fwd"):
+        check(lib.spk_ann_vqvae_train_loss_fwd(_p(x_recon), _p(x), _p(dv), _p(l_rec), _p(l_real), _p(ws), nb, B, C, H, W, st), "spk_ann_vqvae_train_loss_fwd")
+    rec = dict(x=x, a1=a1, a2=a2, z=z, idx=idx, e=e, d1=d1, d2=d2, x_recon=x_recon, data_variance=dv)
+    return (l_eq, l_rec, l_real), rec
+
+
+def ann_vqvae_train_backward(rec, enc_params, dec_params, codebook, beta, g_eq, g_recon, g_real):
+    """Gradients of the thirteen parameters, in (enc_params, dec_params, codebook) order and each in its parameter's memory
+    format, from the record of ann_vqvae_train_forward and the gradients of the three losses (device scalars or None): the loss
+    backward, five data-gradient launches (four masked by the saved post-ReLU activation; ConvT D->64's is not: the quantiser
+    is behind it), the quantiser's backward and six weight gradients with their bias gradients."""
+    enc = _ann_params(enc_params, 6, "ann_vqvae_train_backward")
+    dec = _ann_params(dec_params, 6, "ann_vqvae_train_backward")
+    cb = _dev(codebook.detach(), "codebook", torch.float32)
+    x, xr, z = rec["x"], rec["x_recon"], rec["z"]
+    B, C, H, W = x.shape
+    K, D = cb.shape
+    N = rec["idx"].numel()
+    st = _stream(x)
+
+    def scalar(g):
+        return None if g is None else _dev(g.detach().reshape(1), "loss gradient", torch.float32)
+
+    g_eq, g_recon, g_real = scalar(g_eq), scalar(g_recon), scalar(g_real)
+    L, all3 = ANN_TRAIN_LAYERS, (True, True, True)
+    g = _empty_cl(tuple(xr.shape), x.device)
+    with timed("train.ann_loss_bwd"):
+        check(lib.spk_ann_vqvae_train_loss_bwd(_p(xr), _p(x), _p(g_recon), _p(g_real), _p(rec["data_variance"]), _p(g), B, C, H, W,
+                                               st), "spk_ann_vqvae_train_loss_bwd")
+    g, gw6, gb6 = conv_train_backward(g, rec["d2"], dec[4], *L[5][:4], all3, relu_input=True)
+    g, gw5, gb5 = conv_train_backward(g, rec["d1"], dec[2], *L[4][:4], all3, relu_input=True)
+    g_e, gw4, gb4 = conv_train_backward(g, rec["e"], dec[0], *L[3][:4], all3)
+    g_z = _empty_cl(tuple(z.shape), x.device)
+    g_cb = torch.empty_like(cb)
+    with timed("train.ann_vq_bwd"):
+        check(lib.spk_ann_vqvae_train_vq_bwd(_p(g_e), _p(g_eq), _p(z), _p(rec["idx"]), _p(cb), float(beta), _p(g_z), _p(g_cb), N, D,
+                                             K, st), "spk_ann_vqvae_train_vq_bwd")
+    g, gw3, gb3 = conv_train_backward(g_z, rec["a2"], enc[4], *L[2][:4], all3, relu_input=True)
+    g, gw2, gb2 = conv_train_backward(g, rec["a1"], enc[2], *L[1][:4], all3, relu_input=True)
+    _, gw1, gb1 = conv_train_backward(g, x, enc[0], *L[0][:4], (False, True, True))
+    return gw1, gb1, gw2, gb2, gw3, gb3, gw4, gb4, gw5, gb5, gw6, gb6, g_cb
+
+
+class ANNVQVAETrainFunction(torch.autograd.Function):
+    """VQVAE.forward in train() mode as one autograd node: apply(x, beta, data_variance, *enc_params, *dec_params, codebook) ->
+    (e_q_loss, recon_loss, real_loss_rec).  The image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, beta, data_variance, *params):
+        enc, dec, cb = params[:6], params[6:12], params[12]
+        losses, rec = ann_vqvae_train_forward(x, enc, dec, cb, beta, data_variance)
+        ctx.keys = tuple(rec)
+        ctx.save_for_backward(*params, *rec.values())
+        ctx.beta = float(beta)
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_eq, g_recon, g_real):
+        saved = ctx.saved_tensors
+        params, rec = saved[:13], dict(zip(ctx.keys, saved[13:]))
+        grads = ann_vqvae_train_backward(rec, params[:6], params[6:12], params[12], ctx.beta, g_eq, g_recon, g_real)
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
