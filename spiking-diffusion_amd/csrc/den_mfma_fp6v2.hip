@@ -1270,8 +1270,31 @@ __device__ __forceinline__ void fp6v2_fixup_body(const V2Args& a, long long n_wo
 // thirteen tiles (19.5 KB: the four contributing taps' digit pairs, three fifth-digit tiles, two sixth-digit tiles; four runs
 // of the slab) come in ONCE per workgroup by LDS-DMA, double-buffered (39 KB), one barrier per chunk: 80 MB.  No partial sums
 // cross waves; the epilogue is the exact one of fp6v2_lastpos_body.
+// THE CHUNK PIPELINE.  A wave's chain is nch chunks of thirteen MFMAs (~0.25 us each); what it can wait for is the L2 -> LDS round trip
+// of a chunk's tiles and the L2 -> register round trip of its four spike fragments.  Step c issues the fragment loads of chunk c + 1,
+// then the wave's five tile pieces of chunk c + 1 into the other buffer, then runs chunk c's thirteen MFMAs, and only THEN waits --
+// once, for both: both round trips lie under the MFMAs.  What that takes, with copies the compiler cannot see and loads it can:
+//   - the fragment loads are unconditional (a wave whose image pair lies past the batch reads the last image's fragments: its rows
+//     are never stored).  Zero-filled registers with a load under `if (image < Bn)` made hipcc protect the zero moves with a
+//     vmcnt(0) right BEHIND the copies of chunk c + 1: that round trip was fully exposed;
+//   - the step ends in an empty asm that takes the next fragments as in/out operands: hipcc waits for them there (vmcnt(0): it
+//     counts only the loads it can see, so the wait also retires the copies, which barrier c + 1 needs anyway) and the registers
+//     the next step's MFMAs read carry no pending load.  Before, a vmcnt(1) in front of the step's first MFMA stood BEHIND the
+//     fragment loads just issued for chunk c + 1 and retired three of the four: the second exposed round trip.  Together ~1.2 us
+//     per chunk, 16 / 8 / 4 / 2 chunks.
+// Deeper (profiles/lastpos_ring_ab.txt): a ring of three tile buffers and a counted wait need the fragments out of the compiler's
+// sight as well (its own vmcnt in front of a visible fragment's use drains the copies issued behind it).  Assembly loads into
+// registers are moved by hipcc while in flight (loop copies in front of the wait that names them); through LDS-DMA into two
+// wave-private sets the ring of three (76 KB) and the same form with two buffers (56 KB) are bit-equal and measured
+// den.conv4 / conv5 +5 us per launch: the dynamic LDS of a launch is every workgroup's, the repair workgroups' too, and over 40 KB
+// only two of them are resident per CU, not four.  The repair half sets the length of these launches once the last positions are
+// short; a ring of four needs a third fragment set on top (the in-order counter retires chunk c + 2's tiles with chunk c + 1's
+// fragments): 82.5 KB, one workgroup per CU.
 constexpr int LPS_TILES = 13, LPS_BUF = LPS_TILES * WT;                  // 19 968 B per chunk
-constexpr size_t LPS_LDS = 2 * (size_t)LPS_BUF;
+constexpr int LPS_RING = 2;             // chunk buffers
+constexpr size_t LPS_LDS = LPS_RING * (size_t)LPS_BUF;
+static_assert(LPS_RING == 2 && 4 * (LPS_LDS + 128) <= 160 * 1024,
+              "barrier c releases buffer (c + 1) % 2, the one chunk c - 1 was read from, never chunk c's; four workgroups per CU (128 B static each)");
 template <int H, int W>
 __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const int bid) {
   constexpr int HW = H * W;
@@ -1304,14 +1327,14 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
     }
   };
   const int py = H - 1, px = W - 1;
-  const int bA = b0 + 2 * wave + hsel;                      // the image whose rows this lane feeds (A layout)
+  // the image whose rows this lane feeds (A layout); past the batch: the last image's (loaded, multiplied, never stored)
+  const int bA = b0 + 2 * wave + hsel, bAc = bA < Bn ? bA : Bn - 1;
   auto load_spikes = [&](int c, v4i (&sp)[4]) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int tap = (u >> 1) * 3 + (u & 1);
       const int yy = py + tap / 3 - 1, xx = px + tap % 3 - 1;
-      sp[u] = v4i{0, 0, 0, 0};
-      if (bA < Bn) sp[u] = *reinterpret_cast<const v4i*>(a.in0 + (((long long)bA * nch + c) * HW + yy * W + xx) * POSB + tt * 16);
+      sp[u] = *reinterpret_cast<const v4i*>(a.in0 + (((long long)bAc * nch + c) * HW + yy * W + xx) * POSB + tt * 16);
     }
   };
   v16f acc[3];
@@ -1320,13 +1343,16 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
   v4i sp[4], spn[4];
-  issue_chunk(0, 0);
   load_spikes(0, sp);
+  issue_chunk(0, 0);
+  asm volatile("" : "+v"(sp[0]), "+v"(sp[1]), "+v"(sp[2]), "+v"(sp[3]));
   for (int c = 0; c < nch; ++c) {
-    const int buf = c & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of chunk c (and its spike fragments) are in
+    const int buf = c & (LPS_RING - 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's pieces of chunk c are in (with the fragments, at the end of step c - 1)
     __syncthreads();                                        // everyone's are; everyone is done with the other buffer
-    if (c + 1 < nch) { issue_chunk(c + 1, buf ^ 1); load_spikes(c + 1, spn); }
+    // (clamped, not skipped: the loads of the last step re-read chunk nch - 1's fragments -- no branch, no moves into spn)
+    load_spikes(c + 1 < nch ? c + 1 : c, spn);
+    if (c + 1 < nch) issue_chunk(c + 1, buf ^ 1);
     const uint8_t* Wb = lds + buf * LPS_BUF;
     // (the assembly form of the main kernel: four- and six-register operands; the builtin wants eight-register tuples padded
     //  with zeros for both, which is what pushed this body past 168 registers)
@@ -1359,10 +1385,10 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
       mm(acc[2], a01, t11, sc_lo); mm(acc[2], a34, t12, sc_lo);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (c + 1 < nch) {
+    // the one wait of the step: hipcc waits for the visible fragment loads in front of this statement
+    asm volatile("" : "+v"(spn[0]), "+v"(spn[1]), "+v"(spn[2]), "+v"(spn[3]));
 #pragma unroll
-      for (int u = 0; u < 4; ++u) sp[u] = spn[u];
-    }
+    for (int u = 0; u < 4; ++u) sp[u] = spn[u];
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");        // (the MFMAs are opaque to the hazard recognizer: accumulator reads below)
   const int co = g * 32 + (lane & 31);
@@ -1391,7 +1417,7 @@ __device__ __forceinline__ void fp6v2_lastpos_shared_body(const V2Args& a, const
 // batches, where either part fills the device by itself: the merged form measured 1.3 % slower there).
 // PART 3 (round 5): PART 0 with the last positions of fp6v2_lastpos_shared_body (39 KB of dynamic LDS per workgroup: four per CU).
 // (HIP's second launch-bound argument = waves per SIMD the kernel must leave room for: four workgroups of PART 3 per CU -> 128 registers;
-//  one address spills, outside the chunk loop)
+//  123 used, no scratch: profiles/lastpos_ring_resources.txt)
 template <int H, int W, int PART>
 __global__ __launch_bounds__(256, PART == 3 ? 4 : 1) void fp6v2_tail_kernel(V2Args a, long long n_words, int n_lp) {
   __shared__ float red[(PART == 1 || PART == 3) ? 1 : (PART == 2 ? 9 : 3)][16][64];
