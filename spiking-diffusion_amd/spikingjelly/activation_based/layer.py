@@ -125,8 +125,19 @@ class BatchNorm2d(nn.BatchNorm2d, base.StepModule):
     def extra_repr(self):
         return super().extra_repr() + f', step_mode={self.step_mode}'
 
+    def train(self, mode: bool = True):
+        if mode != self.training:
+            # a train-mode forward moves running_mean / running_var without moving their _version (torch's operator and this
+            # library's fused BN + LIF alike): whatever was folded from them goes with the mode, also when this module is toggled
+            # on its own or sits in a plain nn.Sequential
+            from spkdiff import fused
+            fused.invalidate_derived(self)
+        return super().train(mode)
+
     def affine_terms(self):
-        """(a, b) with y = fma(x, a, b); recomputed when any of the four tensors changed (in place or replaced)."""
+        """(a, b) with y = fma(x, a, b); recomputed when any of the four tensors changed (in place or replaced).  The entry is
+        (key, (a, b), aliases of the four tensors): see spkdiff.fused._alias; writes through ``.data`` need
+        ``spkdiff.fused.invalidate_derived``."""
         if self.training or not self.track_running_stats:
             raise NotImplementedError('spkdiff: BatchNorm2d batch statistics (training) are outside the inference '
                                       'hot path; call .eval()')
@@ -134,7 +145,7 @@ class BatchNorm2d(nn.BatchNorm2d, base.StepModule):
         key = tuple((None if t is None else (t.data_ptr(), t._version, str(t.device))) for t in tens)
         if self._affine_cache is None or self._affine_cache[0] != key:
             self._affine_cache = (key, ops.bn_prepare(self.weight, self.bias, self.running_mean, self.running_var,
-                                                      self.eps))
+                                                      self.eps), tuple(None if t is None else t.detach() for t in tens))
         return self._affine_cache[1]
 
     def forward(self, x: torch.Tensor):

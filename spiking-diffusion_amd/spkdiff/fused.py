@@ -23,6 +23,14 @@ def _ver(t):
     return None if t is None else (t.data_ptr(), t._version, str(t.device))
 
 
+def _alias(t):
+    """A second handle on the storage of ``t``.  Every cache entry keeps one for each tensor its key names: while the entry lives the
+    storage cannot be freed and handed out again, so an equal ``(data_ptr, _version)`` is the same storage -- also after the
+    parameter's ``.data`` was replaced (``p.data = new``, ``module.double().float()``, ``keep_channels_last``, ``.cpu()`` and back:
+    none of them moves the parameter's ``_version``, and the allocator may hand the freed block to the replacement)."""
+    return None if t is None else t.detach()
+
+
 class ConvParams:
     """Prepared weights of one conv layer, one cached entry per form, each rebuilt on first use after the parameters change:
     ``get``  -> fp32 packed [k*k][Cin][Cout] for the direct kernels;
@@ -30,7 +38,7 @@ class ConvParams:
     other matrix-core kernels."""
 
     def __init__(self):
-        self.forms = {}                 # form -> (parameter versions it was built from, the derived tensor(s))
+        self.forms = {}                 # form -> (parameter versions it was built from, the derived tensor(s), aliases of the parameters)
 
     @staticmethod
     def version(conv):
@@ -44,7 +52,7 @@ class ConvParams:
         key = self.version(conv) + extra
         ent = self.forms.get(name)
         if ent is None or ent[0] != key:
-            ent = self.forms[name] = (key, build())
+            ent = self.forms[name] = (key, build(), (_alias(conv.weight), _alias(conv.bias)))
         return ent[1]
 
     def get(self, conv):
@@ -147,8 +155,12 @@ def invalidate_derived(module):
     """Drop every cached derived form of the parameters below ``module``: packed convolution weights (fp32 / int8 /
     fp6 digit planes), folded BatchNorm terms, captured sampler graphs.  The caches are keyed by ``(data_ptr,
     _version)``, which in-place writes through ``.data`` (``p.data.copy_(ema)``) do NOT change -- call this after such a
-    write.  ``load_state_dict`` and train()/eval() transitions call it on their own, and the sampler compares a content
-    checksum of the denoiser's tensors on every ``sample()`` call (``AbsorbingDiffusion.verify_weights``).
+    write.  ``load_state_dict`` and train()/eval() transitions call it on their own (a ``FusedSequential``'s, a ``DummyModel``'s and
+    a ``layer.BatchNorm2d``'s own: a train-mode forward moves the running statistics without moving their ``_version``), the fused
+    training forward calls it on its BatchNorm, the captured training steps call it after every replay, and the sampler compares a
+    content checksum of the denoiser's tensors on every ``sample()`` call (``AbsorbingDiffusion.verify_weights``).  A REPLACED tensor
+    (``p.data = new``, ``module.double().float()``, ``keep_channels_last``, a round trip through the host) needs no call: every cache
+    entry holds an alias of the tensors it was built from, so the replacement never gets their address while the entry lives.
 
     Every module below ``module`` also gets its ``_derived_epoch`` bumped: a captured graph bakes the ADDRESSES of the
     derived tensors, so whoever captured one keys it on ``derived_epoch(root)`` and re-captures after an invalidation
@@ -165,7 +177,7 @@ def invalidate_derived(module):
         tab = getattr(m, '_spikegen_tab', None)
         if isinstance(tab, dict):                   # the per-token spike-pattern tables of a spike generator (tokens_to_s32):
             for ent in tab.values():                # contents unknown from here on; the buffer stays (a captured graph may address it)
-                ent[1] = ent[2] = None
+                ent[1:] = [None] * (len(ent) - 1)
         object.__setattr__(m, '_derived_epoch', getattr(m, '_derived_epoch', 0) + 1)
 
 
@@ -181,7 +193,7 @@ def derived_refs(module):
     for m in module.modules():
         pr = getattr(m, '_spk_params', None)
         if pr is not None:
-            refs.append(tuple(v for _, v in pr.forms.values()))
+            refs.append(tuple(ent[1] for ent in pr.forms.values()))
         if isinstance(m, layer.BatchNorm2d) and m._affine_cache is not None:
             refs.append(m._affine_cache)
     return refs
@@ -284,6 +296,7 @@ class FusedSequential(nn.Sequential):
                                                bn.momentum, bn.eps, lif.tau, lif.v_threshold, lif.v_reset,
                                                float(lif.surrogate_function.alpha), lif.detach_reset, emit)
             x, lif.v = out[0], out[1]
+            invalidate_derived(bn)                    # (the operator wrote the running statistics through raw pointers: no _version moved)
             if emit and out[2] is not None:
                 x._spk_c4 = (out[2], x._version)
             sink = getattr(self, '_nbt_sink', None)
@@ -353,11 +366,13 @@ class FusedSequential(nn.Sequential):
         bias = None if conv.bias is None else conv.bias.detach()
         packed = conv_params(conv).get(conv)
         # the table is kept while the parameter versions that went into it AND the invalidation epochs are unchanged; the buffer
-        # belongs to this container (no table is shared between models)
+        # belongs to this container (no table is shared between models); the entry holds an alias of every tensor the key names
         key = (ConvParams.version(conv), bn._affine_cache[0], _ver(codebook), derived_epoch(self), tuple(epoch))
+        hold = (_alias(conv.weight), bias, bn._affine_cache[2], _alias(codebook))
         if not isinstance(getattr(self, '_spikegen_tab', None), dict):
             object.__setattr__(self, '_spikegen_tab', {})
-        return ops.spikegen_tokens_s32(tokens, codebook, packed, bias, a, b, T=T, table_key=key, table_slot=self._spikegen_tab)
+        return ops.spikegen_tokens_s32(tokens, codebook, packed, bias, a, b, T=T, table_key=key, table_slot=self._spikegen_tab,
+                                       table_hold=hold)
 
     def run(self, x, in_kind, final='f32', T=None, in1=None, coef=None, apply_tanh=False, want_u8=False,
             stateful=True, want_pre=False, chunk_out=None, impl='auto', want_counts=False, need_radius=None):

@@ -1591,7 +1591,7 @@ def convT_fp6_collapsed(in_s32, packed, Cout, *, bn_a, bn_b, coef):
     return vae_fp6_fwd(in_s32, packed, Cout, bn_a=bn_a, bn_b=bn_b, transposed=True, out_kind=VAE_OUT_COLLAPSED, coef=coef)
 
 
-_COEF_SUMS = {}
+_COEF_SUMS = {}      # (data_ptr, _version, numel) of a coefficient tensor -> (its fp32 sum, an alias of the tensor)
 
 
 def readout_collapsed_supported(Cin, Cout, k):
@@ -1613,14 +1613,15 @@ def readout_collapsed(x_bhwc, weight, bias, coef, *, apply_tanh=False, want_u8=F
     out_f = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
     out_u = torch.empty((B, Cout, H, W), dtype=torch.uint8, device=x.device) if want_u8 else None
     ckey = (coef.data_ptr(), coef._version, coef.numel())
-    csum = _COEF_SUMS.get(ckey)
+    ent = _COEF_SUMS.get(ckey)
+    csum = None if ent is None else ent[0]
     if csum is None:                    # (a device -> host copy: once per coefficient tensor, not per call)
         csum = 0.0
         for c in coef.detach().reshape(-1).float().cpu().tolist():      # fp32 left-to-right, as torch.sum over T would add
             csum = float(torch.tensor(csum, dtype=torch.float32) + torch.tensor(c, dtype=torch.float32))
         if len(_COEF_SUMS) > 16:
             _COEF_SUMS.clear()
-        _COEF_SUMS[ckey] = csum
+        _COEF_SUMS[ckey] = (csum, coef.detach())    # (the alias keeps the storage: no other tensor gets this address under this key)
     check(lib.spk_readout_collapsed_fwd(_p(x), _p(w), _p(bias), float(csum), _p(out_f), _p(out_u), int(apply_tanh), B, H, W,
                                         Cin, Cout, int(k), int(pad), int(transposed), _stream(x)), "spk_readout_collapsed_fwd")
     return {"f32": out_f, "u8": out_u}
@@ -1903,13 +1904,14 @@ def embedding(tokens, codebook, nchw_hw=None):
     return out
 
 
-def spikegen_tokens_s32(tokens, codebook, w_packed, bias, bn_a, bn_b, T=16, table_key=None, table_slot=None):
+def spikegen_tokens_s32(tokens, codebook, w_packed, bias, bn_a, bn_b, T=16, table_key=None, table_slot=None, table_hold=None):
     """tokens int64 [B,h,w] -> S32 spikes [B,1,h,w,16,16] of the spike generator (embedding + 1x1 conv + BN + LIF from the reset state on
     the repeated code vector), by a per-token pattern table (spk_spikegen_tokens_s32).  w_packed: [1][D][Cout], Cout 16 or 32.
     table_slot: a dict OWNED BY THE CALLER's module (one per spike generator: no table is shared between models) that keeps the table
     buffer per (device, K, Cout) with the key and the stream of its last eager build.  table_key: anything that changes whenever
     codebook, weights or BN terms do (parameter versions + the owner's invalidation epoch); the slot's table is reused while the key
-    AND the stream are equal.  A call under stream capture always builds, into a buffer of its own (the graph's pool), and never touches
+    AND the stream are equal.  table_hold: aliases of the tensors the key names, kept with it (their storage cannot be recycled under an
+    equal key).  A call under stream capture always builds, into a buffer of its own (the graph's pool), and never touches
     the slot: a replay bakes the derived inputs of capture time and must not leave its table behind an eager call's key."""
     tokens = _dev(tokens, "tokens", torch.int64)
     codebook = _dev(codebook.detach(), "codebook", torch.float32)
@@ -1927,13 +1929,13 @@ def spikegen_tokens_s32(tokens, codebook, w_packed, bias, bn_a, bn_b, T=16, tabl
         skey = (tokens.device, K, Cout)             #  -- which bake the derived inputs of capture time -- never write the eager slot)
         ent = table_slot.get(skey)
         if ent is None:
-            ent = table_slot[skey] = [torch.empty(nbytes // 2, dtype=torch.int16, device=tokens.device), None, None]
+            ent = table_slot[skey] = [torch.empty(nbytes // 2, dtype=torch.int16, device=tokens.device), None, None, None]
     if ent is None:
         ws, build = torch.empty(nbytes // 2, dtype=torch.int16, device=tokens.device), True
     else:
         ws = ent[0]
         build = table_key is None or ent[1] != table_key or ent[2] != stream
-        ent[1], ent[2] = (None, None) if table_key is None else (table_key, stream)
+        ent[1:] = (None, None, None) if table_key is None else (table_key, stream, table_hold)
     B, h, w = tokens.shape
     out = empty_spikes(S32, B, Cout, h, w, T, tokens.device)
     check(lib.spk_spikegen_tokens_s32(_p(tokens), _p(codebook), _p(w_packed), _p(bias), _p(bn_a), _p(bn_b), _p(ws), int(build), _p(out),

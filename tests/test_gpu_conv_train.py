@@ -310,11 +310,22 @@ def test_graphed_vqvae_training_step_equals_the_eager_loop(dev):
         assert float((p1.detach() - p2.detach()).abs().max()) <= 1e-6 * (1 + float(p1.detach().abs().max())), k
     with pytest.raises(RuntimeError):
         GraphedVQVAETrainStep(m2, torch.optim.AdamW(m2.parameters(), lr=1e-3), imgs[0])
+    # the captured optimizer steps are visible to the inference path: eval equals a fresh model loaded from the trained state (the
+    # same kernels without history: exact; tests/test_gpu_derived_state.py has the other routes)
+    import copy
     m2.eval()
-    with torch.inference_mode():                       # the captured optimizer steps are visible to the inference path
-        _, xr, idx = m2(imgs[0].unsqueeze(0).repeat(16, 1, 1, 1, 1), imgs[0])
-    functional.reset_net(m2)
+    m3 = SNN_VQVAE(1, 16, 128, 0.08)
+    functional.set_step_mode(net=m3, step_mode='m')
+    m3.load_state_dict(copy.deepcopy(m2.state_dict()))
+    m3 = m3.to(dev).eval()
+    outs = []
+    for m in (m2, m3):
+        with torch.inference_mode():
+            outs.append(m(imgs[0].unsqueeze(0).repeat(16, 1, 1, 1, 1), imgs[0]))
+        functional.reset_net(m)
+    (e, xr, idx), (e3, xr3, idx3) = outs
     assert xr.shape == (8, 1, 28, 28) and bool(torch.isfinite(xr).all())
+    assert torch.equal(e, e3) and torch.equal(xr, xr3) and torch.equal(idx, idx3)
 
 
 def test_native_and_framework_convolutions_give_the_same_training_step(dev, ops):
