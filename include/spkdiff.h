@@ -653,6 +653,33 @@ int spk_psample_step_topk(const float* logits_bkhw, long long* x_t_inout, uint8_
                           unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                           long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null,
                           const int* n_active_or_null, float* next_input_b2hw_or_null, spk_stream_t stream);
+/* Nucleus (top-p) truncated sampling: spk_psample_step_topp and spk_den_step_tail_topp take the arguments, checks
+ * and properties of their `_topk` siblings plus `const float* topp_b`, a device array of B fp32 values placed after topk_b and
+ * indexed by IMAGE like it.  For a position of image i whose token is drawn let z_c = logits_c / temp_b[i] (the one fp32 division,
+ * classes c < K), k = topk_b[i] and p = topp_b[i]:
+ *   1. the top-k truncation with k, exactly as spk_psample_step_topk makes it (k <= 0 or k >= K: none);
+ *   2. !(p > 0 && p < 1) -- 1, 0, a negative, a NaN: the row is not nucleus-truncated; every output is then bit for bit the `_topk`
+ *      entry point's, and with k off too the `_temps` entry point's;
+ *   3. otherwise mx = the row maximum of z_c by fmaxf (NaNs ignored); mx not finite: the row stays as it is;
+ *   4. integer masses: w_c = expf(z_c - mx) (one fp32 subtraction, one expf, no contraction), m_c = (uint32) rint(w_c * 2^20), round
+ *      to nearest even; m_c = 0 for a NaN z_c and for the classes top-k set to -inf; total = sum m_c in uint32 (K <= 2048: <= 2^31);
+ *   5. P = (double)p * (double)total, one IEEE fp64 multiplication;
+ *   6. with the order-preserving 32-bit keys of the top-k select (a NaN does not count), S(T) = the sum of m_c over the classes with
+ *      key_c >= T; tau's key is the largest T with (double)S(T) >= P (built from bit 31 down, 32 integer wave sums);
+ *   7. every class with z_c < tau (IEEE comparison) becomes -inf, and the row goes through the unchanged race: same operations, same
+ *      order, same noise counters.
+ * The kept set is the smallest set of top classes, closed under ties with tau, whose mass reaches p of the total: the row maximum
+ * always stays, p -> 0+ leaves only the maxima (a unique maximum: the arg max whatever the noise), classes tying with tau all stay,
+ * a NaN is never replaced (such a row still gets token 0).  After the expf everything is integer or single-rounded IEEE arithmetic:
+ * no permutation of lanes or classes changes tau, and every launch form computes the same one.  A dropped class's draw is simply
+ * not used: no other draw moves, so split independence, philox_state and hipGraph capture hold as before.  The only check on
+ * temp_b / topk_b / topp_b is for NULL (SPK_ERR_ARG before any launch).  There is no nucleus score entry point. */
+int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                          const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
+                          unsigned long long philox_seed, unsigned long long philox_offset,
+                          const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B, int HW, int K,
+                          const int* active_or_null, const int* n_active_or_null, float* next_input_b2hw_or_null,
+                          spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -695,7 +722,7 @@ int spk_pscore_step_temps(const float* logits_bkhw, const long long* x0, long lo
  * serves slot s of the list: cnt5 / cnt1 / logits_out are indexed by slot (what the active-set denoiser launches produced), x_t / unmasked /
  * the noise by image active[s], so the draws are those of the dense form; x1_s32_out must be NULL there (the next step's first layer is
  * the next step's active set's). */
-#define SPK_STEP_TAIL_MAX_K 512 /* the largest K spk_den_step_tail and its _temps / _topk forms take */
+#define SPK_STEP_TAIL_MAX_K 512 /* the largest K spk_den_step_tail and its _temps / _topk / _topp forms take */
 int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                       const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                       float temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
@@ -719,6 +746,16 @@ int spk_den_step_tail_topk(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, i
                            const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
                            int t, const float* temp_b, const int* topk_b, const float* u_or_null, const float* q_or_null,
                            unsigned long long philox_seed, unsigned long long philox_offset,
+                           const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                           const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                           uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                           const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
+/* spk_den_step_tail with top-k and nucleus truncation (1 <= K <= 512; workgroup s of the active-set form reads temp_b[active[s]],
+ * topk_b[active[s]] and topp_b[active[s]]): see spk_psample_step_topp. */
+int spk_den_step_tail_topp(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                           const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                           int t, const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                           const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
                            const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
                            const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                            uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,

@@ -31,9 +31,11 @@ __device__ __forceinline__ bool __any_sync_quad(bool v) {      // OR over the 4 
 // separate instantiation: the scalar kernel's code does not change.
 // TK = top-k truncation (spk_psample_step_topk; always with PT): `temp` is then the pair of per-image arrays {temperatures, k}, and
 // a position whose token is drawn has its scaled logits truncated (truncate_top_k, psample_common.h) ahead of the unchanged race.
-template <int KPL, bool PT = false, bool TK = false>
+// TP = nucleus truncation after the top-k one (spk_psample_step_topp; always with PT and TK): the triple {temperatures, k, p} and
+// truncate_top_p between truncate_top_k and the race.
+template <int KPL, bool PT = false, bool TK = false, bool TP = false>
 __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
-                                                      uint8_t* __restrict__ unmasked, int t, spk_temp_arg_t<PT, TK> temp,
+                                                      uint8_t* __restrict__ unmasked, int t, spk_temp_arg_t<PT, TK, TP> temp,
                                                       const float* __restrict__ u_in, const float* __restrict__ q_in,
                                                       unsigned long long seed, unsigned long long offset,
                                                       const unsigned long long* __restrict__ philox_state,
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       }
     }
     float l[KPL];
-    const float tp = spk_temp_of<PT, TK>(temp, active ? active[b] : b);
+    const float tp = spk_temp_of<PT, TK, TP>(temp, active ? active[b] : b);
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
       const int k = lane + 64 * j;
@@ -69,6 +71,7 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
       l[j] = k < K ? lg / tp : -INFINITY;
     }
     if constexpr (TK) truncate_top_k<KPL>(l, lane, K, temp.topk[active ? active[b] : b]);
+    if constexpr (TP) truncate_top_p<KPL>(l, lane, K, temp.topp[active ? active[b] : b]);
     const int besti = categorical_race<KPL>(l, lane, K, q_in, seed, offset, p);
     if (lane == 0) {
       const float u = reveal_u(u_in, seed, offset, p, K);
@@ -339,13 +342,13 @@ extern "C" int spk_den_build_input(const float* x_float_or_null, const long long
 }
 
 namespace {
-template <bool PT, bool TK = false>
-int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_arg_t<PT, TK> temp,
+template <bool PT, bool TK = false, bool TP = false>
+int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_arg_t<PT, TK, TP> temp,
                    const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
                    unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                    long long* x0_hat_out_or_null, int B, int HW, int K, const int* active_or_null, const int* n_active_or_null,
                    float* next_input_b2hw_or_null, hipStream_t stream) {
-  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK>(temp) || B <= 0 || HW <= 0 || K <= 0)
+  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK, TP>(temp) || B <= 0 || HW <= 0 || K <= 0)
     return SPK_ERR_ARG;
   if (next_input_b2hw_or_null && active_or_null) return SPK_ERR_ARG;      // (the active-set form gathers its input by slot)
   if ((active_or_null == nullptr) != (n_active_or_null == nullptr) || (active_or_null && x0_hat_out_or_null))
@@ -355,7 +358,7 @@ int psample_launch(const float* logits_bkhw, long long* x_t_inout, uint8_t* unma
   int grid = (int)((npos + 3) / 4);
   if (grid > 4096) grid = 4096;
 #define SPK_PSAMPLE_LAUNCH(KPL)                                                                                          \
-  hipLaunchKernelGGL((psample_kernel<KPL, PT, TK>), dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, \
+  hipLaunchKernelGGL((psample_kernel<KPL, PT, TK, TP>), dim3(grid), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, \
                      t, temp, u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, \
                      active_or_null, n_active_or_null, B, HW, K, next_input_b2hw_or_null, (float)(t - 1))
   if (K <= 256) SPK_PSAMPLE_LAUNCH(4);
@@ -402,4 +405,17 @@ extern "C" int spk_psample_step_topk(const float* logits_bkhw, long long* x_t_in
   return psample_launch<true, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topk{temp_b, topk_b}, u_or_null, q_or_null,
                                     philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, B, HW, K, active_or_null,
                                     n_active_or_null, next_input_b2hw_or_null, stream);
+}
+
+// The same step with nucleus (top-p) truncation after the top-k one: per IMAGE a temperature, a k and a p (topp_b fp32 [B]; !(0 < p
+// < 1): that image is not nucleus-truncated) on the device (include/spkdiff.h).
+extern "C" int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                     const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                     const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                     const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B,
+                                     int HW, int K, const int* active_or_null, const int* n_active_or_null,
+                                     float* next_input_b2hw_or_null, hipStream_t stream) {
+  return psample_launch<true, true, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                          q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, B, HW, K,
+                                          active_or_null, n_active_or_null, next_input_b2hw_or_null, stream);
 }

@@ -1,7 +1,7 @@
 // The token update of a reverse step, defined once for the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10
 // counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
-// offset + position * K + class), the categorical draw categorical_race, the top-k truncation truncate_top_k that may precede it, the
-// 64-lane max / sum and the prologues every kernel shares.
+// offset + position * K + class), the categorical draw categorical_race, the top-k and nucleus truncations truncate_top_k /
+// truncate_top_p that may precede it, the 64-lane max / sum and the prologues every kernel shares.
 // Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
@@ -78,22 +78,28 @@ __device__ __forceinline__ void write_next_input(float* __restrict__ next_input,
 // gets the scalar call's results bit for bit.  The host can check a value (> 0), of an array only the pointer.
 // TK, the `_topk` entry points (top-k truncation, below): the argument is the pair of per-image arrays, temperatures fp32 [B] and k
 // int32 [B], both indexed by IMAGE.  The scalar and `_temps` kernels keep the argument they always had.
+// TP, the `_topp` entry points (nucleus truncation after the top-k one, below; always with PT and TK): the triple of per-image arrays,
+// temperatures fp32 [B], k int32 [B] and p fp32 [B].  One family serves top-k and top-p together.
 struct spk_temp_topk { const float* temp; const int* topk; };
-template <bool PT, bool TK = false> struct spk_temp_arg { using type = float; };
-template <> struct spk_temp_arg<true, false> { using type = const float*; };
-template <> struct spk_temp_arg<true, true> { using type = spk_temp_topk; };
-template <bool PT, bool TK = false> using spk_temp_arg_t = typename spk_temp_arg<PT, TK>::type;
+struct spk_temp_topp { const float* temp; const int* topk; const float* topp; };
+template <bool PT, bool TK = false, bool TP = false> struct spk_temp_arg { using type = float; };
+template <> struct spk_temp_arg<true, false, false> { using type = const float*; };
+template <> struct spk_temp_arg<true, true, false> { using type = spk_temp_topk; };
+template <> struct spk_temp_arg<true, true, true> { using type = spk_temp_topp; };
+template <bool PT, bool TK = false, bool TP = false> using spk_temp_arg_t = typename spk_temp_arg<PT, TK, TP>::type;
 
-template <bool PT, bool TK = false>
-__device__ __forceinline__ float spk_temp_of(spk_temp_arg_t<PT, TK> temp, int image) {
+template <bool PT, bool TK = false, bool TP = false>
+__device__ __forceinline__ float spk_temp_of(spk_temp_arg_t<PT, TK, TP> temp, int image) {
   static_assert(PT || !TK, "the truncating kernels take per-image arrays");
+  static_assert(TK || !TP, "the nucleus kernels take the top-k array too");
   if constexpr (TK) return temp.temp[image];
   else if constexpr (PT) return temp[image];
   else return temp;
 }
-template <bool PT, bool TK = false>
-inline bool spk_temp_arg_ok(spk_temp_arg_t<PT, TK> temp) {
-  if constexpr (TK) return temp.temp != nullptr && temp.topk != nullptr;
+template <bool PT, bool TK = false, bool TP = false>
+inline bool spk_temp_arg_ok(spk_temp_arg_t<PT, TK, TP> temp) {
+  if constexpr (TP) return temp.temp != nullptr && temp.topk != nullptr && temp.topp != nullptr;
+  else if constexpr (TK) return temp.temp != nullptr && temp.topk != nullptr;
   else if constexpr (PT) return temp != nullptr;
   else return temp > 0.f;
 }
@@ -180,6 +186,53 @@ __device__ __forceinline__ void truncate_top_k(float (&l)[NJ], int lane, int K, 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) n += __popcll(__ballot(key[j] >= trial));
     if (n >= k) T = trial;
+  }
+  const float tau = __uint_as_float((T & 0x80000000u) ? (T & 0x7FFFFFFFu) : ~T);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (l[j] < tau) l[j] = -INFINITY;
+}
+
+// Nucleus (top-p) truncation of one position's temperature-scaled logits, after truncate_top_k and ahead of categorical_race
+// (DESIGN.md §4.14): the smallest set of top classes, closed under ties, whose probability mass reaches p of the row's.  The cut is
+// exact integer arithmetic after one expf per class: with mx the row maximum (fmaxf: NaNs ignored), class c weighs
+// m_c = (uint32) rint(expf(l_c - mx) * 2^20) (0 for a NaN, a class >= K and a class at -inf, top-k's among them), total = sum m_c
+// <= 2048 * 2^20 = 2^31, P = (double)p * (double)total (one fp64 product), and tau's key is the largest key T -- the keys of
+// truncate_top_k -- with (double)S(T) >= P, S(T) = the sum of m_c over the classes with key_c >= T, built from bit 31 down with one
+// compare and one add per held class and a uint32 wave sum (spk_wave_sum_u32, spk_common.h) per step.  S falls as T rises, so the bit descent finds that T, and
+// T is the key of a class with m_c > 0 (the maximum's 2^20 makes S(smallest key) = total > P).  Every class with l < tau (the float
+// comparison) becomes -inf: classes equal to tau all stay, the row maximum always stays, a NaN is never replaced.  !(0 < p < 1) --
+// 1, 0, a negative, a NaN -- and a row whose maximum is not finite leave the row as it is.  No LDS, no sort, no data-dependent loop;
+// integer sums do not depend on their order, so a permutation of lanes or classes cannot move tau.  Wave-uniform arguments K, p.
+template <int NJ>
+__device__ __forceinline__ void truncate_top_p(float (&l)[NJ], int lane, int K, float p) {
+  if (!(p > 0.f && p < 1.f)) return;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) mx = fmaxf(mx, (lane + 64 * j < K) ? l[j] : -INFINITY);
+  mx = wave_max(mx);
+  if (!(fabsf(mx) < INFINITY)) return;
+  uint32_t key[NJ], m[NJ];
+  uint32_t total = 0u;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const uint32_t b = __float_as_uint(l[j]);
+    const bool counts = (lane + 64 * j < K) && !(l[j] != l[j]);
+    key[j] = counts ? ((b & 0x80000000u) ? ~b : (b | 0x80000000u)) : 0u;
+    m[j] = counts ? (uint32_t)rintf(expf(l[j] - mx) * 1048576.0f) : 0u;
+    total += m[j];
+  }
+  total = spk_wave_sum_u32(total);
+  const double P = (double)p * (double)total;
+  uint32_t T = 0u;
+#pragma unroll 1
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t trial = T | (1u << bit);
+    uint32_t s = 0u;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) s += key[j] >= trial ? m[j] : 0u;
+    s = spk_wave_sum_u32(s);
+    if ((double)s >= P) T = trial;
   }
   const float tau = __uint_as_float((T & 0x80000000u) ? (T & 0x7FFFFFFFu) : ~T);
 #pragma unroll

@@ -152,6 +152,20 @@ __device__ __forceinline__ unsigned spk_transpose16_rows(unsigned x, int lane) {
   return x;
 }
 
+// uint32 sum over the 64 lanes of a fully active wave with the same DPP lane exchanges (integers: any order gives the same sum): a
+// butterfly inside each row of 16 lanes (lane ^ 1, lane ^ 2, then the mirror of each half row and of each row: every lane of a row
+// ends with the row's sum), then the four rows' sums through the scalar unit.  The nucleus truncation of the sampler makes 32 such
+// sums in a row per drawn token (truncate_top_p, psample_common.h): as six __shfl_xor steps each was six dependent ds_bpermute round
+// trips, and top_p = 0.9 cost 2.1 - 2.3 % of the B = 256 dense sample where this form costs 0.8 - 1.2 %.
+__device__ __forceinline__ unsigned spk_wave_sum_u32(unsigned v) {
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);    // quad_perm [1, 0, 3, 2]
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);    // quad_perm [2, 3, 0, 1]
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror
+  v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);   // row_mirror
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned)__builtin_amdgcn_readlane((int)v, 16) +
+         (unsigned)__builtin_amdgcn_readlane((int)v, 32) + (unsigned)__builtin_amdgcn_readlane((int)v, 48);
+}
+
 // e2m1 spike records: 16 channels of one (position, step) as 16 nibbles = 8 bytes, channel k in nibble k, a spike as the
 // e2m1 code of 1.0 (0x2).  spk_spread8: bit k -> nibble k of eight channel bits.
 __device__ __forceinline__ unsigned spk_spread8(unsigned x) {

@@ -33,12 +33,13 @@ constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested 
 // PT = per-image temperature (spk_den_step_tail_temps): `temp` is a device array fp32 [B] indexed by IMAGE (psample_common.h); the
 // scalar form's argument block is the one it always was
 // TK = top-k truncation (spk_den_step_tail_topk; always with PT): `temp` is the pair of per-image arrays {temperatures, k}
-template <bool PT, bool TK = false>
+// TP = nucleus truncation after it (spk_den_step_tail_topp; always with PT and TK): the triple {temperatures, k, p}
+template <bool PT, bool TK = false, bool TP = false>
 struct TailArgsT {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
   const int8_t* wq; const double* scale; const double* bias;
   float* logits_out;                              // optional fp32 [B][128][HW]
-  long long* x_t; uint8_t* unmasked; int t; spk_temp_arg_t<PT, TK> temp;
+  long long* x_t; uint8_t* unmasked; int t; spk_temp_arg_t<PT, TK, TP> temp;
   const float* u_in; const float* q_in;
   unsigned long long seed, offset; const unsigned long long* philox_state;
   const float* w1; const float* b1; const float* bn1_a; const float* bn1_b;   // next step's conv1 (packed [9][2][64]); null: none
@@ -52,8 +53,8 @@ struct TailArgsT {
 };
 
 // KG = channel groups per wave (1: K <= 128, the reference's default; 2 .. 4: K <= 256 / 384 / 512)
-template <int H, int W, int KG, bool PT = false, bool TK = false>
-__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK> a) {
+template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false>
+__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP> a) {
   constexpr int HW = H * W;
   static_assert(HW <= 64, "an image is at most two 32-row tiles");
   constexpr int AV = HW * 2 + 1;                  // 16-byte vectors of a chunk's count records + one zero vector
@@ -106,9 +107,11 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK> a) 
   unsigned long long seed = a.seed, offset = a.offset;
   philox_base(a.philox_state, seed, offset);
   const float inv_t = 1.0f / (float)a.t;
-  const float temp = spk_temp_of<PT, TK>(a.temp, bi);  // (per image: requested here, read by the sampling after the K loop)
+  const float temp = spk_temp_of<PT, TK, TP>(a.temp, bi);  // (per image: requested here, read by the sampling after the K loop)
   int topk = 0;
   if constexpr (TK) topk = a.temp.topk[bi];
+  float topp = 1.0f;
+  if constexpr (TP) topp = a.temp.topp[bi];
   if (tid < HW) {
     const long long pi = (long long)bi * HW + tid;
     const uint8_t um = a.unmasked[pi];
@@ -236,6 +239,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK> a) 
     }
     // (the row's largest entry is never below tau: mx is the truncated row's maximum too)
     if constexpr (TK) truncate_top_k<NJ>(l, lane, K, topk);
+    if constexpr (TP) truncate_top_p<NJ>(l, lane, K, topp);
     mx = wave_max(mx);
     float se = 0.f;
 #pragma unroll
@@ -315,15 +319,15 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK> a) 
 }  // namespace
 
 namespace {
-template <bool PT, bool TK = false>
+template <bool PT, bool TK = false, bool TP = false>
 int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                      const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
-                     spk_temp_arg_t<PT, TK> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                     spk_temp_arg_t<PT, TK, TP> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                      const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                      uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                      const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
-  if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK>(temp) || B <= 0 ||
+  if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK, TP>(temp) || B <= 0 ||
       T <= 0)
     return SPK_ERR_ARG;
   if ((x1_s32_out_or_null == nullptr) != (cnt1_out_or_null == nullptr)) return SPK_ERR_ARG;
@@ -335,7 +339,7 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   // the fused first layer writes sixteen 16-byte step records per position and scans with the module-default LIF constants
   // (spk_lif_const_input_bits16): any other step count would write outside x1_s32_out (T < 16) or give wrong spikes (T > 16)
   if (x1_s32_out_or_null && T != 16) return SPK_ERR_UNSUPPORTED;
-  TailArgsT<PT, TK> a;
+  TailArgsT<PT, TK, TP> a;
   a.c5 = cnt5; a.c1 = cnt1; a.wq = wq; a.scale = scale; a.bias = bias_d; a.logits_out = logits_out_or_null;
   a.x_t = x_t_inout; a.unmasked = unmasked_inout; a.t = t; a.temp = temp; a.u_in = u_or_null; a.q_in = q_or_null;
   a.seed = philox_seed; a.offset = philox_offset; a.philox_state = philox_state_or_null;
@@ -346,7 +350,7 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   a.K = K; a.ng = (K + 15) / 16;                    // wq / scale / bias_d hold ng * 16 channels (zero weights beyond K)
   const int kg = (a.ng + 7) / 8;
 #define SPK_TAIL_LAUNCH(H_, W_, KG_)                                                                                          \
-  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
+  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
   if (H == 7) {
     if (kg == 1) SPK_TAIL_LAUNCH(7, 7, 1); else if (kg == 2) SPK_TAIL_LAUNCH(7, 7, 2);
     else if (kg == 3) SPK_TAIL_LAUNCH(7, 7, 3); else SPK_TAIL_LAUNCH(7, 7, 4);
@@ -403,4 +407,21 @@ extern "C" int spk_den_step_tail_topk(const uint8_t* cnt5, int nch5, const uint8
                                       spk_temp_topk{temp_b, topk_b}, u_or_null, q_or_null, philox_seed, philox_offset,
                                       philox_state_or_null, conv1_w_packed_or_null, conv1_bias_or_null, bn1_a, bn1_b,
                                       x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, active_or_null, n_active_or_null, stream);
+}
+
+// The same launch with nucleus (top-p) truncation after the top-k one: per IMAGE a temperature, a k and a p (topp_b fp32 [B]) on the
+// device (include/spkdiff.h).
+extern "C" int spk_den_step_tail_topp(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                      const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                      uint8_t* unmasked_inout, int t, const float* temp_b, const int* topk_b, const float* topp_b,
+                                      const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                      const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a,
+                                      const float* bn1_b, uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H,
+                                      int W, int K, const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
+  return step_tail_launch<true, true, true>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout, unmasked_inout, t,
+                                            spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null, q_or_null, philox_seed, philox_offset,
+                                            philox_state_or_null, conv1_w_packed_or_null, conv1_bias_or_null, bn1_a, bn1_b,
+                                            x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, active_or_null, n_active_or_null,
+                                            stream);
 }

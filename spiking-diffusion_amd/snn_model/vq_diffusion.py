@@ -98,19 +98,21 @@ class Score(NamedTuple):
 
 class _SamplerGraph:
     """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
-    conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``topk`` = int32 [B] of a truncating graph (which always has ``temps`` too); ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
+    conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``topk`` = int32 [B] of a truncating graph (which always has ``temps`` too); ``topp`` = fp32 [B] of a nucleus graph (which always has both); ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
     score graph: ``target[1:]`` = (logp, step), zeroed inside the graph), and every other buffer the captured launches address by raw pointer: freed earlier,
     its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
     (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
-    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False):
+    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False):
         self.graph = self.derived = None                            # set by the capture
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         # per-image temperatures are one more INPUT: the captured token updates read this buffer, filled before each replay
-        self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp or top_k else None
+        self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp or top_k or top_p else None
         # ... and so is the per-image k of a truncating graph (DESIGN.md §4.12)
-        self.topk = torch.zeros(b, dtype=torch.int32, device=dev) if top_k else None
+        self.topk = torch.zeros(b, dtype=torch.int32, device=dev) if top_k or top_p else None
+        # ... and the per-image p of a nucleus graph (DESIGN.md §4.14)
+        self.topp = torch.ones(b, dtype=torch.float32, device=dev) if top_p else None
         self.x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         self.unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self.start_in = (torch.empty((b, h, w), dtype=torch.int64, device=dev),
@@ -259,7 +261,8 @@ class AbsorbingDiffusion(Sampler):
         ``n_samples = B`` under the same seed, and a shard (``set_shard``) gives the tokens the whole job gives.
         ``temp``: a number, or one temperature per image of the call's batch (``_temp_arg``): image i is
         sampled as ``sample(temp[i])`` samples it -- the same tokens under the same key and global image index, in every launch
-        form, and one captured graph serves every vector.  Top-k truncation: ``sample_top_k``."""
+        form, and one captured graph serves every vector.  Top-k truncation: ``sample_top_k``; nucleus truncation:
+        ``sample_top_p``."""
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, None)
 
     @torch.no_grad()
@@ -276,16 +279,36 @@ class AbsorbingDiffusion(Sampler):
         would score -inf, which bounds nothing."""
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k)
 
-    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k):
+    @torch.no_grad()
+    def sample_top_p(self, top_p, temp=1.0, sample_steps=None, noise=None, record=None, x_init=None, known=None, top_k=None):
+        """``sample()`` with nucleus (top-p) truncation: every token is drawn from the likeliest codes of its
+        position whose probability mass reaches ``p`` of the row's, renormalised -- the smallest such set of top classes, closed
+        under ties; the cut is made on integer masses inside the kernels, so it does not depend on a summation order.  ``top_p``:
+        None (``sample_top_k(top_k, ...)`` itself: the same calls with the same arguments), a number in (0, 1] for every image,
+        or one entry per image of the call (``_topp_arg``): finite numbers in (0, 1], where 1 leaves that image untruncated; a
+        device tensor is fp32 [B] and taken as given.  ``top_k``: as ``sample_top_k`` takes it; it is applied first.  Every other
+        argument is sample()'s; same noise contract (a dropped class's draw is simply not used), so the tokens do not depend on the
+        launch form, on the split (``set_shard``) or on eager / captured; the row maximum always stays, and as p -> 0+ an image
+        gets its arg max at every position.  In a captured graph ``top_p``, ``top_k`` and the temperatures are inputs: one graph
+        per (batch, steps, form, conditional) serves every p, k and temperature.  ``score()`` takes no ``top_p``, for the reason it
+        takes no ``top_k``."""
+        return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p)
+
+    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         temp = self._temp_arg(temp, b)
         top_k = self._topk_arg(top_k, b)
+        top_p = self._topp_arg(top_p, b)
         dn = self._denoise_fn
         dev = next(dn.parameters()).device
         if dev.type != 'cuda':
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
         temp = self._temp_on(temp, dev)
+        if top_p is not None:
+            # a nucleus call takes all three per image (the `_topp` kernels read three arrays): no top_k is k = 0 everywhere
+            top_p = self._topp_on(top_p, dev, b)
+            top_k = 0 if top_k is None else top_k
         if top_k is not None:
             # a truncating call takes both per image: the `_topk` kernels read two arrays, and its graph two inputs
             top_k = self._topk_on(top_k, dev, b)
@@ -302,7 +325,50 @@ class AbsorbingDiffusion(Sampler):
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
         form = self._form(b, h, w, record is not None)
-        return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k)
+        return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k,
+                                     **({} if top_p is None else {'top_p': top_p}))
+
+    def _topp_arg(self, top_p, b):
+        """The ``top_p`` of sample_top_p() for a batch of ``b``, checked before anything is drawn or launched.  None: no nucleus
+        truncation.  A number in (0, 1] (anything ``float()`` takes that is no bool: a Python or numpy number, a 0-dim tensor or
+        array): that p for every image -- returns the float.  Otherwise one entry per image: host data (a list / tuple, a numpy
+        array, a CPU tensor) must be ``b`` finite numbers in (0, 1] (1: that image is not truncated; ValueError for a wrong length,
+        an entry outside (0, 1], a NaN or a bool) and comes back as a CPU fp32 tensor [b]; a device tensor is taken as given --
+        fp32 [b], its values are not read (the kernels leave an image whose p is outside (0, 1) untruncated)."""
+        if top_p is None:
+            return None
+        bad = ValueError(f'spkdiff: top_p must be None, a number in (0, 1] or one such number per image of the call ({b}), '
+                         f'got {top_p!r}')
+        if isinstance(top_p, bool):
+            raise bad
+        if isinstance(top_p, torch.Tensor) and top_p.is_cuda:
+            if top_p.dim() != 1 or int(top_p.numel()) != b or top_p.dtype != torch.float32:
+                raise ValueError(f'spkdiff: a per-image top_p on the device must be fp32 [{b}] (one entry per image of the call), '
+                                 f'got {top_p.dtype} {tuple(top_p.shape)}')
+            return top_p.contiguous()
+        try:
+            v = top_p.detach() if isinstance(top_p, torch.Tensor) else torch.as_tensor(top_p)
+            if v.dtype in (torch.bool, torch.complex64, torch.complex128) or v.dim() > 1 or (v.dim() == 1 and int(v.numel()) != b):
+                raise bad
+            # (host numbers are read in fp64: as_tensor alone would round a Python float to fp32 before the range check)
+            v = v.to(torch.float64) if isinstance(top_p, torch.Tensor) else torch.as_tensor(top_p, dtype=torch.float64)
+        except (TypeError, ValueError, RuntimeError):
+            raise bad from None
+        if not bool(torch.isfinite(v).all()) or not bool(((v > 0) & (v <= 1)).all()):
+            raise bad
+        # (what the kernels compare is the fp32 value: a p that rounds to 0 in fp32 would switch the truncation off)
+        if not bool((v.to(torch.float32) > 0).all()):
+            raise bad
+        return float(v) if v.dim() == 0 else v.to(torch.float32)
+
+    @staticmethod
+    def _topp_on(top_p, dev, b):
+        """``_topp_arg``'s result for the kernels: fp32 [b] on the denoiser's device (a number: broadcast; host data: its one copy)."""
+        if not isinstance(top_p, torch.Tensor):
+            return torch.full((b,), float(top_p), dtype=torch.float32, device=dev)
+        if top_p.is_cuda and top_p.device != dev:
+            raise ValueError(f'spkdiff: a per-image top_p must be on the denoiser\'s device {dev}, got {top_p.device}')
+        return top_p.to(dev)
 
     def _topk_arg(self, top_k, b):
         """The ``top_k`` of sample_top_k() for a batch of ``b``, checked before anything is drawn or launched.  None: no
@@ -431,12 +497,14 @@ class AbsorbingDiffusion(Sampler):
                                   None if known is None else start, record, target=(x0, logp[o], step[o]))
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
-    def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None):
+    def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None,
+                         top_p=None):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
-                return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k)
+                return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k,
+                                            **({} if top_p is None else {'top_p': top_p}))
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -454,10 +522,11 @@ class AbsorbingDiffusion(Sampler):
                 torch.cuda.synchronize(dev)
             finally:
                 self._capturing = False
-        return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k)
+        return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k,
+                                  **({} if top_p is None else {'top_p': top_p}))
 
     def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
-                      top_k=None):
+                      top_k=None, top_p=None):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
@@ -473,7 +542,7 @@ class AbsorbingDiffusion(Sampler):
                 noise = lambda t: (torch.rand(b, 1, h, w).to(dev), None)      # noqa: E731
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
         self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
-                            top_k=top_k)
+                            top_k=top_k, **({} if top_p is None else {'top_p': top_p}))
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -485,7 +554,7 @@ class AbsorbingDiffusion(Sampler):
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
     def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
-                       top_k=None):
+                       top_k=None, top_p=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -494,9 +563,12 @@ class AbsorbingDiffusion(Sampler):
         ``target = (x0, logp, step)``: teacher-forced (score()) -- the token update of every step is spk_pscore_step, which writes
         the given token x0 where spk_psample_step writes a sampled one and leaves its log-probability in logp, t in step (never a
         fused-tail form: ``form.tail`` / ``form.tail_act`` are off there); ``top_k``: int32 device tensor [B] -- handed to every token
-        update of sample_top_k() and to nothing else (None: the calls carry no such keyword)."""
+        update of sample_top_k() and to nothing else (None: the calls carry no such keyword); ``top_p``: fp32 device tensor [B] of
+        sample_top_p(), handed on in the same way (then always with ``top_k``)."""
         dn = self._denoise_fn
         trunc = {} if top_k is None else {'top_k': top_k}
+        if top_p is not None:
+            trunc['top_p'] = top_p
         b, _, h, w = x_t.shape
         K = self.num_classes
         seed, state = src.seed, src.state
@@ -660,7 +732,7 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
-    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None):
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -671,7 +743,8 @@ class AbsorbingDiffusion(Sampler):
             temp, first = 'per-image', 'any-shard'
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
-                conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ())
+                conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ()) + \
+            (('top-p',) if top_p is not None else ())
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
@@ -681,9 +754,10 @@ class AbsorbingDiffusion(Sampler):
             g.target[1].zero_()
             g.target[2].zero_()
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
-                            act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk)
+                            act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk,
+                            **({} if g.topp is None else {'top_p': g.topp}))
 
-    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None):
+    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -693,15 +767,17 @@ class AbsorbingDiffusion(Sampler):
         every step's offset: the same counters), so the calls of a sharded job share it; scalar calls keep the shard in the key.
         ``target = (x0, logp, step)``: a score graph (again a key of its own) -- x0 is one more input (with ``start`` it IS the
         codes input), logp / step receive the graph's outputs.  ``top_k`` (int32 device tensor [B]; ``temp`` is then a vector too):
-        a truncating graph -- a marker in the key, the vector copied into the graph's ``topk`` buffer before each replay."""
+        a truncating graph -- a marker in the key, the vector copied into the graph's ``topk`` buffer before each replay.
+        ``top_p`` (fp32 device tensor [B]; then with ``top_k``): a nucleus graph -- one more marker, one more input (``topp``)."""
         dn = self._denoise_fn
-        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k)
+        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p)
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
             g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
-                              per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None)
+                              per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None,
+                              top_p=top_p is not None)
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -728,6 +804,8 @@ class AbsorbingDiffusion(Sampler):
             g.temps.copy_(temp)
         if g.topk is not None:
             g.topk.copy_(top_k)
+        if g.topp is not None:
+            g.topp.copy_(top_p)
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
@@ -880,11 +958,11 @@ class DummyModel(nn.Module):
 
     @torch.no_grad()
     def sample_step(self, x_t, unmasked, t, temp, u=None, q=None, seed=0, offset=0, philox_state=None, pre1=None,
-                    want_next=True, want_logits=False, top_k=None):
+                    want_next=True, want_logits=False, top_k=None, top_p=None):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation).  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation).  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -895,6 +973,8 @@ class DummyModel(nn.Module):
             a1, b1 = bn1.affine_terms()
             nxt = (conv1._spk_params.get(conv1), None if conv1.bias is None else conv1.bias.detach(), a1, b1)
         trunc = {} if top_k is None else {'top_k': top_k}
+        if top_p is not None:
+            trunc['top_p'] = top_p
         with ops.timed('den.tail'):
             return ops.den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
                                      K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,

@@ -54,7 +54,8 @@ def complete_images(model, sampler, images, keep, temp=1.0, sample_steps=None, T
     Returns a ``Completion`` of device tensors.  ``paste``: the given pixels of ``images_u8`` are the input's
     (uint8(clip(image + 0.5, 0, 1) * 255), R/main.py:401), the rest the decoder's; False: the decoder's image everywhere.
     ``temp``: a number or one temperature per image, as ``sample()`` takes it.
-    One key draw from torch's global CPU generator, as every ``sample()`` call.  Top-k truncation: ``complete_images_top_k``."""
+    One key draw from torch's global CPU generator, as every ``sample()`` call.  Top-k truncation: ``complete_images_top_k``; nucleus
+    truncation: ``complete_images_top_p``."""
     return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, None)
 
 
@@ -66,7 +67,15 @@ def complete_images_top_k(model, sampler, images, keep, top_k, temp=1.0, sample_
     return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k)
 
 
-def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k):
+@torch.no_grad()
+def complete_images_top_p(model, sampler, images, keep, top_p, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None):
+    """``complete_images`` with the unknown tokens drawn under nucleus truncation: ``top_p`` is None, a number in
+    (0, 1] or one p per image (1: that image is not truncated), as ``AbsorbingDiffusion.sample_top_p`` takes it, ``top_k`` the
+    top-k truncation that precedes it.  The known tokens are never drawn, so they come back unchanged whatever p is."""
+    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p)
+
+
+def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None):
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)
     h, w = H // 4, W // 4
@@ -75,7 +84,9 @@ def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k)
     codes = model.encode_images(images, T)
     x_init, known, n_known = ops.completion_state(codes, keep, int(sampler.num_classes), int(sampler.mask_id), ENC_STRIDE,
                                                   ENC_RADIUS, want_counts=True)
-    if top_k is None:
+    if top_p is not None:
+        tokens = sampler.sample_top_p(top_p, temp=temp, sample_steps=sample_steps, x_init=x_init, known=known, top_k=top_k)
+    elif top_k is None:
         tokens = sampler.sample(temp=temp, sample_steps=sample_steps, x_init=x_init, known=known)
     else:
         tokens = sampler.sample_top_k(top_k, temp=temp, sample_steps=sample_steps, x_init=x_init, known=known)

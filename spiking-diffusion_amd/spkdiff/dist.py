@@ -87,18 +87,23 @@ def _per_image(v):
     return isinstance(v, (list, tuple)) or (getattr(v, 'ndim', 0) == 1 and len(v) > 1)
 
 
-def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None):
+def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None, top_p=None):
     """``spkdiff.complete.complete_images`` of one job over the ranks: every rank holds the whole job's ``images`` / ``keep``,
     completes its ``shard_range`` of them as a shard of the job (``set_shard``: shared key, counters on the global image index,
     so the images do not depend on the split) and one gather returns all uint8 images [total, C, H, W] on every rank.
     ``temp``: a number, or one temperature per image of the whole job (every rank passes the whole vector; a rank uses its
     shard's slice).  ``top_k``: None, an int >= 1 or one k per image of the whole job, sliced in the same way
-    (``spkdiff.complete.complete_images_top_k``)."""
-    from .complete import complete_images, complete_images_top_k
-    per_image, per_image_k = _per_image(temp), _per_image(top_k)
+    (``spkdiff.complete.complete_images_top_k``); ``top_p``: None, a number in (0, 1] or one p per image of the
+    whole job, sliced likewise (``spkdiff.complete.complete_images_top_p``)."""
+    from .complete import complete_images, complete_images_top_k, complete_images_top_p
+    per_image, per_image_k, per_image_p = _per_image(temp), _per_image(top_k), _per_image(top_p)
 
     def generate_local(lo, hi):
         tl = temp[lo:hi] if per_image else temp
+        if top_p is not None:
+            return complete_images_top_p(model, sampler, images[lo:hi], keep[lo:hi], top_p[lo:hi] if per_image_p else top_p, temp=tl,
+                                         sample_steps=sample_steps, T=T, paste=paste,
+                                         top_k=top_k[lo:hi] if per_image_k else top_k).images_u8
         if top_k is None:
             return complete_images(model, sampler, images[lo:hi], keep[lo:hi], temp=tl, sample_steps=sample_steps, T=T,
                                    paste=paste).images_u8
@@ -107,17 +112,19 @@ def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps
     return sample_images_sharded(generate_local, int(images.shape[0]), sampler=sampler)
 
 
-def temperature_sweep_sharded(model, sampler, temps, n_per_temp, sample_steps=None, batch=256, T=16, top_k=None):
+def temperature_sweep_sharded(model, sampler, temps, n_per_temp, sample_steps=None, batch=256, T=16, top_k=None, top_p=None):
     """``spkdiff.evaluate.temperature_sweep`` of one job over the ranks: every rank runs its ``shard_range`` of the job's
     ``len(temps) * n_per_temp`` images (``temperature_sweep_range``: calls of at most ``batch`` images, one key for the whole
     job, broadcast from rank 0) and one gather returns the uint8 images [len(temps), n_per_temp, C, H, W] on every rank -- the
-    images of the one-rank sweep under the same key.  ``top_k``: None, an int or one k per temperature (``temperature_sweep_top_k``)."""
+    images of the one-rank sweep under the same key.  ``top_k``: None, an int or one k per temperature (``temperature_sweep_top_k``);
+    ``top_p``: None, a number or one p per temperature (``temperature_sweep_top_p``)."""
     from .evaluate import temperature_sweep_range
     G, n = len(temps), int(n_per_temp)
     keep = (sampler.n_samples, sampler.global_first)
 
     def generate_local(lo, hi):
-        return temperature_sweep_range(model, sampler, temps, n, lo, hi, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k)[0]
+        return temperature_sweep_range(model, sampler, temps, n, lo, hi, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k,
+                                       **({} if top_p is None else {'top_p': top_p}))[0]
     try:
         u8 = sample_images_sharded(generate_local, G * n, sampler=sampler)
     finally:

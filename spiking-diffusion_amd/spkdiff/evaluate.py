@@ -105,17 +105,41 @@ def _sweep_top_k(top_k, n_temps, n_per_temp):
     return kv.to(torch.int32).repeat_interleave(int(n_per_temp))
 
 
+def _sweep_top_p(top_p, n_temps, n_per_temp):
+    """The ``top_p`` of a sweep, per image of the job as ``_sweep_temps`` expands the temperatures: None, or fp32 [n_temps *
+    n_per_temp] on the host from a number in (0, 1] (every image) or one p per temperature (image g * n_per_temp + j has top_p[g];
+    1: that group is not truncated)."""
+    if top_p is None:
+        return None
+    bad = ValueError(f"temperature_sweep: top_p must be None, a number in (0, 1] or one per temperature ({n_temps}), got {top_p!r}")
+    if isinstance(top_p, bool):
+        raise bad
+    try:
+        pv = torch.as_tensor(top_p).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise bad from None
+    if pv.dtype in (torch.bool, torch.complex64, torch.complex128) or pv.dim() > 1:
+        raise bad
+    pv = pv.to(torch.float64)
+    pv = pv.reshape(-1).expand(n_temps) if pv.numel() == 1 else pv
+    if pv.numel() != n_temps or not bool(torch.isfinite(pv).all()) or not bool(((pv.to(torch.float32) > 0) & (pv <= 1)).all()):
+        raise bad
+    return pv.to(torch.float32).repeat_interleave(int(n_per_temp))
+
+
 @torch.no_grad()
-def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_steps=None, batch=256, T=16, top_k=None):
+def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_steps=None, batch=256, T=16, top_k=None, top_p=None):
     """Images [lo, hi) of the job ``temperature_sweep`` describes -- what one rank of ``spkdiff.dist.temperature_sweep_sharded``
     runs: (uint8 [hi - lo, C, H, W], tokens int64 [hi - lo, h, w]).  Calls of at most ``batch`` images (None: one call), each a
     shard of the job (``set_shard(first, count)``) with its slice of the per-image temperature vector, all under ONE noise key
     (``AbsorbingDiffusion._one_key``: one draw from torch's CPU generator, broadcast from rank 0 inside a process group), so the
     images depend on neither ``batch`` nor the range.  ``n_samples`` / ``global_first`` of the sampler are restored.
     ``top_k``: None, an int or one k per temperature (``temperature_sweep_top_k``); every call takes its slice of the per-image
-    vector through ``sample_top_k``."""
+    vector through ``sample_top_k``.  ``top_p``: None, a number or one p per temperature (``temperature_sweep_top_p``), sliced in
+    the same way and handed to ``sample_top_p``."""
     tv = _sweep_temps(temps, n_per_temp)
     kv = _sweep_top_k(top_k, len(temps), n_per_temp)
+    pv = _sweep_top_p(top_p, len(temps), n_per_temp)
     lo, hi = int(lo), int(hi)
     if not 0 <= lo < hi <= tv.numel():
         raise ValueError(f"temperature_sweep: the range [{lo}, {hi}) is not inside the job's {tv.numel()} images")
@@ -126,6 +150,7 @@ def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_st
         raise ValueError("temperature_sweep: batch must be >= 1 or None")
     tv = tv.to(next(model.parameters()).device)        # one copy: every call takes a slice
     kv = None if kv is None else kv.to(tv.device)
+    pv = None if pv is None else pv.to(tv.device)
     keep = (sampler.n_samples, sampler.global_first)
     images, tokens = [], []
     try:
@@ -134,7 +159,10 @@ def temperature_sweep_range(model, sampler, temps, n_per_temp, lo, hi, sample_st
             for first in range(lo, hi, step):
                 count = min(step, hi - first)
                 sampler.set_shard(first, count)
-                if kv is None:
+                if pv is not None:
+                    tok = sampler.sample_top_p(pv[first:first + count], temp=tv[first:first + count], sample_steps=sample_steps,
+                                               top_k=None if kv is None else kv[first:first + count])
+                elif kv is None:
                     tok = sampler.sample(temp=tv[first:first + count], sample_steps=sample_steps)
                 else:
                     tok = sampler.sample_top_k(kv[first:first + count], temp=tv[first:first + count], sample_steps=sample_steps)
@@ -166,6 +194,19 @@ def temperature_sweep_top_k(model, sampler, temps, n_per_temp, top_k, sample_ste
     split, and one captured graph per call size serves every temperature and every k."""
     G, n = len(temps), int(n_per_temp)
     u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k)
+    return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
+
+
+@torch.no_grad()
+def temperature_sweep_top_p(model, sampler, temps, n_per_temp, top_p, sample_steps=None, batch=256, T=16, top_k=None):
+    """``temperature_sweep`` with nucleus truncation: ``top_p`` is None (the sweep ``top_k`` describes), a number
+    in (0, 1] for every image or one p per temperature -- image (g, j) is drawn at temperature ``temps[g]`` from the likeliest
+    codes whose mass reaches ``top_p[g]`` (1: group g is not truncated), after the top-k truncation ``top_k`` asks for.  Same job,
+    same key rule, same result shapes; the images depend on neither ``batch`` nor the split, and one captured graph per call size
+    serves every temperature, every k and every p."""
+    G, n = len(temps), int(n_per_temp)
+    u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k,
+                                      top_p=top_p)
     return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
 
 

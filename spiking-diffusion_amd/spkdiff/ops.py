@@ -2034,9 +2034,31 @@ def _topk_arg(top_k, temp, B, what, device):
     return top_k, temp_b if temp_b is not None else torch.full((B,), temp, dtype=torch.float32, device=device)
 
 
-def _launch_by_temp(name, temp_b, temp, head, tail, top_k=None):
+def _topp_arg(top_p, top_k, temp, B, what, device):
+    """``top_p`` of a token update: None -- the call as it was, (None, top_k, temp) -- or a contiguous fp32 device
+    tensor [B], one p per image of the call (index = image, also inside an ``active_set`` scope; a p outside (0, 1): that image is
+    not nucleus-truncated), taken as given: returns (top_p, top_k, temp).  The ``_topp`` entry points take all three per image: a
+    missing ``top_k`` becomes zeros (no top-k truncation), and a scalar ``temp`` is broadcast by ``_topk_arg``."""
+    if top_p is None:
+        return None, top_k, temp
+    B = int(B)
+    if (not isinstance(top_p, torch.Tensor) or top_p.dtype != torch.float32 or not top_p.is_cuda or not top_p.is_contiguous() or
+            top_p.dim() != 1 or top_p.numel() != B):
+        got = f"{top_p.dtype} {tuple(top_p.shape)} on '{top_p.device}'" if isinstance(top_p, torch.Tensor) else repr(type(top_p))
+        raise ValueError(f"{what}: top_p must be a contiguous fp32 device tensor of B = {B} entries, got {got}")
+    if top_k is None:
+        top_k = torch.zeros(B, dtype=torch.int32, device=device)
+    return top_p, top_k, temp
+
+
+def _launch_by_temp(name, temp_b, temp, head, tail, top_k=None, top_p=None):
     """Launch ``name(*head, temp, *tail)`` or, ``temp_b`` given, its ``_temps`` sibling with the vector (looked up per call);
-    ``top_k`` given (then with ``temp_b``): its ``_topk`` sibling with both vectors."""
+    ``top_k`` given (then with ``temp_b``): its ``_topk`` sibling with both vectors; ``top_p`` given (then with both): its
+    ``_topp`` sibling with the three."""
+    if top_p is not None:
+        name = name + "_topp"
+        check(getattr(lib, name)(*head, _p(temp_b), _p(top_k), _p(top_p), *tail), name)
+        return
     if top_k is not None:
         name = name + "_topk"
         check(getattr(lib, name)(*head, _p(temp_b), _p(top_k), *tail), name)
@@ -2047,15 +2069,18 @@ def _launch_by_temp(name, temp_b, temp, head, tail, top_k=None):
 
 
 def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, philox_state=None,
-                 next_input=None, top_k=None):
+                 next_input=None, top_k=None, top_p=None):
     """In-place update of x_t (int64) and unmasked (bool/u8) from logits [B,K,h,w].  next_input (dense form only): fp32
     [B,2,h,w] that receives the denoiser input of the next reverse step, cat(x_t, t - 1).  ``temp``: a number, or a contiguous
     fp32 device tensor with one temperature per image (spk_psample_step_temps).  ``top_k``: int32 device tensor with one k per
-    image -- every drawn token comes from its position's k likeliest classes (spk_psample_step_topk; 0: not truncated)."""
+    image -- every drawn token comes from its position's k likeliest classes (spk_psample_step_topk; 0: not truncated).
+    ``top_p``: fp32 device tensor with one p per image -- nucleus truncation after the top-k one (spk_psample_step_topp; a p
+    outside (0, 1): none); a scalar ``temp`` is then broadcast and a missing ``top_k`` becomes zeros."""
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
     n = B * HW
+    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, x_t.numel() // HW, "psample_step", logits.device)
     top_k, temp = _topk_arg(top_k, temp, x_t.numel() // HW, "psample_step", logits.device)
     temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, x_t.numel() // HW, "psample_step")
     _token_state(x_t, unmasked, n, "(updated in place)")
@@ -2064,7 +2089,7 @@ def psample_step(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, off
     next_input = _next_input_arg(next_input, n)
     _launch_by_temp("spk_psample_step", temp_b, temp, (_p(logits), _p(x_t), _p(unmasked), int(t)),
                     (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(x0_hat), B, HW, K, _p(act), _p(nact), _p(next_input),
-                     _stream(logits)), top_k=top_k)
+                     _stream(logits)), top_k=top_k, top_p=top_p)
     return x_t, unmasked
 
 
@@ -2098,18 +2123,20 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
 
 
 def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
-                  conv1=None, want_logits=False, top_k=None):
+                  conv1=None, want_logits=False, top_k=None, top_p=None):
     """The tail of one dense reverse step as one launch (spk_den_step_tail): conv6 on the spike counts + time mean, the token
     update of ``psample_step`` (x_t / unmasked in place, same noise arguments) and -- with ``conv1 = (w_packed [9,2,64], bias,
     bn_a, bn_b)`` -- the first denoiser layer of the next step.  Returns (x1 S32 [B,2,h,w,16,16], cnt1 u8 [B,2,h,w,32]) or None,
     and the logits fp32 [B,K,h,w] when asked for.  Inside an ``active_set`` scope (the untouched-image elimination) cnt5 / cnt1 / logits
     are per SLOT of the active list and x_t / unmasked / the noise per image; ``conv1`` must be None there (the next step's first layer
     belongs to the next step's active set).  ``temp``: a number or a per-image fp32 device tensor (spk_den_step_tail_temps);
-    ``top_k``: int32 device tensor, one k per image, as for psample_step (spk_den_step_tail_topk)."""
+    ``top_k``: int32 device tensor, one k per image, as for psample_step (spk_den_step_tail_topk); ``top_p``: fp32 device tensor,
+    one p per image, as for psample_step (spk_den_step_tail_topp)."""
     cnt5 = _dev(cnt5, "cnt5", torch.uint8)
     cnt1 = _dev(cnt1, "cnt1", torch.uint8)
     B, nch5, H, W, _ = cnt5.shape
     n = B * H * W
+    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, x_t.numel() // (H * W), "den_step_tail", cnt5.device)
     top_k, temp = _topk_arg(top_k, temp, x_t.numel() // (H * W), "den_step_tail", cnt5.device)
     temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
     wq, scale, bias_d = packed6
@@ -2130,7 +2157,7 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     _launch_by_temp("spk_den_step_tail", temp_b, temp, (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale),
                                                         _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t)),
                     (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T),
-                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)), top_k=top_k)
+                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)), top_k=top_k, top_p=top_p)
     return (None if x1 is None else (x1, c1o)), logits
 
 
