@@ -10,13 +10,19 @@ could not tell from its own: each saved activation is recomputed in fp64 from th
 the counted forward bound of an fp32 dot product, a mask may differ from ``preact64 > 0`` only where |preact64| is within that
 bound, and an index must satisfy F20's tau rule.
 """
+import functools
+import os
+import re
+
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 import _ann_vqvae_oracle as orc
 import _conv_train_cases as ctc
-from spkdiff import synth
+from spkdiff import _lib, synth
+
+SRC = os.path.join(os.path.dirname(ctc.SRC), "ann_vqvae_train.hip")
 
 EPS = 2.0 ** -24                  # unit round-off of fp32
 D = 16                            # embedding_dim of every case (SPK_ANN_VQVAE_D)
@@ -170,8 +176,38 @@ BIG_LAYERS = tuple((name, layer, op, epi) for name, layer, op, epi in vqvae_laye
                    if name in ("enc2.fwd", "dec0.fwd", "dec2.dgrad"))
 
 
+def second_trip(L):
+    """Whether a launch of ctc.gather_launch walks its loop a second time: a workgroup of the few-channel kernels takes a second
+    row (rows > CT_C1_ROWS_CAP), a wave of the main gather kernel a second item (passes >= 2)."""
+    return L["rows"] > L["grid"] if L["kernel"] in ("c1in", "c1out") else L["passes"] >= 2
+
+
+def second_trip_threshold(layer, op):
+    """Smallest N at which the gather launch of (layer, op) takes a second trip."""
+    n = 1
+    while not second_trip(ctc.gather_launch(*ctc.gather_args(layer, n, op))):
+        n += 1
+    return n
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_cases():
+    """[(id, layer, N, op, epilogue)]: the smallest N with a second trip of each of the eight epilogue launches at H = 28 (grey)
+    and of the RGB few-channel pair at H = 32."""
+    out = []
+    for name, layer, op, epi in vqvae_layers(1, 28):
+        n = second_trip_threshold(layer, op)
+        out.append((f"{name}-H28-second_trip-N{n}", layer, n, op, epi))
+    for name, layer, op, epi in vqvae_layers(3, 32):
+        if name in ("enc0.fwd", "dec4.dgrad"):
+            n = second_trip_threshold(layer, op)
+            out.append((f"{name}-H32-second_trip-N{n}", layer, n, op, epi))
+    return tuple(out)
+
+
 def epilogue_cases():
-    """[(id, layer, N, op, epilogue)]: every layer at H = 28 (grey) and 32 (RGB), N = 1 and 3, and the CT_BIG_ITEMS pairs."""
+    """[(id, layer, N, op, epilogue)]: every layer at H = 28 (grey) and 32 (RGB), N = 1 and 3, the CT_BIG_ITEMS pairs, and the
+    second-trip cases."""
     out = []
     for C, H in ((1, 28), (3, 32)):
         for name, layer, op, epi in vqvae_layers(C, H):
@@ -180,12 +216,153 @@ def epilogue_cases():
     for name, layer, op, epi in BIG_LAYERS:
         n = big_threshold(layer, op)
         out += [(f"{name}-below_big-N{n - 1}", layer, n - 1, op, epi), (f"{name}-at_big-N{n}", layer, n, op, epi)]
-    return out
+    return out + list(second_trip_cases())
+
+
+# ---- the launch arithmetic of the quantiser and loss entry points (csrc/ann_vqvae_train.hip), mirrored on the host ---------------
+# The caps are read from the source and the chunk from the header, so a retuned cap moves the cases below with it; every case
+# carries the side of the cap it claims, and tests/test_ann_vqvae_train_host.py checks the claim on a machine without a GPU.
+def _cap(name):
+    m = re.search(r"\b" + name + r"\s*=\s*(\d+)\s*[,;]", open(SRC).read())
+    assert m, f"{name} not found in {SRC}"
+    return int(m.group(1))
+
+
+AT_VQ_GRID, AT_EW_GRID, AT_LOSS_GRID = _cap("AT_VQ_GRID"), _cap("AT_EW_GRID"), _cap("AT_LOSS_GRID")
+CHUNK = _lib.CONSTANTS["SPK_ANN_VQVAE_TRAIN_CHUNK"]
+MAX_D = _lib.CONSTANTS["SPK_VQ_TRAIN_MAX_D"]
+VQ_WAVES = 4                      # rows a workgroup of ann_vq_fwd_kernel takes per trip (a wave each)
+SCAN = 256                        # rows the per-code workgroups of ann_vq_bwd_kernel scan at a time
+SMALL_N = 33 * 64                 # the largest row count of the one-trip cases: the prefix the row-independence checks repeat
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _ew_grid(elems):
+    """spk_grid(elems, AT_EW_GRID): one thread per element, 256 to a workgroup, capped."""
+    return max(1, min(_cdiv(elems, 256), AT_EW_GRID))
+
+
+def ws_doubles(rows, elems):
+    """spk_ann_vqvae_train_ws_bytes / 8: a partial per row or per chunk, whichever is more (at least one)."""
+    return max(rows, _cdiv(elems, CHUNK), 1)
+
+
+def vq_fwd_launch(N, D, K):
+    grid = min(_cdiv(N, VQ_WAVES), AT_VQ_GRID)
+    return dict(kernel="vq_fwd<16>" if D == 16 else "vq_fwd<0>", grid=grid, second_trip=N > grid * VQ_WAVES, partials=N, nb_x=0,
+                last_trip_rows=N % (grid * VQ_WAVES), ws_doubles=ws_doubles(N, 0))
+
+
+def vq_bwd_launch(N, D, K):
+    nb_x = _ew_grid(N * D)
+    return dict(kernel="vq_bwd", grid=nb_x + K, second_trip=N * D > nb_x * 256, partials=0, nb_x=nb_x,
+                last_trip_elems=(N * D) % (nb_x * 256), scans=_cdiv(N, SCAN), last_scan_rows=N % SCAN, RL=256 // D)
+
+
+def loss_fwd_launch(B, C, H):
+    n = B * C * H * H
+    chunks = _cdiv(n, CHUNK)
+    grid = min(chunks, AT_LOSS_GRID)
+    return dict(kernel="loss_fwd", n=n, grid=grid, second_trip=chunks > grid, partials=chunks, nb_x=0, last_chunk_elems=n % CHUNK,
+                last_trip_chunks=chunks % grid, ws_doubles=ws_doubles(0, n))
+
+
+def loss_bwd_launch(B, C, H):
+    n = B * C * H * H
+    nb_x = _ew_grid(n)
+    return dict(kernel="loss_bwd", n=n, grid=nb_x, second_trip=n > nb_x * 256, partials=0, nb_x=nb_x,
+                last_trip_elems=n % (nb_x * 256), last_block_elems=n % 256)
+
+
+def _first(pred, start=1):
+    n = start
+    while not pred(n):
+        n += 1
+    return n
+
+
+# The quantiser cases: (kind, N, D, K, claim, why).  Each past-the-cap size is the smallest with a second trip plus a ragged
+# remainder (the forward's second trip is 37 rows: nine whole workgroups and one wave of a tenth, and a partial 256-row scan of
+# the backward; the backward's is 19 rows: one partial workgroup at D = 16, five at D = 64).
+FWD_RAGGED, BWD_RAGGED = 36, 18
+N_PAST_FWD = {D: _first(lambda n, D=D: vq_fwd_launch(n, D, 1)["second_trip"]) + FWD_RAGGED for D in (16, 24)}
+N_PAST_BWD = {D: _first(lambda n, D=D: vq_bwd_launch(n, D, 1)["second_trip"], (AT_EW_GRID * 256) // D - 2) + BWD_RAGGED
+              for D in (16, 64)}
+
+
+def _past_fwd(N, D, K):
+    f, b = vq_fwd_launch(N, D, K), vq_bwd_launch(N, D, K)
+    return (f["second_trip"] and f["grid"] == AT_VQ_GRID and 0 < f["last_trip_rows"] < f["grid"] * VQ_WAVES
+            and f["last_trip_rows"] % VQ_WAVES != 0 and b["last_scan_rows"] != 0 and N > SMALL_N)
+
+
+def _past_bwd(N, D, K):
+    b = vq_bwd_launch(N, D, K)
+    return (b["second_trip"] and b["nb_x"] == AT_EW_GRID and 0 < b["last_trip_elems"] < b["nb_x"] * 256
+            and b["last_trip_elems"] % 256 != 0 and b["last_scan_rows"] != 0 and b["scans"] >= 2 and N > SMALL_N)
+
+
+def _one_trip(N, D, K):
+    f, b = vq_fwd_launch(N, D, K), vq_bwd_launch(N, D, K)
+    return not f["second_trip"] and not b["second_trip"] and b["nb_x"] < AT_EW_GRID
+
+
+def _dc0(claim):
+    return lambda N, D, K: D != 16 and 1 <= D <= MAX_D and vq_fwd_launch(N, D, K)["kernel"] == "vq_fwd<0>" and claim(N, D, K)
+
+
+DC0_D, DC0_K, DC0_N = (1, 3, 8, 24, 33, 64), (1, 63, 65, 244), (3 * 49, SMALL_N)
+VQ_CASES = (
+    [(kind, N, D, K, _one_trip, "one trip of every loop") for kind, N, K in
+     (("random", 49, 100), ("random", 3 * 49, 128), ("random", SMALL_N, 256), ("one_code", 3 * 49, 128), ("few_codes", SMALL_N, 256))]
+    + [(kind, N_PAST_FWD[16], 16, 128, _past_fwd, "ann_vq_fwd_kernel<16>: some waves walk a second row") for kind in ("random", "few_codes")]
+    + [("random", N_PAST_BWD[16], 16, 100, _past_bwd, "ann_vq_bwd_kernel: the element-wise blocks walk a second element (and the forward "
+        "a third row)"),
+       ("random", N_PAST_BWD[64], 64, 64, _dc0(_past_bwd), "the same with a row per wave-width: D = 64"),
+       ("random", N_PAST_FWD[24], 24, 65, _dc0(_past_fwd), "ann_vq_fwd_kernel<0> past the forward's cap")]
+    + [("random", N, D, K, _dc0(_one_trip), "the DC == 0 form") for D in DC0_D for K in DC0_K for N in DC0_N]
+)
+
+
+def vq_case_id(c):
+    return f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" if c[2] != D else f"{c[0]}-{c[1]}-{c[3]}"
+
+
+# The loss cases: (B, C, H, claim).  Forward: the smallest B with more chunks than AT_LOSS_GRID and a partial last chunk.
+# Backward: the smallest B with more than 256 AT_EW_GRID elements and a second trip that covers part of the grid (a CIFAR image
+# is twelve whole workgroups, so there the ragged end is a partial trip; at 28 x 28 the last workgroup is partial as well).
+def _loss_one_trip(B, C, H):
+    return not loss_fwd_launch(B, C, H)["second_trip"] and not loss_bwd_launch(B, C, H)["second_trip"]
+
+
+def _loss_past_fwd(B, C, H):
+    f = loss_fwd_launch(B, C, H)
+    return (f["second_trip"] and f["grid"] == AT_LOSS_GRID and f["last_chunk_elems"] != 0 and f["last_trip_chunks"] != 0
+            and loss_bwd_launch(B, C, H)["second_trip"])
+
+
+def _loss_past_bwd(B, C, H):
+    b = loss_bwd_launch(B, C, H)
+    return (b["second_trip"] and b["grid"] == AT_EW_GRID and 0 < b["last_trip_elems"] < b["grid"] * 256
+            and (b["last_block_elems"] != 0 or (C * H * H) % 256 == 0) and not loss_bwd_launch(B - 1, C, H)["second_trip"])
+
+
+LOSS_CASES = (
+    [(B, C, H, _loss_one_trip) for B, C, H in ((1, 1, 28), (3, 3, 32), (33, 1, 28), (5, 3, 28))]
+    + [(_first(lambda b: loss_bwd_launch(b, C, H)["second_trip"]), C, H, _loss_past_bwd) for C, H in ((1, 28), (3, 32))]
+    + [(_first(lambda b: loss_fwd_launch(b, C, H)["second_trip"] and loss_fwd_launch(b, C, H)["last_chunk_elems"] != 0), C, H,
+        _loss_past_fwd) for C, H in ((3, 32), (1, 28))]
+)
 
 
 # ---- the model cases: (id, shape name of _ann_vqvae_oracle.SHAPES, B); "f20" = the fixture's images and state -------------------
 MODEL_CASES = (("f20", "mnist_k128", 8), ("mnist_k128-B1", "mnist_k128", 1), ("mnist_k128-B3", "mnist_k128", 3),
-               ("mnist_k128-B33", "mnist_k128", 33), ("cifar_k256-B3", "cifar_k256", 3), ("mnist_k100-B3", "mnist_k100", 3))
+               ("mnist_k128-B33", "mnist_k128", 33), ("cifar_k256-B3", "cifar_k256", 3), ("mnist_k100-B3", "mnist_k100", 3),
+               # past the quantiser's forward cap (8232 and 8320 rows) and the read-out kernels' row cap (4704 and 4160 rows)
+               ("mnist_k128-B168", "mnist_k128", 168), ("cifar_k256-B130", "cifar_k256", 130))
 
 
 def model_inputs(case):

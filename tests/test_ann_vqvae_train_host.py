@@ -1,6 +1,8 @@
 """CPU tests of the plain-CNN VQVAE baseline's training step on HIP (no GPU): the fp64 oracle of the GPU tests
 meets fixture F20 when it is given the module path's decisions, the new entry points are declared, bound and exported and
-refuse bad arguments before they touch a device, the epilogue case table lands on the launch forms it claims, and on the CPU
+refuse bad arguments before they touch a device, the epilogue case table lands on the launch forms it claims, every
+past-the-cap case of the quantiser, loss and epilogue tables really is past its cap with a ragged remainder (the launch
+arithmetic restated on the host, the caps read from the sources), the workspace size is the launch model's, and on the CPU
 VQVAE.train() still takes the module path."""
 import numpy as np
 import pytest
@@ -184,6 +186,100 @@ def test_epilogue_cases_land_on_the_launch_forms_they_claim():
         for name, layer, op, _ in tor.vqvae_layers(C, H):
             L = ctc.gather_launch(*ctc.gather_args(layer, 32, op))
             assert L["kernel"] == "c1in" or L["CN"] == 1 or L["CNT"] == 1, name
+
+
+def test_second_trip_epilogue_cases_take_a_second_trip():
+    """The smallest N at which each epilogue launch walks its loop again: a second row per workgroup in the few-channel kernels
+    (rows > CT_C1_ROWS_CAP), a second item per wave in the main gather kernel (passes >= 2) -- and one image fewer does not."""
+    cases = tor.second_trip_cases()
+    ids = [c[0] for c in tor.epilogue_cases()]
+    names = [n for n, *_ in tor.vqvae_layers(1, 28)]
+    assert [c[0].split("-")[0] for c in cases] == names + ["enc0.fwd", "dec4.dgrad"] and len(names) == 8
+    seen = set()
+    for cid, layer, N, op, epi in cases:
+        assert cid in ids, cid
+        at, below = (ctc.gather_launch(*ctc.gather_args(layer, n, op)) for n in (N, N - 1))
+        print(f"{cid}: {at}")
+        assert tor.second_trip(at) and not tor.second_trip(below), cid
+        if at["kernel"] == "c1in":
+            assert ctc.CT_C1_ROWS_CAP < at["rows"] < 2 * ctc.CT_C1_ROWS_CAP and at["grid"] == ctc.CT_C1_ROWS_CAP, cid
+        else:
+            assert at["kernel"] == "gather" and at["passes"] == 2 and at["gx"] * 8 < at["items"] < at["gx"] * 16, cid
+        seen.add((at["kernel"], epi))
+    assert seen == {("gather", "relu"), ("gather", "masked"), ("c1in", "relu"), ("c1in", "masked")}
+    dec4 = next(c for c in cases if c[0].startswith("dec4.dgrad-H28"))
+    assert dec4[2] == ctc.CT_C1_ROWS_CAP // 28 + 1                  # (147 at a cap of 4096 rows)
+
+
+def test_quantiser_and_loss_cases_sit_past_the_caps_they_claim():
+    """The launch arithmetic of csrc/ann_vqvae_train.hip on the host (the caps read from the source): every case lands on the side
+    of its cap it claims -- past it with a ragged remainder, or within one trip -- so a retuned cap cannot leave the GPU tests
+    below it unnoticed."""
+    assert (tor.AT_VQ_GRID, tor.AT_EW_GRID, tor.AT_LOSS_GRID) == (2048, 1024, 1024) and tor.CHUNK == 2048     # today's values
+    ids = [tor.vq_case_id(c) for c in tor.VQ_CASES]
+    assert len(set(ids)) == len(ids)
+    for kind, N, D, K, claim, why in tor.VQ_CASES:
+        f, b = tor.vq_fwd_launch(N, D, K), tor.vq_bwd_launch(N, D, K)
+        assert claim(N, D, K), (kind, N, D, K, why, f, b)
+        assert f["partials"] == N and f["grid"] <= tor.AT_VQ_GRID and b["grid"] == b["nb_x"] + K and b["nb_x"] <= tor.AT_EW_GRID
+    by = {(N, D, K): (tor.vq_fwd_launch(N, D, K), tor.vq_bwd_launch(N, D, K)) for _, N, D, K, *_ in tor.VQ_CASES}
+    # the sizes the cases were derived to be
+    f, b = by[(4 * tor.AT_VQ_GRID + 37, 16, 128)]
+    assert f["second_trip"] and f["last_trip_rows"] == 37 and not b["second_trip"] and b["last_scan_rows"] != 0
+    f, b = by[(256 * tor.AT_EW_GRID // 16 + 19, 16, 100)]
+    assert b["second_trip"] and b["last_trip_elems"] == 19 * 16 and b["last_scan_rows"] == 19 and f["second_trip"]
+    f, b = by[(256 * tor.AT_EW_GRID // 64 + 19, 64, 64)]
+    assert b["second_trip"] and b["last_trip_elems"] == 19 * 64 and b["last_scan_rows"] == 19 and b["RL"] == 4 and not f["second_trip"]
+    f, b = by[(4 * tor.AT_VQ_GRID + 37, 24, 65)]
+    assert f["kernel"] == "vq_fwd<0>" and f["second_trip"] and b["RL"] == 10 and 256 % 24
+    # at the cap itself nothing walks twice: the cases are the first sizes that do, plus their remainders
+    assert not tor.vq_fwd_launch(4 * tor.AT_VQ_GRID, 16, 128)["second_trip"]
+    assert not tor.vq_bwd_launch(256 * tor.AT_EW_GRID // 16, 16, 100)["second_trip"]
+    # every width and codebook size of the DC == 0 form, at both row counts, and the LDS ceiling of D = 64
+    from spkdiff import _lib
+    L = _lib.lib
+    for D in tor.DC0_D:
+        for K in tor.DC0_K:
+            for N in tor.DC0_N:
+                assert (N, D, K) in by and L.spk_ann_vqvae_train_supported(D, K), (N, D, K)
+    assert tor.DC0_D == (1, 3, 8, 24, 33, 64) and tor.DC0_K == (1, 63, 65, 244) and tor.DC0_N == (147, 2112)
+    assert not L.spk_ann_vqvae_train_supported(64, 245)
+    for B, C, H, claim in tor.LOSS_CASES:
+        assert claim(B, C, H), (B, C, H, tor.loss_fwd_launch(B, C, H), tor.loss_bwd_launch(B, C, H))
+    shapes = [c[:3] for c in tor.LOSS_CASES]
+    assert len(set(shapes)) == len(shapes)
+    past_fwd = [c[:3] for c in tor.LOSS_CASES if c[3] is tor._loss_past_fwd]
+    past_bwd = [c[:3] for c in tor.LOSS_CASES if c[3] is tor._loss_past_bwd]
+    assert past_fwd == [(683, 3, 32), (2675, 1, 28)] and past_bwd == [(335, 1, 28), (86, 3, 32)]           # at today's caps
+    for B, C, H in past_fwd:
+        f = tor.loss_fwd_launch(B, C, H)
+        assert f["partials"] == tor.AT_LOSS_GRID + 1 and 0 < f["last_chunk_elems"] < tor.CHUNK
+    assert tor.loss_bwd_launch(335, 1, 28)["last_block_elems"] != 0
+
+
+def test_ws_bytes_is_what_the_launch_model_says():
+    """spk_ann_vqvae_train_ws_bytes is max(rows, chunks) doubles, exactly: the GPU tests hand the kernels that many and guard the
+    bytes behind them."""
+    from spkdiff import _lib
+    L = _lib.lib
+    for _, N, D, K, *_ in tor.VQ_CASES:
+        assert L.spk_ann_vqvae_train_ws_bytes(N, 0) == 8 * tor.vq_fwd_launch(N, D, K)["ws_doubles"] == 8 * N
+    for B, C, H, _ in tor.LOSS_CASES:
+        f = tor.loss_fwd_launch(B, C, H)
+        assert L.spk_ann_vqvae_train_ws_bytes(0, f["n"]) == 8 * f["ws_doubles"] == 8 * f["partials"]
+    for rows, elems in ((0, 0), (1, 0), (0, 1), (0, tor.CHUNK), (0, tor.CHUNK + 1), (49, 784), (1, 4097), (8232, 168 * 784),
+                        (8320, 130 * 3072), (3, 1 << 33), ((1 << 31) - 1, 5)):
+        want = max(rows, -(-elems // tor.CHUNK), 1)
+        assert tor.ws_doubles(rows, elems) == want and L.spk_ann_vqvae_train_ws_bytes(rows, elems) == 8 * want, (rows, elems)
+    # the two model cases past the caps: the quantiser's rows outnumber the loss's chunks, and both loops walk twice
+    for case, rows, readout_rows in (("mnist_k128-B168", 8232, 4704), ("cifar_k256-B130", 8320, 4160)):
+        cid, shape, B = next(c for c in tor.MODEL_CASES if c[0] == case)
+        _, cfg, K = next(s for s in orc.SHAPES if s[0] == shape)
+        assert B * (cfg.img // 4) ** 2 == rows and B * cfg.img == readout_rows > ctc.CT_C1_ROWS_CAP
+        assert tor.vq_fwd_launch(rows, tor.D, K)["second_trip"]
+        for name, layer, op, _ in tor.vqvae_layers(cfg.in_dim, cfg.img):
+            if name == "dec4.dgrad":
+                assert tor.second_trip(ctc.gather_launch(*ctc.gather_args(layer, B, op)))
 
 
 def test_vqvae_train_on_the_cpu_still_takes_the_module_path(monkeypatch):

@@ -1,7 +1,10 @@
 """GPU tests of the plain-CNN VQVAE baseline's training step on HIP (run with ``-m gpu`` on an MI355X): the two
 fused epilogues of csrc/conv_train.hip bit for bit against the plain gather launch, the quantiser and loss kernels of
 csrc/ann_vqvae_train.hip against fp64 given the indices, the model's iteration against the fp64 oracle given the kernel's
-decisions (tests/_ann_vqvae_train_oracle.py), the dispatch, the captured step and the loop of R/main.py:130-142."""
+decisions (tests/_ann_vqvae_train_oracle.py), the dispatch, the captured step and the loop of R/main.py:130-142.  Every
+grid-stride loop of those kernels also runs past its first trip (the case tables derive the sizes from the caps in the sources;
+tests/test_ann_vqvae_train_host.py checks that they are past them), the quantiser in its DC == 0 form at D != 16, and its own
+arg min on ties, NaN and inf."""
 import numpy as np
 import pytest
 import torch
@@ -12,13 +15,16 @@ pytestmark = pytest.mark.gpu
 import _ann_vqvae_oracle as orc             # noqa: E402
 import _ann_vqvae_train_oracle as tor       # noqa: E402
 import _conv_train_cases as ctc             # noqa: E402
+from oracle import snn_ref                  # noqa: E402
 from parity_report import record as parity  # noqa: E402
 from spkdiff import synth                  # noqa: E402
 
 NEW_ENTRY_POINTS = ("spk_conv_train_gather_relu", "spk_conv_train_gather_masked", "spk_ann_vqvae_train_vq_fwd",
                     "spk_ann_vqvae_train_vq_bwd", "spk_ann_vqvae_train_loss_fwd", "spk_ann_vqvae_train_loss_bwd")
 POISON = 12345.0
+SENTINEL = -7.5                             # what the guard bands around a workspace hold
 GUARD = 4096
+NAN, INF = float("nan"), float("inf")
 
 
 @pytest.fixture(scope="module")
@@ -82,60 +88,111 @@ def test_epilogue_equals_the_plain_launch_bit_for_bit(dev, cid, layer, N, op, ep
 
 
 # ------------------------------------------------------------------------------------------------ 2. quantiser and loss kernels
-def _vq_case(kind, N, K, g):
-    cb = torch.randn(K, tor.D, generator=g)
+def _vq_case(kind, N, K, g, D=tor.D):
+    cb = torch.randn(K, D, generator=g)
     if kind == "one_code":                                          # one code owns every row
-        z = cb[5] + 0.01 * torch.randn(N, tor.D, generator=g)
+        z = cb[5] + 0.01 * torch.randn(N, D, generator=g)
     elif kind == "few_codes":                                       # most codes unused
-        z = cb[torch.randint(0, 3, (N,), generator=g) * 7] + 0.01 * torch.randn(N, tor.D, generator=g)
+        z = cb[torch.randint(0, 3, (N,), generator=g) * 7] + 0.01 * torch.randn(N, D, generator=g)
     else:
-        z = torch.randn(N, tor.D, generator=g)
+        z = torch.randn(N, D, generator=g)
     return z, cb
 
 
-VQ_CASES = [("random", 49, 100), ("random", 3 * 49, 128), ("random", 33 * 64, 256), ("one_code", 3 * 49, 128),
-            ("few_codes", 33 * 64, 256)]
+def _guarded(dev, n, dtype=torch.float32, fill=POISON):
+    """(buffer, its n middle elements): GUARD elements of ``fill`` on either side of what a kernel is handed."""
+    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=dev)
+    return buf, buf[GUARD:GUARD + n]
 
 
-@pytest.mark.parametrize("kind,N,K", VQ_CASES)
-def test_vq_kernels_meet_fp64_given_the_indices(dev, kind, N, K):
+def _intact(buf, n, fill=POISON):
+    return bool((buf[:GUARD] == fill).all()) and bool((buf[GUARD + n:] == fill).all())
+
+
+def _same_bits(a, b):
+    """Equal bit for bit, except that any NaN equals any NaN (the payload a NaN carries is not part of the contract)."""
+    a, b = a.reshape(-1), b.reshape(-1)
+    na, nb = torch.isnan(a), torch.isnan(b)
+    return torch.equal(na, nb) and torch.equal(_bits(a[~na]), _bits(b[~nb]))
+
+
+def _vq_fwd(dev, zd, cbd, beta):
+    """spk_ann_vqvae_train_vq_fwd on poisoned, guarded outputs and a workspace of exactly the bytes the library asks for, itself
+    between guard bands -> (idx, e, loss)."""
     from spkdiff import ops
     L = ops.lib
-    g = torch.Generator().manual_seed(N + K)
-    z, cb = _vq_case(kind, N, K, g)
-    g_e = torch.randn(N, tor.D, generator=g)
+    (N, D), K = zd.shape, cbd.shape[0]
+    nb = int(L.spk_ann_vqvae_train_ws_bytes(N, 0))
+    assert nb == 8 * tor.vq_fwd_launch(N, D, K)["ws_doubles"]
+    ibuf, idx = _guarded(dev, N, torch.int64, -1)
+    ebuf, e = _guarded(dev, N * D)
+    loss = torch.full((1,), POISON, device=dev)
+    wbuf, ws = _guarded(dev, nb // 8, torch.float64, SENTINEL)
+    ws.fill_(NAN)                                                   # scratch: nothing is expected of its contents
+    assert L.spk_ann_vqvae_train_vq_fwd(zd.data_ptr(), cbd.data_ptr(), idx.data_ptr(), e.data_ptr(), loss.data_ptr(), beta,
+                                        ws.data_ptr(), nb, N, D, K, torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert _intact(wbuf, nb // 8, SENTINEL), "the forward wrote outside the workspace it asked for"
+    assert _intact(ibuf, N, -1) and _intact(ebuf, N * D), "the forward wrote outside idx or e"
+    assert bool(((idx >= 0) & (idx < K)).all()), "an index is unwritten or outside [0, K)"
+    assert not bool((e == POISON).any()) and not bool((loss == POISON).any()), "the forward left an output unwritten"
+    return idx.clone(), e.clone().view(N, D), loss
+
+
+def _vq_bwd(dev, ged, gl, zd, idx, cbd, beta):
+    """spk_ann_vqvae_train_vq_bwd on poisoned, guarded outputs -> (gz, gcodebook); ged and gl may be None."""
+    from spkdiff import ops
+    (N, D), K = zd.shape, cbd.shape[0]
+    zbuf, gz = _guarded(dev, N * D)
+    cbuf, gcb = _guarded(dev, K * D)
+    assert ops.lib.spk_ann_vqvae_train_vq_bwd(None if ged is None else ged.data_ptr(), None if gl is None else gl.data_ptr(),
+                                              zd.data_ptr(), idx.data_ptr(), cbd.data_ptr(), beta, gz.data_ptr(), gcb.data_ptr(),
+                                              N, D, K, torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert _intact(zbuf, N * D) and _intact(cbuf, K * D), "the backward wrote outside its gradients"
+    assert not bool((gz == POISON).any()) and not bool((gcb == POISON).any()), "the backward left a gradient element unwritten"
+    return gz.clone().view(N, D), gcb.clone().view(K, D)
+
+
+@pytest.mark.parametrize("kind,N,D,K", [c[:4] for c in tor.VQ_CASES], ids=[tor.vq_case_id(c) for c in tor.VQ_CASES])
+def test_vq_kernels_meet_fp64_given_the_indices(dev, kind, N, D, K):
+    from spkdiff import ops
+    L = ops.lib
+    assert L.spk_ann_vqvae_train_supported(D, K)
+    g = torch.Generator().manual_seed(N + K + (0 if D == tor.D else 1000 * D))
+    z, cb = _vq_case(kind, N, K, g, D)
+    g_e = torch.randn(N, D, generator=g)
     beta, g_loss = 0.25, 0.75
     zd, cbd, ged = z.to(dev), cb.to(dev), g_e.to(dev)
     gl = torch.tensor([g_loss], device=dev)
-    st = torch.cuda.current_stream().cuda_stream
-    nb = int(L.spk_ann_vqvae_train_ws_bytes(N, 0))
 
     def run():
-        idx = torch.full((N,), -1, dtype=torch.int64, device=dev)
-        e = torch.full((N, tor.D), POISON, device=dev)
-        loss = torch.full((1,), POISON, device=dev)
-        ws = torch.full((nb // 8,), float("nan"), dtype=torch.float64, device=dev)      # scratch: nothing is expected of its contents
-        assert L.spk_ann_vqvae_train_vq_fwd(zd.data_ptr(), cbd.data_ptr(), idx.data_ptr(), e.data_ptr(), loss.data_ptr(), beta,
-                                            ws.data_ptr(), nb, N, tor.D, K, st) == 0
-        gz = torch.full((N, tor.D), POISON, device=dev)
-        gcb = torch.full((K, tor.D), POISON, device=dev)
-        assert L.spk_ann_vqvae_train_vq_bwd(ged.data_ptr(), gl.data_ptr(), zd.data_ptr(), idx.data_ptr(), cbd.data_ptr(), beta,
-                                            gz.data_ptr(), gcb.data_ptr(), N, tor.D, K, st) == 0
-        torch.cuda.synchronize()
-        return idx, e, loss, gz, gcb
+        idx, e, loss = _vq_fwd(dev, zd, cbd, beta)
+        return (idx, e, loss) + _vq_bwd(dev, ged, gl, zd, idx, cbd, beta)
 
     idx, e, loss, gz, gcb = run()
-    assert torch.equal(idx, ops.vq_argmin(zd, cbd)), "the training kernel and spk_vq_argmin choose different codes"
+    try:
+        want_idx = ops.vq_argmin(zd, cbd)
+    except (NotImplementedError, ValueError):                       # a width spk_vq_argmin does not take: the fp64 distances decide
+        want_idx = None
+        orc.check_indices(snn_ref.vq_distances_f64(z, cb), idx, f"vq {kind} N={N} D={D} K={K}")
+    assert want_idx is not None or D != tor.D
+    if want_idx is not None:
+        assert torch.equal(idx, want_idx), "the training kernel and spk_vq_argmin choose different codes"
     used = int(idx.unique().numel())
-    assert used == 1 if kind == "one_code" else used <= 3 if kind == "few_codes" else used > 8
+    assert used == 1 if kind == "one_code" else used <= 3 if kind == "few_codes" else used > min(8, K - 1)
+    if N > tor.SMALL_N:                                             # a row's index and value depend on that row alone
+        idx_s, e_s, _ = _vq_fwd(dev, zd[:tor.SMALL_N].contiguous(), cbd, beta)
+        assert torch.equal(idx[:tor.SMALL_N], idx_s) and torch.equal(_bits(e[:tor.SMALL_N]), _bits(e_s)), \
+            f"the first {tor.SMALL_N} of {N} rows differ from a call on those rows alone"
     q = cbd[idx]
     assert torch.equal(_bits(e), _bits(zd + (q - zd))), "e is not the fp32 value z + (q - z)"
     r = tor.vq_reference(z, cb, idx, beta, g_e, g_loss)
     worst = {"loss": abs(float(loss) - r["loss"]) / r["loss_bound"],
              "gz": float(((gz.cpu().double() - r["gz"]).abs() / r["gz_bound"].clamp_min(1e-300)).max()),
              "gcb": float(((gcb.cpu().double() - r["gcb"]).abs() / r["gcb_bound"].clamp_min(1e-300))[r["gcb_bound"] > 0].max())}
-    print(f"vq {kind} N={N} K={K}: {used} codes used; worst error / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
-    parity(f"ann_vqvae_train_vq[{kind}-{N}-{K}]", **worst)
+    print(f"vq {kind} N={N} D={D} K={K}: {used} codes used; worst error / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    parity(f"ann_vqvae_train_vq[{tor.vq_case_id((kind, N, D, K))}]", **worst)
     assert max(worst.values()) <= 1.0, worst
     unused = torch.ones(K, dtype=torch.bool)
     unused[idx.cpu().unique()] = False
@@ -144,14 +201,139 @@ def test_vq_kernels_meet_fp64_given_the_indices(dev, kind, N, K):
     for a, b in zip((idx, e, loss, gz, gcb), again):
         assert torch.equal(_bits(a) if a.dtype == torch.float32 else a, _bits(b) if b.dtype == torch.float32 else b)
     # NULL gradients are zeros
-    gz0 = torch.full((N, tor.D), POISON, device=dev)
-    gcb0 = torch.full((K, tor.D), POISON, device=dev)
-    assert L.spk_ann_vqvae_train_vq_bwd(None, None, zd.data_ptr(), idx.data_ptr(), cbd.data_ptr(), beta, gz0.data_ptr(),
-                                        gcb0.data_ptr(), N, tor.D, K, st) == 0
+    gz0, gcb0 = _vq_bwd(dev, None, None, zd, idx, cbd, beta)
     assert not bool(gz0.any()) and not bool(gcb0.any())
 
 
-@pytest.mark.parametrize("B,C,H", [(1, 1, 28), (3, 3, 32), (33, 1, 28), (5, 3, 28)])
+def test_vq_kernels_stop_at_the_lds_ceiling(dev):
+    """K = 244 is the largest codebook of D = 64 that fits in 64 KB of LDS (it runs: VQ_CASES); K = 245 is refused by the predicate
+    and by the forward, which touches nothing."""
+    from spkdiff import _lib, ops
+    L, UNS = ops.lib, _lib.CONSTANTS["SPK_ERR_UNSUPPORTED"]
+    D = tor.MAX_D
+    K = max(tor.DC0_K)
+    assert L.spk_ann_vqvae_train_supported(D, K) and not L.spk_ann_vqvae_train_supported(D, K + 1)
+    assert ("random", tor.SMALL_N, D, K) in [c[:4] for c in tor.VQ_CASES]
+    N = 49
+    zd, cbd = torch.randn(N, D, device=dev), torch.randn(K + 1, D, device=dev)
+    idx = torch.full((N,), -1, dtype=torch.int64, device=dev)
+    e = torch.full((N, D), POISON, device=dev)
+    loss = torch.full((1,), POISON, device=dev)
+    ws = torch.full((N,), SENTINEL, dtype=torch.float64, device=dev)
+    assert L.spk_ann_vqvae_train_vq_fwd(zd.data_ptr(), cbd.data_ptr(), idx.data_ptr(), e.data_ptr(), loss.data_ptr(), 0.25,
+                                        ws.data_ptr(), N * 8, N, D, K + 1, torch.cuda.current_stream().cuda_stream) == UNS
+    torch.cuda.synchronize()
+    assert bool((idx == -1).all()) and bool((e == POISON).all()) and bool((loss == POISON).all()) and bool((ws == SENTINEL).all())
+
+
+# ---- the kernel's own arg min (its copy of vq_kernel's lane loop): ties, NaN and inf, as tests/test_gpu_vq_shapes.py pins them
+# for spk_vq_argmin.  The index is torch.argmin's on the fp64 distances of oracle/snn_ref.py -- the first NaN, else the first
+# minimum -- and always in [0, K); D = 16 is the DC form, D = 24 the DC == 0 form; K = 37 < 64 leaves lanes on the clamped code.
+ARGMIN_FORMS = [(16, 128), (24, 128), (16, 37), (24, 37)]
+
+
+def _argmin64(z, cb):
+    return torch.argmin(snn_ref.vq_distances_f64(z, cb), dim=1)
+
+
+@pytest.mark.parametrize("D,K", ARGMIN_FORMS)
+def test_vq_fwd_ties_take_the_lower_index(dev, D, K):
+    """Duplicate codes at (k, k + 1), (k, k + 64) (the same lane) and (k, K - 1), with rows placed on them: the lower index wins,
+    the row's value is the row itself, and the twin that lost gets an exactly-zero gradient."""
+    g = torch.Generator().manual_seed(77 + D + K)
+    N = 3 * 49
+    z, cb = torch.randn(N, D, generator=g), torch.randn(K, D, generator=g)
+    pairs = [(3, 4), (20, K - 1)] + ([(10, 74)] if K > 74 else [])
+    want = {}
+    for j, (a, b) in enumerate(pairs):
+        p = 5 + 11 * j
+        cb[a] = cb[b] = z[p]
+        want[p] = a
+    zd, cbd = z.to(dev), cb.to(dev)
+    idx, e, loss = _vq_fwd(dev, zd, cbd, 0.25)
+    assert torch.equal(idx.cpu(), _argmin64(z, cb))
+    for p, a in want.items():
+        assert int(idx[p]) == a, (p, int(idx[p]), a)
+        assert torch.equal(_bits(e[p]), _bits(zd[p]))
+    gz, gcb = _vq_bwd(dev, None, torch.ones(1, device=dev), zd, idx, cbd, 0.25)
+    for a, b in pairs:
+        assert not bool(gcb[b].any()), f"code {b}, the twin of {a}, is no row's code and has a gradient"
+    flat = torch.full((K, D), 0.25, device=dev)                     # every code equal: index 0 everywhere
+    idx, e, loss = _vq_fwd(dev, zd, flat, 0.25)
+    assert int(idx.abs().max()) == 0
+
+
+@pytest.mark.parametrize("D,K,N", [(16, 100, tor.N_PAST_FWD[16]), (24, 37, tor.SMALL_N)])
+def test_vq_nan_and_inf_rows_stay_in_their_rows(dev, D, K, N):
+    """Rows with one NaN component, rows of NaN and rows of +-inf (generated; every index comes from the forward).  Forward: the
+    index is torch.argmin's, e and the loss carry the NaN.  Backward: gz is non-finite exactly where z is, gcodebook exactly in
+    the components of the chosen codes that a non-finite component fed, and every other entry is within its counted bound of
+    the fp64 reference without those components' contribution (z = q there)."""
+    g = torch.Generator().manual_seed(D + K)
+    z = torch.randn(N, D, generator=g)
+    z[::7, D // 2] = NAN
+    z[3::11] = NAN
+    z[5::13] = INF
+    z[6::17] = -INF
+    cb = torch.randn(K, D, generator=g)
+    g_e = torch.randn(N, D, generator=g)
+    beta, g_loss = 0.25, 0.75
+    zd, cbd, ged = z.to(dev), cb.to(dev), g_e.to(dev)
+    idx, e, loss = _vq_fwd(dev, zd, cbd, beta)
+    want = _argmin64(z, cb)
+    bad = (idx.cpu() != want).nonzero().flatten()
+    assert bad.numel() == 0, f"{bad.numel()} of {N} indices differ from torch.argmin's, first rows {bad[:8].tolist()}"
+    assert int(idx[0]) == 0 and int(idx[3]) == 0 and idx.unique().numel() > 8       # every distance of a NaN row is NaN: code 0
+    assert _same_bits(e, zd + (cbd[idx] - zd)), "e is not the fp32 value z + (q - z)"
+    finite = torch.isfinite(z)
+    assert torch.equal(torch.isnan(e).cpu(), ~finite) and bool(torch.isnan(loss).all())
+    gz, gcb = _vq_bwd(dev, ged, torch.tensor([g_loss], device=dev), zd, idx, cbd, beta)
+    gz, gcb, idx = gz.cpu(), gcb.cpu(), idx.cpu()
+    assert torch.equal(~torch.isfinite(gz), ~finite), "gz is non-finite somewhere else than z"
+    assert bool(torch.isnan(gz)[torch.isnan(z)].all())
+    fed = torch.zeros(K, D).index_add_(0, idx, (~finite).float()) > 0
+    assert torch.equal(~torch.isfinite(gcb), fed), "gcodebook is non-finite somewhere else than where a non-finite component went"
+    assert set(fed.any(dim=1).nonzero().flatten().tolist()) == set(idx[~finite.all(dim=1)].unique().tolist())
+    r = tor.vq_reference(torch.where(finite, z, cb[idx]), cb, idx, beta, g_e, g_loss)
+    worst = {"gz": float(((gz.double() - r["gz"]).abs() / r["gz_bound"].clamp_min(1e-300))[finite].max()),
+             "gcb": float(((gcb.double() - r["gcb"]).abs() / r["gcb_bound"].clamp_min(1e-300))[~fed & (r["gcb_bound"] > 0)].max())}
+    print(f"vq nan rows N={N} D={D} K={K}: {int((~finite.all(dim=1)).sum())} bad rows, codes fed {int(fed.any(dim=1).sum())}; "
+          "worst error / bound " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    parity(f"ann_vqvae_train_vq[nan_rows-{N}-{D}-{K}]", **worst)
+    assert max(worst.values()) <= 1.0, worst
+    unused = torch.ones(K, dtype=torch.bool)
+    unused[idx.unique()] = False
+    assert bool((gcb[unused] == 0).all())
+
+
+@pytest.mark.parametrize("D,K", ARGMIN_FORMS)
+def test_vq_fwd_nan_and_inf_codes(dev, D, K):
+    """A NaN code row (every distance to it NaN: it is every row's code unless an earlier distance is NaN) and an inf row before
+    it: its distance is NaN where the signs cancel inf against inf, and +inf for the rows whose every product with it is -inf
+    (every third row is given those signs) -- those rows take the NaN code, or, once it is gone, a finite one."""
+    g = torch.Generator().manual_seed(9 + D + K)
+    N = 3 * 49
+    z, cb = torch.randn(N, D, generator=g), torch.randn(K, D, generator=g)
+    k_inf, k_nan = (40, 90) if K > 90 else (10, 30)
+    cb[k_inf] = INF
+    cb[k_inf, 1::2] = -INF
+    cb[k_nan, 2] = NAN
+    z[::3] = z[::3].abs() * torch.tensor([-1.0, 1.0]).repeat(D // 2)
+    zd = z.to(dev)
+    for book in (cb, torch.cat([cb[:k_nan], torch.full((1, D), 0.5), cb[k_nan + 1:]])):     # ... and the inf row alone
+        cbd = book.to(dev)
+        idx, e, loss = _vq_fwd(dev, zd, cbd, 0.25)
+        assert torch.equal(idx.cpu(), _argmin64(z, book))
+        chosen = set(idx.cpu().unique().tolist())
+        assert chosen == {k_inf, k_nan} if book is cb else (k_inf in chosen and len(chosen) > 4)        # (the inputs' variety)
+        assert bool((idx[1::3] == k_inf).all()) and not bool((idx[::3] == k_inf).any())
+        assert _same_bits(e, zd + (cbd[idx] - zd)) and not bool(torch.isfinite(loss).any())
+
+
+LOSS_CASES = [c[:3] for c in tor.LOSS_CASES]
+
+
+@pytest.mark.parametrize("B,C,H", LOSS_CASES)
 def test_loss_kernels_meet_fp64(dev, B, C, H):
     from spkdiff import ops
     L = ops.lib
@@ -163,20 +345,35 @@ def test_loss_kernels_meet_fp64(dev, B, C, H):
     xr_cl = xr.to(dev).permute(0, 2, 3, 1).contiguous()              # the kernel's channels-last reconstruction
     dvd, grd, gld = (torch.tensor([v], device=dev) for v in (dv, g_recon, g_real))
     st = torch.cuda.current_stream().cuda_stream
-    nb = int(L.spk_ann_vqvae_train_ws_bytes(0, x.numel()))
+    n = x.numel()
+    nb = int(L.spk_ann_vqvae_train_ws_bytes(0, n))
+    assert nb == 8 * tor.loss_fwd_launch(B, C, H)["ws_doubles"]
+
+    def backward(g_recon_ptr, g_real_ptr):
+        gbuf, gx = _guarded(dev, n)
+        assert L.spk_ann_vqvae_train_loss_bwd(xr_cl.data_ptr(), xd.data_ptr(), g_recon_ptr, g_real_ptr, dvd.data_ptr(), gx.data_ptr(),
+                                              B, C, H, H, st) == 0
+        torch.cuda.synchronize()
+        assert _intact(gbuf, n), "the backward wrote outside its gradient"
+        assert not bool((gx == POISON).any()), "the backward left a gradient element unwritten"
+        return gx.clone().view(B, H, H, C)
 
     def run():
-        out = torch.full((2,), POISON, device=dev)
-        ws = torch.full((nb // 8,), float("nan"), dtype=torch.float64, device=dev)
+        obuf, out = _guarded(dev, 2)
+        wbuf, ws = _guarded(dev, nb // 8, torch.float64, SENTINEL)  # exactly the bytes the library asks for, between guard bands
+        ws.fill_(NAN)
         assert L.spk_ann_vqvae_train_loss_fwd(xr_cl.data_ptr(), xd.data_ptr(), dvd.data_ptr(), out[0:].data_ptr(), out[1:].data_ptr(),
                                               ws.data_ptr(), nb, B, C, H, H, st) == 0
-        gx = torch.full((B, H, H, C), POISON, device=dev)
-        assert L.spk_ann_vqvae_train_loss_bwd(xr_cl.data_ptr(), xd.data_ptr(), grd.data_ptr(), gld.data_ptr(), dvd.data_ptr(),
-                                              gx.data_ptr(), B, C, H, H, st) == 0
         torch.cuda.synchronize()
-        return out, gx
+        assert _intact(wbuf, nb // 8, SENTINEL), "the forward wrote outside the workspace it asked for"
+        assert _intact(obuf, 2) and not bool((out == POISON).any())
+        return out.clone(), backward(grd.data_ptr(), gld.data_ptr())
 
     out, gx = run()
+    # a gradient element depends on its own pair alone: the first image's, from the kernel's c in fp32 on the host
+    c = (np.float32(g_recon) / np.float32(dv) + np.float32(g_real)) * (np.float32(2.0) / np.float32(n))
+    want0 = torch.tensor(c) * (xr[0].permute(1, 2, 0).contiguous() - x[0].permute(1, 2, 0).contiguous())
+    assert want0.dtype == torch.float32 and torch.equal(_bits(gx[0].cpu()), _bits(want0)), "the first image's gradient is not c (xr - x)"
     r = tor.loss_reference(xr, x, dv, g_recon, g_real)
     worst = {"recon": abs(float(out[0]) - r["recon"]) / r["recon_bound"], "real": abs(float(out[1]) - r["real"]) / r["bound"],
              "g": float(((gx.permute(0, 3, 1, 2).cpu().double() - r["g"]).abs() / r["g_bound"].clamp_min(1e-300)).max())}
@@ -185,9 +382,7 @@ def test_loss_kernels_meet_fp64(dev, B, C, H):
     assert max(worst.values()) <= 1.0, worst
     out2, gx2 = run()
     assert torch.equal(_bits(out), _bits(out2)) and torch.equal(_bits(gx), _bits(gx2))
-    gx0 = torch.full((B, H, H, C), POISON, device=dev)
-    assert L.spk_ann_vqvae_train_loss_bwd(xr_cl.data_ptr(), xd.data_ptr(), None, None, dvd.data_ptr(), gx0.data_ptr(), B, C, H, H, st) == 0
-    assert not bool(gx0.any())
+    assert not bool(backward(None, None).any())                     # NULL gradients are zeros
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. the model
