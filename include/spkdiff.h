@@ -680,6 +680,31 @@ int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_inout, uint8_
                           const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, int B, int HW, int K,
                           const int* active_or_null, const int* n_active_or_null, float* next_input_b2hw_or_null,
                           spk_stream_t stream);
+/* Confidence-ordered decoding: spk_psample_step_conf and spk_den_step_tail_conf take the arguments, checks and
+ * truncation of their `_topp` siblings WITHOUT active / n_active, plus `float* conf_out_or_null` (fp32 [B*HW]; the step tail: also
+ * `long long* x0_hat_out_or_null`).  What changes is WHERE a step reveals.  At reverse step t, for each image i on its own:
+ *   1. m = the number of positions masked at entry; n = (m + t - 1) / t in integer arithmetic, ceil(m / t): everything at t = 1,
+ *      one per step at m = 49 and 49 steps, 7, 6, 6, 6, 6, 6, 6, 6 at 8 steps;
+ *   2. every masked position p gets a candidate token: the unchanged race on logits / temp_b[i] after the top-k and the nucleus
+ *      truncation, noise of stream 1 at counter offset + p * K + class (or the injected q) -- bit for bit the x0_hat_out of
+ *      spk_psample_step_topp for the same inputs.  The stream-0 uniform of the coin is neither drawn nor read (its per-position
+ *      counter stays free), and u_or_null is ignored;
+ *   3. the confidence of p is the fp32 log-probability the race itself holds for the drawn class under the truncated, renormalised
+ *      row -- z_c - (mx + logf(sum expf(z - mx))) as csrc/psample_common.h computes it, no new arithmetic -- and its order key is
+ *      the 32-bit key of the top-k select, under which a NaN (a row with a NaN logit, or all at -inf) has key 0 and orders last;
+ *   4. p is revealed iff fewer than n masked positions p' of image i have (key, -p') above (key, -p): larger key first, equal keys
+ *      to the lower position.  A revealed position takes its candidate and unmasked = 1; every other position keeps its state and
+ *      its candidate is discarded.
+ * x0_hat_out (the candidates) and conf_out (the confidences) are written at the positions masked at entry and nowhere else.
+ * next_input_b2hw_or_null is written from the committed state.  One workgroup per image, no global workspace, no selection noise;
+ * HW > 64: SPK_ERR_UNSUPPORTED with nothing launched; K <= 2048.  There is no active-list form -- which positions change depends
+ * on the logits, so no image and no position can be ruled out ahead of the denoiser -- and no score form.  Deterministic, split
+ * independent (the draws are the sibling's), capturable in a hipGraph; allocates nothing. */
+int spk_psample_step_conf(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                          const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
+                          unsigned long long philox_seed, unsigned long long philox_offset,
+                          const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, float* conf_out_or_null,
+                          int B, int HW, int K, float* next_input_b2hw_or_null, spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -722,7 +747,7 @@ int spk_pscore_step_temps(const float* logits_bkhw, const long long* x0, long lo
  * serves slot s of the list: cnt5 / cnt1 / logits_out are indexed by slot (what the active-set denoiser launches produced), x_t / unmasked /
  * the noise by image active[s], so the draws are those of the dense form; x1_s32_out must be NULL there (the next step's first layer is
  * the next step's active set's). */
-#define SPK_STEP_TAIL_MAX_K 512 /* the largest K spk_den_step_tail and its _temps / _topk / _topp forms take */
+#define SPK_STEP_TAIL_MAX_K 512 /* the largest K spk_den_step_tail and its _temps / _topk / _topp / _conf forms take */
 int spk_den_step_tail(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                       const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                       float temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
@@ -760,6 +785,18 @@ int spk_den_step_tail_topp(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, i
                            const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                            uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                            const int* active_or_null, const int* n_active_or_null, spk_stream_t stream);
+/* spk_den_step_tail under the confidence-ordered reveal (1 <= K <= 512, 7x7 or 8x8; no active list): conv6 on the counts, a
+ * candidate at every masked position, the commit of the n = ceil(m / t) surest by one wave, then the fused first layer on the
+ * committed tokens -- bit for bit spk_den_conv3x3_counts_mfma, spk_psample_step_conf and the first layer as three launches: see
+ * spk_psample_step_conf.  x0_hat_out / conf_out optional, written at the positions masked at entry. */
+int spk_den_step_tail_conf(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                           const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                           int t, const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                           const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                           const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                           const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                           uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                           long long* x0_hat_out_or_null, float* conf_out_or_null, spk_stream_t stream);
 /* q_sample of the diffusion training step, R/snn_model/vq_diffusion.py:61-75: mask = u < t[b] / num_timesteps (fp32, as there);
  * x_t = mask ? mask_id : x_0;  x_0_ignore = mask ? x_0 : -1 (the loss's ignore index).  x0 / u / outputs fp32 [B*HW], t int64 [B],
  * mask_out optional u8.  u is the caller's draw (torch.rand_like in the reference's order). */

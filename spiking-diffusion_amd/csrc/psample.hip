@@ -83,6 +83,58 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
   }
 }
 
+// The same step under the confidence-ordered reveal (psample_common.h, "THE rule"; spk_psample_step_conf): one workgroup per
+// image, no global workspace.  The four waves stride over the image's positions and run the `_topp` family's draw at every
+// position masked at entry (candidate -> x0_hat_out, confidence -> conf_out, candidate and order key -> LDS); behind a barrier
+// wave 0 -- lane = position -- ranks the keys, commits the n surest candidates and writes the next step's input from the
+// committed state.  HW <= 64 (the host checks).  The stream-0 uniform is not drawn; there is no active-list form: which
+// positions change depends on the logits.
+template <int KPL>
+__global__ __launch_bounds__(256) void psample_conf_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
+                                                           uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
+                                                           const float* __restrict__ q_in, unsigned long long seed,
+                                                           unsigned long long offset,
+                                                           const unsigned long long* __restrict__ philox_state,
+                                                           long long* __restrict__ x0_hat_out, float* __restrict__ conf_out,
+                                                           int HW, int K, float* __restrict__ next_input, float t_next) {
+  __shared__ int s_cand[64];
+  __shared__ uint32_t s_key[64];
+  philox_base(philox_state, seed, offset);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x;
+  const float tp = temp.temp[b];
+  const int topk = temp.topk[b];
+  const float topp = temp.topp[b];
+  for (int hw = wave; hw < HW; hw += 4) {
+    const long long p = (long long)b * HW + hw;
+    if (unmasked[p]) continue;                                      // (wave-uniform)
+    float l[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      const int k = lane + 64 * j;
+      const float lg = logits[((long long)b * K + (k < K ? k : K - 1)) * HW + hw];
+      l[j] = k < K ? lg / tp : -INFINITY;
+    }
+    truncate_top_k<KPL>(l, lane, K, topk);
+    truncate_top_p<KPL>(l, lane, K, topp);
+    float conf;
+    const int besti = categorical_race<KPL, true>(l, lane, K, q_in, seed, offset, p, &conf);
+    if (lane == 0) {
+      s_cand[hw] = besti;
+      s_key[hw] = spk_conf_key(conf);
+      if (x0_hat_out) x0_hat_out[p] = (long long)besti;
+      if (conf_out) conf_out[p] = conf;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const long long p = (long long)b * HW + (lane < HW ? lane : 0);
+  const bool masked = lane < HW && !unmasked[p];
+  const bool reveal = confident_reveal(masked, lane, HW, t, s_key);
+  if (reveal) { unmasked[p] = 1; x_t[p] = (long long)s_cand[lane]; }
+  if (next_input && lane < HW) write_next_input(next_input, b, lane, HW, reveal ? (float)s_cand[lane] : (float)x_t[p], t_next);
+}
+
 // Denoiser input map, R/snn_model/vq_diffusion.py:195-197:  cat(x, ones_like(x) * t[:,None,None,None]) -> [B,2,h,w]
 // x comes either as float [B,1,h,w] (the module API) or as the int64 token state x_t of the sampler.
 __global__ void den_input_kernel(const float* __restrict__ xf, const long long* __restrict__ xi,
@@ -418,4 +470,30 @@ extern "C" int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_in
   return psample_launch<true, true, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
                                           q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, B, HW, K,
                                           active_or_null, n_active_or_null, next_input_b2hw_or_null, stream);
+}
+
+// The same step under the confidence-ordered reveal (include/spkdiff.h; the rule: psample_common.h): the `_topp` arguments without an
+// active list, plus conf_out_or_null.  u_or_null is accepted and ignored (the coin is not part of the rule).
+extern "C" int spk_psample_step_conf(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                     const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                     const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                     const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                     float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
+                                     hipStream_t stream) {
+  (void)u_or_null;
+  const spk_temp_topp temp{temp_b, topk_b, topp_b};
+  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0)
+    return SPK_ERR_ARG;
+  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
+#define SPK_PSAMPLE_CONF_LAUNCH(KPL)                                                                                     \
+  hipLaunchKernelGGL((psample_conf_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, t, temp, \
+                     q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, HW, K, \
+                     next_input_b2hw_or_null, (float)(t - 1))
+  if (K <= 256) SPK_PSAMPLE_CONF_LAUNCH(4);
+  else if (K <= 512) SPK_PSAMPLE_CONF_LAUNCH(8);
+  else if (K <= 1024) SPK_PSAMPLE_CONF_LAUNCH(16);
+  else SPK_PSAMPLE_CONF_LAUNCH(32);
+#undef SPK_PSAMPLE_CONF_LAUNCH
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
 }

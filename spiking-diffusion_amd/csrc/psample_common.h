@@ -1,7 +1,8 @@
 // The token update of a reverse step, defined once for the sampler kernels (psample.hip, pscore.hip, step_tail.hip): the Philox4x32-10
 // counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
 // offset + position * K + class), the categorical draw categorical_race, the top-k and nucleus truncations truncate_top_k /
-// truncate_top_p that may precede it, the 64-lane max / sum and the prologues every kernel shares.
+// truncate_top_p that may precede it, the confidence-ordered reveal rule confident_reveal (what a step commits when it does not toss
+// the coin), the 64-lane max / sum and the prologues every kernel shares.
 // Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
@@ -115,12 +116,24 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The entry of l (class lane + 64 * j in l[j]) for class `cls`, in every lane: cls is wave-uniform.
+template <int NJ>
+__device__ __forceinline__ float spk_race_conf(const float (&l)[NJ], int cls) {
+  float c = l[0];
+#pragma unroll
+  for (int j = 1; j < NJ; ++j) c = (cls >> 6) == j ? l[j] : c;
+  return __shfl(c, cls & 63);
+}
+
 // x0_hat = Categorical(logits = l).sample() of one position, by one wave: l[j] is the temperature-scaled logit of class lane + 64 * j
 // (-inf for a class >= K; overwritten).  probs = softmax(l - logsumexp l), the draw argmax_k probs_k / q_k (torch.multinomial's one-draw
 // path), ties to the lower class; every lane returns it.  These fp32 operations in this order are the definition (-ffp-contract=off).
-template <int NJ>
+// CONF (the confidence-ordered reveal, below): *conf also receives, in every lane, the value l holds for the drawn class after the
+// `l[j] = l[j] - lse` line -- the log-probability of the token under the row as it was raced.  Nothing new is computed.
+template <int NJ, bool CONF = false>
 __device__ __forceinline__ int categorical_race(float (&l)[NJ], int lane, int K, const float* __restrict__ q_in,
-                                                unsigned long long seed, unsigned long long offset, long long p) {
+                                                unsigned long long seed, unsigned long long offset, long long p,
+                                                float* conf = nullptr) {
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) mx = fmaxf(mx, l[j]);
@@ -157,6 +170,7 @@ __device__ __forceinline__ int categorical_race(float (&l)[NJ], int lane, int K,
     const int oi = __shfl_xor(besti, off);
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
   }
+  if constexpr (CONF) *conf = spk_race_conf<NJ>(l, besti);
   return besti;
 }
 
@@ -238,6 +252,36 @@ __device__ __forceinline__ void truncate_top_p(float (&l)[NJ], int lane, int K, 
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
     if (l[j] < tau) l[j] = -INFINITY;
+}
+
+// The confidence-ordered reveal (spk_psample_step_conf, spk_den_step_tail_conf) -- THE rule, stated once.  At
+// reverse step t, for each image on its own:
+//   1. m = the number of positions masked at entry, n = (m + t - 1) / t in integer arithmetic (ceil(m / t): everything at t = 1);
+//   2. every masked position p gets a candidate: the unchanged race on the temperature-scaled logits after truncate_top_k and
+//      truncate_top_p, noise of stream 1 at offset + p * K + class -- bit for bit the x0_hat of the `_topp` entry points.  The
+//      stream-0 uniform of reveal_u is neither drawn nor read (its counter stays free), an injected u is ignored;
+//   3. the confidence of p is the fp32 value categorical_race holds for the drawn class after `l[j] = l[j] - lse` (CONF above);
+//      its order key is the 32-bit key of truncate_top_k (spk_conf_key: a NaN has key 0 and orders last);
+//   4. p is revealed iff fewer than n masked positions p' of the image have (key, -p') above (key, -p): larger key first, equal
+//      keys to the lower position.  A revealed position takes its candidate and unmasked = 1, every other keeps its state.
+// confident_reveal is step 4 for one image by ONE wave, lane = position (h*w <= 64): `masked` = this lane's position is masked at
+// entry (false for lane >= h*w), s_key = the image's keys in LDS (read at masked positions only; the writes are behind a barrier).
+__device__ __forceinline__ uint32_t spk_conf_key(float conf) {
+  const uint32_t b = __float_as_uint(conf);
+  return (conf != conf) ? 0u : ((b & 0x80000000u) ? ~b : (b | 0x80000000u));
+}
+__device__ __forceinline__ bool confident_reveal(bool masked, int lane, int HW, int t, const uint32_t* s_key) {
+  const unsigned long long mm = __ballot(masked);
+  const unsigned m = (unsigned)__popcll(mm);
+  const unsigned n = (m + (unsigned)t - 1u) / (unsigned)t;
+  const uint32_t key = masked ? s_key[lane] : 0u;
+  unsigned rank = 0;
+  for (int q = 0; q < HW; ++q) {
+    if (!((mm >> q) & 1ull)) continue;                            // (wave-uniform)
+    const uint32_t kq = s_key[q];                                 // (one address for the wave: a broadcast read)
+    rank += (kq > key || (kq == key && q < lane)) ? 1u : 0u;
+  }
+  return masked && rank < n;
 }
 
 }  // namespace

@@ -34,8 +34,13 @@ constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested 
 // scalar form's argument block is the one it always was
 // TK = top-k truncation (spk_den_step_tail_topk; always with PT): `temp` is the pair of per-image arrays {temperatures, k}
 // TP = nucleus truncation after it (spk_den_step_tail_topp; always with PT and TK): the triple {temperatures, k, p}
-template <bool PT, bool TK = false, bool TP = false>
-struct TailArgsT {
+// CF = the confidence-ordered reveal (spk_den_step_tail_conf; only on top of PT, TK and TP; the rule: psample_common.h): the draw
+// runs at every position masked at entry, candidate and order key meet in LDS, and one wave commits the n surest before the fused
+// first layer.  Its two optional outputs are a base of the argument block, empty in every other form (whose block does not change).
+template <bool CF> struct TailConfOutT {};
+template <> struct TailConfOutT<true> { long long* x0_hat_out; float* conf_out; };   // candidates / confidences, at the masked positions
+template <bool PT, bool TK = false, bool TP = false, bool CF = false>
+struct TailArgsT : TailConfOutT<CF> {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
   const int8_t* wq; const double* scale; const double* bias;
   float* logits_out;                              // optional fp32 [B][128][HW]
@@ -53,8 +58,9 @@ struct TailArgsT {
 };
 
 // KG = channel groups per wave (1: K <= 128, the reference's default; 2 .. 4: K <= 256 / 384 / 512)
-template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false>
-__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP> a) {
+template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false, bool CF = false>
+__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP, CF> a) {
+  static_assert(!CF || (PT && TK && TP), "the confidence form exists on top of the most general family only");
   constexpr int HW = H * W;
   static_assert(HW <= 64, "an image is at most two 32-row tiles");
   constexpr int AV = HW * 2 + 1;                  // 16-byte vectors of a chunk's count records + one zero vector
@@ -67,6 +73,15 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP>
   __shared__ int s_chg[64];
   __shared__ float s_th[16];
   __shared__ unsigned s_pat[18];
+  int* s_cand = nullptr;                          // CF: the candidate token and the order key of every masked position
+  uint32_t* s_key = nullptr;
+  unsigned long long* s_cfarg = nullptr;          // CF: {x0_hat_out, conf_out, t} parked in LDS over the K loop (scalar registers are
+  if constexpr (CF) {                             //  what that loop is short of: held there they were spilled)
+    __shared__ int s_cand_[64];
+    __shared__ uint32_t s_key_[64];
+    __shared__ unsigned long long s_cfarg_[3];
+    s_cand = s_cand_; s_key = s_key_; s_cfarg = s_cfarg_;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;                       // slot: index of the count records and of the logits
   int bi = b;                                     // image: index of tokens, unmasked and noise
@@ -102,6 +117,12 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP>
     s_a[c * AV + r] = *reinterpret_cast<const v4i*>(src);
   }
   if (tid < TNCH) s_a[tid * AV + HW * 2] = (v4i){0, 0, 0, 0};
+  if constexpr (CF) {
+    if (tid == 0) {
+      s_cfarg[0] = (unsigned long long)a.x0_hat_out; s_cfarg[1] = (unsigned long long)a.conf_out;
+      s_cfarg[2] = (unsigned long long)(unsigned)a.t;
+    }
+  }
   // ---- which positions change at this step, and the tokens as they are: one thread per position, up front (fetched row by row
   //      in the sampling loop these were seven dependent memory round trips per wave)
   unsigned long long seed = a.seed, offset = a.offset;
@@ -116,8 +137,12 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP>
     const long long pi = (long long)bi * HW + tid;
     const uint8_t um = a.unmasked[pi];
     const long long tk = a.x_t[pi];
-    const float u = reveal_u(a.u_in, seed, offset, pi, K);
-    s_chg[tid] = ((u < inv_t) && !um) ? 1 : 0;
+    if constexpr (CF) {
+      s_chg[tid] = um ? 0 : 1;                     // (every masked position draws a candidate; the coin is not drawn)
+    } else {
+      const float u = reveal_u(a.u_in, seed, offset, pi, K);
+      s_chg[tid] = ((u < inv_t) && !um) ? 1 : 0;
+    }
     s_tok[tid] = (float)tk;
   }
   // ---- per-channel constants of the next step's first layer, requested before the K loop
@@ -270,10 +295,34 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP>
       const int oi = __shfl_xor(besti, off);
       if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
     }
-    if (lane == 0) {
+    if constexpr (CF) {
+      const float conf = spk_race_conf<NJ>(l, besti);   // (categorical_race's CONF value: l after `l[j] - lse`, at the drawn class)
+      if (lane == 0) {
+        s_cand[p] = besti;
+        s_key[p] = spk_conf_key(conf);
+        long long* x0_hat_out = reinterpret_cast<long long*>(s_cfarg[0]);
+        float* conf_out = reinterpret_cast<float*>(s_cfarg[1]);
+        if (x0_hat_out) x0_hat_out[pi] = (long long)besti;
+        if (conf_out) conf_out[pi] = conf;
+      }
+    } else if (lane == 0) {
       a.unmasked[pi] = 1;
       a.x_t[pi] = (long long)besti;
       s_tok[p] = (float)besti;
+    }
+  }
+  if constexpr (CF) {
+    // ---- the commit: one wave, lane = position; the n = ceil(m / t) surest candidates of the image become its tokens
+    __syncthreads();
+    if (wave == 0) {
+      const bool masked = lane < HW && s_chg[lane < HW ? lane : 0] != 0;
+      if (confident_reveal(masked, lane, HW, (int)s_cfarg[2], s_key)) {
+        const long long pi = (long long)bi * HW + lane;
+        const int tk = s_cand[lane];
+        a.unmasked[pi] = 1;
+        a.x_t[pi] = (long long)tk;
+        s_tok[lane] = (float)tk;
+      }
     }
   }
   if (!a.x1_out) return;                         // (uniform: the last reverse step has no successor)
@@ -319,14 +368,15 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP>
 }  // namespace
 
 namespace {
-template <bool PT, bool TK = false, bool TP = false>
+template <bool PT, bool TK = false, bool TP = false, bool CF = false>
 int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                      const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                      spk_temp_arg_t<PT, TK, TP> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                      const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                      uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
-                     const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
+                     const int* active_or_null, const int* n_active_or_null, hipStream_t stream,
+                     long long* x0_hat_out_or_null = nullptr, float* conf_out_or_null = nullptr) {
   if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK, TP>(temp) || B <= 0 ||
       T <= 0)
     return SPK_ERR_ARG;
@@ -339,7 +389,13 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   // the fused first layer writes sixteen 16-byte step records per position and scans with the module-default LIF constants
   // (spk_lif_const_input_bits16): any other step count would write outside x1_s32_out (T < 16) or give wrong spikes (T > 16)
   if (x1_s32_out_or_null && T != 16) return SPK_ERR_UNSUPPORTED;
-  TailArgsT<PT, TK, TP> a;
+  TailArgsT<PT, TK, TP, CF> a;
+  if constexpr (CF) {
+    // (the K = 512, 8 x 8 launch holds 150 KB of logits and counts; with the form's 544 bytes more it is checked against the device's
+    //  grant -- the static part counted as 22 KB for either latent: 21 840 bytes on 8 x 8, 17 040 on 7 x 7, where the check is conservative)
+    if ((long long)64 * (128 * ((K + 127) / 128) + 4) * (long long)sizeof(float) + 22 * 1024 > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;
+    a.x0_hat_out = x0_hat_out_or_null; a.conf_out = conf_out_or_null;
+  }
   a.c5 = cnt5; a.c1 = cnt1; a.wq = wq; a.scale = scale; a.bias = bias_d; a.logits_out = logits_out_or_null;
   a.x_t = x_t_inout; a.unmasked = unmasked_inout; a.t = t; a.temp = temp; a.u_in = u_or_null; a.q_in = q_or_null;
   a.seed = philox_seed; a.offset = philox_offset; a.philox_state = philox_state_or_null;
@@ -350,7 +406,7 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   a.K = K; a.ng = (K + 15) / 16;                    // wq / scale / bias_d hold ng * 16 channels (zero weights beyond K)
   const int kg = (a.ng + 7) / 8;
 #define SPK_TAIL_LAUNCH(H_, W_, KG_)                                                                                          \
-  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
+  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP, CF>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
   if (H == 7) {
     if (kg == 1) SPK_TAIL_LAUNCH(7, 7, 1); else if (kg == 2) SPK_TAIL_LAUNCH(7, 7, 2);
     else if (kg == 3) SPK_TAIL_LAUNCH(7, 7, 3); else SPK_TAIL_LAUNCH(7, 7, 4);
@@ -424,4 +480,22 @@ extern "C" int spk_den_step_tail_topp(const uint8_t* cnt5, int nch5, const uint8
                                             philox_state_or_null, conv1_w_packed_or_null, conv1_bias_or_null, bn1_a, bn1_b,
                                             x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, active_or_null, n_active_or_null,
                                             stream);
+}
+
+// The same launch under the confidence-ordered reveal (include/spkdiff.h; the rule: csrc/psample_common.h): the `_topp` arguments
+// without an active list, plus the two optional outputs.  u_or_null is accepted and ignored.
+extern "C" int spk_den_step_tail_conf(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                      const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                      uint8_t* unmasked_inout, int t, const float* temp_b, const int* topk_b, const float* topp_b,
+                                      const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                      unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                      const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a,
+                                      const float* bn1_b, uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H,
+                                      int W, int K, long long* x0_hat_out_or_null, float* conf_out_or_null, hipStream_t stream) {
+  (void)u_or_null;
+  return step_tail_launch<true, true, true, true>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout, unmasked_inout,
+                                                  t, spk_temp_topp{temp_b, topk_b, topp_b}, nullptr, q_or_null, philox_seed,
+                                                  philox_offset, philox_state_or_null, conv1_w_packed_or_null, conv1_bias_or_null,
+                                                  bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, nullptr, nullptr,
+                                                  stream, x0_hat_out_or_null, conf_out_or_null);
 }

@@ -104,8 +104,10 @@ class _SamplerGraph:
     (``derived``: an invalidation re-keys the graph, but until the stale entry is evicted their memory must not be recycled)
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
-    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False):
+    def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False,
+                 confident=False):
         self.graph = self.derived = None                            # set by the capture
+        self.confident = bool(confident)                            # the captured token updates are the confidence-ordered ones (§4.15)
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         # per-image temperatures are one more INPUT: the captured token updates read this buffer, filled before each replay
         self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp or top_k or top_p else None
@@ -294,7 +296,28 @@ class AbsorbingDiffusion(Sampler):
         takes no ``top_k``."""
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p)
 
-    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None):
+    @torch.no_grad()
+    def sample_confident(self, sample_steps=None, temp=1.0, noise=None, record=None, x_init=None, known=None, top_k=None, top_p=None):
+        """Confidence-ordered decoding: ``sample()`` with another rule for WHERE a step reveals.  At step t every
+        still-masked position of an image draws a candidate token -- the draw of ``sample_top_p(top_p, top_k=top_k)``, same noise
+        counters -- and the ceil(m / t) candidates the denoiser is surest of (m = positions masked at entry; the order is the
+        log-probability of the candidate under the truncated, renormalised row as the draw itself computes it in fp32, ties to the
+        lower position) are committed; the others stay masked and draw again at the next step.  t = 1 reveals what is left, so the
+        result holds no ``mask_id`` at any ``sample_steps``; the coin of sample() (``u < 1/t``) is not drawn, and there is no
+        selection noise and no other schedule.  ``temp`` / ``top_k`` / ``top_p``: as sample_top_p() takes them (numbers are broadcast:
+        the kernels read all three per image; None: no truncation); ``top_k = 1`` is greedy decoding, the same tokens under every
+        key.  ``noise`` / ``record`` / ``x_init`` / ``known``: sample()'s (of an injected (u, q) only q is read).  Same noise contract
+        -- one key draw, counters on the global image index -- so ``set_shard`` works unchanged, eager and captured give the same
+        tokens, and one captured graph per (batch, steps, conditional) serves every temperature, k and p.  The launch form is the
+        dense one whatever ``skip_untouched`` says (fused step tail where the denoiser allows it): which positions change depends
+        on the logits, so no image and no position can be ruled out before the denoiser ran.  Latents of more than 64 positions:
+        NotImplementedError before anything is launched.  ``score()`` has no such form."""
+        h, w = self.shape
+        if h * w > 64:
+            raise NotImplementedError(f'spkdiff: sample_confident() ranks an image\'s positions in one wave: h * w <= 64, got {h} x {w}')
+        return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p, confident=True)
+
+    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None, confident=False):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         temp = self._temp_arg(temp, b)
@@ -305,6 +328,11 @@ class AbsorbingDiffusion(Sampler):
         if dev.type != 'cuda':
             raise RuntimeError('spkdiff: the sampler runs on a ROCm device; move the denoiser with .cuda()')
         temp = self._temp_on(temp, dev)
+        if confident:
+            # the confidence-ordered kernels exist on top of the most general family only: k = 0 / p = 1 are "untruncated"
+            if not isinstance(temp, torch.Tensor) and not (temp > 0 and math.isfinite(temp)):
+                raise ValueError(f'spkdiff: temp must be finite and > 0, got {temp!r}')
+            top_p = 1.0 if top_p is None else top_p
         if top_p is not None:
             # a nucleus call takes all three per image (the `_topp` kernels read three arrays): no top_k is k = 0 everywhere
             top_p = self._topp_on(top_p, dev, b)
@@ -325,8 +353,10 @@ class AbsorbingDiffusion(Sampler):
             self.last_key = seed               # (read-only record: bench.py compares it across ranks after a timed region)
         self._check_weights(dn)
         form = self._form(b, h, w, record is not None)
+        if confident:
+            form = SampleForm(skip=False, lists=False, tail=dn.tail_fusable(h, w), tail_act=False)
         return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k,
-                                     **({} if top_p is None else {'top_p': top_p}))
+                                     **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
 
     def _topp_arg(self, top_p, b):
         """The ``top_p`` of sample_top_p() for a batch of ``b``, checked before anything is drawn or launched.  None: no nucleus
@@ -337,15 +367,16 @@ class AbsorbingDiffusion(Sampler):
         fp32 [b], its values are not read (the kernels leave an image whose p is outside (0, 1) untruncated)."""
         if top_p is None:
             return None
-        bad = ValueError(f'spkdiff: top_p must be None, a number in (0, 1] or one such number per image of the call ({b}), '
-                         f'got {top_p!r}')
-        if isinstance(top_p, bool):
-            raise bad
+        # (a device tensor first: the message below prints its argument, which for a device tensor is a read-back of every entry)
         if isinstance(top_p, torch.Tensor) and top_p.is_cuda:
             if top_p.dim() != 1 or int(top_p.numel()) != b or top_p.dtype != torch.float32:
                 raise ValueError(f'spkdiff: a per-image top_p on the device must be fp32 [{b}] (one entry per image of the call), '
                                  f'got {top_p.dtype} {tuple(top_p.shape)}')
             return top_p.contiguous()
+        bad = ValueError(f'spkdiff: top_p must be None, a number in (0, 1] or one such number per image of the call ({b}), '
+                         f'got {top_p!r}')
+        if isinstance(top_p, bool):
+            raise bad
         try:
             v = top_p.detach() if isinstance(top_p, torch.Tensor) else torch.as_tensor(top_p)
             if v.dtype in (torch.bool, torch.complex64, torch.complex128) or v.dim() > 1 or (v.dim() == 1 and int(v.numel()) != b):
@@ -378,14 +409,15 @@ class AbsorbingDiffusion(Sampler):
         and comes back as a CPU int32 tensor [b]; a device tensor is taken as given -- int32 [b], its values are not read."""
         if top_k is None:
             return None
-        bad = ValueError(f'spkdiff: top_k must be None, an int >= 1 or one integer >= 0 per image of the call ({b}), got {top_k!r}')
-        if isinstance(top_k, bool):
-            raise bad
+        # (a device tensor first: the message below prints its argument, which for a device tensor is a read-back of every entry)
         if isinstance(top_k, torch.Tensor) and top_k.is_cuda:
             if top_k.dim() != 1 or int(top_k.numel()) != b or top_k.dtype != torch.int32:
                 raise ValueError(f'spkdiff: a per-image top_k on the device must be int32 [{b}] (one entry per image of the call), '
                                  f'got {top_k.dtype} {tuple(top_k.shape)}')
             return top_k.contiguous()
+        bad = ValueError(f'spkdiff: top_k must be None, an int >= 1 or one integer >= 0 per image of the call ({b}), got {top_k!r}')
+        if isinstance(top_k, bool):
+            raise bad
         try:
             v = top_k.detach() if isinstance(top_k, torch.Tensor) else torch.as_tensor(top_k)
         except (TypeError, ValueError, RuntimeError):
@@ -464,7 +496,9 @@ class AbsorbingDiffusion(Sampler):
         sample() (dense form).  With ``use_graph`` and neither ``noise`` nor ``record`` an order is one replay of a captured graph
         that takes x_0 and ``known`` as inputs (a key of its own; sample()'s graphs and keys are untouched).
         ``temp``: a number or one temperature per image, as in sample() (every order scores image i at ``temp[i]``).  There is no
-        ``top_k`` here (sample_top_k): under truncation a given token outside the kept set scores -inf, not a useful bound."""
+        ``top_k`` here (sample_top_k): under truncation a given token outside the kept set scores -inf, not a useful bound.  Nor is there a
+        ``confident`` flag (sample_confident): the bound is derived for the coin's reveal order, which does not look at the logits;
+        an order chosen from them is another process, whose likelihood this loop does not bound."""
         if isinstance(x_0, torch.Tensor) and x_0.dim() in (3, 4):      # (host checks of a per-image temp: before the device is looked at)
             temp = self._temp_arg(temp, int(x_0.shape[0]))
         start = self._start_state_args(x_0, known, what='x_0', call='score()', alone=True)
@@ -498,13 +532,14 @@ class AbsorbingDiffusion(Sampler):
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
     def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None,
-                         top_p=None):
+                         top_p=None, confident=False):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
                 return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k,
-                                            **({} if top_p is None else {'top_p': top_p}))
+                                            **({} if top_p is None else {'top_p': top_p}),
+                                            **({'confident': True} if confident else {}))
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -523,10 +558,10 @@ class AbsorbingDiffusion(Sampler):
             finally:
                 self._capturing = False
         return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k,
-                                  **({} if top_p is None else {'top_p': top_p}))
+                                  **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
 
     def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
-                      top_k=None, top_p=None):
+                      top_k=None, top_p=None, confident=False):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
@@ -542,7 +577,7 @@ class AbsorbingDiffusion(Sampler):
                 noise = lambda t: (torch.rand(b, 1, h, w).to(dev), None)      # noqa: E731
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
         self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
-                            top_k=top_k, **({} if top_p is None else {'top_p': top_p}))
+                            top_k=top_k, **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -554,7 +589,7 @@ class AbsorbingDiffusion(Sampler):
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
     def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
-                       top_k=None, top_p=None):
+                       top_k=None, top_p=None, confident=False):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -564,11 +599,15 @@ class AbsorbingDiffusion(Sampler):
         the given token x0 where spk_psample_step writes a sampled one and leaves its log-probability in logp, t in step (never a
         fused-tail form: ``form.tail`` / ``form.tail_act`` are off there); ``top_k``: int32 device tensor [B] -- handed to every token
         update of sample_top_k() and to nothing else (None: the calls carry no such keyword); ``top_p``: fp32 device tensor [B] of
-        sample_top_p(), handed on in the same way (then always with ``top_k``)."""
+        sample_top_p(), handed on in the same way (then always with ``top_k``); ``confident``: sample_confident() -- the token update of
+        every step is the confidence-ordered one (spk_den_step_tail_conf, or spk_psample_step_conf after the denoiser; always the
+        dense form, always with ``top_k`` and ``top_p``, never with ``target``)."""
         dn = self._denoise_fn
         trunc = {} if top_k is None else {'top_k': top_k}
         if top_p is not None:
             trunc['top_p'] = top_p
+        if confident:
+            trunc['confident'] = True
         b, _, h, w = x_t.shape
         K = self.num_classes
         seed, state = src.seed, src.state
@@ -590,7 +629,10 @@ class AbsorbingDiffusion(Sampler):
                                                   want_next=form.tail and t > 1, want_logits=record is not None, **trunc)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
-                    if target is None:
+                    if confident:
+                        ops.psample_step_conf(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
+                                              next_input=inp if t > 1 else None, top_k=top_k, top_p=top_p)
+                    elif target is None:
                         ops.psample_step(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
                                          next_input=inp if t > 1 else None, **trunc)
                     else:
@@ -732,7 +774,7 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
-    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None):
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None, confident=False):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -744,7 +786,7 @@ class AbsorbingDiffusion(Sampler):
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
                 conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ()) + \
-            (('top-p',) if top_p is not None else ())
+            (('top-p',) if top_p is not None else ()) + (('confident',) if confident else ())
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
@@ -755,9 +797,10 @@ class AbsorbingDiffusion(Sampler):
             g.target[2].zero_()
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
                             act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk,
-                            **({} if g.topp is None else {'top_p': g.topp}))
+                            **({} if g.topp is None else {'top_p': g.topp}), **({'confident': True} if g.confident else {}))
 
-    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None):
+    def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None,
+                        confident=False):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -768,16 +811,19 @@ class AbsorbingDiffusion(Sampler):
         ``target = (x0, logp, step)``: a score graph (again a key of its own) -- x0 is one more input (with ``start`` it IS the
         codes input), logp / step receive the graph's outputs.  ``top_k`` (int32 device tensor [B]; ``temp`` is then a vector too):
         a truncating graph -- a marker in the key, the vector copied into the graph's ``topk`` buffer before each replay.
-        ``top_p`` (fp32 device tensor [B]; then with ``top_k``): a nucleus graph -- one more marker, one more input (``topp``)."""
+        ``top_p`` (fp32 device tensor [B]; then with ``top_k``): a nucleus graph -- one more marker, one more input (``topp``).
+        ``confident``: the graph of sample_confident() (a nucleus graph whose token updates are the confidence-ordered ones): one more
+        marker in the key, no further input."""
         dn = self._denoise_fn
-        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p)
+        key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p,
+                              **({'confident': True} if confident else {}))
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
             g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
                               per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None,
-                              top_p=top_p is not None)
+                              top_p=top_p is not None, **({'confident': True} if confident else {}))
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -958,11 +1004,11 @@ class DummyModel(nn.Module):
 
     @torch.no_grad()
     def sample_step(self, x_t, unmasked, t, temp, u=None, q=None, seed=0, offset=0, philox_state=None, pre1=None,
-                    want_next=True, want_logits=False, top_k=None, top_p=None):
+                    want_next=True, want_logits=False, top_k=None, top_p=None, confident=False):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation).  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation); ``confident``: the tail launch is the confidence-ordered one (spk_den_step_tail_conf).  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -976,6 +1022,10 @@ class DummyModel(nn.Module):
         if top_p is not None:
             trunc['top_p'] = top_p
         with ops.timed('den.tail'):
+            if confident:
+                return ops.den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
+                                              K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,
+                                              conv1=nxt, want_logits=want_logits, **trunc)
             return ops.den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
                                      K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,
                                      conv1=nxt, want_logits=want_logits, **trunc)

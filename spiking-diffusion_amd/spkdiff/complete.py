@@ -75,7 +75,17 @@ def complete_images_top_p(model, sampler, images, keep, top_p, temp=1.0, sample_
     return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p)
 
 
-def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None):
+@torch.no_grad()
+def complete_images_confident(model, sampler, images, keep, sample_steps=None, temp=1.0, T=16, paste=True, top_k=None, top_p=None):
+    """``complete_images`` with the unknown tokens revealed in the order of the denoiser's confidence (DESIGN.md §4.15;
+    ``AbsorbingDiffusion.sample_confident``): every step commits the ceil(m / t) surest candidates of each image, m counting the
+    positions still unknown, so a few steps serve a small hole.  ``temp`` / ``top_k`` / ``top_p`` as sample_confident() takes them.
+    The known tokens are never drawn, so they come back unchanged; with nothing known the tokens are sample_confident()'s under
+    the same key."""
+    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p, confident=True)
+
+
+def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None, confident=False):
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)
     h, w = H // 4, W // 4
@@ -84,7 +94,9 @@ def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k,
     codes = model.encode_images(images, T)
     x_init, known, n_known = ops.completion_state(codes, keep, int(sampler.num_classes), int(sampler.mask_id), ENC_STRIDE,
                                                   ENC_RADIUS, want_counts=True)
-    if top_p is not None:
+    if confident:
+        tokens = sampler.sample_confident(sample_steps=sample_steps, temp=temp, x_init=x_init, known=known, top_k=top_k, top_p=top_p)
+    elif top_p is not None:
         tokens = sampler.sample_top_p(top_p, temp=temp, sample_steps=sample_steps, x_init=x_init, known=known, top_k=top_k)
     elif top_k is None:
         tokens = sampler.sample(temp=temp, sample_steps=sample_steps, x_init=x_init, known=known)

@@ -87,19 +87,26 @@ def _per_image(v):
     return isinstance(v, (list, tuple)) or (getattr(v, 'ndim', 0) == 1 and len(v) > 1)
 
 
-def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None, top_p=None):
+def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None, top_p=None,
+                            confident=False):
     """``spkdiff.complete.complete_images`` of one job over the ranks: every rank holds the whole job's ``images`` / ``keep``,
     completes its ``shard_range`` of them as a shard of the job (``set_shard``: shared key, counters on the global image index,
     so the images do not depend on the split) and one gather returns all uint8 images [total, C, H, W] on every rank.
     ``temp``: a number, or one temperature per image of the whole job (every rank passes the whole vector; a rank uses its
     shard's slice).  ``top_k``: None, an int >= 1 or one k per image of the whole job, sliced in the same way
     (``spkdiff.complete.complete_images_top_k``); ``top_p``: None, a number in (0, 1] or one p per image of the
-    whole job, sliced likewise (``spkdiff.complete.complete_images_top_p``)."""
-    from .complete import complete_images, complete_images_top_k, complete_images_top_p
+    whole job, sliced likewise (``spkdiff.complete.complete_images_top_p``).  ``confident``: every shard reveals
+    in the order of the denoiser's confidence (``spkdiff.complete.complete_images_confident`` with the same ``temp`` / ``top_k`` /
+    ``top_p``); False: the calls made before."""
+    from .complete import complete_images, complete_images_confident, complete_images_top_k, complete_images_top_p
     per_image, per_image_k, per_image_p = _per_image(temp), _per_image(top_k), _per_image(top_p)
 
     def generate_local(lo, hi):
         tl = temp[lo:hi] if per_image else temp
+        if confident:
+            return complete_images_confident(model, sampler, images[lo:hi], keep[lo:hi], sample_steps=sample_steps, temp=tl, T=T,
+                                             paste=paste, top_k=top_k[lo:hi] if per_image_k else top_k,
+                                             top_p=top_p[lo:hi] if per_image_p else top_p).images_u8
         if top_p is not None:
             return complete_images_top_p(model, sampler, images[lo:hi], keep[lo:hi], top_p[lo:hi] if per_image_p else top_p, temp=tl,
                                          sample_steps=sample_steps, T=T, paste=paste,

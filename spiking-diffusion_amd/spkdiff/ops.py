@@ -2161,6 +2161,96 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     return (None if x1 is None else (x1, c1o)), logits
 
 
+def _conf_args(temp, top_k, top_p, B, what, device):
+    """The three per-image arrays of a confidence-ordered token update after the checks of the ``_topp`` siblings
+    (``_topp_arg`` / ``_topk_arg``: ``top_k`` / ``top_p``, where given, are device tensors of B entries -- a number is refused as
+    the siblings refuse it): a missing ``top_p`` becomes ones and a missing ``top_k`` zeros (neither truncates), a scalar ``temp``
+    (> 0) is broadcast, a per-image ``temp`` is taken as given -> (temp_b, top_k, top_p).  There is no active-list form: inside an ``active_set`` scope the call is
+    refused before anything is launched."""
+    if ACTIVE is not None:
+        raise ValueError(f"{what}: the confidence-ordered reveal has no active-list form (which positions change depends on the "
+                         "logits): call it outside an active_set scope")
+    B = int(B)
+    # scalar or vector as ``_topk_arg`` decides it: a device tensor of B entries is per-image and never read back (B = 1 too: the
+    # sampler hands its graph's one-entry buffer down, and a read-back is refused inside a capture)
+    per_image = isinstance(temp, torch.Tensor) and (temp.numel() > 1 or (temp.is_cuda and temp.dim() == 1 and temp.numel() == B))
+    if not per_image and not float(temp) > 0:
+        raise ValueError(f"{what}: temp must be > 0 (what the scalar entry points check), got {float(temp)}")
+    if top_p is None:
+        top_p = torch.ones(B, dtype=torch.float32, device=device)
+    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, what, device)
+    top_k, temp_b = _topk_arg(top_k, temp, B, what, device)
+    return temp_b, top_k, top_p
+
+
+def _conf_out(conf, n):
+    if conf is not None and (not isinstance(conf, torch.Tensor) or conf.dtype != torch.float32 or not conf.is_cuda or
+                             not conf.is_contiguous() or conf.numel() != n):
+        raise ValueError("conf must be a contiguous fp32 device tensor with one entry per position (written where a position is masked)")
+    return conf
+
+
+def _x0_hat_out(x0_hat, n):
+    if x0_hat is not None and (not isinstance(x0_hat, torch.Tensor) or x0_hat.dtype != torch.int64 or not x0_hat.is_cuda or
+                               not x0_hat.is_contiguous() or x0_hat.numel() != n):
+        raise ValueError("x0_hat must be a contiguous int64 device tensor with one entry per position (written where a position is masked)")
+    return x0_hat
+
+
+def psample_step_conf(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, conf=None,
+                      philox_state=None, next_input=None, top_k=None, top_p=None):
+    """``psample_step`` under the confidence-ordered reveal (spk_psample_step_conf): every position masked at entry
+    draws the candidate ``psample_step(..., top_k, top_p, x0_hat=)`` reports for it, and the ceil(m / t) candidates of each image
+    with the largest log-probability (ties to the lower position) are committed; x_t / unmasked in place.  ``x0_hat`` (int64) /
+    ``conf`` (fp32): optional outputs, written at the masked positions only.  ``u`` is accepted and ignored (the coin is not part
+    of the rule).  ``temp`` / ``top_k`` / ``top_p`` as for psample_step: ``top_k`` (int32) and ``top_p`` (fp32) are device
+    tensors with one entry per image or None, ``temp`` a number or such a tensor.  The entry point takes all three per image, so a
+    scalar ``temp`` is broadcast and a missing truncation becomes k = 0 / p = 1 everywhere.  Not inside an ``active_set`` scope; h * w <= 64."""
+    logits = _dev(logits, "logits", torch.float32)
+    B, K = logits.shape[0], logits.shape[1]
+    HW = logits[0, 0].numel()
+    n = B * HW
+    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // HW, "psample_step_conf", logits.device)
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
+    next_input = _next_input_arg(next_input, n)
+    check(lib.spk_psample_step_conf(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
+                                    int(seed), int(offset), _p(philox_state), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)),
+                                    B, HW, K, _p(next_input), _stream(logits)), "spk_psample_step_conf")
+    return x_t, unmasked
+
+
+def den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
+                       conv1=None, want_logits=False, top_k=None, top_p=None, x0_hat=None, conf=None):
+    """``den_step_tail`` under the confidence-ordered reveal (spk_den_step_tail_conf): conv6 on the counts, the token update of
+    ``psample_step_conf`` and -- with ``conv1`` -- the next step's first layer on the committed tokens, one launch.  Same
+    arguments, checks and results as den_step_tail, plus the optional outputs ``x0_hat`` / ``conf`` of psample_step_conf; not
+    inside an ``active_set`` scope."""
+    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
+    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
+    B, nch5, H, W, _ = cnt5.shape
+    n = B * H * W
+    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // (H * W), "den_step_tail_conf", cnt5.device)
+    wq, scale, bias_d = packed6
+    _token_state(x_t, unmasked, n, "[B,1,h,w]")
+    u, q = _step_noise(u, q, philox_state, n, int(K))
+    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
+    x1 = c1o = w1 = b1 = a1 = bb1 = None
+    if conv1 is not None and int(T) != 16:
+        raise NotImplementedError("spk_den_step_tail_conf: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
+                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
+    if conv1 is not None:
+        w1, b1, a1, bb1 = conv1
+        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
+        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
+    check(lib.spk_den_step_tail_conf(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
+                                     _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
+                                     int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W,
+                                     int(K), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), _stream(cnt5)),
+          "spk_den_step_tail_conf")
+    return (None if x1 is None else (x1, c1o)), logits
+
+
 def q_sample(x_0, t, u, num_timesteps, mask_id):
     """(x_t, x_0_ignore, mask) of R/snn_model/vq_diffusion.py:61-75 from x_0 fp32 [B,1,h,w], t int64 [B] and the uniforms u
     (spk_q_sample: one launch)."""
