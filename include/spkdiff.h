@@ -37,7 +37,8 @@ typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
                            * predicates spk_*_supported / spk_vae_fp6_kind: 106); spkdiff/_lib.py reads its signatures from this header and
                            * refuses a library whose spk_version() differs.  Purely additive entry points (the SNN_VAE
                            * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
-                           * symbol at import, so a library that lacks one fails there */
+                           * symbol at import, so a library that lacks one fails there; so do spk_select_pending /
+                           * spk_psample_step_conf_listed, DESIGN.md §4.16: additive, still 106) */
 
 /* return codes below zero (0: success; above zero: a hipError_t) */
 #define SPK_ERR_ARG (-1)         /* bad argument: null pointer, non-positive size, contradictory combination */
@@ -698,13 +699,44 @@ int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_inout, uint8_
  * x0_hat_out (the candidates) and conf_out (the confidences) are written at the positions masked at entry and nowhere else.
  * next_input_b2hw_or_null is written from the committed state.  One workgroup per image, no global workspace, no selection noise;
  * HW > 64: SPK_ERR_UNSUPPORTED with nothing launched; K <= 2048.  There is no active-list form -- which positions change depends
- * on the logits, so no image and no position can be ruled out ahead of the denoiser -- and no score form.  Deterministic, split
+ * on the logits, so no position can be ruled out ahead of the denoiser, and with one step count for the batch no image either
+ * (per-image step counts: spk_psample_step_conf_listed below) -- and no score form.  Deterministic, split
  * independent (the draws are the sibling's), capturable in a hipGraph; allocates nothing. */
 int spk_psample_step_conf(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
                           const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
                           unsigned long long philox_seed, unsigned long long philox_offset,
                           const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null, float* conf_out_or_null,
                           int B, int HW, int K, float* next_input_b2hw_or_null, spk_stream_t stream);
+/* Per-image step counts for confidence-ordered decoding: spk_select_pending and spk_psample_step_conf_listed.
+ * THE rule.  Let S be the step count of the loop (t = S .. 1), steps_b[i] (int32 [B], device, indexed by IMAGE) the count of image
+ * i and e_i = min(steps_b[i], S).  At reverse step t image i is PENDING iff 1 <= t <= e_i and at least one of its positions is
+ * masked; steps_b[i] < 1: never.  A pending image takes exactly the update of spk_psample_step_conf with this t -- a candidate at
+ * every masked position, then the commit of the ceil(m / t) surest; a non-pending image is not read, not evaluated and not written.
+ * Noise: image i draws the counters it would draw ALONE in a run of e_i steps -- its step index at loop step t is e_i - t, not
+ * S - t -- so with the caller's per-step counter stride step_stride (2^40 in the sampler's 'global' layout) the kernel uses
+ * philox_offset - (S - e_i) * step_stride for image i, in unsigned 64-bit arithmetic, plus the philox_state base as before; for a
+ * pending image that is philox_offset's shard base + (e_i - t) * step_stride and never wraps.  An injected q is used as given.
+ * Hence image i of a per-image run equals, bit for bit, image i of a run of e_i steps with the same key, global index, temperature /
+ * k / p and start state, whatever S and the other images' counts are.
+ *
+ * spk_select_pending writes the ascending list of pending images and its length in spk_select_active's output contract
+ * (active_out [B] int32; n_active_out [2] int32: [0] the length, [1] a work word ZERO before the first call and left zero;
+ * deterministic slots), from `unmasked` and steps_b alone: it draws no noise.  HW > 64: SPK_ERR_UNSUPPORTED.
+ *
+ * spk_psample_step_conf_listed takes the arguments of spk_psample_step_conf without next_input_b2hw, plus steps_b, S, step_stride
+ * and the list (all four pointers required; 1 <= t <= S).  Workgroup s serves slot s and returns at once past *n_active (clamped to
+ * B).  logits_skhw hold one slot per listed image (slot s = image active[s]); x_t, unmasked, temp_b / topk_b / topp_b, steps_b, the
+ * noise and x0_hat_out / conf_out are indexed by image active[s].  A listed image with t > e_i is left as it is.  A separate
+ * kernel: spk_psample_step_conf and spk_den_step_tail_conf keep their code paths, signatures and results.  HW <= 64, K <= 2048;
+ * argument errors before any launch; capturable; allocates nothing.  There is no fused step tail on the list. */
+int spk_select_pending(const uint8_t* unmasked, int t, const int* steps_b, int* active_out, int* n_active_out, int B, int HW,
+                       spk_stream_t stream);
+int spk_psample_step_conf_listed(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                                 const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
+                                 unsigned long long philox_seed, unsigned long long philox_offset,
+                                 const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                 float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                                 unsigned long long step_stride, const int* active, const int* n_active, spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p

@@ -87,8 +87,8 @@ __global__ __launch_bounds__(256) void psample_kernel(const float* __restrict__ 
 // image, no global workspace.  The four waves stride over the image's positions and run the `_topp` family's draw at every
 // position masked at entry (candidate -> x0_hat_out, confidence -> conf_out, candidate and order key -> LDS); behind a barrier
 // wave 0 -- lane = position -- ranks the keys, commits the n surest candidates and writes the next step's input from the
-// committed state.  HW <= 64 (the host checks).  The stream-0 uniform is not drawn; there is no active-list form: which
-// positions change depends on the logits.
+// committed state.  HW <= 64 (the host checks).  The stream-0 uniform is not drawn.  Which POSITIONS change depends on the
+// logits, so there are no position lists; which IMAGES have nothing to do does not (psample_conf_listed_kernel below).
 template <int KPL>
 __global__ __launch_bounds__(256) void psample_conf_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
                                                            uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
@@ -135,6 +135,66 @@ __global__ __launch_bounds__(256) void psample_conf_kernel(const float* __restri
   if (next_input && lane < HW) write_next_input(next_input, b, lane, HW, reveal ? (float)s_cand[lane] : (float)x_t[p], t_next);
 }
 
+// The same update on the list of PENDING images (spk_psample_step_conf_listed; the rule: include/spkdiff.h):
+// workgroup s serves slot s of the list spk_select_pending wrote and returns at once past its length.  The logits lie by slot;
+// state, noise, the per-image arrays and the two outputs by image b = active[s].  Image b runs e = min(steps_b[b], S) steps of
+// its own inside a loop of S, so its step index at loop step t is e - t, not S - t: it draws at offset - (S - e) * step_stride,
+// the counters it would draw alone in a run of e steps.  An image with t > e is not pending and is left as it is whatever the
+// list says.  No next_input: the listed form gathers its denoiser input by slot.  A kernel of its own -- the body is the dense
+// kernel's with the two indices apart -- so that psample_conf_kernel keeps the instruction stream it has.
+template <int KPL>
+__global__ __launch_bounds__(256) void psample_conf_listed_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
+                                                                  uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
+                                                                  const float* __restrict__ q_in, unsigned long long seed,
+                                                                  unsigned long long offset,
+                                                                  const unsigned long long* __restrict__ philox_state,
+                                                                  long long* __restrict__ x0_hat_out, float* __restrict__ conf_out,
+                                                                  const int* __restrict__ steps_b, int S,
+                                                                  unsigned long long step_stride, const int* __restrict__ active,
+                                                                  const int* __restrict__ n_active, int B, int HW, int K) {
+  __shared__ int s_cand[64];
+  __shared__ uint32_t s_key[64];
+  const int s = blockIdx.x;                                         // the logits' slot
+  if (s >= spk_active_count(active, n_active, B)) return;          // (workgroup-uniform, ahead of the barrier)
+  const int b = active[s];                                          // the image: state, noise, per-image arrays, outputs
+  const int sb = steps_b[b];
+  const int e = sb < S ? sb : S;
+  if (t > e) return;
+  philox_base(philox_state, seed, offset);
+  offset -= (unsigned long long)(S - e) * step_stride;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float tp = temp.temp[b];
+  const int topk = temp.topk[b];
+  const float topp = temp.topp[b];
+  for (int hw = wave; hw < HW; hw += 4) {
+    const long long p = (long long)b * HW + hw;
+    if (unmasked[p]) continue;                                      // (wave-uniform)
+    float l[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      const int k = lane + 64 * j;
+      const float lg = logits[((long long)s * K + (k < K ? k : K - 1)) * HW + hw];
+      l[j] = k < K ? lg / tp : -INFINITY;
+    }
+    truncate_top_k<KPL>(l, lane, K, topk);
+    truncate_top_p<KPL>(l, lane, K, topp);
+    float conf;
+    const int besti = categorical_race<KPL, true>(l, lane, K, q_in, seed, offset, p, &conf);
+    if (lane == 0) {
+      s_cand[hw] = besti;
+      s_key[hw] = spk_conf_key(conf);
+      if (x0_hat_out) x0_hat_out[p] = (long long)besti;
+      if (conf_out) conf_out[p] = conf;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const long long p = (long long)b * HW + (lane < HW ? lane : 0);
+  const bool masked = lane < HW && !unmasked[p];
+  const bool reveal = confident_reveal(masked, lane, HW, t, s_key);
+  if (reveal) { unmasked[p] = 1; x_t[p] = (long long)s_cand[lane]; }
+}
+
 // Denoiser input map, R/snn_model/vq_diffusion.py:195-197:  cat(x, ones_like(x) * t[:,None,None,None]) -> [B,2,h,w]
 // x comes either as float [B,1,h,w] (the module API) or as the int64 token state x_t of the sampler.
 __global__ void den_input_kernel(const float* __restrict__ xf, const long long* __restrict__ xi,
@@ -161,6 +221,28 @@ __global__ void den_input_kernel(const float* __restrict__ xf, const long long* 
 // (ticket) compacts the flags in place into the ordered list: slots are deterministic.  (The first form ran as ONE 1024-thread
 // workgroup with a chain of conditional loads per thread: 10.7 us per reverse step.)  The ticket is n_active[1]: zero before the
 // first call, left zero by every call (the caller's buffer, so calls on different streams with different buffers do not meet).
+
+// The end of a select kernel (spk_select_active, spk_select_pending): every one-wave workgroup has written its images' flags to
+// active[b]; the workgroup that finishes last (ticket n_active[1]) compacts them in place into the ascending list, writes its
+// length to n_active[0] and re-arms the ticket.  Called by every lane of every workgroup.
+__device__ __forceinline__ void compact_flags_by_last(int* __restrict__ active, int* __restrict__ n_active, int B, int lane) {
+  __threadfence();
+  int last = 0;
+  if (lane == 0) last = atomicAdd(reinterpret_cast<unsigned*>(n_active + 1), 1u) == gridDim.x - 1 ? 1 : 0;
+  last = __shfl(last, 0);
+  if (!last) return;
+  __threadfence();
+  int base = 0;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int bi = b0 + lane;
+    const int fl = bi < B ? __hip_atomic_load(&active[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    const unsigned long long m = __ballot(fl != 0);
+    // (every lane of the wave has read its flag before any lane writes: list entries land at or below b0 + lane)
+    if (fl) active[base + __popcll(m & ((1ull << lane) - 1ull))] = bi;
+    base += __popcll(m);
+  }
+  if (lane == 0) { n_active[0] = base; n_active[1] = 0; }
+}
 
 __global__ __launch_bounds__(64) void select_active_kernel(const uint8_t* __restrict__ unmasked, int t,
                                                            const float* __restrict__ u_in, unsigned long long seed,
@@ -199,22 +281,33 @@ __global__ __launch_bounds__(64) void select_active_kernel(const uint8_t* __rest
   int f = any ? 1 : 0;
   f |= __shfl_xor(f, 1); f |= __shfl_xor(f, 2); f |= __shfl_xor(f, 4);
   if (q == 0 && b < B) active[b] = f;
-  __threadfence();
-  int last = 0;
-  if (lane == 0) last = atomicAdd(reinterpret_cast<unsigned*>(n_active + 1), 1u) == gridDim.x - 1 ? 1 : 0;
-  last = __shfl(last, 0);
-  if (!last) return;
-  __threadfence();
-  int base = 0;
-  for (int b0 = 0; b0 < B; b0 += 64) {
-    const int bi = b0 + lane;
-    const int fl = bi < B ? __hip_atomic_load(&active[bi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    const unsigned long long m = __ballot(fl != 0);
-    // (every lane of the wave has read its flag before any lane writes: list entries land at or below b0 + lane)
-    if (fl) active[base + __popcll(m & ((1ull << lane) - 1ull))] = bi;
-    base += __popcll(m);
+  compact_flags_by_last(active, n_active, B, lane);
+}
+
+// Which images are PENDING at reverse step t of per-image confidence-ordered decoding (spk_select_pending)?
+// Image b is pending iff 1 <= t <= steps_b[b] and at least one of its positions is masked -- no noise, no logits: the ceil(m / t)
+// rule needs nothing but t, so a non-pending image can be left out of the step exactly.  The launch shape of select_active_kernel:
+// eight threads per image over its `unmasked` bytes (h*w <= 64), flags, the shared compaction.
+__global__ __launch_bounds__(64) void select_pending_kernel(const uint8_t* __restrict__ unmasked, int t,
+                                                            const int* __restrict__ steps_b, int* __restrict__ active,
+                                                            int* __restrict__ n_active, int B, int HW) {
+  const int lane = threadIdx.x;
+  const int gid = blockIdx.x * 64 + lane;
+  const int b = gid >> 3, q = gid & 7;
+  bool any = false;
+  if (b < B) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int hw = q + 8 * k;
+      const uint8_t ld = unmasked[(long long)b * HW + (hw < HW ? hw : 0)];
+      any = any || (hw < HW && !ld);
+    }
+    any = any && t <= steps_b[b];
   }
-  if (lane == 0) { n_active[0] = base; n_active[1] = 0; }
+  int f = any ? 1 : 0;
+  f |= __shfl_xor(f, 1); f |= __shfl_xor(f, 2); f |= __shfl_xor(f, 4);
+  if (q == 0 && b < B) active[b] = f;
+  compact_flags_by_last(active, n_active, B, lane);
 }
 
 // Which POSITIONS of an active image does reverse step t need from each denoiser layer?  The sampler reads the logits only
@@ -381,6 +474,16 @@ extern "C" int spk_select_active(const uint8_t* unmasked, int t, const float* u_
   return SPK_OK;
 }
 
+extern "C" int spk_select_pending(const uint8_t* unmasked, int t, const int* steps_b, int* active_out, int* n_active_out, int B,
+                                  int HW, hipStream_t stream) {
+  if (!unmasked || !steps_b || !active_out || !n_active_out || t <= 0 || B <= 0 || HW <= 0) return SPK_ERR_ARG;
+  if (HW > 64) return SPK_ERR_UNSUPPORTED;                      // (eight threads x eight positions; the listed update's own limit)
+  hipLaunchKernelGGL(select_pending_kernel, dim3((B * 8 + 63) / 64), dim3(64), 0, stream, unmasked, t, steps_b, active_out,
+                     n_active_out, B, HW);
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+
 extern "C" int spk_den_build_input(const float* x_float_or_null, const long long* x_tokens_or_null,
                                    const long long* t_vec_or_null, long long t_scalar, float* out_b2hw, int B, int HW,
                                    const int* active_or_null, const int* n_active_or_null, hipStream_t stream) {
@@ -494,6 +597,33 @@ extern "C" int spk_psample_step_conf(const float* logits_bkhw, long long* x_t_in
   else if (K <= 1024) SPK_PSAMPLE_CONF_LAUNCH(16);
   else SPK_PSAMPLE_CONF_LAUNCH(32);
 #undef SPK_PSAMPLE_CONF_LAUNCH
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+
+// The confidence-ordered update on the list of pending images, each at its own step count (include/spkdiff.h).
+extern "C" int spk_psample_step_conf_listed(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                            const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                            const float* q_or_null, unsigned long long philox_seed,
+                                            unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                            long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K,
+                                            const int* steps_b, int S, unsigned long long step_stride, const int* active,
+                                            const int* n_active, hipStream_t stream) {
+  (void)u_or_null;
+  const spk_temp_topp temp{temp_b, topk_b, topp_b};
+  if (!logits_skhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 ||
+      K <= 0 || !steps_b || !active || !n_active || S <= 0 || t > S)
+    return SPK_ERR_ARG;
+  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
+#define SPK_PSAMPLE_CONF_LISTED_LAUNCH(KPL)                                                                              \
+  hipLaunchKernelGGL((psample_conf_listed_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits_skhw, x_t_inout, unmasked_inout, t, \
+                     temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, \
+                     steps_b, S, step_stride, active, n_active, B, HW, K)
+  if (K <= 256) SPK_PSAMPLE_CONF_LISTED_LAUNCH(4);
+  else if (K <= 512) SPK_PSAMPLE_CONF_LISTED_LAUNCH(8);
+  else if (K <= 1024) SPK_PSAMPLE_CONF_LISTED_LAUNCH(16);
+  else SPK_PSAMPLE_CONF_LISTED_LAUNCH(32);
+#undef SPK_PSAMPLE_CONF_LISTED_LAUNCH
   SPK_LAUNCH_CHECK();
   return SPK_OK;
 }

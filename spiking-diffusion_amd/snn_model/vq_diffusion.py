@@ -97,7 +97,7 @@ class Score(NamedTuple):
 
 
 class _SamplerGraph:
-    """One captured reverse process: the graph, its inputs (``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
+    """One captured reverse process: the graph, its inputs (``steps`` = int32 [B] of a per-image-steps graph; ``state`` = {seed, counter base}; ``start_in`` = (codes, keep) of the
     conditional form; ``temps`` = fp32 [B] of a per-image-temperature graph; ``topk`` = int32 [B] of a truncating graph (which always has ``temps`` too); ``topp`` = fp32 [B] of a nucleus graph (which always has both); ``target[0]`` = the tokens a score graph is forced to, which are also its ``codes``), its result ``x_t`` (a
     score graph: ``target[1:]`` = (logp, step), zeroed inside the graph), and every other buffer the captured launches address by raw pointer: freed earlier,
     its block would go to the next allocation while replays keep writing to it.  That includes the denoiser's derived tensors
@@ -105,9 +105,11 @@ class _SamplerGraph:
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
     def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False,
-                 confident=False):
+                 confident=False, per_image_steps=False):
         self.graph = self.derived = None                            # set by the capture
         self.confident = bool(confident)                            # the captured token updates are the confidence-ordered ones (§4.15)
+        # per-image step counts (DESIGN.md §4.16) are one more INPUT: the captured select_pending / listed updates read this buffer
+        self.steps = torch.ones(b, dtype=torch.int32, device=dev) if per_image_steps else None
         self.state = torch.zeros(2, dtype=torch.int64, device=dev)
         # per-image temperatures are one more INPUT: the captured token updates read this buffer, filled before each replay
         self.temps = torch.ones(b, dtype=torch.float32, device=dev) if per_image_temp or top_k or top_p else None
@@ -311,15 +313,58 @@ class AbsorbingDiffusion(Sampler):
         tokens, and one captured graph per (batch, steps, conditional) serves every temperature, k and p.  The launch form is the
         dense one whatever ``skip_untouched`` says (fused step tail where the denoiser allows it): which positions change depends
         on the logits, so no image and no position can be ruled out before the denoiser ran.  Latents of more than 64 positions:
-        NotImplementedError before anything is launched.  ``score()`` has no such form."""
+        NotImplementedError before anything is launched.  ``score()`` has no such form.
+
+        Per-image step counts: ``sample_steps`` may be a sequence or 1-D tensor of B integers >= 1, one per image
+        of the call (``_steps_arg``; a device tensor is read back once, before the key is drawn).  The loop runs S = max of them
+        steps; image i joins at t = s_i and is revealed by the ceil(m / t) rule from there, with the noise counters of its own run
+        (step index s_i - t): under the 'global' layout image i equals, bit for bit, image i of ``sample_confident(s_i, ...)`` with
+        the same key, global index, temperature / k / p and start state, whatever the other images' counts are -- so the result
+        depends neither on the batch nor on the split.  Every step runs on the device-side list of PENDING images (t <= s_i and
+        something still masked: spk_select_pending) -- the denoiser on the list, spk_psample_step_conf_listed for the update -- so
+        the work is proportional to the sum of the s_i (an image with nothing masked is never evaluated).  In a captured graph the
+        vector is an input: one graph per (batch, S, conditional) serves every vector with that maximum.  Refused before a key is
+        drawn: ``record=``, the 'rank' layout, a wrong length, an entry < 1 (ValueError).  An int takes the path above unchanged."""
         h, w = self.shape
         if h * w > 64:
             raise NotImplementedError(f'spkdiff: sample_confident() ranks an image\'s positions in one wave: h * w <= 64, got {h} x {w}')
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p, confident=True)
 
+    @staticmethod
+    def _steps_arg(sample_steps, b):
+        """The ``sample_steps`` of sample_confident() for a batch of ``b``: None or anything that is one integer (a Python or numpy
+        integer, a 0-dim tensor or array) is the one-count call -- returned as it came; a list / tuple or a 1-D tensor / array is one
+        count per image -- ``b`` integers >= 1 (ValueError otherwise), returned as a CPU int32 tensor [b] (a device tensor: its one
+        read-back)."""
+        if sample_steps is None or not (isinstance(sample_steps, (list, tuple)) or getattr(sample_steps, 'ndim', 0) >= 1):
+            return sample_steps
+        on_device = isinstance(sample_steps, torch.Tensor) and sample_steps.is_cuda
+        got = f'a device tensor {sample_steps.dtype} {tuple(sample_steps.shape)}' if on_device else repr(sample_steps)
+        bad = ValueError(f'spkdiff: per-image sample_steps takes one integer >= 1 per image of the call ({b}), got {got}')
+        try:
+            v = sample_steps.detach().cpu() if isinstance(sample_steps, torch.Tensor) else torch.as_tensor(sample_steps)
+        except (TypeError, ValueError, RuntimeError):
+            raise bad from None
+        if v.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise bad
+        if v.dim() != 1 or int(v.numel()) != b or bool((v < 1).any()) or bool((v > 0x7FFFFFFF).any()):
+            raise bad
+        return v.to(torch.int32)
+
     def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None, confident=False):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
+        steps_b = None
+        if confident:
+            sample_steps = self._steps_arg(sample_steps, b)
+            if isinstance(sample_steps, torch.Tensor) and sample_steps.dim() == 1:
+                # per-image step counts (DESIGN.md §4.16): the loop runs the largest, every image its own
+                if record is not None:
+                    raise ValueError('spkdiff: sample_confident() with per-image sample_steps takes no record= (a record holds the '
+                                     'logits of every image at every step; the steps run on the pending images only)')
+                if self.noise_layout != 'global':
+                    raise ValueError("spkdiff: per-image sample_steps needs the 'global' noise layout (one counter stride per step)")
+                steps_b, sample_steps = sample_steps, int(sample_steps.max())
         temp = self._temp_arg(temp, b)
         top_k = self._topk_arg(top_k, b)
         top_p = self._topp_arg(top_p, b)
@@ -347,6 +392,8 @@ class AbsorbingDiffusion(Sampler):
             raise ValueError(f'spkdiff: x_init / known must be on the denoiser\'s device {dev}')
         if sample_steps is None:
             sample_steps = self.num_timesteps
+        if steps_b is not None:
+            steps_b = steps_b.to(dev)
         seed = 0
         if noise is None and self.noise_source == 'philox':
             seed = self._philox_key()
@@ -355,8 +402,12 @@ class AbsorbingDiffusion(Sampler):
         form = self._form(b, h, w, record is not None)
         if confident:
             form = SampleForm(skip=False, lists=False, tail=dn.tail_fusable(h, w), tail_act=False)
+        if steps_b is not None:
+            # the pending images as an active list; no position lists (which positions change depends on the logits), no step tail
+            form = SampleForm(skip=True, lists=False, tail=False, tail_act=False)
         return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k,
-                                     **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
+                                     **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
+                                     **({} if steps_b is None else {'steps_b': steps_b}))
 
     def _topp_arg(self, top_p, b):
         """The ``top_p`` of sample_top_p() for a batch of ``b``, checked before anything is drawn or launched.  None: no nucleus
@@ -532,14 +583,15 @@ class AbsorbingDiffusion(Sampler):
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
     def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None,
-                         top_p=None, confident=False):
+                         top_p=None, confident=False, steps_b=None):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
             try:
                 return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k,
                                             **({} if top_p is None else {'top_p': top_p}),
-                                            **({'confident': True} if confident else {}))
+                                            **({'confident': True} if confident else {}),
+                                            **({} if steps_b is None else {'steps_b': steps_b}))
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -558,10 +610,11 @@ class AbsorbingDiffusion(Sampler):
             finally:
                 self._capturing = False
         return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k,
-                                  **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
+                                  **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
+                                  **({} if steps_b is None else {'steps_b': steps_b}))
 
     def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
-                      top_k=None, top_p=None, confident=False):
+                      top_k=None, top_p=None, confident=False, steps_b=None):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
@@ -577,7 +630,8 @@ class AbsorbingDiffusion(Sampler):
                 noise = lambda t: (torch.rand(b, 1, h, w).to(dev), None)      # noqa: E731
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
         self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
-                            top_k=top_k, **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}))
+                            top_k=top_k, **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
+                            **({} if steps_b is None else {'steps_b': steps_b}))
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -589,7 +643,7 @@ class AbsorbingDiffusion(Sampler):
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
     def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
-                       top_k=None, top_p=None, confident=False):
+                       top_k=None, top_p=None, confident=False, steps_b=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -601,7 +655,10 @@ class AbsorbingDiffusion(Sampler):
         update of sample_top_k() and to nothing else (None: the calls carry no such keyword); ``top_p``: fp32 device tensor [B] of
         sample_top_p(), handed on in the same way (then always with ``top_k``); ``confident``: sample_confident() -- the token update of
         every step is the confidence-ordered one (spk_den_step_tail_conf, or spk_psample_step_conf after the denoiser; always the
-        dense form, always with ``top_k`` and ``top_p``, never with ``target``)."""
+        dense form, always with ``top_k`` and ``top_p``, never with ``target``); ``steps_b``: int32 device tensor [B], the per-image
+        step counts of sample_confident() (``sample_steps`` is then their maximum S, ``form`` the elimination form
+        without lists or tails) -- every step runs on the list spk_select_pending writes: the denoiser by slot, then
+        spk_psample_step_conf_listed, which shifts image i's counters to those of its own run of min(steps_b[i], S) steps."""
         dn = self._denoise_fn
         trunc = {} if top_k is None else {'top_k': top_k}
         if top_p is not None:
@@ -615,7 +672,9 @@ class AbsorbingDiffusion(Sampler):
         for t in reversed(range(1, sample_steps + 1)):
             u, q = (None, None) if src.draw is None else src.draw(t)
             off = self._step_offset(sample_steps - t, b, h, w, K)
-            if form.skip:
+            if steps_b is not None:
+                act = ops.select_pending(unmasked, t, steps_b, out=act)
+            elif form.skip:
                 act = ops.select_active(unmasked, t, u, seed, off, philox_state=state, out=act, K=K)
                 if form.lists:
                     ops.select_needed(unmasked, t, act, need, u, seed, off, philox_state=state, K=K)
@@ -629,7 +688,10 @@ class AbsorbingDiffusion(Sampler):
                                                   want_next=form.tail and t > 1, want_logits=record is not None, **trunc)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
-                    if confident:
+                    if steps_b is not None:
+                        ops.psample_step_conf_listed(logits, x_t, unmasked, t, temp, steps_b, sample_steps, self.STEP_STRIDE, u, q,
+                                                     seed, off, philox_state=state, top_k=top_k, top_p=top_p)
+                    elif confident:
                         ops.psample_step_conf(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
                                               next_input=inp if t > 1 else None, top_k=top_k, top_p=top_p)
                     elif target is None:
@@ -774,7 +836,8 @@ class AbsorbingDiffusion(Sampler):
             self.invalidate()
         ws[1] = v
 
-    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None, confident=False):
+    def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None, confident=False,
+                   per_image_steps=False):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -786,7 +849,8 @@ class AbsorbingDiffusion(Sampler):
         return (str(dev), b, h, w, self.num_classes, temp, sample_steps, int(self.mask_id), form, int(self.list_radii),
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
                 conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ()) + \
-            (('top-p',) if top_p is not None else ()) + (('confident',) if confident else ())
+            (('top-p',) if top_p is not None else ()) + (('confident',) if confident else ()) + \
+            (('per-image-steps',) if per_image_steps else ())       # (sample_steps is then S, the vector's maximum)
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
@@ -797,10 +861,11 @@ class AbsorbingDiffusion(Sampler):
             g.target[2].zero_()
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
                             act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk,
-                            **({} if g.topp is None else {'top_p': g.topp}), **({'confident': True} if g.confident else {}))
+                            **({} if g.topp is None else {'top_p': g.topp}), **({'confident': True} if g.confident else {}),
+                            **({} if g.steps is None else {'steps_b': g.steps}))
 
     def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None,
-                        confident=False):
+                        confident=False, steps_b=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -813,17 +878,21 @@ class AbsorbingDiffusion(Sampler):
         a truncating graph -- a marker in the key, the vector copied into the graph's ``topk`` buffer before each replay.
         ``top_p`` (fp32 device tensor [B]; then with ``top_k``): a nucleus graph -- one more marker, one more input (``topp``).
         ``confident``: the graph of sample_confident() (a nucleus graph whose token updates are the confidence-ordered ones): one more
-        marker in the key, no further input."""
+        marker in the key, no further input.  ``steps_b`` (int32 device tensor [B]; then ``confident``, ``sample_steps`` = its maximum):
+        a per-image-steps graph -- one more marker, one more input (``steps``): one graph serves every vector with
+        the same maximum."""
         dn = self._denoise_fn
         key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p,
-                              **({'confident': True} if confident else {}))
+                              **({'confident': True} if confident else {}),
+                              **({} if steps_b is None else {'per_image_steps': True}))
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
                 self._graphs.clear()                                #  elimination forms): their buffers are not small
             g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
                               per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None,
-                              top_p=top_p is not None, **({'confident': True} if confident else {}))
+                              top_p=top_p is not None, **({'confident': True} if confident else {}),
+                              **({} if steps_b is None else {'per_image_steps': True}))
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -852,6 +921,8 @@ class AbsorbingDiffusion(Sampler):
             g.topk.copy_(top_k)
         if g.topp is not None:
             g.topp.copy_(top_p)
+        if g.steps is not None:
+            g.steps.copy_(steps_b)
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])

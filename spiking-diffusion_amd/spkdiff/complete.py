@@ -76,16 +76,36 @@ def complete_images_top_p(model, sampler, images, keep, top_p, temp=1.0, sample_
 
 
 @torch.no_grad()
-def complete_images_confident(model, sampler, images, keep, sample_steps=None, temp=1.0, T=16, paste=True, top_k=None, top_p=None):
+def complete_images_confident(model, sampler, images, keep, sample_steps=None, temp=1.0, T=16, paste=True, top_k=None, top_p=None,
+                              positions_per_step=None):
     """``complete_images`` with the unknown tokens revealed in the order of the denoiser's confidence (DESIGN.md §4.15;
     ``AbsorbingDiffusion.sample_confident``): every step commits the ceil(m / t) surest candidates of each image, m counting the
     positions still unknown, so a few steps serve a small hole.  ``temp`` / ``top_k`` / ``top_p`` as sample_confident() takes them.
     The known tokens are never drawn, so they come back unchanged; with nothing known the tokens are sample_confident()'s under
-    the same key."""
-    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p, confident=True)
+    the same key.
+    ``sample_steps`` may be one step count per image, as sample_confident() takes it: image i is completed as
+    ``sample_steps=s_i`` alone completes it, and every step evaluates the pending images only.  ``positions_per_step = r`` (an int
+    >= 1; not together with ``sample_steps``) chooses the counts from the holes: s_i = max(1, ceil(m_i / r)) with m_i = h * w -
+    n_known_i the number of unknown codes of image i, so every step commits at most r tokens per image, a 4-token hole takes one
+    step beside a full image's 13 (r = 4, 7 x 7), and an image with nothing to fill is never evaluated.  It costs ONE host read
+    (the ``n_known`` vector, B int32) ahead of the sampler call -- the only synchronisation of this function."""
+    if positions_per_step is not None:
+        if sample_steps is not None:
+            raise ValueError("complete_images_confident: give sample_steps or positions_per_step, not both")
+        if isinstance(positions_per_step, bool) or not isinstance(positions_per_step, int) or positions_per_step < 1:
+            raise ValueError(f"complete_images_confident: positions_per_step must be an int >= 1, got {positions_per_step!r}")
+    return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p, confident=True,
+                     positions_per_step=positions_per_step)
 
 
-def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None, confident=False):
+def steps_for_holes(n_unknown, positions_per_step):
+    """s_i = max(1, ceil(m_i / r)): the step counts ``positions_per_step = r`` gives holes of ``n_unknown`` = m_i positions (an
+    integer tensor; the result has its dtype and device)."""
+    r = int(positions_per_step)
+    return ((n_unknown + (r - 1)) // r).clamp(min=1)
+
+
+def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None, confident=False, positions_per_step=None):
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)
     h, w = H // 4, W // 4
@@ -94,6 +114,8 @@ def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k,
     codes = model.encode_images(images, T)
     x_init, known, n_known = ops.completion_state(codes, keep, int(sampler.num_classes), int(sampler.mask_id), ENC_STRIDE,
                                                   ENC_RADIUS, want_counts=True)
+    if positions_per_step is not None:
+        sample_steps = steps_for_holes(h * w - n_known.cpu().to(torch.int64), positions_per_step)     # (the one host read)
     if confident:
         tokens = sampler.sample_confident(sample_steps=sample_steps, temp=temp, x_init=x_init, known=known, top_k=top_k, top_p=top_p)
     elif top_p is not None:

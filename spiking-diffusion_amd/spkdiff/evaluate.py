@@ -10,7 +10,8 @@ buffer; after the last batch one vectorised epilogue rounds every slot to the fp
 own reverse process (``AbsorbingDiffusion.score``), again with one read at the end.
 
 ``temperature_sweep`` is the sampling sweep of R/main.py:379-443 (per temperature: many ``abdiff.sample(temp=tem)`` calls of 16
-images, decoded) run as ONE job with a per-image temperature."""
+images, decoded) run as ONE job with a per-image temperature; ``step_count_sweep`` is its counterpart over the
+step count of confidence-ordered decoding, one job with a per-image step count."""
 from __future__ import annotations
 
 import math
@@ -207,6 +208,52 @@ def temperature_sweep_top_p(model, sampler, temps, n_per_temp, top_p, sample_ste
     G, n = len(temps), int(n_per_temp)
     u8, tok = temperature_sweep_range(model, sampler, temps, n, 0, G * n, sample_steps=sample_steps, batch=batch, T=T, top_k=top_k,
                                       top_p=top_p)
+    return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
+
+
+@torch.no_grad()
+def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1.0, top_k=None, top_p=None):
+    """"How few steps are enough?" as ONE job: ``n_per_steps`` confidence-ordered samples for every entry of
+    ``steps`` (integers >= 1) -- image ``g * n_per_steps + j`` of the job runs ``steps[g]`` steps -- through
+    ``AbsorbingDiffusion.sample_confident`` with per-image step counts.  Returns (uint8 images [len(steps), n_per_steps, C, H, W],
+    tokens int64 [len(steps), n_per_steps, h, w]) on the device.  The job runs in calls of at most ``batch`` images whatever the
+    group boundaries (None: one call), each a shard of the job (``set_shard``) under ONE noise key (``_one_key``), every call at
+    the largest count among its images; image (g, j) is the image ``sample_confident(steps[g])`` gives at global index
+    ``g * n_per_steps + j`` under the sweep's key, so neither ``batch`` nor the grouping changes an image.  ``temp`` / ``top_k`` /
+    ``top_p``: one value for the whole job, as sample_confident() takes a number.  ``n_samples`` / ``global_first`` of the sampler
+    are restored."""
+    n = int(n_per_steps)
+    try:
+        sv = torch.as_tensor(steps)
+        ok = sv.dim() == 1 and sv.numel() >= 1 and sv.dtype in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64) and \
+            bool((sv >= 1).all())
+    except (TypeError, ValueError, RuntimeError):
+        ok = False
+    if not ok or n < 1:
+        raise ValueError(f"step_count_sweep: steps must be a sequence of integers >= 1 and n_per_steps >= 1, got {steps!r}, {n_per_steps!r}")
+    if getattr(sampler, "noise_source", "philox") != "philox":
+        raise ValueError("step_count_sweep: one job in several calls needs the counter-based noise (noise_source = 'philox')")
+    sv = sv.to(torch.int32).cpu().repeat_interleave(n)
+    total = int(sv.numel())
+    step = total if batch is None else int(batch)
+    if step < 1:
+        raise ValueError("step_count_sweep: batch must be >= 1 or None")
+    keep = (sampler.n_samples, sampler.global_first)
+    images, tokens = [], []
+    try:
+        sampler.set_shard(0, min(step, total))          # (declares the shard before the key is drawn: the broadcast rule)
+        with sampler._one_key():
+            for first in range(0, total, step):
+                count = min(step, total - first)
+                sampler.set_shard(first, count)
+                tok = sampler.sample_confident(sv[first:first + count], temp=temp, top_k=top_k, top_p=top_p)
+                tok = tok.reshape(count, tok.shape[-2], tok.shape[-1])
+                images.append(model.decode_tokens(tok, T, want_u8=True)[1])
+                tokens.append(tok)
+    finally:
+        sampler.n_samples, sampler.global_first = keep
+    u8, tok = torch.cat(images), torch.cat(tokens)
+    G = total // n
     return u8.reshape((G, n) + tuple(u8.shape[1:])), tok.reshape((G, n) + tuple(tok.shape[1:]))
 
 

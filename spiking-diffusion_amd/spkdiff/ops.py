@@ -2168,8 +2168,8 @@ def _conf_args(temp, top_k, top_p, B, what, device):
     (> 0) is broadcast, a per-image ``temp`` is taken as given -> (temp_b, top_k, top_p).  There is no active-list form: inside an ``active_set`` scope the call is
     refused before anything is launched."""
     if ACTIVE is not None:
-        raise ValueError(f"{what}: the confidence-ordered reveal has no active-list form (which positions change depends on the "
-                         "logits): call it outside an active_set scope")
+        raise ValueError(f"{what}: this entry point has no active-list form (which positions change depends on the logits): call it "
+                         "outside an active_set scope; the list of pending images is psample_step_conf_listed's")
     B = int(B)
     # scalar or vector as ``_topk_arg`` decides it: a device tensor of B entries is per-image and never read back (B = 1 too: the
     # sampler hands its graph's one-entry buffer down, and a read-back is refused inside a capture)
@@ -2217,6 +2217,76 @@ def psample_step_conf(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0
     check(lib.spk_psample_step_conf(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
                                     int(seed), int(offset), _p(philox_state), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)),
                                     B, HW, K, _p(next_input), _stream(logits)), "spk_psample_step_conf")
+    return x_t, unmasked
+
+
+def _steps_arg(steps_b, B, what):
+    """``steps_b`` of the per-image confidence-ordered calls: a contiguous int32 device tensor with one step count
+    per image of the call (index = image), taken as given."""
+    B = int(B)
+    if (not isinstance(steps_b, torch.Tensor) or steps_b.dtype != torch.int32 or not steps_b.is_cuda or not steps_b.is_contiguous() or
+            steps_b.dim() != 1 or steps_b.numel() != B):
+        got = f"{steps_b.dtype} {tuple(steps_b.shape)} on '{steps_b.device}'" if isinstance(steps_b, torch.Tensor) else repr(type(steps_b))
+        raise ValueError(f"{what}: steps_b must be a contiguous int32 device tensor of B = {B} entries, got {got}")
+    return steps_b
+
+
+def select_pending(unmasked, t, steps_b, out=None):
+    """Images PENDING at reverse step t of per-image confidence-ordered decoding (spk_select_pending): those with
+    t <= steps_b[i] and at least one masked position.  Returns select_active's pair (active int32 [B] ascending image list, n_active
+    int32 [2]: count and a work word) on the device -- a drop-in for ``active_set``; no noise is drawn.  h * w <= 64."""
+    if unmasked.dtype not in (torch.bool, torch.uint8) or not unmasked.is_cuda or not unmasked.is_contiguous():
+        raise ValueError("unmasked must be a contiguous bool/uint8 device tensor")
+    B = unmasked.shape[0]
+    HW = unmasked[0].numel()
+    steps_b = _steps_arg(steps_b, B, "select_pending")
+    if out is None:
+        out = (torch.empty(B, dtype=torch.int32, device=unmasked.device),
+               torch.zeros(2, dtype=torch.int32, device=unmasked.device))     # [count, work word (zero between calls)]
+    elif out[0].numel() < B or out[1].numel() < 2:
+        raise ValueError("out = (active int32 [B], n_active int32 [2]: count, work word (zero before the first call))")
+    check(lib.spk_select_pending(_p(unmasked), int(t), _p(steps_b), _p(out[0]), _p(out[1]), B, HW, _stream(unmasked)),
+          "spk_select_pending")
+    return out
+
+
+def psample_step_conf_listed(logits, x_t, unmasked, t, temp, steps_b, S, step_stride, u=None, q=None, seed=0, offset=0, x0_hat=None,
+                             conf=None, philox_state=None, top_k=None, top_p=None):
+    """``psample_step_conf`` on the list of the enclosing ``active_set`` scope (spk_psample_step_conf_listed; refused
+    outside one): ``logits`` [B,K,h,w] hold one SLOT per listed image, everything else -- x_t / unmasked, ``temp`` / ``top_k`` /
+    ``top_p``, ``steps_b`` (int32 device tensor, one step count per image), the noise, ``x0_hat`` / ``conf`` -- is indexed by image.
+    A listed image takes psample_step_conf's update at this ``t`` with the noise of its own run of e = min(steps_b[i], S) steps:
+    counters at ``offset - (S - e) * step_stride`` (``S``: the loop's step count, ``step_stride``: its counters per step);
+    images off the list keep their state.  No ``next_input``: the listed form gathers its denoiser input by slot."""
+    if ACTIVE is None:
+        raise ValueError("psample_step_conf_listed: the list of pending images comes from the enclosing active_set scope "
+                         "(ops.select_pending); outside one call psample_step_conf")
+    act, nact = ACTIVE
+    logits = _dev(logits, "logits", torch.float32)
+    K = logits.shape[1]
+    HW = logits[0, 0].numel()
+    B = x_t.numel() // HW
+    n = B * HW
+    if logits.shape[0] != B:
+        raise ValueError(f"psample_step_conf_listed: logits hold one slot per image of the batch ({B}), got {logits.shape[0]}")
+    top_p = torch.ones(B, dtype=torch.float32, device=logits.device) if top_p is None else top_p
+    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, "psample_step_conf_listed", logits.device)
+    per_image = isinstance(temp, torch.Tensor) and (temp.numel() > 1 or (temp.is_cuda and temp.dim() == 1 and temp.numel() == B))
+    if not per_image and not float(temp) > 0:
+        raise ValueError(f"psample_step_conf_listed: temp must be > 0 (what the scalar entry points check), got {float(temp)}")
+    top_k, temp_b = _topk_arg(top_k, temp, B, "psample_step_conf_listed", logits.device)
+    steps_b = _steps_arg(steps_b, B, "psample_step_conf_listed")
+    S, step_stride = int(S), int(step_stride)
+    if not 1 <= int(t) <= S or step_stride < 0:
+        raise ValueError(f"psample_step_conf_listed: 1 <= t <= S and step_stride >= 0, got t = {int(t)}, S = {S}, stride {step_stride}")
+    if act.numel() < B or nact.numel() < 2:
+        raise ValueError("psample_step_conf_listed: the active_set pair must hold B slots and two count words")
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
+    check(lib.spk_psample_step_conf_listed(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
+                                           int(seed), int(offset) & 0xFFFFFFFFFFFFFFFF, _p(philox_state), _p(_x0_hat_out(x0_hat, n)),
+                                           _p(_conf_out(conf, n)), B, HW, K, _p(steps_b), S, step_stride, _p(act), _p(nact),
+                                           _stream(logits)), "spk_psample_step_conf_listed")
     return x_t, unmasked
 
 
