@@ -38,7 +38,7 @@ typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
                            * refuses a library whose spk_version() differs.  Purely additive entry points (the SNN_VAE
                            * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
                            * symbol at import, so a library that lacks one fails there; so do spk_select_pending /
-                           * spk_psample_step_conf_listed, DESIGN.md §4.16: additive, still 106) */
+                           * spk_psample_step_conf_listed, DESIGN.md §4.16, and the three `_sched` entry points, §4.17: additive, still 106) */
 
 /* return codes below zero (0: success; above zero: a hipError_t) */
 #define SPK_ERR_ARG (-1)         /* bad argument: null pointer, non-positive size, contradictory combination */
@@ -737,6 +737,45 @@ int spk_psample_step_conf_listed(const float* logits_skhw, long long* x_t_inout,
                                  const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
                                  float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
                                  unsigned long long step_stride, const int* active, const int* n_active, spk_stream_t stream);
+/* Reveal schedules and annealed selection noise for confidence-ordered decoding (the rule: csrc/psample_common.h):
+ * spk_psample_step_conf_sched, spk_psample_step_conf_listed_sched and spk_den_step_tail_conf_sched take the arguments of their
+ * `_conf` siblings plus `const uint32_t* sched_w` (required), `const float* noise_a_or_null`, `int S` (where the sibling has none)
+ * and `float* score_out_or_null` (fp32 [B*HW], written at the positions masked at entry).  Everything of the `_conf` rule stays --
+ * the candidates, their stream-1 counters, the truncation, the fp32 confidence: x0_hat_out and conf_out are bit for bit the
+ * sibling's whatever the tables hold -- and two things become inputs, both device tables [B][S + 1] whose row i belongs to IMAGE i
+ * and is indexed by the loop's t (1 <= t <= S; entry 0 is read as w[t - 1] at t = 1):
+ *   1. HOW MANY.  w = row i of sched_w, entries at most 2^24.  With m positions masked at entry, in unsigned 64-bit arithmetic
+ *        keep = w[t] == 0 ? 0 : min(m, (m * w[t - 1]) / w[t]);   n = m - keep;   if m > 0 and n == 0 then n = 1.
+ *      Everything is revealed where w[t - 1] == 0, in particular at t = 1 under w[0] = 0.  The linear table w[t] = t gives
+ *      m - floor(m (t - 1) / t) = ceil(m / t), the `_conf` count for every m and t; the cosine table of a run of e steps is
+ *      w[t] = rint(2^24 sin(pi t / (2 e))), computed in fp64 on the host (masked fraction cos(pi r / 2) after progress r).  A
+ *      non-monotone or arbitrary table is legal: the min and the forced 1 define what it means.
+ *   2. IN WHAT ORDER.  a = noise_a[i][t]; a null table or a == 0: nothing is drawn and the order key is that of the confidence,
+ *      exactly as in the sibling.  Otherwise u is the uniform of the position -- u_or_null[p], which these entry points READ, or
+ *      stream 0 at counter offset + p * K, the coin's own counter that the `_conf` kernels leave undrawn, a value in [0, 1) -- and,
+ *      each operation rounded once to fp32 (no contraction),
+ *        g = -logf(-logf(u));   score = conf + a * g;   key = the 32-bit order key of score.
+ *      u = 0 gives g = -inf and (a > 0) score = -inf: the position orders last among the numbers, ahead of the NaNs (key 0).  The
+ *      rank rule does not change: (key, -position), larger key first, ties to the lower position.  The noise touches stream 0 only.
+ * In the listed form image i draws the Gumbel uniform at its own shifted offset, exactly as its race noise is shifted, and reads
+ * row i of both tables at the loop's t (the caller builds row i for e_i = min(steps_b[i], S) steps).  Argument errors before any
+ * launch: a null sched_w, S < 1, t outside 1 .. S (SPK_ERR_ARG); HW > 64 (SPK_ERR_UNSUPPORTED).  A family of kernels of its own:
+ * the `_conf` entry points keep their code paths, signatures and results.  Capturable; allocates nothing. */
+int spk_psample_step_conf_sched(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                                const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
+                                unsigned long long philox_seed, unsigned long long philox_offset,
+                                const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
+                                const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                spk_stream_t stream);
+int spk_psample_step_conf_listed_sched(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                       const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                       const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                       const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                       float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                                       unsigned long long step_stride, const int* active, const int* n_active,
+                                       const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null,
+                                       spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -829,6 +868,18 @@ int spk_den_step_tail_conf(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, i
                            const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                            uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                            long long* x0_hat_out_or_null, float* conf_out_or_null, spk_stream_t stream);
+/* spk_den_step_tail_conf under a reveal schedule and annealed selection noise (the rule and the four added
+ * arguments: spk_psample_step_conf_sched): bit for bit spk_den_conv3x3_counts_mfma, spk_psample_step_conf_sched and the first
+ * layer as three launches.  u_or_null is read (the Gumbel uniform).  A null sched_w, S < 1 or t outside 1 .. S: SPK_ERR_ARG. */
+int spk_den_step_tail_conf_sched(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                                 const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                                 int t, const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                 const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                 const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                                 const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                                 uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                                 long long* x0_hat_out_or_null, float* conf_out_or_null, const uint32_t* sched_w,
+                                 const float* noise_a_or_null, int S, float* score_out_or_null, spk_stream_t stream);
 /* q_sample of the diffusion training step, R/snn_model/vq_diffusion.py:61-75: mask = u < t[b] / num_timesteps (fp32, as there);
  * x_t = mask ? mask_id : x_0;  x_0_ignore = mask ? x_0 : -1 (the loss's ignore index).  x0 / u / outputs fp32 [B*HW], t int64 [B],
  * mask_out optional u8.  u is the caller's draw (torch.rand_like in the reference's order). */

@@ -195,6 +195,89 @@ __global__ __launch_bounds__(256) void psample_conf_listed_kernel(const float* _
   if (reveal) { unmasked[p] = 1; x_t[p] = (long long)s_cand[lane]; }
 }
 
+// The confidence-ordered update under a reveal schedule and annealed selection noise (spk_psample_step_conf_sched and, LISTED,
+// spk_psample_step_conf_listed_sched; the rule: psample_common.h): the two kernels above with the count read from
+// the image's row of sched_w and the order key taken from score = conf + a * g, which wave 0 computes for all positions at once
+// between the draw and the rank.  A family of its own, so that the `_conf` kernels
+// keep the instruction stream they have.  The candidate draw is theirs, line for line: x0_hat_out and conf_out are the sibling's.
+// LISTED: workgroup = slot of the pending list, logits by slot, everything else -- the two tables too -- by image active[s], the
+// counters (those of the Gumbel uniform included) shifted to the image's own run of e steps; no next_input.
+struct spk_sched_arg {
+  const uint32_t* w;                              // [B][S + 1]
+  const float* a;                                 // [B][S + 1] or null
+  const float* u_in;                              // injected uniforms [B*HW] or null
+  float* score_out;                               // [B*HW] or null
+  int S;
+};
+template <int KPL, bool LISTED>
+__global__ __launch_bounds__(256) void psample_conf_sched_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
+                                                                 uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
+                                                                 const float* __restrict__ q_in, unsigned long long seed,
+                                                                 unsigned long long offset,
+                                                                 const unsigned long long* __restrict__ philox_state,
+                                                                 long long* __restrict__ x0_hat_out, float* __restrict__ conf_out,
+                                                                 spk_sched_arg sc, const int* __restrict__ steps_b,
+                                                                 unsigned long long step_stride, const int* __restrict__ active,
+                                                                 const int* __restrict__ n_active, int B, int HW, int K,
+                                                                 float* __restrict__ next_input, float t_next) {
+  __shared__ int s_cand[64];
+  __shared__ uint32_t s_key[64];
+  const int s = blockIdx.x;                                         // the logits' slot
+  int b = s;                                                        // the image: state, noise, per-image arrays, tables, outputs
+  int e = sc.S;
+  if constexpr (LISTED) {
+    if (s >= spk_active_count(active, n_active, B)) return;        // (workgroup-uniform, ahead of the barrier)
+    b = active[s];
+    const int sb = steps_b[b];
+    e = sb < sc.S ? sb : sc.S;
+    if (t > e) return;
+  }
+  philox_base(philox_state, seed, offset);
+  if constexpr (LISTED) offset -= (unsigned long long)(sc.S - e) * step_stride;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float tp = temp.temp[b];
+  const int topk = temp.topk[b];
+  const float topp = temp.topp[b];
+  for (int hw = wave; hw < HW; hw += 4) {
+    const long long p = (long long)b * HW + hw;
+    if (unmasked[p]) continue;                                      // (wave-uniform)
+    float l[KPL];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+      const int k = lane + 64 * j;
+      const float lg = logits[((long long)s * K + (k < K ? k : K - 1)) * HW + hw];
+      l[j] = k < K ? lg / tp : -INFINITY;
+    }
+    truncate_top_k<KPL>(l, lane, K, topk);
+    truncate_top_p<KPL>(l, lane, K, topp);
+    float conf;
+    const int besti = categorical_race<KPL, true>(l, lane, K, q_in, seed, offset, p, &conf);
+    if (lane == 0) {
+      s_cand[hw] = besti;
+      s_key[hw] = __float_as_uint(conf);                            // (the confidence itself: its key is taken below)
+      if (x0_hat_out) x0_hat_out[p] = (long long)besti;
+      if (conf_out) conf_out[p] = conf;
+    }
+  }
+  __syncthreads();
+  // the scores, by the wave that ranks them -- lane = position, so the Gumbel draws of an image run side by side, once
+  const long long p = (long long)b * HW + (lane < HW ? lane : 0);
+  const bool masked = lane < HW && !unmasked[p];
+  const long long row = (long long)b * (sc.S + 1);
+  if (wave == 0 && masked) {
+    const float score = sched_score(__uint_as_float(s_key[lane]), sc.a ? sc.a[row + t] : 0.f, sc.u_in, seed, offset, p, K);
+    s_key[lane] = spk_conf_key(score);
+    if (sc.score_out) sc.score_out[p] = score;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const bool reveal = confident_reveal_sched(masked, lane, HW, sc.w[row + t - 1], sc.w[row + t], s_key);
+  if (reveal) { unmasked[p] = 1; x_t[p] = (long long)s_cand[lane]; }
+  if constexpr (!LISTED) {
+    if (next_input && lane < HW) write_next_input(next_input, b, lane, HW, reveal ? (float)s_cand[lane] : (float)x_t[p], t_next);
+  }
+}
+
 // Denoiser input map, R/snn_model/vq_diffusion.py:195-197:  cat(x, ones_like(x) * t[:,None,None,None]) -> [B,2,h,w]
 // x comes either as float [B,1,h,w] (the module API) or as the int64 token state x_t of the sampler.
 __global__ void den_input_kernel(const float* __restrict__ xf, const long long* __restrict__ xi,
@@ -626,4 +709,63 @@ extern "C" int spk_psample_step_conf_listed(const float* logits_skhw, long long*
 #undef SPK_PSAMPLE_CONF_LISTED_LAUNCH
   SPK_LAUNCH_CHECK();
   return SPK_OK;
+}
+
+// The two updates above under a reveal schedule and annealed selection noise (include/spkdiff.h; the rule: psample_common.h,
+// DESIGN.md §4.17): one launcher for the dense and the listed form.
+namespace {
+template <bool LISTED>
+int psample_conf_sched_launch(const float* logits, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_topp temp,
+                              const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                              unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                              long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K, const int* steps_b,
+                              unsigned long long step_stride, const int* active, const int* n_active, float* next_input_or_null,
+                              const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                              hipStream_t stream) {
+  if (!logits || !x_t_inout || !unmasked_inout || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0 ||
+      !sched_w || S <= 0 || t <= 0 || t > S)
+    return SPK_ERR_ARG;
+  if (LISTED && (!steps_b || !active || !n_active)) return SPK_ERR_ARG;
+  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
+  const spk_sched_arg sc{sched_w, noise_a_or_null, u_or_null, score_out_or_null, S};
+#define SPK_PSAMPLE_SCHED_LAUNCH(KPL)                                                                                    \
+  hipLaunchKernelGGL((psample_conf_sched_kernel<KPL, LISTED>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, \
+                     temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, sc, \
+                     steps_b, step_stride, active, n_active, B, HW, K, next_input_or_null, (float)(t - 1))
+  if (K <= 256) SPK_PSAMPLE_SCHED_LAUNCH(4);
+  else if (K <= 512) SPK_PSAMPLE_SCHED_LAUNCH(8);
+  else if (K <= 1024) SPK_PSAMPLE_SCHED_LAUNCH(16);
+  else SPK_PSAMPLE_SCHED_LAUNCH(32);
+#undef SPK_PSAMPLE_SCHED_LAUNCH
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_psample_step_conf_sched(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                           const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                           const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                           const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                           float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
+                                           const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                           hipStream_t stream) {
+  return psample_conf_sched_launch<false>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                          q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
+                                          conf_out_or_null, B, HW, K, nullptr, 0ull, nullptr, nullptr, next_input_b2hw_or_null,
+                                          sched_w, noise_a_or_null, S, score_out_or_null, stream);
+}
+
+extern "C" int spk_psample_step_conf_listed_sched(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                                  const float* temp_b, const int* topk_b, const float* topp_b,
+                                                  const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                                  unsigned long long philox_offset,
+                                                  const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                                  float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                                                  unsigned long long step_stride, const int* active, const int* n_active,
+                                                  const uint32_t* sched_w, const float* noise_a_or_null,
+                                                  float* score_out_or_null, hipStream_t stream) {
+  return psample_conf_sched_launch<true>(logits_skhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                         q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
+                                         conf_out_or_null, B, HW, K, steps_b, step_stride, active, n_active, nullptr, sched_w,
+                                         noise_a_or_null, S, score_out_or_null, stream);
 }

@@ -2,7 +2,7 @@
 // counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
 // offset + position * K + class), the categorical draw categorical_race, the top-k and nucleus truncations truncate_top_k /
 // truncate_top_p that may precede it, the confidence-ordered reveal rule confident_reveal (what a step commits when it does not toss
-// the coin), the 64-lane max / sum and the prologues every kernel shares.
+// the coin) with its scheduled form (sched_reveal_count, sched_score, confident_reveal_sched), the 64-lane max / sum and the prologues every kernel shares.
 // Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
@@ -274,6 +274,53 @@ __device__ __forceinline__ bool confident_reveal(bool masked, int lane, int HW, 
   const unsigned long long mm = __ballot(masked);
   const unsigned m = (unsigned)__popcll(mm);
   const unsigned n = (m + (unsigned)t - 1u) / (unsigned)t;
+  const uint32_t key = masked ? s_key[lane] : 0u;
+  unsigned rank = 0;
+  for (int q = 0; q < HW; ++q) {
+    if (!((mm >> q) & 1ull)) continue;                            // (wave-uniform)
+    const uint32_t kq = s_key[q];                                 // (one address for the wave: a broadcast read)
+    rank += (kq > key || (kq == key && q < lane)) ? 1u : 0u;
+  }
+  return masked && rank < n;
+}
+
+// Reveal schedules and annealed selection noise (the `_sched` entry points spk_psample_step_conf_sched,
+// spk_psample_step_conf_listed_sched, spk_den_step_tail_conf_sched) -- THE rule, stated once.  Steps 2 and 3 above stay as they
+// are (the candidates, their stream-1 counters, the truncation, the fp32 confidence: x0_hat_out and conf_out are bit for bit the
+// `_conf` sibling's whatever the tables hold); steps 1 and 4 take two per-image tables indexed [image][t], t = 0 .. S:
+//   1'. HOW MANY.  w = row i of sched_w (uint32 [B][S + 1], entries <= 2^24).  In unsigned 64-bit arithmetic
+//         keep = w[t] == 0 ? 0 : min(m, (m * w[t - 1]) / w[t]);   n = m - keep;   m > 0 and n == 0: n = 1
+//       (sched_reveal_count: m <= 64 and w <= 2^24, so the product is below 2^31).  w[t - 1] == 0 reveals everything -- t = 1 under
+//       w[0] = 0 --, w[t] = t gives m - floor(m (t - 1) / t) = ceil(m / t), the `_conf` count, and a non-monotone table is legal:
+//       the min and the forced 1 are what it means.
+//   4'. IN WHAT ORDER.  a = noise_a[i][t] (fp32 [B][S + 1]; a null table: a = 0).  a == 0: nothing is drawn, score = conf.  Else
+//       u = reveal_u of the position -- the injected u, or stream 0 at offset + p * K, the coin's own counter that the `_conf`
+//       kernels leave undrawn, a value in [0, 1) -- and, every operation one fp32 rounding (-ffp-contract=off):
+//         g = -logf(-logf(u));   score = conf + a * g      (sched_score)
+//       u = 0 gives g = -inf, so score = -inf under a > 0: such a position orders last among the numbers, ahead of the NaNs (key 0).
+//       The order key is spk_conf_key(score), the rank rule is confident_reveal's: (key, -position), ties to the lower position.
+//       score_out receives the score at the positions masked at entry.
+__device__ __forceinline__ unsigned sched_reveal_count(unsigned m, uint32_t w_prev, uint32_t w_cur) {   // w[t - 1], w[t]
+  const unsigned long long wp = w_prev, wc = w_cur, mu = m;
+  unsigned long long keep = 0ull;
+  if (wc != 0ull) { keep = (mu * wp) / wc; keep = keep < mu ? keep : mu; }
+  unsigned n = (unsigned)(mu - keep);
+  if (m > 0u && n == 0u) n = 1u;
+  return n;
+}
+__device__ __forceinline__ float sched_score(float conf, float a, const float* __restrict__ u_in, unsigned long long seed,
+                                             unsigned long long offset, long long p, int K) {
+  if (a == 0.f) return conf;
+  const float u = reveal_u(u_in, seed, offset, p, K);
+  const float g = -logf(-logf(u));
+  const float ag = a * g;
+  return conf + ag;
+}
+__device__ __forceinline__ bool confident_reveal_sched(bool masked, int lane, int HW, uint32_t w_prev, uint32_t w_cur,
+                                                       const uint32_t* s_key) {
+  // (confident_reveal with the count from the table: a copy of its eight lines, so that the `_conf` kernels keep the text they have)
+  const unsigned long long mm = __ballot(masked);
+  const unsigned n = sched_reveal_count((unsigned)__popcll(mm), w_prev, w_cur);
   const uint32_t key = masked ? s_key[lane] : 0u;
   unsigned rank = 0;
   for (int q = 0; q < HW; ++q) {

@@ -39,8 +39,13 @@ constexpr int SPK_TAIL_PF = 8;                    // weight tiles are requested 
 // first layer.  Its two optional outputs are a base of the argument block, empty in every other form (whose block does not change).
 template <bool CF> struct TailConfOutT {};
 template <> struct TailConfOutT<true> { long long* x0_hat_out; float* conf_out; };   // candidates / confidences, at the masked positions
-template <bool PT, bool TK = false, bool TP = false, bool CF = false>
-struct TailArgsT : TailConfOutT<CF> {
+// SC = a reveal schedule and annealed selection noise on top of CF (spk_den_step_tail_conf_sched; the rule: psample_common.h, DESIGN.md
+// §4.17): the count comes from the image's row of sched_w, the order key from score = conf + a * g.  One more base of the argument
+// block, empty in every other form.
+template <bool SC> struct TailSchedT {};
+template <> struct TailSchedT<true> { const uint32_t* sched_w; const float* noise_a; float* score_out; int S; };   // tables [B][S + 1]; scores at the masked positions
+template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
+struct TailArgsT : TailConfOutT<CF>, TailSchedT<SC> {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
   const int8_t* wq; const double* scale; const double* bias;
   float* logits_out;                              // optional fp32 [B][128][HW]
@@ -58,9 +63,10 @@ struct TailArgsT : TailConfOutT<CF> {
 };
 
 // KG = channel groups per wave (1: K <= 128, the reference's default; 2 .. 4: K <= 256 / 384 / 512)
-template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false, bool CF = false>
-__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP, CF> a) {
+template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
+__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP, CF, SC> a) {
   static_assert(!CF || (PT && TK && TP), "the confidence form exists on top of the most general family only");
+  static_assert(!SC || CF, "a schedule orders the confidence form's commit");
   constexpr int HW = H * W;
   static_assert(HW <= 64, "an image is at most two 32-row tiles");
   constexpr int AV = HW * 2 + 1;                  // 16-byte vectors of a chunk's count records + one zero vector
@@ -79,7 +85,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
   if constexpr (CF) {                             //  what that loop is short of: held there they were spilled)
     __shared__ int s_cand_[64];
     __shared__ uint32_t s_key_[64];
-    __shared__ unsigned long long s_cfarg_[3];
+    __shared__ unsigned long long s_cfarg_[SC ? 8 : 3];       // SC: + {score_out, u_in, bits of a, w[t - 1], w[t]} of this image and step
     s_cand = s_cand_; s_key = s_key_; s_cfarg = s_cfarg_;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,6 +127,12 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
     if (tid == 0) {
       s_cfarg[0] = (unsigned long long)a.x0_hat_out; s_cfarg[1] = (unsigned long long)a.conf_out;
       s_cfarg[2] = (unsigned long long)(unsigned)a.t;
+      if constexpr (SC) {
+        const long long srow = (long long)bi * (a.S + 1) + a.t;       // (1 <= t <= S: the host checks)
+        s_cfarg[3] = (unsigned long long)a.score_out; s_cfarg[4] = (unsigned long long)a.u_in;
+        s_cfarg[5] = (unsigned long long)__float_as_uint(a.noise_a ? a.noise_a[srow] : 0.f);
+        s_cfarg[6] = (unsigned long long)a.sched_w[srow - 1]; s_cfarg[7] = (unsigned long long)a.sched_w[srow];
+      }
     }
   }
   // ---- which positions change at this step, and the tokens as they are: one thread per position, up front (fetched row by row
@@ -299,7 +311,8 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
       const float conf = spk_race_conf<NJ>(l, besti);   // (categorical_race's CONF value: l after `l[j] - lse`, at the drawn class)
       if (lane == 0) {
         s_cand[p] = besti;
-        s_key[p] = spk_conf_key(conf);
+        if constexpr (SC) s_key[p] = __float_as_uint(conf);   // (the confidence itself: its key is taken below, from the score)
+        else s_key[p] = spk_conf_key(conf);
         long long* x0_hat_out = reinterpret_cast<long long*>(s_cfarg[0]);
         float* conf_out = reinterpret_cast<float*>(s_cfarg[1]);
         if (x0_hat_out) x0_hat_out[pi] = (long long)besti;
@@ -314,9 +327,23 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
   if constexpr (CF) {
     // ---- the commit: one wave, lane = position; the n = ceil(m / t) surest candidates of the image become its tokens
     __syncthreads();
+    if constexpr (SC) {
+      // the scores, by the wave that ranks them: lane = position, the Gumbel draws of the image side by side
+      if (wave == 0 && lane < HW && s_chg[lane < HW ? lane : 0] != 0) {
+        const long long pi = (long long)bi * HW + lane;
+        const float score = sched_score(__uint_as_float(s_key[lane]), __uint_as_float((uint32_t)s_cfarg[5]),
+                                        reinterpret_cast<const float*>(s_cfarg[4]), seed, offset, pi, K);
+        float* score_out = reinterpret_cast<float*>(s_cfarg[3]);
+        s_key[lane] = spk_conf_key(score);
+        if (score_out) score_out[pi] = score;
+      }
+      __syncthreads();
+    }
     if (wave == 0) {
       const bool masked = lane < HW && s_chg[lane < HW ? lane : 0] != 0;
-      if (confident_reveal(masked, lane, HW, (int)s_cfarg[2], s_key)) {
+      // (SC is a template constant: one of the two calls is compiled)
+      if (SC ? confident_reveal_sched(masked, lane, HW, (uint32_t)s_cfarg[SC ? 6 : 0], (uint32_t)s_cfarg[SC ? 7 : 0], s_key)
+             : confident_reveal(masked, lane, HW, (int)s_cfarg[2], s_key)) {
         const long long pi = (long long)bi * HW + lane;
         const int tk = s_cand[lane];
         a.unmasked[pi] = 1;
@@ -368,7 +395,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
 }  // namespace
 
 namespace {
-template <bool PT, bool TK = false, bool TP = false, bool CF = false>
+template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
 int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                      const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                      spk_temp_arg_t<PT, TK, TP> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
@@ -376,7 +403,8 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
                      const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
                      uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                      const int* active_or_null, const int* n_active_or_null, hipStream_t stream,
-                     long long* x0_hat_out_or_null = nullptr, float* conf_out_or_null = nullptr) {
+                     long long* x0_hat_out_or_null = nullptr, float* conf_out_or_null = nullptr, const uint32_t* sched_w = nullptr,
+                     const float* noise_a_or_null = nullptr, int S = 0, float* score_out_or_null = nullptr) {
   if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK, TP>(temp) || B <= 0 ||
       T <= 0)
     return SPK_ERR_ARG;
@@ -389,9 +417,11 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   // the fused first layer writes sixteen 16-byte step records per position and scans with the module-default LIF constants
   // (spk_lif_const_input_bits16): any other step count would write outside x1_s32_out (T < 16) or give wrong spikes (T > 16)
   if (x1_s32_out_or_null && T != 16) return SPK_ERR_UNSUPPORTED;
-  TailArgsT<PT, TK, TP, CF> a;
+  if (SC && (!sched_w || S <= 0 || t > S)) return SPK_ERR_ARG;
+  TailArgsT<PT, TK, TP, CF, SC> a;
+  if constexpr (SC) { a.sched_w = sched_w; a.noise_a = noise_a_or_null; a.score_out = score_out_or_null; a.S = S; }
   if constexpr (CF) {
-    // (the K = 512, 8 x 8 launch holds 150 KB of logits and counts; with the form's 544 bytes more it is checked against the device's
+    // (the K = 512, 8 x 8 launch holds 150 KB of logits and counts; with the form's 544 bytes (560 with a schedule: 21 856 on 8 x 8) more it is checked against the device's
     //  grant -- the static part counted as 22 KB for either latent: 21 840 bytes on 8 x 8, 17 040 on 7 x 7, where the check is conservative)
     if ((long long)64 * (128 * ((K + 127) / 128) + 4) * (long long)sizeof(float) + 22 * 1024 > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;
     a.x0_hat_out = x0_hat_out_or_null; a.conf_out = conf_out_or_null;
@@ -406,7 +436,7 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   a.K = K; a.ng = (K + 15) / 16;                    // wq / scale / bias_d hold ng * 16 channels (zero weights beyond K)
   const int kg = (a.ng + 7) / 8;
 #define SPK_TAIL_LAUNCH(H_, W_, KG_)                                                                                          \
-  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP, CF>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
+  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP, CF, SC>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
   if (H == 7) {
     if (kg == 1) SPK_TAIL_LAUNCH(7, 7, 1); else if (kg == 2) SPK_TAIL_LAUNCH(7, 7, 2);
     else if (kg == 3) SPK_TAIL_LAUNCH(7, 7, 3); else SPK_TAIL_LAUNCH(7, 7, 4);
@@ -498,4 +528,24 @@ extern "C" int spk_den_step_tail_conf(const uint8_t* cnt5, int nch5, const uint8
                                                   philox_offset, philox_state_or_null, conv1_w_packed_or_null, conv1_bias_or_null,
                                                   bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, nullptr, nullptr,
                                                   stream, x0_hat_out_or_null, conf_out_or_null);
+}
+
+// The same launch under a reveal schedule and annealed selection noise (include/spkdiff.h; the rule: csrc/psample_common.h, DESIGN.md
+// §4.17): spk_den_step_tail_conf's arguments plus the two tables, S and score_out_or_null.  u_or_null is read: it is the Gumbel uniform.
+extern "C" int spk_den_step_tail_conf_sched(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                            const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                            uint8_t* unmasked_inout, int t, const float* temp_b, const int* topk_b, const float* topp_b,
+                                            const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                            unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                            const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a,
+                                            const float* bn1_b, uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B,
+                                            int H, int W, int K, long long* x0_hat_out_or_null, float* conf_out_or_null,
+                                            const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                            hipStream_t stream) {
+  return step_tail_launch<true, true, true, true, true>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout,
+                                                        unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null, q_or_null,
+                                                        philox_seed, philox_offset, philox_state_or_null, conv1_w_packed_or_null,
+                                                        conv1_bias_or_null, bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H,
+                                                        W, K, nullptr, nullptr, stream, x0_hat_out_or_null, conf_out_or_null, sched_w,
+                                                        noise_a_or_null, S, score_out_or_null);
 }

@@ -105,8 +105,12 @@ class _SamplerGraph:
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
     def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False,
-                 confident=False, per_image_steps=False):
+                 confident=False, per_image_steps=False, sched_steps=0):
         self.graph = self.derived = None                            # set by the capture
+        # a reveal schedule and annealed selection noise (DESIGN.md §4.17) are two more INPUTS of fixed shape [B][S + 1]: the captured
+        # `_sched` token updates read these buffers, so one graph serves every schedule and every noise scale
+        self.sched = (torch.zeros((b, sched_steps + 1), dtype=torch.int32, device=dev),
+                      torch.zeros((b, sched_steps + 1), dtype=torch.float32, device=dev)) if sched_steps else None
         self.confident = bool(confident)                            # the captured token updates are the confidence-ordered ones (§4.15)
         # per-image step counts (DESIGN.md §4.16) are one more INPUT: the captured select_pending / listed updates read this buffer
         self.steps = torch.ones(b, dtype=torch.int32, device=dev) if per_image_steps else None
@@ -299,7 +303,8 @@ class AbsorbingDiffusion(Sampler):
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p)
 
     @torch.no_grad()
-    def sample_confident(self, sample_steps=None, temp=1.0, noise=None, record=None, x_init=None, known=None, top_k=None, top_p=None):
+    def sample_confident(self, sample_steps=None, temp=1.0, noise=None, record=None, x_init=None, known=None, top_k=None, top_p=None,
+                         schedule=None, selection_noise=None):
         """Confidence-ordered decoding: ``sample()`` with another rule for WHERE a step reveals.  At step t every
         still-masked position of an image draws a candidate token -- the draw of ``sample_top_p(top_p, top_k=top_k)``, same noise
         counters -- and the ceil(m / t) candidates the denoiser is surest of (m = positions masked at entry; the order is the
@@ -324,11 +329,87 @@ class AbsorbingDiffusion(Sampler):
         something still masked: spk_select_pending) -- the denoiser on the list, spk_psample_step_conf_listed for the update -- so
         the work is proportional to the sum of the s_i (an image with nothing masked is never evaluated).  In a captured graph the
         vector is an input: one graph per (batch, S, conditional) serves every vector with that maximum.  Refused before a key is
-        drawn: ``record=``, the 'rank' layout, a wrong length, an entry < 1 (ValueError).  An int takes the path above unchanged."""
+        drawn: ``record=``, the 'rank' layout, a wrong length, an entry < 1 (ValueError).  An int takes the path above unchanged.
+
+        Reveal schedules and annealed selection noise.  ``schedule`` says HOW MANY positions a step commits:
+        None (the ceil(m / t) count above, the calls made before), 'linear' (the same counts from a weight table), 'cosine' (few
+        tokens on the empty context, most at the end: the masked fraction after progress r is cos(pi r / 2)), a sequence of
+        sample_steps + 1 integer weights w[0 .. S] in 0 .. 2^24 -- step t keeps min(m, floor(m w[t - 1] / w[t])) of its m masked
+        positions masked, reveals the rest and at least one (``spkdiff.schedules.reveal_counts`` lists the counts) -- or one of
+        these per image of the call (a list of B entries, or a 2-D array / tensor [B, S + 1]).  ``selection_noise`` says IN WHAT
+        ORDER: tau >= 0, finite, a number or one per image; the candidates are ranked by confidence + a * Gumbel(0, 1) with a =
+        tau * (t - 1) / e annealed linearly to zero at the image's last step (e: the image's step count), the Gumbel from the
+        position's stream-0 counter -- the coin's, free under this rule (of an injected (u, q), u is that uniform).  The candidates
+        themselves do not change, and ``top_k = 1`` with tau > 0 commits the arg max tokens in a key-dependent order.  With both at
+        None the call is the one above, launch for launch; anything else runs the ``_sched`` kernels (``schedule='linear'`` with
+        tau = 0: the same tokens).  Under per-image step counts row i is built for the image's own e_i steps, so image i still
+        equals image i of ``sample_confident(s_i, schedule=its row, selection_noise=tau_i)``.  In a captured graph both tables are
+        inputs [B][S + 1]: one graph per (batch, S, conditional, per-image steps) serves every schedule and every tau.  Refused
+        before a key is drawn (ValueError): tau negative or not finite, an unknown name, a table of the wrong length, a weight
+        outside 0 .. 2^24 or no integer, a per-image list of the wrong length."""
         h, w = self.shape
         if h * w > 64:
             raise NotImplementedError(f'spkdiff: sample_confident() ranks an image\'s positions in one wave: h * w <= 64, got {h} x {w}')
-        return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p, confident=True)
+        return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p, confident=True,
+                                 **({} if schedule is None and selection_noise is None else
+                                    {'schedule': schedule, 'selection_noise': selection_noise, 'scheduled': True}))
+
+    @staticmethod
+    def _sched_arg(schedule, selection_noise, b, steps, S):
+        """The two tables of a scheduled sample_confident() call for a batch of ``b``, checked and built on the
+        host: ``steps`` = the b per-image step counts e_i <= S (a list) -> (w int32 [b, S + 1], a fp32 [b, S + 1]) CPU tensors;
+        a = fp32(tau_i * (t - 1) / e_i) computed in fp64."""
+        from spkdiff import schedules as sch
+        what = 'spkdiff: sample_confident(schedule=)'
+        if hasattr(schedule, 'detach'):
+            schedule = schedule.detach().cpu()
+        if hasattr(schedule, 'tolist') and getattr(schedule, 'ndim', 0) >= 1:
+            integers = (not schedule.is_floating_point() and schedule.dtype != torch.bool) if isinstance(schedule, torch.Tensor) \
+                else getattr(schedule.dtype, 'kind', 'i') in 'iu'
+            if not integers:
+                raise ValueError(f'{what}: weights are integers, got an array of {schedule.dtype}')
+            if schedule.ndim > 2:
+                raise ValueError(f'{what}: a table is 1-D, per-image tables are [B, S + 1], got {tuple(schedule.shape)}')
+            schedule = schedule.tolist()
+        if not (schedule is None or isinstance(schedule, (str, list, tuple))):
+            raise ValueError(f"{what}: None, 'linear', 'cosine', a table of integer weights or one of these per image, got {schedule!r}")
+        per_image = isinstance(schedule, (list, tuple)) and len(schedule) > 0 and \
+            any(v is None or isinstance(v, (str, list, tuple)) or getattr(v, 'ndim', 0) >= 1 for v in schedule)
+        if per_image and len(schedule) != b:
+            raise ValueError(f'{what}: per-image schedules take one entry per image of the call ({b}), got {len(schedule)}')
+        # every distinct (schedule, step count) builds its row once: a batch of 256 with one schedule is one row, not 256
+        built, index = {}, []
+        shared = tuple(schedule) if isinstance(schedule, list) and not per_image else schedule      # (a hashable key)
+        for i in range(b):
+            si = shared
+            if per_image:
+                si = schedule[i]
+                si = tuple(si.tolist() if hasattr(si, 'tolist') else si) if not (si is None or isinstance(si, str)) else si
+            key = (si, steps[i])
+            if key not in built:
+                built[key] = (len(built), sch.weights_row(si, key[1], S, what))
+            index.append(built[key][0])
+        rows = torch.tensor([r for _, r in built.values()], dtype=torch.int32).reshape(len(built), S + 1)
+        rows = rows.expand(b, S + 1).contiguous() if len(built) == 1 else rows[torch.tensor(index)]
+        tau = selection_noise
+        if tau is None:
+            taus = [0.0] * b
+        elif isinstance(tau, (list, tuple)) or getattr(tau, 'ndim', 0) >= 1:
+            tl = tau.detach().cpu().tolist() if hasattr(tau, 'detach') else (tau.tolist() if hasattr(tau, 'tolist') else list(tau))
+            if getattr(tau, 'ndim', 1) != 1 or len(tl) != b:
+                raise ValueError(f'spkdiff: per-image selection_noise takes one number per image of the call ({b}), got {tau!r}')
+            taus = [sch.check_tau(v, 'spkdiff: selection_noise') for v in tl]
+        else:
+            taus = [sch.check_tau(tau.item() if hasattr(tau, 'item') else tau, 'spkdiff: selection_noise')] * b
+        # a[i][t] = tau_i * (t - 1) / e_i for 1 <= t <= e_i (spkdiff.schedules.noise_scales, all rows at once: the same two fp64
+        # operations), 0 elsewhere; rounded to fp32 once
+        t = torch.arange(S + 1, dtype=torch.float64)[None, :]
+        e = torch.tensor(steps, dtype=torch.float64)[:, None]
+        a = torch.tensor(taus, dtype=torch.float64)[:, None] * (t - 1) / e
+        a = torch.where((t >= 1) & (t <= e), a, torch.zeros((), dtype=torch.float64)).to(torch.float32)
+        if not bool(torch.isfinite(a).all()):
+            raise ValueError('spkdiff: selection_noise is too large for fp32')
+        return rows, a.reshape(b, S + 1)
 
     @staticmethod
     def _steps_arg(sample_steps, b):
@@ -351,7 +432,8 @@ class AbsorbingDiffusion(Sampler):
             raise bad
         return v.to(torch.int32)
 
-    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None, confident=False):
+    def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None, confident=False, schedule=None,
+                     selection_noise=None, scheduled=False):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         steps_b = None
@@ -365,6 +447,13 @@ class AbsorbingDiffusion(Sampler):
                 if self.noise_layout != 'global':
                     raise ValueError("spkdiff: per-image sample_steps needs the 'global' noise layout (one counter stride per step)")
                 steps_b, sample_steps = sample_steps, int(sample_steps.max())
+        sched = None
+        if scheduled:
+            # a reveal schedule / selection noise: both tables built on the host before anything is drawn
+            S = int(self.num_timesteps if sample_steps is None else sample_steps)
+            if S < 1:
+                raise ValueError(f'spkdiff: sample_confident(schedule=, selection_noise=) takes sample_steps >= 1, got {S}')
+            sched = self._sched_arg(schedule, selection_noise, b, [S] * b if steps_b is None else steps_b.tolist(), S)
         temp = self._temp_arg(temp, b)
         top_k = self._topk_arg(top_k, b)
         top_p = self._topp_arg(top_p, b)
@@ -407,7 +496,8 @@ class AbsorbingDiffusion(Sampler):
             form = SampleForm(skip=True, lists=False, tail=False, tail_act=False)
         return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k,
                                      **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
-                                     **({} if steps_b is None else {'steps_b': steps_b}))
+                                     **({} if steps_b is None else {'steps_b': steps_b}),
+                                     **({} if sched is None else {'sched': sched}))
 
     def _topp_arg(self, top_p, b):
         """The ``top_p`` of sample_top_p() for a batch of ``b``, checked before anything is drawn or launched.  None: no nucleus
@@ -583,7 +673,7 @@ class AbsorbingDiffusion(Sampler):
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
     def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None,
-                         top_p=None, confident=False, steps_b=None):
+                         top_p=None, confident=False, steps_b=None, sched=None):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
@@ -591,7 +681,8 @@ class AbsorbingDiffusion(Sampler):
                 return self._sample_graphed(dev, b, h, w, form, temp, sample_steps, seed, start=start, target=target, top_k=top_k,
                                             **({} if top_p is None else {'top_p': top_p}),
                                             **({'confident': True} if confident else {}),
-                                            **({} if steps_b is None else {'steps_b': steps_b}))
+                                            **({} if steps_b is None else {'steps_b': steps_b}),
+                                            **({} if sched is None else {'sched': sched}))
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -611,15 +702,17 @@ class AbsorbingDiffusion(Sampler):
                 self._capturing = False
         return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k,
                                   **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
-                                  **({} if steps_b is None else {'steps_b': steps_b}))
+                                  **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}))
 
     def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
-                      top_k=None, top_p=None, confident=False, steps_b=None):
+                      top_k=None, top_p=None, confident=False, steps_b=None, sched=None):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
         unmasked = torch.empty((b, 1, h, w), dtype=torch.bool, device=dev)
         self._fill_start(x_t, unmasked, start)
+        if sched is not None:
+            sched = (sched[0].to(dev), sched[1].to(dev))            # (the host-built tables of sample_confident(schedule=, ...))
         if noise is None and self.noise_source == 'host':
             # u and q from torch's global CPU generator in the reference's order: rand_like(x_t.float()) (:116), then
             # multinomial's one-draw fast path (:138); the denoiser call between them there draws nothing
@@ -631,7 +724,7 @@ class AbsorbingDiffusion(Sampler):
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
         self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
                             top_k=top_k, **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
-                            **({} if steps_b is None else {'steps_b': steps_b}))
+                            **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}))
         return x_t
 
     def _fill_start(self, x_t, unmasked, start):
@@ -643,7 +736,7 @@ class AbsorbingDiffusion(Sampler):
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
     def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
-                       top_k=None, top_p=None, confident=False, steps_b=None):
+                       top_k=None, top_p=None, confident=False, steps_b=None, sched=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -658,13 +751,18 @@ class AbsorbingDiffusion(Sampler):
         dense form, always with ``top_k`` and ``top_p``, never with ``target``); ``steps_b``: int32 device tensor [B], the per-image
         step counts of sample_confident() (``sample_steps`` is then their maximum S, ``form`` the elimination form
         without lists or tails) -- every step runs on the list spk_select_pending writes: the denoiser by slot, then
-        spk_psample_step_conf_listed, which shifts image i's counters to those of its own run of min(steps_b[i], S) steps."""
+        spk_psample_step_conf_listed, which shifts image i's counters to those of its own run of min(steps_b[i], S) steps;
+        ``sched = (w int32 [B, S + 1], a fp32 [B, S + 1])`` on the loop's device: a scheduled sample_confident() (then
+        ``confident``, S = ``sample_steps``) -- every token update is the ``_sched`` sibling of the one it would be, with the two
+        tables, and an injected u is handed on as the Gumbel uniform."""
         dn = self._denoise_fn
         trunc = {} if top_k is None else {'top_k': top_k}
         if top_p is not None:
             trunc['top_p'] = top_p
         if confident:
             trunc['confident'] = True
+        if sched is not None:
+            trunc['sched'] = sched + (sample_steps,)
         b, _, h, w = x_t.shape
         K = self.num_classes
         seed, state = src.seed, src.state
@@ -688,9 +786,16 @@ class AbsorbingDiffusion(Sampler):
                                                   want_next=form.tail and t > 1, want_logits=record is not None, **trunc)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
-                    if steps_b is not None:
+                    if steps_b is not None and sched is not None:
+                        ops.psample_step_conf_listed_sched(logits, x_t, unmasked, t, temp, steps_b, sample_steps, self.STEP_STRIDE,
+                                                           sched[0], sched[1], u, q, seed, off, philox_state=state, top_k=top_k,
+                                                           top_p=top_p)
+                    elif steps_b is not None:
                         ops.psample_step_conf_listed(logits, x_t, unmasked, t, temp, steps_b, sample_steps, self.STEP_STRIDE, u, q,
                                                      seed, off, philox_state=state, top_k=top_k, top_p=top_p)
+                    elif sched is not None:
+                        ops.psample_step_conf_sched(logits, x_t, unmasked, t, temp, sched[0], sample_steps, sched[1], u, q, seed, off,
+                                                    philox_state=state, next_input=inp if t > 1 else None, top_k=top_k, top_p=top_p)
                     elif confident:
                         ops.psample_step_conf(logits, x_t, unmasked, t, temp, u, q, seed, off, philox_state=state,
                                               next_input=inp if t > 1 else None, top_k=top_k, top_p=top_p)
@@ -837,7 +942,7 @@ class AbsorbingDiffusion(Sampler):
         ws[1] = v
 
     def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None, confident=False,
-                   per_image_steps=False):
+                   per_image_steps=False, scheduled=False):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -850,7 +955,8 @@ class AbsorbingDiffusion(Sampler):
                 bool(dn.use_step_tail), bool(self.step_tail_in_elimination), self.noise_layout, first, weights,
                 conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ()) + \
             (('top-p',) if top_p is not None else ()) + (('confident',) if confident else ()) + \
-            (('per-image-steps',) if per_image_steps else ())       # (sample_steps is then S, the vector's maximum)
+            (('per-image-steps',) if per_image_steps else ()) + \
+            (('scheduled',) if scheduled else ())                   # (sample_steps is then S, the vector's maximum; both tables are inputs)
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
@@ -862,10 +968,10 @@ class AbsorbingDiffusion(Sampler):
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
                             act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk,
                             **({} if g.topp is None else {'top_p': g.topp}), **({'confident': True} if g.confident else {}),
-                            **({} if g.steps is None else {'steps_b': g.steps}))
+                            **({} if g.steps is None else {'steps_b': g.steps}), **({} if g.sched is None else {'sched': g.sched}))
 
     def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None,
-                        confident=False, steps_b=None):
+                        confident=False, steps_b=None, sched=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -880,11 +986,14 @@ class AbsorbingDiffusion(Sampler):
         ``confident``: the graph of sample_confident() (a nucleus graph whose token updates are the confidence-ordered ones): one more
         marker in the key, no further input.  ``steps_b`` (int32 device tensor [B]; then ``confident``, ``sample_steps`` = its maximum):
         a per-image-steps graph -- one more marker, one more input (``steps``): one graph serves every vector with
-        the same maximum."""
+        the same maximum.  ``sched`` (the two device tables [B, S + 1] of a scheduled sample_confident()): one
+        more marker, two more inputs of fixed shape -- one graph serves every schedule and every noise scale; they come as the
+        host tensors they were built as and are copied straight into the graph's buffers."""
         dn = self._denoise_fn
         key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p,
                               **({'confident': True} if confident else {}),
-                              **({} if steps_b is None else {'per_image_steps': True}))
+                              **({} if steps_b is None else {'per_image_steps': True}),
+                              **({} if sched is None else {'scheduled': True}))
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
@@ -892,7 +1001,8 @@ class AbsorbingDiffusion(Sampler):
             g = _SamplerGraph(dev, b, h, w, form, int(self.list_radii), start is not None, target is not None,
                               per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None,
                               top_p=top_p is not None, **({'confident': True} if confident else {}),
-                              **({} if steps_b is None else {'per_image_steps': True}))
+                              **({} if steps_b is None else {'per_image_steps': True}),
+                              **({} if sched is None else {'sched_steps': sample_steps}))
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -923,6 +1033,9 @@ class AbsorbingDiffusion(Sampler):
             g.topp.copy_(top_p)
         if g.steps is not None:
             g.steps.copy_(steps_b)
+        if g.sched is not None:
+            g.sched[0].copy_(sched[0])
+            g.sched[1].copy_(sched[1])
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
@@ -1075,11 +1188,11 @@ class DummyModel(nn.Module):
 
     @torch.no_grad()
     def sample_step(self, x_t, unmasked, t, temp, u=None, q=None, seed=0, offset=0, philox_state=None, pre1=None,
-                    want_next=True, want_logits=False, top_k=None, top_p=None, confident=False):
+                    want_next=True, want_logits=False, top_k=None, top_p=None, confident=False, sched=None):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation); ``confident``: the tail launch is the confidence-ordered one (spk_den_step_tail_conf).  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation); ``confident``: the tail launch is the confidence-ordered one (spk_den_step_tail_conf); ``sched = (w, a, S)``: with ``confident``, its sibling under a reveal schedule and selection noise (spk_den_step_tail_conf_sched; ``u`` is then the Gumbel uniform).  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -1093,6 +1206,11 @@ class DummyModel(nn.Module):
         if top_p is not None:
             trunc['top_p'] = top_p
         with ops.timed('den.tail'):
+            if confident and sched is not None:
+                return ops.den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, sched[0], sched[2],
+                                                    T=self.n_steps, K=conv6.out_channels, noise_a=sched[1], u=u, q=q, seed=seed,
+                                                    offset=offset, philox_state=philox_state, conv1=nxt, want_logits=want_logits,
+                                                    **trunc)
             if confident:
                 return ops.den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, T=self.n_steps,
                                               K=conv6.out_channels, u=u, q=q, seed=seed, offset=offset, philox_state=philox_state,

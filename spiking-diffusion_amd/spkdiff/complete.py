@@ -77,7 +77,7 @@ def complete_images_top_p(model, sampler, images, keep, top_p, temp=1.0, sample_
 
 @torch.no_grad()
 def complete_images_confident(model, sampler, images, keep, sample_steps=None, temp=1.0, T=16, paste=True, top_k=None, top_p=None,
-                              positions_per_step=None):
+                              positions_per_step=None, schedule=None, selection_noise=None):
     """``complete_images`` with the unknown tokens revealed in the order of the denoiser's confidence (DESIGN.md §4.15;
     ``AbsorbingDiffusion.sample_confident``): every step commits the ceil(m / t) surest candidates of each image, m counting the
     positions still unknown, so a few steps serve a small hole.  ``temp`` / ``top_k`` / ``top_p`` as sample_confident() takes them.
@@ -88,14 +88,18 @@ def complete_images_confident(model, sampler, images, keep, sample_steps=None, t
     >= 1; not together with ``sample_steps``) chooses the counts from the holes: s_i = max(1, ceil(m_i / r)) with m_i = h * w -
     n_known_i the number of unknown codes of image i, so every step commits at most r tokens per image, a 4-token hole takes one
     step beside a full image's 13 (r = 4, 7 x 7), and an image with nothing to fill is never evaluated.  It costs ONE host read
-    (the ``n_known`` vector, B int32) ahead of the sampler call -- the only synchronisation of this function."""
+    (the ``n_known`` vector, B int32) ahead of the sampler call -- the only synchronisation of this function.
+    ``schedule`` / ``selection_noise``: handed to sample_confident() as given -- how many of the unknown tokens a
+    step commits ('cosine': few at first, most at the end) and how much annealed Gumbel noise their order carries; both None:
+    the call made before.  The known tokens come back unchanged under every schedule and noise scale."""
     if positions_per_step is not None:
         if sample_steps is not None:
             raise ValueError("complete_images_confident: give sample_steps or positions_per_step, not both")
         if isinstance(positions_per_step, bool) or not isinstance(positions_per_step, int) or positions_per_step < 1:
             raise ValueError(f"complete_images_confident: positions_per_step must be an int >= 1, got {positions_per_step!r}")
     return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p, confident=True,
-                     positions_per_step=positions_per_step)
+                     positions_per_step=positions_per_step,
+                     **({} if schedule is None and selection_noise is None else {'schedule': schedule, 'selection_noise': selection_noise}))
 
 
 def steps_for_holes(n_unknown, positions_per_step):
@@ -105,7 +109,8 @@ def steps_for_holes(n_unknown, positions_per_step):
     return ((n_unknown + (r - 1)) // r).clamp(min=1)
 
 
-def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None, confident=False, positions_per_step=None):
+def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p=None, confident=False, positions_per_step=None,
+              **sched):
     images, keep = _check_inputs(images, keep)
     B, C, H, W = (int(v) for v in images.shape)
     h, w = H // 4, W // 4
@@ -117,7 +122,8 @@ def _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k,
     if positions_per_step is not None:
         sample_steps = steps_for_holes(h * w - n_known.cpu().to(torch.int64), positions_per_step)     # (the one host read)
     if confident:
-        tokens = sampler.sample_confident(sample_steps=sample_steps, temp=temp, x_init=x_init, known=known, top_k=top_k, top_p=top_p)
+        tokens = sampler.sample_confident(sample_steps=sample_steps, temp=temp, x_init=x_init, known=known, top_k=top_k, top_p=top_p,
+                                          **sched)
     elif top_p is not None:
         tokens = sampler.sample_top_p(top_p, temp=temp, sample_steps=sample_steps, x_init=x_init, known=known, top_k=top_k)
     elif top_k is None:

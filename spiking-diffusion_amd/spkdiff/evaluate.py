@@ -212,7 +212,8 @@ def temperature_sweep_top_p(model, sampler, temps, n_per_temp, top_p, sample_ste
 
 
 @torch.no_grad()
-def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1.0, top_k=None, top_p=None):
+def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1.0, top_k=None, top_p=None, schedule=None,
+                     selection_noise=None):
     """"How few steps are enough?" as ONE job: ``n_per_steps`` confidence-ordered samples for every entry of
     ``steps`` (integers >= 1) -- image ``g * n_per_steps + j`` of the job runs ``steps[g]`` steps -- through
     ``AbsorbingDiffusion.sample_confident`` with per-image step counts.  Returns (uint8 images [len(steps), n_per_steps, C, H, W],
@@ -220,8 +221,10 @@ def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1
     group boundaries (None: one call), each a shard of the job (``set_shard``) under ONE noise key (``_one_key``), every call at
     the largest count among its images; image (g, j) is the image ``sample_confident(steps[g])`` gives at global index
     ``g * n_per_steps + j`` under the sweep's key, so neither ``batch`` nor the grouping changes an image.  ``temp`` / ``top_k`` /
-    ``top_p``: one value for the whole job, as sample_confident() takes a number.  ``n_samples`` / ``global_first`` of the sampler
-    are restored."""
+    ``top_p``: one value for the whole job, as sample_confident() takes a number.  ``schedule`` (None, 'linear' or 'cosine': every
+    image gets the named table of its own step count) and ``selection_noise`` (one tau >= 0, annealed over each image's own steps):
+    DESIGN.md §4.17, handed to every call; both None: the calls made before.  ``n_samples`` / ``global_first`` of the sampler are
+    restored."""
     n = int(n_per_steps)
     try:
         sv = torch.as_tensor(steps)
@@ -231,6 +234,9 @@ def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1
         ok = False
     if not ok or n < 1:
         raise ValueError(f"step_count_sweep: steps must be a sequence of integers >= 1 and n_per_steps >= 1, got {steps!r}, {n_per_steps!r}")
+    if not (schedule is None or isinstance(schedule, str)):
+        raise ValueError(f"step_count_sweep: schedule is None, 'linear' or 'cosine' (a table fits one step count), got {schedule!r}")
+    sched = {} if schedule is None and selection_noise is None else {'schedule': schedule, 'selection_noise': selection_noise}
     if getattr(sampler, "noise_source", "philox") != "philox":
         raise ValueError("step_count_sweep: one job in several calls needs the counter-based noise (noise_source = 'philox')")
     sv = sv.to(torch.int32).cpu().repeat_interleave(n)
@@ -246,7 +252,7 @@ def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1
             for first in range(0, total, step):
                 count = min(step, total - first)
                 sampler.set_shard(first, count)
-                tok = sampler.sample_confident(sv[first:first + count], temp=temp, top_k=top_k, top_p=top_p)
+                tok = sampler.sample_confident(sv[first:first + count], temp=temp, top_k=top_k, top_p=top_p, **sched)
                 tok = tok.reshape(count, tok.shape[-2], tok.shape[-1])
                 images.append(model.decode_tokens(tok, T, want_u8=True)[1])
                 tokens.append(tok)

@@ -2321,6 +2321,123 @@ def den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=N
     return (None if x1 is None else (x1, c1o)), logits
 
 
+def _sched_args(sched_w, noise_a, score, B, S, t, n, what):
+    """The tables of a ``_sched`` token update: ``sched_w`` a contiguous int32 device tensor [B, S + 1]
+    (the entry points read uint32: weights 0 .. 2^24 have the same bits in both), ``noise_a`` None or contiguous fp32 [B, S + 1] on the
+    device, both taken as given; ``score`` None or fp32 with one entry per position; 1 <= t <= S."""
+    B, S = int(B), int(S)
+    if S < 1 or not 1 <= int(t) <= S:
+        raise ValueError(f"{what}: 1 <= t <= S, got t = {int(t)}, S = {S}")
+    if (not isinstance(sched_w, torch.Tensor) or sched_w.dtype != torch.int32 or not sched_w.is_cuda or
+            not sched_w.is_contiguous() or tuple(sched_w.shape) != (B, S + 1)):
+        got = f"{sched_w.dtype} {tuple(sched_w.shape)} on '{sched_w.device}'" if isinstance(sched_w, torch.Tensor) else repr(type(sched_w))
+        raise ValueError(f"{what}: sched_w must be a contiguous int32 device tensor [B = {B}, S + 1 = {S + 1}], got {got}")
+    if noise_a is not None and (not isinstance(noise_a, torch.Tensor) or noise_a.dtype != torch.float32 or not noise_a.is_cuda or
+                                not noise_a.is_contiguous() or tuple(noise_a.shape) != (B, S + 1)):
+        got = f"{noise_a.dtype} {tuple(noise_a.shape)} on '{noise_a.device}'" if isinstance(noise_a, torch.Tensor) else repr(type(noise_a))
+        raise ValueError(f"{what}: noise_a must be None or a contiguous fp32 device tensor [B = {B}, S + 1 = {S + 1}], got {got}")
+    if score is not None and (not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or not score.is_cuda or
+                              not score.is_contiguous() or score.numel() != n):
+        raise ValueError(f"{what}: score must be a contiguous fp32 device tensor with one entry per position (written where a position is masked)")
+    return sched_w, noise_a, score
+
+
+def psample_step_conf_sched(logits, x_t, unmasked, t, temp, sched_w, S, noise_a=None, u=None, q=None, seed=0, offset=0, x0_hat=None,
+                            conf=None, score=None, philox_state=None, next_input=None, top_k=None, top_p=None):
+    """``psample_step_conf`` under a reveal schedule and annealed selection noise (spk_psample_step_conf_sched):
+    the count of image i at step ``t`` comes from row i of ``sched_w`` (int32 [B, S + 1] on the device; spkdiff.schedules
+    builds rows), the order from score = conf + noise_a[i][t] * g with g the Gumbel of the position's stream-0 uniform (``noise_a``:
+    fp32 [B, S + 1] on the device or None = no noise; ``u``, where injected, IS that uniform).  ``score``: optional fp32 output, at
+    the masked positions.  Candidates, ``x0_hat`` and ``conf`` are psample_step_conf's bit for bit.  Every other argument is the
+    sibling's."""
+    logits = _dev(logits, "logits", torch.float32)
+    B, K = logits.shape[0], logits.shape[1]
+    HW = logits[0, 0].numel()
+    n = B * HW
+    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // HW, "psample_step_conf_sched", logits.device)
+    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, x_t.numel() // HW, S, t, n, "psample_step_conf_sched")
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
+    next_input = _next_input_arg(next_input, n)
+    check(lib.spk_psample_step_conf_sched(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
+                                          int(seed), int(offset), _p(philox_state), _p(_x0_hat_out(x0_hat, n)),
+                                          _p(_conf_out(conf, n)), B, HW, K, _p(next_input), _p(sched_w), _p(noise_a), int(S), _p(score),
+                                          _stream(logits)), "spk_psample_step_conf_sched")
+    return x_t, unmasked
+
+
+def psample_step_conf_listed_sched(logits, x_t, unmasked, t, temp, steps_b, S, step_stride, sched_w, noise_a=None, u=None, q=None,
+                                   seed=0, offset=0, x0_hat=None, conf=None, score=None, philox_state=None, top_k=None, top_p=None):
+    """``psample_step_conf_listed`` under a reveal schedule and annealed selection noise (spk_psample_step_conf_listed_sched;
+    DESIGN.md §4.17): the tables of psample_step_conf_sched, indexed by image and by the loop's ``t``; a listed image draws its
+    Gumbel uniform at its own shifted counters, as it draws its race noise.  Every other argument is the sibling's."""
+    if ACTIVE is None:
+        raise ValueError("psample_step_conf_listed_sched: the list of pending images comes from the enclosing active_set scope "
+                         "(ops.select_pending); outside one call psample_step_conf_sched")
+    act, nact = ACTIVE
+    logits = _dev(logits, "logits", torch.float32)
+    K = logits.shape[1]
+    HW = logits[0, 0].numel()
+    B = x_t.numel() // HW
+    n = B * HW
+    what = "psample_step_conf_listed_sched"
+    if logits.shape[0] != B:
+        raise ValueError(f"{what}: logits hold one slot per image of the batch ({B}), got {logits.shape[0]}")
+    top_p = torch.ones(B, dtype=torch.float32, device=logits.device) if top_p is None else top_p
+    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, what, logits.device)
+    per_image = isinstance(temp, torch.Tensor) and (temp.numel() > 1 or (temp.is_cuda and temp.dim() == 1 and temp.numel() == B))
+    if not per_image and not float(temp) > 0:
+        raise ValueError(f"{what}: temp must be > 0 (what the scalar entry points check), got {float(temp)}")
+    top_k, temp_b = _topk_arg(top_k, temp, B, what, logits.device)
+    steps_b = _steps_arg(steps_b, B, what)
+    S, step_stride = int(S), int(step_stride)
+    if step_stride < 0:
+        raise ValueError(f"{what}: step_stride >= 0, got {step_stride}")
+    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, B, S, t, n, what)
+    if act.numel() < B or nact.numel() < 2:
+        raise ValueError(f"{what}: the active_set pair must hold B slots and two count words")
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
+    check(lib.spk_psample_step_conf_listed_sched(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u),
+                                                 _p(q), int(seed), int(offset) & 0xFFFFFFFFFFFFFFFF, _p(philox_state),
+                                                 _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), B, HW, K, _p(steps_b), S,
+                                                 step_stride, _p(act), _p(nact), _p(sched_w), _p(noise_a), _p(score),
+                                                 _stream(logits)), "spk_psample_step_conf_listed_sched")
+    return x_t, unmasked
+
+
+def den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, t, temp, sched_w, S, *, T, K, noise_a=None, u=None, q=None, seed=0,
+                             offset=0, philox_state=None, conv1=None, want_logits=False, top_k=None, top_p=None, x0_hat=None,
+                             conf=None, score=None):
+    """``den_step_tail_conf`` under a reveal schedule and annealed selection noise (spk_den_step_tail_conf_sched):
+    conv6 on the counts, the token update of ``psample_step_conf_sched`` and -- with ``conv1`` -- the next step's first layer, one
+    launch.  The sibling's arguments, checks and results plus the tables and the optional ``score`` of psample_step_conf_sched."""
+    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
+    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
+    B, nch5, H, W, _ = cnt5.shape
+    n = B * H * W
+    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // (H * W), "den_step_tail_conf_sched", cnt5.device)
+    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, x_t.numel() // (H * W), S, t, n, "den_step_tail_conf_sched")
+    wq, scale, bias_d = packed6
+    _token_state(x_t, unmasked, n, "[B,1,h,w]")
+    u, q = _step_noise(u, q, philox_state, n, int(K))
+    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
+    x1 = c1o = w1 = b1 = a1 = bb1 = None
+    if conv1 is not None and int(T) != 16:
+        raise NotImplementedError("spk_den_step_tail_conf_sched: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
+                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
+    if conv1 is not None:
+        w1, b1, a1, bb1 = conv1
+        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
+        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
+    check(lib.spk_den_step_tail_conf_sched(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
+                                           _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
+                                           int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H,
+                                           W, int(K), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), _p(sched_w), _p(noise_a),
+                                           int(S), _p(score), _stream(cnt5)), "spk_den_step_tail_conf_sched")
+    return (None if x1 is None else (x1, c1o)), logits
+
+
 def q_sample(x_0, t, u, num_timesteps, mask_id):
     """(x_t, x_0_ignore, mask) of R/snn_model/vq_diffusion.py:61-75 from x_0 fp32 [B,1,h,w], t int64 [B] and the uniforms u
     (spk_q_sample: one launch)."""
