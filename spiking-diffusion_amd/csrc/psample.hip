@@ -140,8 +140,11 @@ __global__ __launch_bounds__(256) void psample_conf_kernel(const float* __restri
 // state, noise, the per-image arrays and the two outputs by image b = active[s].  Image b runs e = min(steps_b[b], S) steps of
 // its own inside a loop of S, so its step index at loop step t is e - t, not S - t: it draws at offset - (S - e) * step_stride,
 // the counters it would draw alone in a run of e steps.  An image with t > e is not pending and is left as it is whatever the
-// list says.  No next_input: the listed form gathers its denoiser input by slot.  A kernel of its own -- the body is the dense
-// kernel's with the two indices apart -- so that psample_conf_kernel keeps the instruction stream it has.
+// list says.  No next_input: the listed form gathers its denoiser input by slot.
+// The body is the dense kernel's with the two indices apart, and psample_conf_sched_kernel below repeats the candidate draw a third
+// time, line for line.  The copies are deliberate: drawing through one shared __forceinline__ helper changed the instruction
+// stream of all 16 instances of the three kernels (profiles/conf_launcher_resources.txt has the numbers).  Only the host side is
+// shared (psample_conf_launch).
 template <int KPL>
 __global__ __launch_bounds__(256) void psample_conf_listed_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
                                                                   uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
@@ -198,8 +201,7 @@ __global__ __launch_bounds__(256) void psample_conf_listed_kernel(const float* _
 // The confidence-ordered update under a reveal schedule and annealed selection noise (spk_psample_step_conf_sched and, LISTED,
 // spk_psample_step_conf_listed_sched; the rule: psample_common.h): the two kernels above with the count read from
 // the image's row of sched_w and the order key taken from score = conf + a * g, which wave 0 computes for all positions at once
-// between the draw and the rank.  A family of its own, so that the `_conf` kernels
-// keep the instruction stream they have.  The candidate draw is theirs, line for line: x0_hat_out and conf_out are the sibling's.
+// between the draw and the rank.  x0_hat_out and conf_out are the sibling's.
 // LISTED: workgroup = slot of the pending list, logits by slot, everything else -- the two tables too -- by image active[s], the
 // counters (those of the Gumbel uniform included) shifted to the image's own run of e steps; no next_input.
 struct spk_sched_arg {
@@ -658,30 +660,58 @@ extern "C" int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_in
                                           active_or_null, n_active_or_null, next_input_b2hw_or_null, stream);
 }
 
-// The same step under the confidence-ordered reveal (include/spkdiff.h; the rule: psample_common.h): the `_topp` arguments without an
-// active list, plus conf_out_or_null.  u_or_null is accepted and ignored (the coin is not part of the rule).
+// The confidence-ordered updates (include/spkdiff.h; the rule: psample_common.h): one launcher for the four
+// entry points.  LISTED: on the list of pending images, each at its own step count (steps_b / active / n_active required, no
+// next_input); SCHED: under a reveal schedule and annealed selection noise (sched_w required; u_or_null is the Gumbel uniform --
+// without a schedule it is accepted and ignored: the coin is not part of the rule).  1 <= t <= S wherever the form has an S.
+namespace {
+template <bool LISTED, bool SCHED>
+int psample_conf_launch(const float* logits, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_topp temp,
+                        const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                        unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                        long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                        unsigned long long step_stride, const int* active, const int* n_active, float* next_input_or_null,
+                        const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null, hipStream_t stream) {
+  if (!logits || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0)
+    return SPK_ERR_ARG;
+  if ((LISTED || SCHED) && (S <= 0 || t > S)) return SPK_ERR_ARG;
+  if (LISTED && (!steps_b || !active || !n_active)) return SPK_ERR_ARG;
+  if (SCHED && !sched_w) return SPK_ERR_ARG;
+  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
+#define SPK_PSAMPLE_CONF_LAUNCH(KPL)                                                                                     \
+  if constexpr (SCHED)                                                                                                   \
+    hipLaunchKernelGGL((psample_conf_sched_kernel<KPL, LISTED>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, \
+                       temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, \
+                       spk_sched_arg{sched_w, noise_a_or_null, u_or_null, score_out_or_null, S}, steps_b, step_stride, active, \
+                       n_active, B, HW, K, next_input_or_null, (float)(t - 1));                                         \
+  else if constexpr (LISTED)                                                                                             \
+    hipLaunchKernelGGL((psample_conf_listed_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, temp, \
+                       q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, steps_b, S, \
+                       step_stride, active, n_active, B, HW, K);                                                         \
+  else                                                                                                                   \
+    hipLaunchKernelGGL((psample_conf_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, temp, \
+                       q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, HW, K, \
+                       next_input_or_null, (float)(t - 1))
+  if (K <= 256) { SPK_PSAMPLE_CONF_LAUNCH(4); }
+  else if (K <= 512) { SPK_PSAMPLE_CONF_LAUNCH(8); }
+  else if (K <= 1024) { SPK_PSAMPLE_CONF_LAUNCH(16); }
+  else { SPK_PSAMPLE_CONF_LAUNCH(32); }
+#undef SPK_PSAMPLE_CONF_LAUNCH
+  SPK_LAUNCH_CHECK();
+  return SPK_OK;
+}
+}  // namespace
+
 extern "C" int spk_psample_step_conf(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                                      const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
                                      const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
                                      const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
                                      float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
                                      hipStream_t stream) {
-  (void)u_or_null;
-  const spk_temp_topp temp{temp_b, topk_b, topp_b};
-  if (!logits_bkhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0)
-    return SPK_ERR_ARG;
-  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
-#define SPK_PSAMPLE_CONF_LAUNCH(KPL)                                                                                     \
-  hipLaunchKernelGGL((psample_conf_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits_bkhw, x_t_inout, unmasked_inout, t, temp, \
-                     q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, HW, K, \
-                     next_input_b2hw_or_null, (float)(t - 1))
-  if (K <= 256) SPK_PSAMPLE_CONF_LAUNCH(4);
-  else if (K <= 512) SPK_PSAMPLE_CONF_LAUNCH(8);
-  else if (K <= 1024) SPK_PSAMPLE_CONF_LAUNCH(16);
-  else SPK_PSAMPLE_CONF_LAUNCH(32);
-#undef SPK_PSAMPLE_CONF_LAUNCH
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
+  return psample_conf_launch<false, false>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                           q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
+                                           conf_out_or_null, B, HW, K, nullptr, 0, 0ull, nullptr, nullptr, next_input_b2hw_or_null,
+                                           nullptr, nullptr, nullptr, stream);
 }
 
 // The confidence-ordered update on the list of pending images, each at its own step count (include/spkdiff.h).
@@ -692,55 +722,11 @@ extern "C" int spk_psample_step_conf_listed(const float* logits_skhw, long long*
                                             long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K,
                                             const int* steps_b, int S, unsigned long long step_stride, const int* active,
                                             const int* n_active, hipStream_t stream) {
-  (void)u_or_null;
-  const spk_temp_topp temp{temp_b, topk_b, topp_b};
-  if (!logits_skhw || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 ||
-      K <= 0 || !steps_b || !active || !n_active || S <= 0 || t > S)
-    return SPK_ERR_ARG;
-  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
-#define SPK_PSAMPLE_CONF_LISTED_LAUNCH(KPL)                                                                              \
-  hipLaunchKernelGGL((psample_conf_listed_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits_skhw, x_t_inout, unmasked_inout, t, \
-                     temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, \
-                     steps_b, S, step_stride, active, n_active, B, HW, K)
-  if (K <= 256) SPK_PSAMPLE_CONF_LISTED_LAUNCH(4);
-  else if (K <= 512) SPK_PSAMPLE_CONF_LISTED_LAUNCH(8);
-  else if (K <= 1024) SPK_PSAMPLE_CONF_LISTED_LAUNCH(16);
-  else SPK_PSAMPLE_CONF_LISTED_LAUNCH(32);
-#undef SPK_PSAMPLE_CONF_LISTED_LAUNCH
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
+  return psample_conf_launch<true, false>(logits_skhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                          q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
+                                          conf_out_or_null, B, HW, K, steps_b, S, step_stride, active, n_active, nullptr, nullptr,
+                                          nullptr, nullptr, stream);
 }
-
-// The two updates above under a reveal schedule and annealed selection noise (include/spkdiff.h; the rule: psample_common.h,
-// DESIGN.md §4.17): one launcher for the dense and the listed form.
-namespace {
-template <bool LISTED>
-int psample_conf_sched_launch(const float* logits, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_topp temp,
-                              const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
-                              unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
-                              long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K, const int* steps_b,
-                              unsigned long long step_stride, const int* active, const int* n_active, float* next_input_or_null,
-                              const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
-                              hipStream_t stream) {
-  if (!logits || !x_t_inout || !unmasked_inout || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0 ||
-      !sched_w || S <= 0 || t <= 0 || t > S)
-    return SPK_ERR_ARG;
-  if (LISTED && (!steps_b || !active || !n_active)) return SPK_ERR_ARG;
-  if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
-  const spk_sched_arg sc{sched_w, noise_a_or_null, u_or_null, score_out_or_null, S};
-#define SPK_PSAMPLE_SCHED_LAUNCH(KPL)                                                                                    \
-  hipLaunchKernelGGL((psample_conf_sched_kernel<KPL, LISTED>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, \
-                     temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, sc, \
-                     steps_b, step_stride, active, n_active, B, HW, K, next_input_or_null, (float)(t - 1))
-  if (K <= 256) SPK_PSAMPLE_SCHED_LAUNCH(4);
-  else if (K <= 512) SPK_PSAMPLE_SCHED_LAUNCH(8);
-  else if (K <= 1024) SPK_PSAMPLE_SCHED_LAUNCH(16);
-  else SPK_PSAMPLE_SCHED_LAUNCH(32);
-#undef SPK_PSAMPLE_SCHED_LAUNCH
-  SPK_LAUNCH_CHECK();
-  return SPK_OK;
-}
-}  // namespace
 
 extern "C" int spk_psample_step_conf_sched(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                                            const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
@@ -749,10 +735,10 @@ extern "C" int spk_psample_step_conf_sched(const float* logits_bkhw, long long* 
                                            float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
                                            const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
                                            hipStream_t stream) {
-  return psample_conf_sched_launch<false>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+  return psample_conf_launch<false, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
                                           q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
-                                          conf_out_or_null, B, HW, K, nullptr, 0ull, nullptr, nullptr, next_input_b2hw_or_null,
-                                          sched_w, noise_a_or_null, S, score_out_or_null, stream);
+                                          conf_out_or_null, B, HW, K, nullptr, S, 0ull, nullptr, nullptr, next_input_b2hw_or_null,
+                                          sched_w, noise_a_or_null, score_out_or_null, stream);
 }
 
 extern "C" int spk_psample_step_conf_listed_sched(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
@@ -764,8 +750,8 @@ extern "C" int spk_psample_step_conf_listed_sched(const float* logits_skhw, long
                                                   unsigned long long step_stride, const int* active, const int* n_active,
                                                   const uint32_t* sched_w, const float* noise_a_or_null,
                                                   float* score_out_or_null, hipStream_t stream) {
-  return psample_conf_sched_launch<true>(logits_skhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+  return psample_conf_launch<true, true>(logits_skhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
                                          q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
-                                         conf_out_or_null, B, HW, K, steps_b, step_stride, active, n_active, nullptr, sched_w,
-                                         noise_a_or_null, S, score_out_or_null, stream);
+                                         conf_out_or_null, B, HW, K, steps_b, S, step_stride, active, n_active, nullptr, sched_w,
+                                         noise_a_or_null, score_out_or_null, stream);
 }

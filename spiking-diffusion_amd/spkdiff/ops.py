@@ -2122,6 +2122,55 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
     return logp, step
 
 
+def _den_step_tail(what, cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset, philox_state, conv1, want_logits,
+                   top_k, top_p, conf_outs=None, sched=None):
+    """The body of ``den_step_tail`` and its two confidence-ordered siblings (``what``: the caller's name; its entry point is
+    ``spk_`` + that).  ``conf_outs``: None -- the plain family, launched by the form of its temperature, inside an ``active_set``
+    scope too -- or the (x0_hat, conf) of a confidence-ordered tail; ``sched``: None or its (sched_w, S, noise_a, score)."""
+    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
+    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
+    B, nch5, H, W, _ = cnt5.shape
+    n = B * H * W
+    images = x_t.numel() // (H * W)
+    act = nact = None
+    if conf_outs is None:
+        top_p, top_k, temp = _topp_arg(top_p, top_k, temp, images, what, cnt5.device)
+        top_k, temp = _topk_arg(top_k, temp, images, what, cnt5.device)
+        temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, images, what)
+        act, nact = (None, None) if ACTIVE is None else ACTIVE
+    else:
+        temp_b, top_k, top_p, _ = _conf_args(temp, top_k, top_p, images, what, cnt5.device)
+    if sched is not None:
+        sched_w, S, noise_a, score = sched
+        sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, images, S, t, n, what)
+    wq, scale, bias_d = packed6
+    _token_state(x_t, unmasked, n, "[B,1,h,w]")
+    u, q = _step_noise(u, q, philox_state, n, int(K))
+    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
+    if act is not None and conv1 is not None:
+        raise ValueError(f"{what}: the fused first layer is the dense form's (inside an active_set scope pass conv1=None)")
+    x1 = c1o = w1 = b1 = a1 = bb1 = None
+    if conv1 is not None and int(T) != 16:
+        raise NotImplementedError(f"spk_{what}: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
+                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
+    if conv1 is not None:
+        w1, b1, a1, bb1 = conv1
+        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
+        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
+    name = "spk_" + what
+    head = (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t))
+    tail = (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W,
+            int(K))
+    if conf_outs is None:
+        _launch_by_temp(name, temp_b, temp, head, tail + (_p(act), _p(nact), _stream(cnt5)), top_k=top_k, top_p=top_p)
+    else:
+        tail += (_p(_x0_hat_out(conf_outs[0], n)), _p(_conf_out(conf_outs[1], n)))
+        if sched is not None:
+            tail += (_p(sched_w), _p(noise_a), int(S), _p(score))
+        check(getattr(lib, name)(*head, _p(temp_b), _p(top_k), _p(top_p), *tail, _stream(cnt5)), name)
+    return (None if x1 is None else (x1, c1o)), logits
+
+
 def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
                   conv1=None, want_logits=False, top_k=None, top_p=None):
     """The tail of one dense reverse step as one launch (spk_den_step_tail): conv6 on the spike counts + time mean, the token
@@ -2132,44 +2181,26 @@ def den_step_tail(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, 
     belongs to the next step's active set).  ``temp``: a number or a per-image fp32 device tensor (spk_den_step_tail_temps);
     ``top_k``: int32 device tensor, one k per image, as for psample_step (spk_den_step_tail_topk); ``top_p``: fp32 device tensor,
     one p per image, as for psample_step (spk_den_step_tail_topp)."""
-    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
-    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
-    B, nch5, H, W, _ = cnt5.shape
-    n = B * H * W
-    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, x_t.numel() // (H * W), "den_step_tail", cnt5.device)
-    top_k, temp = _topk_arg(top_k, temp, x_t.numel() // (H * W), "den_step_tail", cnt5.device)
-    temp_b, temp = (temp, None) if top_k is not None else _temp_arg(temp, x_t.numel() // (H * W), "den_step_tail")
-    wq, scale, bias_d = packed6
-    _token_state(x_t, unmasked, n, "[B,1,h,w]")
-    u, q = _step_noise(u, q, philox_state, n, int(K))
-    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
-    act, nact = (None, None) if ACTIVE is None else ACTIVE
-    if act is not None and conv1 is not None:
-        raise ValueError("den_step_tail: the fused first layer is the dense form's (inside an active_set scope pass conv1=None)")
-    x1 = c1o = w1 = b1 = a1 = bb1 = None
-    if conv1 is not None and int(T) != 16:
-        raise NotImplementedError("spk_den_step_tail: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
-                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
-    if conv1 is not None:
-        w1, b1, a1, bb1 = conv1
-        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
-        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
-    _launch_by_temp("spk_den_step_tail", temp_b, temp, (_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale),
-                                                        _p(bias_d), _p(logits), _p(x_t), _p(unmasked), int(t)),
-                    (_p(u), _p(q), int(seed), int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T),
-                     B, H, W, int(K), _p(act), _p(nact), _stream(cnt5)), top_k=top_k, top_p=top_p)
-    return (None if x1 is None else (x1, c1o)), logits
+    return _den_step_tail("den_step_tail", cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset, philox_state, conv1,
+                          want_logits, top_k, top_p)
 
 
-def _conf_args(temp, top_k, top_p, B, what, device):
+def _conf_args(temp, top_k, top_p, B, what, device, listed=False):
     """The three per-image arrays of a confidence-ordered token update after the checks of the ``_topp`` siblings
     (``_topp_arg`` / ``_topk_arg``: ``top_k`` / ``top_p``, where given, are device tensors of B entries -- a number is refused as
     the siblings refuse it): a missing ``top_p`` becomes ones and a missing ``top_k`` zeros (neither truncates), a scalar ``temp``
-    (> 0) is broadcast, a per-image ``temp`` is taken as given -> (temp_b, top_k, top_p).  There is no active-list form: inside an ``active_set`` scope the call is
-    refused before anything is launched."""
-    if ACTIVE is not None:
+    (> 0) is broadcast, a per-image ``temp`` is taken as given -> (temp_b, top_k, top_p, pair).  ``listed`` false: there is no
+    active-list form, so inside an ``active_set`` scope the call is refused before anything is launched, and ``pair`` is None.
+    ``listed`` true: the call is refused OUTSIDE a scope, and ``pair`` is the scope's (active, n_active), which
+    must hold B slots and two count words."""
+    if not listed and ACTIVE is not None:
         raise ValueError(f"{what}: this entry point has no active-list form (which positions change depends on the logits): call it "
                          "outside an active_set scope; the list of pending images is psample_step_conf_listed's")
+    if listed and ACTIVE is None:
+        raise ValueError(f"{what}: the list of pending images comes from the enclosing active_set scope "
+                         f"(ops.select_pending); outside one call {what.replace('_listed', '')}")
+    if listed and (ACTIVE[0].numel() < int(B) or ACTIVE[1].numel() < 2):
+        raise ValueError(f"{what}: the active_set pair must hold B slots and two count words")
     B = int(B)
     # scalar or vector as ``_topk_arg`` decides it: a device tensor of B entries is per-image and never read back (B = 1 too: the
     # sampler hands its graph's one-entry buffer down, and a read-back is refused inside a capture)
@@ -2180,7 +2211,7 @@ def _conf_args(temp, top_k, top_p, B, what, device):
         top_p = torch.ones(B, dtype=torch.float32, device=device)
     top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, what, device)
     top_k, temp_b = _topk_arg(top_k, temp, B, what, device)
-    return temp_b, top_k, top_p
+    return temp_b, top_k, top_p, (ACTIVE if listed else None)
 
 
 def _conf_out(conf, n):
@@ -2197,6 +2228,40 @@ def _x0_hat_out(x0_hat, n):
     return x0_hat
 
 
+def _psample_conf(what, logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state, top_k, top_p, next_input=None,
+                  listed=None, sched=None):
+    """The body of the four ``psample_step_conf*`` wrappers (``what``: the caller's name; its entry point is ``spk_`` + that).
+    ``listed``: None -- the dense form, which may write ``next_input`` -- or the (steps_b, S, step_stride) of the update on the list
+    of the enclosing ``active_set`` scope, whose logits lie by slot; ``sched``: None or (sched_w, S, noise_a, score)."""
+    logits = _dev(logits, "logits", torch.float32)
+    B, K = logits.shape[0], logits.shape[1]
+    HW = logits[0, 0].numel()
+    n = B * HW
+    images = x_t.numel() // HW
+    temp_b, top_k, top_p, pair = _conf_args(temp, top_k, top_p, images, what, logits.device, listed=listed is not None)
+    if listed is None:
+        offset, tail = int(offset), (_p(_next_input_arg(next_input, n)),)
+    else:
+        if B != images:
+            raise ValueError(f"{what}: logits hold one slot per image of the batch ({images}), got {B}")
+        steps_b, S, step_stride = _steps_arg(listed[0], B, what), int(listed[1]), int(listed[2])
+        if not 1 <= int(t) <= S or step_stride < 0:
+            raise ValueError(f"{what}: 1 <= t <= S and step_stride >= 0, got t = {int(t)}, S = {S}, stride {step_stride}")
+        offset, tail = int(offset) & 0xFFFFFFFFFFFFFFFF, (_p(steps_b), S, step_stride, _p(pair[0]), _p(pair[1]))
+    if sched is not None:
+        sched_w, S, noise_a, score = sched
+        sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, images, S, t, n, what)
+    _token_state(x_t, unmasked, n, "(updated in place)")
+    u, q = _step_noise(u, q, philox_state, n, K)
+    if sched is not None:                           # (the listed form has its S among the list's arguments)
+        tail += (_p(sched_w), _p(noise_a), int(S), _p(score)) if listed is None else (_p(sched_w), _p(noise_a), _p(score))
+    name = "spk_" + what
+    check(getattr(lib, name)(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
+                             offset, _p(philox_state), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), B, HW, K, *tail,
+                             _stream(logits)), name)
+    return x_t, unmasked
+
+
 def psample_step_conf(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0, offset=0, x0_hat=None, conf=None,
                       philox_state=None, next_input=None, top_k=None, top_p=None):
     """``psample_step`` under the confidence-ordered reveal (spk_psample_step_conf): every position masked at entry
@@ -2206,18 +2271,8 @@ def psample_step_conf(logits, x_t, unmasked, t, temp=1.0, u=None, q=None, seed=0
     of the rule).  ``temp`` / ``top_k`` / ``top_p`` as for psample_step: ``top_k`` (int32) and ``top_p`` (fp32) are device
     tensors with one entry per image or None, ``temp`` a number or such a tensor.  The entry point takes all three per image, so a
     scalar ``temp`` is broadcast and a missing truncation becomes k = 0 / p = 1 everywhere.  Not inside an ``active_set`` scope; h * w <= 64."""
-    logits = _dev(logits, "logits", torch.float32)
-    B, K = logits.shape[0], logits.shape[1]
-    HW = logits[0, 0].numel()
-    n = B * HW
-    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // HW, "psample_step_conf", logits.device)
-    _token_state(x_t, unmasked, n, "(updated in place)")
-    u, q = _step_noise(u, q, philox_state, n, K)
-    next_input = _next_input_arg(next_input, n)
-    check(lib.spk_psample_step_conf(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
-                                    int(seed), int(offset), _p(philox_state), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)),
-                                    B, HW, K, _p(next_input), _stream(logits)), "spk_psample_step_conf")
-    return x_t, unmasked
+    return _psample_conf("psample_step_conf", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state, top_k,
+                         top_p, next_input)
 
 
 def _steps_arg(steps_b, B, what):
@@ -2258,36 +2313,8 @@ def psample_step_conf_listed(logits, x_t, unmasked, t, temp, steps_b, S, step_st
     A listed image takes psample_step_conf's update at this ``t`` with the noise of its own run of e = min(steps_b[i], S) steps:
     counters at ``offset - (S - e) * step_stride`` (``S``: the loop's step count, ``step_stride``: its counters per step);
     images off the list keep their state.  No ``next_input``: the listed form gathers its denoiser input by slot."""
-    if ACTIVE is None:
-        raise ValueError("psample_step_conf_listed: the list of pending images comes from the enclosing active_set scope "
-                         "(ops.select_pending); outside one call psample_step_conf")
-    act, nact = ACTIVE
-    logits = _dev(logits, "logits", torch.float32)
-    K = logits.shape[1]
-    HW = logits[0, 0].numel()
-    B = x_t.numel() // HW
-    n = B * HW
-    if logits.shape[0] != B:
-        raise ValueError(f"psample_step_conf_listed: logits hold one slot per image of the batch ({B}), got {logits.shape[0]}")
-    top_p = torch.ones(B, dtype=torch.float32, device=logits.device) if top_p is None else top_p
-    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, "psample_step_conf_listed", logits.device)
-    per_image = isinstance(temp, torch.Tensor) and (temp.numel() > 1 or (temp.is_cuda and temp.dim() == 1 and temp.numel() == B))
-    if not per_image and not float(temp) > 0:
-        raise ValueError(f"psample_step_conf_listed: temp must be > 0 (what the scalar entry points check), got {float(temp)}")
-    top_k, temp_b = _topk_arg(top_k, temp, B, "psample_step_conf_listed", logits.device)
-    steps_b = _steps_arg(steps_b, B, "psample_step_conf_listed")
-    S, step_stride = int(S), int(step_stride)
-    if not 1 <= int(t) <= S or step_stride < 0:
-        raise ValueError(f"psample_step_conf_listed: 1 <= t <= S and step_stride >= 0, got t = {int(t)}, S = {S}, stride {step_stride}")
-    if act.numel() < B or nact.numel() < 2:
-        raise ValueError("psample_step_conf_listed: the active_set pair must hold B slots and two count words")
-    _token_state(x_t, unmasked, n, "(updated in place)")
-    u, q = _step_noise(u, q, philox_state, n, K)
-    check(lib.spk_psample_step_conf_listed(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
-                                           int(seed), int(offset) & 0xFFFFFFFFFFFFFFFF, _p(philox_state), _p(_x0_hat_out(x0_hat, n)),
-                                           _p(_conf_out(conf, n)), B, HW, K, _p(steps_b), S, step_stride, _p(act), _p(nact),
-                                           _stream(logits)), "spk_psample_step_conf_listed")
-    return x_t, unmasked
+    return _psample_conf("psample_step_conf_listed", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state,
+                         top_k, top_p, listed=(steps_b, S, step_stride))
 
 
 def den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=None, q=None, seed=0, offset=0, philox_state=None,
@@ -2296,29 +2323,8 @@ def den_step_tail_conf(cnt5, cnt1, packed6, x_t, unmasked, t, temp, *, T, K, u=N
     ``psample_step_conf`` and -- with ``conv1`` -- the next step's first layer on the committed tokens, one launch.  Same
     arguments, checks and results as den_step_tail, plus the optional outputs ``x0_hat`` / ``conf`` of psample_step_conf; not
     inside an ``active_set`` scope."""
-    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
-    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
-    B, nch5, H, W, _ = cnt5.shape
-    n = B * H * W
-    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // (H * W), "den_step_tail_conf", cnt5.device)
-    wq, scale, bias_d = packed6
-    _token_state(x_t, unmasked, n, "[B,1,h,w]")
-    u, q = _step_noise(u, q, philox_state, n, int(K))
-    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
-    x1 = c1o = w1 = b1 = a1 = bb1 = None
-    if conv1 is not None and int(T) != 16:
-        raise NotImplementedError("spk_den_step_tail_conf: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
-                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
-    if conv1 is not None:
-        w1, b1, a1, bb1 = conv1
-        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
-        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
-    check(lib.spk_den_step_tail_conf(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
-                                     _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
-                                     int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H, W,
-                                     int(K), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), _stream(cnt5)),
-          "spk_den_step_tail_conf")
-    return (None if x1 is None else (x1, c1o)), logits
+    return _den_step_tail("den_step_tail_conf", cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset, philox_state,
+                          conv1, want_logits, top_k, top_p, conf_outs=(x0_hat, conf))
 
 
 def _sched_args(sched_w, noise_a, score, B, S, t, n, what):
@@ -2350,20 +2356,8 @@ def psample_step_conf_sched(logits, x_t, unmasked, t, temp, sched_w, S, noise_a=
     fp32 [B, S + 1] on the device or None = no noise; ``u``, where injected, IS that uniform).  ``score``: optional fp32 output, at
     the masked positions.  Candidates, ``x0_hat`` and ``conf`` are psample_step_conf's bit for bit.  Every other argument is the
     sibling's."""
-    logits = _dev(logits, "logits", torch.float32)
-    B, K = logits.shape[0], logits.shape[1]
-    HW = logits[0, 0].numel()
-    n = B * HW
-    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // HW, "psample_step_conf_sched", logits.device)
-    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, x_t.numel() // HW, S, t, n, "psample_step_conf_sched")
-    _token_state(x_t, unmasked, n, "(updated in place)")
-    u, q = _step_noise(u, q, philox_state, n, K)
-    next_input = _next_input_arg(next_input, n)
-    check(lib.spk_psample_step_conf_sched(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q),
-                                          int(seed), int(offset), _p(philox_state), _p(_x0_hat_out(x0_hat, n)),
-                                          _p(_conf_out(conf, n)), B, HW, K, _p(next_input), _p(sched_w), _p(noise_a), int(S), _p(score),
-                                          _stream(logits)), "spk_psample_step_conf_sched")
-    return x_t, unmasked
+    return _psample_conf("psample_step_conf_sched", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state,
+                         top_k, top_p, next_input, sched=(sched_w, S, noise_a, score))
 
 
 def psample_step_conf_listed_sched(logits, x_t, unmasked, t, temp, steps_b, S, step_stride, sched_w, noise_a=None, u=None, q=None,
@@ -2371,39 +2365,8 @@ def psample_step_conf_listed_sched(logits, x_t, unmasked, t, temp, steps_b, S, s
     """``psample_step_conf_listed`` under a reveal schedule and annealed selection noise (spk_psample_step_conf_listed_sched;
     DESIGN.md §4.17): the tables of psample_step_conf_sched, indexed by image and by the loop's ``t``; a listed image draws its
     Gumbel uniform at its own shifted counters, as it draws its race noise.  Every other argument is the sibling's."""
-    if ACTIVE is None:
-        raise ValueError("psample_step_conf_listed_sched: the list of pending images comes from the enclosing active_set scope "
-                         "(ops.select_pending); outside one call psample_step_conf_sched")
-    act, nact = ACTIVE
-    logits = _dev(logits, "logits", torch.float32)
-    K = logits.shape[1]
-    HW = logits[0, 0].numel()
-    B = x_t.numel() // HW
-    n = B * HW
-    what = "psample_step_conf_listed_sched"
-    if logits.shape[0] != B:
-        raise ValueError(f"{what}: logits hold one slot per image of the batch ({B}), got {logits.shape[0]}")
-    top_p = torch.ones(B, dtype=torch.float32, device=logits.device) if top_p is None else top_p
-    top_p, top_k, temp = _topp_arg(top_p, top_k, temp, B, what, logits.device)
-    per_image = isinstance(temp, torch.Tensor) and (temp.numel() > 1 or (temp.is_cuda and temp.dim() == 1 and temp.numel() == B))
-    if not per_image and not float(temp) > 0:
-        raise ValueError(f"{what}: temp must be > 0 (what the scalar entry points check), got {float(temp)}")
-    top_k, temp_b = _topk_arg(top_k, temp, B, what, logits.device)
-    steps_b = _steps_arg(steps_b, B, what)
-    S, step_stride = int(S), int(step_stride)
-    if step_stride < 0:
-        raise ValueError(f"{what}: step_stride >= 0, got {step_stride}")
-    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, B, S, t, n, what)
-    if act.numel() < B or nact.numel() < 2:
-        raise ValueError(f"{what}: the active_set pair must hold B slots and two count words")
-    _token_state(x_t, unmasked, n, "(updated in place)")
-    u, q = _step_noise(u, q, philox_state, n, K)
-    check(lib.spk_psample_step_conf_listed_sched(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u),
-                                                 _p(q), int(seed), int(offset) & 0xFFFFFFFFFFFFFFFF, _p(philox_state),
-                                                 _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), B, HW, K, _p(steps_b), S,
-                                                 step_stride, _p(act), _p(nact), _p(sched_w), _p(noise_a), _p(score),
-                                                 _stream(logits)), "spk_psample_step_conf_listed_sched")
-    return x_t, unmasked
+    return _psample_conf("psample_step_conf_listed_sched", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf,
+                         philox_state, top_k, top_p, listed=(steps_b, S, step_stride), sched=(sched_w, S, noise_a, score))
 
 
 def den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, t, temp, sched_w, S, *, T, K, noise_a=None, u=None, q=None, seed=0,
@@ -2412,30 +2375,8 @@ def den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, t, temp, sched_
     """``den_step_tail_conf`` under a reveal schedule and annealed selection noise (spk_den_step_tail_conf_sched):
     conv6 on the counts, the token update of ``psample_step_conf_sched`` and -- with ``conv1`` -- the next step's first layer, one
     launch.  The sibling's arguments, checks and results plus the tables and the optional ``score`` of psample_step_conf_sched."""
-    cnt5 = _dev(cnt5, "cnt5", torch.uint8)
-    cnt1 = _dev(cnt1, "cnt1", torch.uint8)
-    B, nch5, H, W, _ = cnt5.shape
-    n = B * H * W
-    temp_b, top_k, top_p = _conf_args(temp, top_k, top_p, x_t.numel() // (H * W), "den_step_tail_conf_sched", cnt5.device)
-    sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, x_t.numel() // (H * W), S, t, n, "den_step_tail_conf_sched")
-    wq, scale, bias_d = packed6
-    _token_state(x_t, unmasked, n, "[B,1,h,w]")
-    u, q = _step_noise(u, q, philox_state, n, int(K))
-    logits = torch.empty((B, K, H, W), dtype=torch.float32, device=cnt5.device) if want_logits else None
-    x1 = c1o = w1 = b1 = a1 = bb1 = None
-    if conv1 is not None and int(T) != 16:
-        raise NotImplementedError("spk_den_step_tail_conf_sched: the fused first layer is the T = 16, LIFNode(tau=2, v_threshold=1, "
-                                  "v_reset=0) form; run conv1 as its own launch for other step counts")
-    if conv1 is not None:
-        w1, b1, a1, bb1 = conv1
-        x1 = empty_spikes(S32, B, 64, H, W, T, cnt5.device)
-        c1o = torch.empty((B, 2, H, W, 32), dtype=torch.uint8, device=cnt5.device)
-    check(lib.spk_den_step_tail_conf_sched(_p(cnt5), int(nch5), _p(cnt1), int(cnt1.shape[1]), _p(wq), _p(scale), _p(bias_d), _p(logits),
-                                           _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
-                                           int(offset), _p(philox_state), _p(w1), _p(b1), _p(a1), _p(bb1), _p(x1), _p(c1o), int(T), B, H,
-                                           W, int(K), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), _p(sched_w), _p(noise_a),
-                                           int(S), _p(score), _stream(cnt5)), "spk_den_step_tail_conf_sched")
-    return (None if x1 is None else (x1, c1o)), logits
+    return _den_step_tail("den_step_tail_conf_sched", cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset,
+                          philox_state, conv1, want_logits, top_k, top_p, conf_outs=(x0_hat, conf), sched=(sched_w, S, noise_a, score))
 
 
 def q_sample(x_0, t, u, num_timesteps, mask_id):
