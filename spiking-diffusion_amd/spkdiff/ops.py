@@ -1601,7 +1601,11 @@ def readout_collapsed_supported(Cin, Cout, k):
 
 def readout_collapsed(x_bhwc, weight, bias, coef, *, apply_tanh=False, want_u8=False, k=3, pad=1, transposed=True):
     """Linear read-out layer on time-collapsed spikes: x_bhwc fp32 [B,H,W,Cin] = sum_t coef[t] * spikes[t] (conv_mfma_fused
-    with collapse_coef) -> dict(f32=[B,Cout,H,W] = conv(x) + bias * sum(coef) (tanh), u8=...).  Stride 1, 'same' padding."""
+    with collapse_coef) -> dict(f32=[B,Cout,H,W] = conv(x) + bias * sum(coef) (tanh), u8=...).  Stride 1, 'same' padding.
+    Refused here although the library takes them: the library's predicate depends on the image width (the kernel keeps
+    4 + k - 1 rows of W positions in LDS), and this wrapper asks it at width 64 whatever W is, so that a layer's answer does
+    not change with the image.  (Cin, Cout, k) that fit only narrower images -- e.g. (32, 9, 3), which
+    spk_readout_collapsed_fwd runs up to W = 63 -- raise NotImplementedError at every width, as does any W > 64."""
     x = _dev(x_bhwc, "x", torch.float32)
     B, H, W, Cin = x.shape
     w = _dev(weight, "weight", torch.float32)
