@@ -38,7 +38,7 @@ typedef struct ihipStream_t* spk_stream_t; /* == hipStream_t */
                            * refuses a library whose spk_version() differs.  Purely additive entry points (the SNN_VAE
                            * kernels spk_linear_lif_fwd / spk_svae_ar_fwd) keep the version: _lib.py resolves every declared
                            * symbol at import, so a library that lacks one fails there; so do spk_select_pending /
-                           * spk_psample_step_conf_listed, DESIGN.md §4.16, and the three `_sched` entry points, §4.17: additive, still 106) */
+                           * spk_psample_step_conf_listed, DESIGN.md §4.16, the three `_sched` entry points, §4.17, and the three `_remask` entry points, §4.18: additive, still 106) */
 
 /* return codes below zero (0: success; above zero: a hipError_t) */
 #define SPK_ERR_ARG (-1)         /* bad argument: null pointer, non-positive size, contradictory combination */
@@ -776,6 +776,51 @@ int spk_psample_step_conf_listed_sched(const float* logits_skhw, long long* x_t_
                                        unsigned long long step_stride, const int* active, const int* n_active,
                                        const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null,
                                        spk_stream_t stream);
+/* Remasking for confidence-ordered decoding (the rule: csrc/psample_common.h): spk_psample_step_conf_remask,
+ * spk_psample_step_conf_listed_remask and spk_den_step_tail_conf_remask take the arguments of their `_sched` siblings plus
+ *   const uint32_t* remask_r        [B][S + 1], required, indexed [image][t] like the two `_sched` tables;
+ *   float* commit_conf_inout        fp32 [B*HW], required, read and written in place like x_t / unmasked;
+ *   long long mask_id               the token a remasked position takes; a value inside [0, K) is SPK_ERR_ARG;
+ *   uint8_t* remasked_out_or_null   [B*HW]: for an image with m > 0, 1 at the positions this step remasked and 0 at its others;
+ *                                   untouched for an image with m = 0 or, in the listed form, with t > e_i.
+ * The family sits on top of the `_sched` family only (a null noise_a is a = 0; the linear table w[t] = t gives the ceil(m / t)
+ * counts).  commit_conf is one more piece of per-position state: +inf at the positions unmasked when the run started -- the known
+ * tokens, never revisited; a committed log-probability is <= 0, so +inf cannot arise otherwise --, the confidence of its reveal at a
+ * position a step revealed, anything (ignored) at a masked position.  The denoiser's logits at an unmasked position are untrained (the
+ * loss ignores those positions), so a committed token is never re-scored: its trust is the confidence it was committed with, and a
+ * remasked position draws again only at the NEXT step, after a denoiser call has seen it masked.  At reverse step t, per image:
+ *   1. m = positions masked at entry.  m == 0: the image is left as the sibling leaves it, and nothing is remasked.
+ *   2. Candidates, confidences, scores, the count n and the revealed set follow the `_sched` rule exactly: x0_hat_out, conf_out,
+ *      score_out and the revealed positions are bit for bit the sibling's on the same state and tables.
+ *   3. A position is revisable iff it was unmasked at entry and commit_conf != +inf (one revealed in this step is not).  c = their
+ *      number, r = min(remask_r[i][t], c); the kernel forces r = 0 at t = 1, so a run never ends with a masked position.  Order key =
+ *      the 32-bit key of commit_conf (a NaN: key 0).  A revisable p is remasked iff fewer than r revisable p' have (key, -p') below
+ *      (key, -p): smaller key first, equal keys to the HIGHER position -- the reveal's order from the other end.  A remasked p gets
+ *      x_t = mask_id and unmasked = 0; its commit_conf stays.
+ *   4. Every revealed p gets commit_conf[p] = its confidence (conf_out's value, not the noise-perturbed score).
+ *   5. next_input_b2hw and the fused first layer of the step tail read the state after 3 and 4.
+ * From m0 masked positions the revisable count at entry of step t is m0 - m_t, so the counts of a run are host integers: n_t = the
+ * `_sched` count of m_t, r_t = t >= 2 ? min(R[t], m0 - m_t) : 0, m_(t-1) = m_t - n_t + r_t.  Listed form: commit_conf, remask_r and
+ * remasked_out are indexed by image active[s].  Argument errors before any launch: the siblings', a null remask_r or
+ * commit_conf_inout, mask_id inside [0, K) (SPK_ERR_ARG).  The `_sched` and `_conf` entry points keep their code paths, signatures
+ * and results.  Capturable; allocates nothing. */
+int spk_psample_step_conf_remask(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t, const float* temp_b,
+                                 const int* topk_b, const float* topp_b, const float* u_or_null, const float* q_or_null,
+                                 unsigned long long philox_seed, unsigned long long philox_offset,
+                                 const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                 float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
+                                 const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                 const uint32_t* remask_r, float* commit_conf_inout, long long mask_id,
+                                 uint8_t* remasked_out_or_null, spk_stream_t stream);
+int spk_psample_step_conf_listed_remask(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                        const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                        const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                        const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                        float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                                        unsigned long long step_stride, const int* active, const int* n_active,
+                                        const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null,
+                                        const uint32_t* remask_r, float* commit_conf_inout, long long mask_id,
+                                        uint8_t* remasked_out_or_null, spk_stream_t stream);
 /* The same loop body run TEACHER-FORCED (csrc/pscore.hip): the reverse process scores given tokens x0 int64
  * [B*HW] instead of drawing tokens.  changes = (u < 1/t) & ~unmasked with the u of spk_psample_step (injected, or the same Philox
  * counters: stream 0 at offset + p * K; the q stream is not drawn), and at a changing position p
@@ -880,6 +925,20 @@ int spk_den_step_tail_conf_sched(const uint8_t* cnt5, int nch5, const uint8_t* c
                                  uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                                  long long* x0_hat_out_or_null, float* conf_out_or_null, const uint32_t* sched_w,
                                  const float* noise_a_or_null, int S, float* score_out_or_null, spk_stream_t stream);
+/* spk_den_step_tail_conf_sched with remasking (the rule and the four added arguments:
+ * spk_psample_step_conf_remask): bit for bit spk_den_conv3x3_counts_mfma, spk_psample_step_conf_remask and the first layer as three
+ * launches -- a remasked position enters the fused first layer as mask_id.  A null remask_r or commit_conf_inout, or mask_id
+ * inside [0, K): SPK_ERR_ARG. */
+int spk_den_step_tail_conf_remask(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
+                                  const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout,
+                                  int t, const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                  const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                  const unsigned long long* philox_state_or_null, const float* conv1_w_packed_or_null,
+                                  const float* conv1_bias_or_null, const float* bn1_a, const float* bn1_b,
+                                  uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
+                                  long long* x0_hat_out_or_null, float* conf_out_or_null, const uint32_t* sched_w,
+                                  const float* noise_a_or_null, int S, float* score_out_or_null, const uint32_t* remask_r,
+                                  float* commit_conf_inout, long long mask_id, uint8_t* remasked_out_or_null, spk_stream_t stream);
 /* q_sample of the diffusion training step, R/snn_model/vq_diffusion.py:61-75: mask = u < t[b] / num_timesteps (fp32, as there);
  * x_t = mask ? mask_id : x_0;  x_0_ignore = mask ? x_0 : -1 (the loss's ignore index).  x0 / u / outputs fp32 [B*HW], t int64 [B],
  * mask_out optional u8.  u is the caller's draw (torch.rand_like in the reference's order). */

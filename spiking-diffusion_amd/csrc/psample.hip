@@ -204,21 +204,32 @@ __global__ __launch_bounds__(256) void psample_conf_listed_kernel(const float* _
 // between the draw and the rank.  x0_hat_out and conf_out are the sibling's.
 // LISTED: workgroup = slot of the pending list, logits by slot, everything else -- the two tables too -- by image active[s], the
 // counters (those of the Gumbel uniform included) shifted to the image's own run of e steps; no next_input.
-struct spk_sched_arg {
+// RM: remasking on top of it (spk_psample_step_conf_remask and, LISTED, spk_psample_step_conf_listed_remask; the rule:
+// psample_common.h): wave 0 -- the wave that commits -- reads the image's commit_conf with its `unmasked` bytes,
+// parks the keys of the revisable positions in the free entries of s_key (the reveal's keys sit at the masked ones), and after the
+// reveal ranks them once more from the other end.  Its four arguments are a base of the argument block, empty without the flag.
+template <bool RM> struct spk_remask_arg_t {};
+template <> struct spk_remask_arg_t<true> {
+  const uint32_t* r;                              // [B][S + 1]
+  float* commit_conf;                             // [B*HW], in place
+  uint8_t* remasked_out;                          // [B*HW] or null
+  long long mask_id;
+};
+template <bool RM = false> struct spk_sched_arg_t : spk_remask_arg_t<RM> {
   const uint32_t* w;                              // [B][S + 1]
   const float* a;                                 // [B][S + 1] or null
   const float* u_in;                              // injected uniforms [B*HW] or null
   float* score_out;                               // [B*HW] or null
   int S;
 };
-template <int KPL, bool LISTED>
+template <int KPL, bool LISTED, bool RM = false>
 __global__ __launch_bounds__(256) void psample_conf_sched_kernel(const float* __restrict__ logits, long long* __restrict__ x_t,
                                                                  uint8_t* __restrict__ unmasked, int t, spk_temp_topp temp,
                                                                  const float* __restrict__ q_in, unsigned long long seed,
                                                                  unsigned long long offset,
                                                                  const unsigned long long* __restrict__ philox_state,
                                                                  long long* __restrict__ x0_hat_out, float* __restrict__ conf_out,
-                                                                 spk_sched_arg sc, const int* __restrict__ steps_b,
+                                                                 spk_sched_arg_t<RM> sc, const int* __restrict__ steps_b,
                                                                  unsigned long long step_stride, const int* __restrict__ active,
                                                                  const int* __restrict__ n_active, int B, int HW, int K,
                                                                  float* __restrict__ next_input, float t_next) {
@@ -266,16 +277,34 @@ __global__ __launch_bounds__(256) void psample_conf_sched_kernel(const float* __
   const long long p = (long long)b * HW + (lane < HW ? lane : 0);
   const bool masked = lane < HW && !unmasked[p];
   const long long row = (long long)b * (sc.S + 1);
+  float conf_l = 0.f;                                               // RM: this lane's confidence, kept for commit_conf
+  bool revisable = false;
   if (wave == 0 && masked) {
-    const float score = sched_score(__uint_as_float(s_key[lane]), sc.a ? sc.a[row + t] : 0.f, sc.u_in, seed, offset, p, K);
+    conf_l = __uint_as_float(s_key[lane]);
+    const float score = sched_score(conf_l, sc.a ? sc.a[row + t] : 0.f, sc.u_in, seed, offset, p, K);
     s_key[lane] = spk_conf_key(score);
     if (sc.score_out) sc.score_out[p] = score;
+  }
+  if constexpr (RM) {
+    if (wave == 0 && lane < HW && !masked) {
+      const float cc = sc.commit_conf[p];
+      revisable = cc != INFINITY;
+      s_key[lane] = spk_conf_key(cc);                               // (an entry the reveal does not read: it reads the masked ones)
+    }
   }
   __syncthreads();
   if (wave != 0) return;
   const bool reveal = confident_reveal_sched(masked, lane, HW, sc.w[row + t - 1], sc.w[row + t], s_key);
   if (reveal) { unmasked[p] = 1; x_t[p] = (long long)s_cand[lane]; }
+  if constexpr (RM) {
+    const bool any_masked = __ballot(masked) != 0ull;               // (m == 0: no remask, nothing written)
+    const bool remask = confident_remask(revisable, lane, HW, (t > 1 && any_masked) ? sc.r[row + t] : 0u, s_key);
+    if (reveal) sc.commit_conf[p] = conf_l;
+    if (remask) { unmasked[p] = 0; x_t[p] = sc.mask_id; }
+    if (sc.remasked_out && any_masked && lane < HW) sc.remasked_out[p] = remask ? 1 : 0;
+  }
   if constexpr (!LISTED) {
+    // (RM: read after this lane's own writes -- a remasked position shows mask_id)
     if (next_input && lane < HW) write_next_input(next_input, b, lane, HW, reveal ? (float)s_cand[lane] : (float)x_t[p], t_next);
   }
 }
@@ -664,26 +693,34 @@ extern "C" int spk_psample_step_topp(const float* logits_bkhw, long long* x_t_in
 // entry points.  LISTED: on the list of pending images, each at its own step count (steps_b / active / n_active required, no
 // next_input); SCHED: under a reveal schedule and annealed selection noise (sched_w required; u_or_null is the Gumbel uniform --
 // without a schedule it is accepted and ignored: the coin is not part of the rule).  1 <= t <= S wherever the form has an S.
+// REMASK (on top of SCHED only): remask_r and commit_conf_inout required, mask_id outside [0, K).
 namespace {
-template <bool LISTED, bool SCHED>
+template <bool LISTED, bool SCHED, bool REMASK = false>
 int psample_conf_launch(const float* logits, long long* x_t_inout, uint8_t* unmasked_inout, int t, spk_temp_topp temp,
                         const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
                         unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
                         long long* x0_hat_out_or_null, float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
                         unsigned long long step_stride, const int* active, const int* n_active, float* next_input_or_null,
-                        const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null, hipStream_t stream) {
+                        const uint32_t* sched_w, const float* noise_a_or_null, float* score_out_or_null, hipStream_t stream,
+                        const uint32_t* remask_r = nullptr, float* commit_conf_inout = nullptr, long long mask_id = -1,
+                        uint8_t* remasked_out_or_null = nullptr) {
+  static_assert(!REMASK || SCHED, "remasking exists on top of the scheduled form only");
   if (!logits || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<true, true, true>(temp) || B <= 0 || HW <= 0 || K <= 0)
     return SPK_ERR_ARG;
   if ((LISTED || SCHED) && (S <= 0 || t > S)) return SPK_ERR_ARG;
   if (LISTED && (!steps_b || !active || !n_active)) return SPK_ERR_ARG;
   if (SCHED && !sched_w) return SPK_ERR_ARG;
+  if (REMASK && (!remask_r || !commit_conf_inout || (mask_id >= 0 && mask_id < K))) return SPK_ERR_ARG;
   if (HW > 64 || K > 64 * 32) return SPK_ERR_UNSUPPORTED;      // (one wave ranks an image: lane = position)
+  spk_sched_arg_t<REMASK> sc;
+  sc.w = sched_w; sc.a = noise_a_or_null; sc.u_in = u_or_null; sc.score_out = score_out_or_null; sc.S = S;
+  if constexpr (REMASK) { sc.r = remask_r; sc.commit_conf = commit_conf_inout; sc.remasked_out = remasked_out_or_null; sc.mask_id = mask_id; }
 #define SPK_PSAMPLE_CONF_LAUNCH(KPL)                                                                                     \
   if constexpr (SCHED)                                                                                                   \
-    hipLaunchKernelGGL((psample_conf_sched_kernel<KPL, LISTED>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, \
-                       temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, \
-                       spk_sched_arg{sched_w, noise_a_or_null, u_or_null, score_out_or_null, S}, steps_b, step_stride, active, \
-                       n_active, B, HW, K, next_input_or_null, (float)(t - 1));                                         \
+    hipLaunchKernelGGL((psample_conf_sched_kernel<KPL, LISTED, REMASK>), dim3(B), dim3(256), 0, stream, logits, x_t_inout,      \
+                       unmasked_inout, t, temp, q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, \
+                       conf_out_or_null, sc, steps_b, step_stride, active, n_active, B, HW, K, next_input_or_null,       \
+                       (float)(t - 1));                                                                                  \
   else if constexpr (LISTED)                                                                                             \
     hipLaunchKernelGGL((psample_conf_listed_kernel<KPL>), dim3(B), dim3(256), 0, stream, logits, x_t_inout, unmasked_inout, t, temp, \
                        q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null, conf_out_or_null, steps_b, S, \
@@ -754,4 +791,38 @@ extern "C" int spk_psample_step_conf_listed_sched(const float* logits_skhw, long
                                          q_or_null, philox_seed, philox_offset, philox_state_or_null, x0_hat_out_or_null,
                                          conf_out_or_null, B, HW, K, steps_b, S, step_stride, active, n_active, nullptr, sched_w,
                                          noise_a_or_null, score_out_or_null, stream);
+}
+
+// The two scheduled updates with remasking (include/spkdiff.h; the rule: psample_common.h): the `_sched` siblings'
+// arguments plus the remask table, the commit confidences (in place), mask_id and the optional record of what was remasked.
+extern "C" int spk_psample_step_conf_remask(const float* logits_bkhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                            const float* temp_b, const int* topk_b, const float* topp_b, const float* u_or_null,
+                                            const float* q_or_null, unsigned long long philox_seed, unsigned long long philox_offset,
+                                            const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                            float* conf_out_or_null, int B, int HW, int K, float* next_input_b2hw_or_null,
+                                            const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                            const uint32_t* remask_r, float* commit_conf_inout, long long mask_id,
+                                            uint8_t* remasked_out_or_null, hipStream_t stream) {
+  return psample_conf_launch<false, true, true>(logits_bkhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b},
+                                                u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null,
+                                                x0_hat_out_or_null, conf_out_or_null, B, HW, K, nullptr, S, 0ull, nullptr, nullptr,
+                                                next_input_b2hw_or_null, sched_w, noise_a_or_null, score_out_or_null, stream, remask_r,
+                                                commit_conf_inout, mask_id, remasked_out_or_null);
+}
+
+extern "C" int spk_psample_step_conf_listed_remask(const float* logits_skhw, long long* x_t_inout, uint8_t* unmasked_inout, int t,
+                                                   const float* temp_b, const int* topk_b, const float* topp_b,
+                                                   const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                                   unsigned long long philox_offset,
+                                                   const unsigned long long* philox_state_or_null, long long* x0_hat_out_or_null,
+                                                   float* conf_out_or_null, int B, int HW, int K, const int* steps_b, int S,
+                                                   unsigned long long step_stride, const int* active, const int* n_active,
+                                                   const uint32_t* sched_w, const float* noise_a_or_null,
+                                                   float* score_out_or_null, const uint32_t* remask_r, float* commit_conf_inout,
+                                                   long long mask_id, uint8_t* remasked_out_or_null, hipStream_t stream) {
+  return psample_conf_launch<true, true, true>(logits_skhw, x_t_inout, unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b},
+                                               u_or_null, q_or_null, philox_seed, philox_offset, philox_state_or_null,
+                                               x0_hat_out_or_null, conf_out_or_null, B, HW, K, steps_b, S, step_stride, active,
+                                               n_active, nullptr, sched_w, noise_a_or_null, score_out_or_null, stream, remask_r,
+                                               commit_conf_inout, mask_id, remasked_out_or_null);
 }

@@ -2,7 +2,8 @@
 // counter scheme of spk_psample_step behind reveal_u (u: stream 0, counter offset + position * K) and race_q (q: stream 1, counter
 // offset + position * K + class), the categorical draw categorical_race, the top-k and nucleus truncations truncate_top_k /
 // truncate_top_p that may precede it, the confidence-ordered reveal rule confident_reveal (what a step commits when it does not toss
-// the coin) with its scheduled form (sched_reveal_count, sched_score, confident_reveal_sched), the 64-lane max / sum and the prologues every kernel shares.
+// the coin) with its scheduled form (sched_reveal_count, sched_score, confident_reveal_sched) and the remask that returns the least trusted commits to the masked state
+// (confident_remask), the 64-lane max / sum and the prologues every kernel shares.
 // Every kernel that draws noise goes through these: every launch form and spk_philox_noise see the same draws.
 #pragma once
 #include "spk_common.h"
@@ -329,6 +330,41 @@ __device__ __forceinline__ bool confident_reveal_sched(bool masked, int lane, in
     rank += (kq > key || (kq == key && q < lane)) ? 1u : 0u;
   }
   return masked && rank < n;
+}
+
+// Remasking (the `_remask` entry points spk_psample_step_conf_remask, spk_psample_step_conf_listed_remask,
+// spk_den_step_tail_conf_remask) -- THE rule, stated once.  On top of the `_sched` rule only; a null noise_a is a = 0, w[t] = t gives
+// the ceil(m / t) counts.  One more piece of per-position state, commit_conf (fp32 [B*HW], in place like x_t / unmasked): +inf at the
+// positions unmasked when the run started (the `known` tokens, never revisited -- a committed log-probability is <= 0, so +inf
+// cannot arise otherwise), the confidence of its reveal at a position a step revealed, anything (ignored) at a masked position.  The
+// denoiser is not trained at unmasked positions (the loss ignores them), so a committed token is never re-scored from the current
+// logits: its trust IS the confidence it was committed with.  At reverse step t, for each image on its own:
+//   1. m = positions masked at entry.  m == 0: the image is left as the `_sched` sibling leaves it -- no remask either.
+//   2. candidates, confidences, scores, the count n and the revealed set are the `_sched` rule's: x0_hat_out, conf_out, score_out and
+//      the revealed positions are bit for bit the sibling's on the same state and tables.
+//   3. REMASK.  p is revisable iff it was unmasked at entry and commit_conf[p] != +inf (a position revealed in this step is not).
+//      c = the number of revisable positions, r = min(remask_r[i][t], c), and r = 0 at t = 1 whatever the table holds: a run never
+//      ends with a masked position.  Order key = spk_conf_key(commit_conf[p]) (a NaN: key 0).  A revisable p is remasked iff fewer
+//      than r revisable p' have (key, -p') below (key, -p): smaller key first, equal keys to the HIGHER position -- the mirror image
+//      of the reveal, so one total order (key, -position) serves both ends.  A remasked p gets x_t = mask_id, unmasked = 0; its
+//      commit_conf stays.  It draws again at the NEXT step, after a denoiser call has seen it masked.
+//   4. every revealed p gets commit_conf[p] = its confidence -- conf_out's value, not the Gumbel-perturbed score.
+//   5. next_input and the fused first layer of the next step read the state after 3 and 4: a remasked position shows mask_id.
+// confident_remask is step 3 for one image by ONE wave, lane = position: `revisable` as above (false for lane >= h*w), r_tab the
+// table entry (the caller zeroes it at t = 1 and for m == 0), s_key = the image's keys in LDS (read at revisable positions only).
+__device__ __forceinline__ bool confident_remask(bool revisable, int lane, int HW, uint32_t r_tab, const uint32_t* s_key) {
+  const unsigned long long rv = __ballot(revisable);
+  const unsigned c = (unsigned)__popcll(rv);
+  const unsigned r = r_tab < c ? r_tab : c;
+  if (r == 0u) return false;                                      // (wave-uniform)
+  const uint32_t key = revisable ? s_key[lane] : 0u;
+  unsigned rank = 0;
+  for (int q = 0; q < HW; ++q) {
+    if (!((rv >> q) & 1ull)) continue;                            // (wave-uniform)
+    const uint32_t kq = s_key[q];                                 // (one address for the wave: a broadcast read)
+    rank += (kq < key || (kq == key && q > lane)) ? 1u : 0u;
+  }
+  return revisable && rank < r;
 }
 
 }  // namespace

@@ -44,8 +44,13 @@ template <> struct TailConfOutT<true> { long long* x0_hat_out; float* conf_out; 
 // block, empty in every other form.
 template <bool SC> struct TailSchedT {};
 template <> struct TailSchedT<true> { const uint32_t* sched_w; const float* noise_a; float* score_out; int S; };   // tables [B][S + 1]; scores at the masked positions
-template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
-struct TailArgsT : TailConfOutT<CF>, TailSchedT<SC> {
+// RM = remasking on top of SC (spk_den_step_tail_conf_remask; the rule: psample_common.h): after the commit the same
+// wave returns the r least trusted earlier commits of the image to the masked state, so the fused first layer reads mask_id there.
+// One more base of the argument block, empty in every other form.
+template <bool RM> struct TailRemaskT {};
+template <> struct TailRemaskT<true> { const uint32_t* remask_r; float* commit_conf; uint8_t* remasked_out; long long mask_id; };   // table [B][S + 1]; state / record [B*HW]
+template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false, bool RM = false>
+struct TailArgsT : TailConfOutT<CF>, TailSchedT<SC>, TailRemaskT<RM> {
   const uint8_t* c5; const uint8_t* c1;           // spike counts u8 [B][8][HW][32], [B][2][HW][32]
   const int8_t* wq; const double* scale; const double* bias;
   float* logits_out;                              // optional fp32 [B][128][HW]
@@ -63,10 +68,11 @@ struct TailArgsT : TailConfOutT<CF>, TailSchedT<SC> {
 };
 
 // KG = channel groups per wave (1: K <= 128, the reference's default; 2 .. 4: K <= 256 / 384 / 512)
-template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
-__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP, CF, SC> a) {
+template <int H, int W, int KG, bool PT = false, bool TK = false, bool TP = false, bool CF = false, bool SC = false, bool RM = false>
+__global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP, CF, SC, RM> a) {
   static_assert(!CF || (PT && TK && TP), "the confidence form exists on top of the most general family only");
   static_assert(!SC || CF, "a schedule orders the confidence form's commit");
+  static_assert(!RM || SC, "remasking exists on top of the scheduled form only");
   constexpr int HW = H * W;
   static_assert(HW <= 64, "an image is at most two 32-row tiles");
   constexpr int AV = HW * 2 + 1;                  // 16-byte vectors of a chunk's count records + one zero vector
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
   if constexpr (CF) {                             //  what that loop is short of: held there they were spilled)
     __shared__ int s_cand_[64];
     __shared__ uint32_t s_key_[64];
-    __shared__ unsigned long long s_cfarg_[SC ? 8 : 3];       // SC: + {score_out, u_in, bits of a, w[t - 1], w[t]} of this image and step
+    __shared__ unsigned long long s_cfarg_[RM ? 12 : SC ? 8 : 3];   // SC: + {score_out, u_in, bits of a, w[t - 1], w[t]} of this image and step; RM: + {r, commit_conf, mask_id, remasked_out}
     s_cand = s_cand_; s_key = s_key_; s_cfarg = s_cfarg_;
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -132,6 +138,11 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
         s_cfarg[3] = (unsigned long long)a.score_out; s_cfarg[4] = (unsigned long long)a.u_in;
         s_cfarg[5] = (unsigned long long)__float_as_uint(a.noise_a ? a.noise_a[srow] : 0.f);
         s_cfarg[6] = (unsigned long long)a.sched_w[srow - 1]; s_cfarg[7] = (unsigned long long)a.sched_w[srow];
+        if constexpr (RM) {
+          s_cfarg[8] = a.t > 1 ? (unsigned long long)a.remask_r[srow] : 0ull;   // (t = 1 never remasks: a run ends without a masked position)
+          s_cfarg[9] = (unsigned long long)a.commit_conf; s_cfarg[10] = (unsigned long long)a.mask_id;
+          s_cfarg[11] = (unsigned long long)a.remasked_out;
+        }
       }
     }
   }
@@ -151,6 +162,9 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
     const long long tk = a.x_t[pi];
     if constexpr (CF) {
       s_chg[tid] = um ? 0 : 1;                     // (every masked position draws a candidate; the coin is not drawn)
+      // RM: the order key of an earlier commit, parked in the entry of s_key the reveal does not use (it reads the masked ones);
+      // +inf -- a token the run started with -- keeps its own key, which no other value has
+      if constexpr (RM) { if (um) s_key[tid] = spk_conf_key(a.commit_conf[pi]); }
     } else {
       const float u = reveal_u(a.u_in, seed, offset, pi, K);
       s_chg[tid] = ((u < inv_t) && !um) ? 1 : 0;
@@ -327,11 +341,13 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
   if constexpr (CF) {
     // ---- the commit: one wave, lane = position; the n = ceil(m / t) surest candidates of the image become its tokens
     __syncthreads();
+    float conf_l = 0.f;                           // RM: this lane's confidence, kept for commit_conf
     if constexpr (SC) {
       // the scores, by the wave that ranks them: lane = position, the Gumbel draws of the image side by side
       if (wave == 0 && lane < HW && s_chg[lane < HW ? lane : 0] != 0) {
         const long long pi = (long long)bi * HW + lane;
-        const float score = sched_score(__uint_as_float(s_key[lane]), __uint_as_float((uint32_t)s_cfarg[5]),
+        conf_l = __uint_as_float(s_key[lane]);
+        const float score = sched_score(conf_l, __uint_as_float((uint32_t)s_cfarg[5]),
                                         reinterpret_cast<const float*>(s_cfarg[4]), seed, offset, pi, K);
         float* score_out = reinterpret_cast<float*>(s_cfarg[3]);
         s_key[lane] = spk_conf_key(score);
@@ -342,13 +358,31 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
     if (wave == 0) {
       const bool masked = lane < HW && s_chg[lane < HW ? lane : 0] != 0;
       // (SC is a template constant: one of the two calls is compiled)
-      if (SC ? confident_reveal_sched(masked, lane, HW, (uint32_t)s_cfarg[SC ? 6 : 0], (uint32_t)s_cfarg[SC ? 7 : 0], s_key)
-             : confident_reveal(masked, lane, HW, (int)s_cfarg[2], s_key)) {
+      const bool reveal = SC ? confident_reveal_sched(masked, lane, HW, (uint32_t)s_cfarg[SC ? 6 : 0], (uint32_t)s_cfarg[SC ? 7 : 0], s_key)
+                             : confident_reveal(masked, lane, HW, (int)s_cfarg[2], s_key);
+      if (reveal) {
         const long long pi = (long long)bi * HW + lane;
         const int tk = s_cand[lane];
         a.unmasked[pi] = 1;
         a.x_t[pi] = (long long)tk;
         s_tok[lane] = (float)tk;
+      }
+      if constexpr (RM) {
+        // ---- the remask: the same wave, the same keys from the other end (confident_remask, psample_common.h)
+        const bool any_masked = __ballot(masked) != 0ull;               // (m == 0: no remask, nothing written)
+        const bool revisable = lane < HW && !masked && s_key[lane < HW ? lane : 0] != 0xFF800000u;   // (the key of +inf)
+        const bool remask = confident_remask(revisable, lane, HW, any_masked ? (uint32_t)s_cfarg[8] : 0u, s_key);
+        const long long pi = (long long)bi * HW + (lane < HW ? lane : 0);
+        float* commit_conf = reinterpret_cast<float*>(s_cfarg[9]);
+        uint8_t* remasked_out = reinterpret_cast<uint8_t*>(s_cfarg[11]);
+        if (reveal) commit_conf[pi] = conf_l;
+        if (remask) {
+          const long long mask_id = (long long)s_cfarg[10];
+          a.unmasked[pi] = 0;
+          a.x_t[pi] = mask_id;
+          s_tok[lane] = (float)mask_id;
+        }
+        if (remasked_out && any_masked && lane < HW) remasked_out[pi] = remask ? 1 : 0;
       }
     }
   }
@@ -395,7 +429,7 @@ __global__ __launch_bounds__(512, 1) void step_tail_kernel(TailArgsT<PT, TK, TP,
 }  // namespace
 
 namespace {
-template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false>
+template <bool PT, bool TK = false, bool TP = false, bool CF = false, bool SC = false, bool RM = false>
 int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq, const double* scale,
                      const double* bias_d, float* logits_out_or_null, long long* x_t_inout, uint8_t* unmasked_inout, int t,
                      spk_temp_arg_t<PT, TK, TP> temp, const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
@@ -404,7 +438,9 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
                      uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B, int H, int W, int K,
                      const int* active_or_null, const int* n_active_or_null, hipStream_t stream,
                      long long* x0_hat_out_or_null = nullptr, float* conf_out_or_null = nullptr, const uint32_t* sched_w = nullptr,
-                     const float* noise_a_or_null = nullptr, int S = 0, float* score_out_or_null = nullptr) {
+                     const float* noise_a_or_null = nullptr, int S = 0, float* score_out_or_null = nullptr,
+                     const uint32_t* remask_r = nullptr, float* commit_conf_inout = nullptr, long long mask_id = -1,
+                     uint8_t* remasked_out_or_null = nullptr) {
   if (!cnt5 || !cnt1 || !wq || !scale || !bias_d || !x_t_inout || !unmasked_inout || t <= 0 || !spk_temp_arg_ok<PT, TK, TP>(temp) || B <= 0 ||
       T <= 0)
     return SPK_ERR_ARG;
@@ -418,10 +454,12 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   // (spk_lif_const_input_bits16): any other step count would write outside x1_s32_out (T < 16) or give wrong spikes (T > 16)
   if (x1_s32_out_or_null && T != 16) return SPK_ERR_UNSUPPORTED;
   if (SC && (!sched_w || S <= 0 || t > S)) return SPK_ERR_ARG;
-  TailArgsT<PT, TK, TP, CF, SC> a;
+  if (RM && (!remask_r || !commit_conf_inout || (mask_id >= 0 && mask_id < K))) return SPK_ERR_ARG;
+  TailArgsT<PT, TK, TP, CF, SC, RM> a;
+  if constexpr (RM) { a.remask_r = remask_r; a.commit_conf = commit_conf_inout; a.remasked_out = remasked_out_or_null; a.mask_id = mask_id; }
   if constexpr (SC) { a.sched_w = sched_w; a.noise_a = noise_a_or_null; a.score_out = score_out_or_null; a.S = S; }
   if constexpr (CF) {
-    // (the K = 512, 8 x 8 launch holds 150 KB of logits and counts; with the form's 544 bytes (560 with a schedule: 21 856 on 8 x 8) more it is checked against the device's
+    // (the K = 512, 8 x 8 launch holds 150 KB of logits and counts; with the form's 544 bytes (560 with a schedule: 21 856 on 8 x 8; 592 with remasking: 21 888) more it is checked against the device's
     //  grant -- the static part counted as 22 KB for either latent: 21 840 bytes on 8 x 8, 17 040 on 7 x 7, where the check is conservative)
     if ((long long)64 * (128 * ((K + 127) / 128) + 4) * (long long)sizeof(float) + 22 * 1024 > spk_lds_limit()) return SPK_ERR_UNSUPPORTED;
     a.x0_hat_out = x0_hat_out_or_null; a.conf_out = conf_out_or_null;
@@ -436,7 +474,7 @@ int step_tail_launch(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch
   a.K = K; a.ng = (K + 15) / 16;                    // wq / scale / bias_d hold ng * 16 channels (zero weights beyond K)
   const int kg = (a.ng + 7) / 8;
 #define SPK_TAIL_LAUNCH(H_, W_, KG_)                                                                                          \
-  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP, CF, SC>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
+  hipLaunchKernelGGL((step_tail_kernel<H_, W_, KG_, PT, TK, TP, CF, SC, RM>), dim3(B), dim3(512), (size_t)64 * (128 * KG_ + 4) * sizeof(float), stream, a)
   if (H == 7) {
     if (kg == 1) SPK_TAIL_LAUNCH(7, 7, 1); else if (kg == 2) SPK_TAIL_LAUNCH(7, 7, 2);
     else if (kg == 3) SPK_TAIL_LAUNCH(7, 7, 3); else SPK_TAIL_LAUNCH(7, 7, 4);
@@ -548,4 +586,27 @@ extern "C" int spk_den_step_tail_conf_sched(const uint8_t* cnt5, int nch5, const
                                                         conv1_bias_or_null, bn1_a, bn1_b, x1_s32_out_or_null, cnt1_out_or_null, T, B, H,
                                                         W, K, nullptr, nullptr, stream, x0_hat_out_or_null, conf_out_or_null, sched_w,
                                                         noise_a_or_null, S, score_out_or_null);
+}
+
+// The same launch with remasking (include/spkdiff.h; the rule: csrc/psample_common.h): spk_den_step_tail_conf_sched's
+// arguments plus the remask table, the commit confidences (in place), mask_id and the optional record of what was remasked.
+extern "C" int spk_den_step_tail_conf_remask(const uint8_t* cnt5, int nch5, const uint8_t* cnt1, int nch1, const int8_t* wq,
+                                             const double* scale, const double* bias_d, float* logits_out_or_null, long long* x_t_inout,
+                                             uint8_t* unmasked_inout, int t, const float* temp_b, const int* topk_b, const float* topp_b,
+                                             const float* u_or_null, const float* q_or_null, unsigned long long philox_seed,
+                                             unsigned long long philox_offset, const unsigned long long* philox_state_or_null,
+                                             const float* conv1_w_packed_or_null, const float* conv1_bias_or_null, const float* bn1_a,
+                                             const float* bn1_b, uint8_t* x1_s32_out_or_null, uint8_t* cnt1_out_or_null, int T, int B,
+                                             int H, int W, int K, long long* x0_hat_out_or_null, float* conf_out_or_null,
+                                             const uint32_t* sched_w, const float* noise_a_or_null, int S, float* score_out_or_null,
+                                             const uint32_t* remask_r, float* commit_conf_inout, long long mask_id,
+                                             uint8_t* remasked_out_or_null, hipStream_t stream) {
+  return step_tail_launch<true, true, true, true, true, true>(cnt5, nch5, cnt1, nch1, wq, scale, bias_d, logits_out_or_null, x_t_inout,
+                                                              unmasked_inout, t, spk_temp_topp{temp_b, topk_b, topp_b}, u_or_null,
+                                                              q_or_null, philox_seed, philox_offset, philox_state_or_null,
+                                                              conv1_w_packed_or_null, conv1_bias_or_null, bn1_a, bn1_b,
+                                                              x1_s32_out_or_null, cnt1_out_or_null, T, B, H, W, K, nullptr, nullptr, stream,
+                                                              x0_hat_out_or_null, conf_out_or_null, sched_w, noise_a_or_null, S,
+                                                              score_out_or_null, remask_r, commit_conf_inout, mask_id,
+                                                              remasked_out_or_null);
 }

@@ -105,8 +105,12 @@ class _SamplerGraph:
     and the flag workspaces of the certified kernels (``flag_ws``)."""
 
     def __init__(self, dev, b, h, w, form, radii, conditional, score=False, per_image_temp=False, top_k=False, top_p=False,
-                 confident=False, per_image_steps=False, sched_steps=0):
+                 confident=False, per_image_steps=False, sched_steps=0, remask=False):
         self.graph = self.derived = None                            # set by the capture
+        # remasking (DESIGN.md §4.18): the table is one more INPUT [B][S + 1] beside the two of the schedule; commit_conf is a buffer
+        # of the graph, re-initialised from the start state by every replay (set by the capture)
+        self.remask = torch.zeros((b, sched_steps + 1), dtype=torch.int32, device=dev) if remask else None
+        self.commit_conf = None
         # a reveal schedule and annealed selection noise (DESIGN.md §4.17) are two more INPUTS of fixed shape [B][S + 1]: the captured
         # `_sched` token updates read these buffers, so one graph serves every schedule and every noise scale
         self.sched = (torch.zeros((b, sched_steps + 1), dtype=torch.int32, device=dev),
@@ -304,7 +308,7 @@ class AbsorbingDiffusion(Sampler):
 
     @torch.no_grad()
     def sample_confident(self, sample_steps=None, temp=1.0, noise=None, record=None, x_init=None, known=None, top_k=None, top_p=None,
-                         schedule=None, selection_noise=None):
+                         schedule=None, selection_noise=None, remask=None):
         """Confidence-ordered decoding: ``sample()`` with another rule for WHERE a step reveals.  At step t every
         still-masked position of an image draws a candidate token -- the draw of ``sample_top_p(top_p, top_k=top_k)``, same noise
         counters -- and the ceil(m / t) candidates the denoiser is surest of (m = positions masked at entry; the order is the
@@ -346,13 +350,66 @@ class AbsorbingDiffusion(Sampler):
         equals image i of ``sample_confident(s_i, schedule=its row, selection_noise=tau_i)``.  In a captured graph both tables are
         inputs [B][S + 1]: one graph per (batch, S, conditional, per-image steps) serves every schedule and every tau.  Refused
         before a key is drawn (ValueError): tau negative or not finite, an unknown name, a table of the wrong length, a weight
-        outside 0 .. 2^24 or no integer, a per-image list of the wrong length."""
+        outside 0 .. 2^24 or no integer, a per-image list of the wrong length.
+
+        Remasking.  ``remask`` lets the sampler change its mind: at the end of a step, after the reveal, the
+        least trusted of the tokens EARLIER steps of this call committed -- smallest confidence at commit, ties to the higher
+        position -- return to the masked state and draw again at the next step, when a denoiser call has seen them masked.  The
+        step count, and so the cost, does not change.  A committed token is never re-scored from the current logits (the denoiser
+        is not trained at unmasked positions): its trust is the confidence it was committed with.  None: the calls made without
+        the argument, launch for launch.  An int r >= 0: up to r tokens per image at every step 2 <= t <= e.  A sequence of e + 1
+        non-negative integers indexed by t (entries 0 and 1 must be 0: the last step remasks nothing, so no ``mask_id`` is
+        left).  Or one of these per image: a list of B entries, or a 2-D array / tensor [B, S + 1].  ``known`` tokens are never
+        remasked.  Anything but None runs the ``_remask`` kernels on top of the ``_sched`` family (``schedule`` None is then the
+        linear table, ``selection_noise`` None no noise: ``remask=0`` gives the tokens of ``schedule='linear'``).  Under per-image
+        step counts row i is built for e_i and image i equals image i of its one-count call.  In a captured graph the table is one
+        more input [B][S + 1]: one graph per (batch, S, conditional, per-image steps) serves every table.  No new noise counters:
+        ``set_shard`` works unchanged.  Refused before a key is drawn (ValueError): a negative or non-integer entry, a non-zero
+        entry at t <= 1, a wrong length.  ``spkdiff.schedules.run_counts_remask`` lists the (revealed, remasked) counts of a run."""
         h, w = self.shape
         if h * w > 64:
             raise NotImplementedError(f'spkdiff: sample_confident() ranks an image\'s positions in one wave: h * w <= 64, got {h} x {w}')
         return self._sample_call(temp, sample_steps, noise, record, x_init, known, top_k, top_p, confident=True,
-                                 **({} if schedule is None and selection_noise is None else
-                                    {'schedule': schedule, 'selection_noise': selection_noise, 'scheduled': True}))
+                                 **({} if schedule is None and selection_noise is None and remask is None else
+                                    {'schedule': schedule, 'selection_noise': selection_noise, 'scheduled': True}),
+                                 **({} if remask is None else {'remask': remask}))
+
+    @staticmethod
+    def _remask_arg(remask, b, steps, S):
+        """The remask table of a sample_confident(remask=) call for a batch of ``b``, checked and built on the
+        host: ``steps`` = the b per-image step counts e_i <= S (a list) -> int32 [b, S + 1] CPU tensor, row i built for e_i and
+        placed as ``spkdiff.schedules.weights_row`` places a schedule row."""
+        from spkdiff import schedules as sch
+        what = 'spkdiff: sample_confident(remask=)'
+        if hasattr(remask, 'detach'):
+            remask = remask.detach().cpu()
+        if hasattr(remask, 'tolist') and getattr(remask, 'ndim', 0) >= 1:
+            integers = (not remask.is_floating_point() and remask.dtype != torch.bool) if isinstance(remask, torch.Tensor) \
+                else getattr(remask.dtype, 'kind', 'i') in 'iu'
+            if not integers:
+                raise ValueError(f'{what}: counts are integers, got an array of {remask.dtype}')
+            if remask.ndim > 2:
+                raise ValueError(f'{what}: a table is 1-D, per-image tables are [B, S + 1], got {tuple(remask.shape)}')
+            remask = remask.tolist()
+        elif hasattr(remask, 'item') and getattr(remask, 'ndim', 1) == 0:
+            remask = remask.item()
+        per_image = isinstance(remask, (list, tuple)) and len(remask) > 0 and \
+            any(v is None or isinstance(v, (list, tuple)) or getattr(v, 'ndim', 0) >= 1 for v in remask)
+        if per_image and len(remask) != b:
+            raise ValueError(f'{what}: per-image tables take one entry per image of the call ({b}), got {len(remask)}')
+        built, rows = {}, []
+        for i in range(b):
+            ri = remask[i] if per_image else remask
+            ri = tuple(ri.tolist() if hasattr(ri, 'tolist') else ri) if isinstance(ri, (list, tuple)) or getattr(ri, 'ndim', 0) >= 1 else ri
+            try:
+                key = (ri, steps[i])
+                hash(key)
+            except TypeError:
+                raise ValueError(f'{what}: an integer >= 0 or a table of integers >= 0, got {ri!r}') from None
+            if key not in built:
+                built[key] = sch.remask_row(ri, steps[i], S, what)
+            rows.append(built[key])
+        return torch.tensor(rows, dtype=torch.int32).reshape(b, S + 1)
 
     @staticmethod
     def _sched_arg(schedule, selection_noise, b, steps, S):
@@ -433,7 +490,7 @@ class AbsorbingDiffusion(Sampler):
         return v.to(torch.int32)
 
     def _sample_call(self, temp, sample_steps, noise, record, x_init, known, top_k, top_p=None, confident=False, schedule=None,
-                     selection_noise=None, scheduled=False):
+                     selection_noise=None, scheduled=False, remask=None):
         start = self._start_state_args(x_init, known)
         b = int(self.n_samples) if start is None else int(start[0].shape[0])
         steps_b = None
@@ -454,6 +511,9 @@ class AbsorbingDiffusion(Sampler):
             if S < 1:
                 raise ValueError(f'spkdiff: sample_confident(schedule=, selection_noise=) takes sample_steps >= 1, got {S}')
             sched = self._sched_arg(schedule, selection_noise, b, [S] * b if steps_b is None else steps_b.tolist(), S)
+            if remask is not None:
+                # remasking: one more host-built table, on top of the scheduled family
+                remask = self._remask_arg(remask, b, [S] * b if steps_b is None else steps_b.tolist(), S)
         temp = self._temp_arg(temp, b)
         top_k = self._topk_arg(top_k, b)
         top_p = self._topp_arg(top_p, b)
@@ -497,7 +557,7 @@ class AbsorbingDiffusion(Sampler):
         return self._reverse_process(dev, b, h, w, form, temp, int(sample_steps), noise, seed, start, record, top_k=top_k,
                                      **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
                                      **({} if steps_b is None else {'steps_b': steps_b}),
-                                     **({} if sched is None else {'sched': sched}))
+                                     **({} if sched is None else {'sched': sched}), **({} if remask is None else {'remask': remask}))
 
     def _topp_arg(self, top_p, b):
         """The ``top_p`` of sample_top_p() for a batch of ``b``, checked before anything is drawn or launched.  None: no nucleus
@@ -673,7 +733,7 @@ class AbsorbingDiffusion(Sampler):
         return Score(logp, step, logp.sum(dim=(2, 3)))
 
     def _reverse_process(self, dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target=None, top_k=None,
-                         top_p=None, confident=False, steps_b=None, sched=None):
+                         top_p=None, confident=False, steps_b=None, sched=None, remask=None):
         """One reverse process of sample() / score(): a replay of its captured graph where the call allows one, else eager."""
         if self.use_graph and noise is None and record is None and self.noise_source == 'philox':
             self._capturing = False
@@ -682,7 +742,8 @@ class AbsorbingDiffusion(Sampler):
                                             **({} if top_p is None else {'top_p': top_p}),
                                             **({'confident': True} if confident else {}),
                                             **({} if steps_b is None else {'steps_b': steps_b}),
-                                            **({} if sched is None else {'sched': sched}))
+                                            **({} if sched is None else {'sched': sched}),
+                                            **({} if remask is None else {'remask': remask}))
             except (NotImplementedError, ValueError, TypeError):
                 raise                          # an argument / support error of a kernel, not a capture problem
             except RuntimeError as e:
@@ -702,10 +763,11 @@ class AbsorbingDiffusion(Sampler):
                 self._capturing = False
         return self._sample_eager(dev, b, h, w, form, temp, sample_steps, noise, seed, start, record, target, top_k,
                                   **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
-                                  **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}))
+                                  **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}),
+                                  **({} if remask is None else {'remask': remask}))
 
     def _sample_eager(self, dev, b, h, w, form, temp, sample_steps, noise=None, seed=0, start=None, record=None, target=None,
-                      top_k=None, top_p=None, confident=False, steps_b=None, sched=None):
+                      top_k=None, top_p=None, confident=False, steps_b=None, sched=None, remask=None):
         """The reverse process launched kernel by kernel: fresh state buffers, the one step loop.  ``target = (x0, logp, step)``:
         the teacher-forced loop of score() -- logp / step are the caller's zeroed outputs, and of the noise only u is drawn."""
         x_t = torch.empty((b, 1, h, w), dtype=torch.int64, device=dev)
@@ -713,6 +775,8 @@ class AbsorbingDiffusion(Sampler):
         self._fill_start(x_t, unmasked, start)
         if sched is not None:
             sched = (sched[0].to(dev), sched[1].to(dev))            # (the host-built tables of sample_confident(schedule=, ...))
+        if remask is not None:
+            remask = (remask.to(dev), self._commit_conf_start(unmasked))
         if noise is None and self.noise_source == 'host':
             # u and q from torch's global CPU generator in the reference's order: rand_like(x_t.float()) (:116), then
             # multinomial's one-draw fast path (:138); the denoiser call between them there draws nothing
@@ -724,8 +788,16 @@ class AbsorbingDiffusion(Sampler):
         need = ops.NeedLists(b, int(self.list_radii), dev) if form.lists else None
         self._reverse_steps(x_t, unmasked, form, _Noise(noise, seed), temp, sample_steps, need=need, record=record, target=target,
                             top_k=top_k, **({} if top_p is None else {'top_p': top_p}), **({'confident': True} if confident else {}),
-                            **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}))
+                            **({} if steps_b is None else {'steps_b': steps_b}), **({} if sched is None else {'sched': sched}),
+                            **({} if remask is None else {'remask': remask}))
         return x_t
+
+    @staticmethod
+    def _commit_conf_start(unmasked):
+        """commit_conf of a remasking run from its start state, one capturable launch: +inf where a position is
+        unmasked -- a known token, never revisited --, 0 (never read before a reveal writes it) elsewhere; fp32, the shape of
+        ``unmasked``."""
+        return torch.where(unmasked, math.inf, 0.0)
 
     def _fill_start(self, x_t, unmasked, start):
         """Start state into the given buffers: all masked, or ``start = (codes, keep)`` through spk_completion_state."""
@@ -736,7 +808,7 @@ class AbsorbingDiffusion(Sampler):
             ops.completion_state(start[0], start[1], self.num_classes, int(self.mask_id), out=(x_t, unmasked))
 
     def _reverse_steps(self, x_t, unmasked, form, src, temp, sample_steps, act=None, need=None, inp=None, record=None, target=None,
-                       top_k=None, top_p=None, confident=False, steps_b=None, sched=None):
+                       top_k=None, top_p=None, confident=False, steps_b=None, sched=None, remask=None):
         """THE reverse-process loop (R/snn_model/vq_diffusion.py:113-140): steps t = sample_steps .. 1 on ``x_t`` / ``unmasked``
         in place, in launch form ``form`` with the noise of ``src`` (_Noise); eager call and captured graph both run it.
         ``act``: the pair spk_select_active writes (None: the first step allocates it); ``need``: the NeedLists of ``form.lists``;
@@ -754,7 +826,9 @@ class AbsorbingDiffusion(Sampler):
         spk_psample_step_conf_listed, which shifts image i's counters to those of its own run of min(steps_b[i], S) steps;
         ``sched = (w int32 [B, S + 1], a fp32 [B, S + 1])`` on the loop's device: a scheduled sample_confident() (then
         ``confident``, S = ``sample_steps``) -- every token update is the ``_sched`` sibling of the one it would be, with the two
-        tables, and an injected u is handed on as the Gumbel uniform."""
+        tables, and an injected u is handed on as the Gumbel uniform; ``remask = (r int32 [B, S + 1], commit_conf fp32 [B,1,h,w])`` on
+        the loop's device (then with ``sched``): every token update is the ``_remask`` sibling, commit_conf holds +inf
+        at the start state's unmasked positions and is updated in place."""
         dn = self._denoise_fn
         trunc = {} if top_k is None else {'top_k': top_k}
         if top_p is not None:
@@ -763,6 +837,9 @@ class AbsorbingDiffusion(Sampler):
             trunc['confident'] = True
         if sched is not None:
             trunc['sched'] = sched + (sample_steps,)
+        if remask is not None:
+            remask = remask + (int(self.mask_id),)
+            trunc['remask'] = remask
         b, _, h, w = x_t.shape
         K = self.num_classes
         seed, state = src.seed, src.state
@@ -786,7 +863,15 @@ class AbsorbingDiffusion(Sampler):
                                                   want_next=form.tail and t > 1, want_logits=record is not None, **trunc)
                 else:
                     logits = dn.logits_from_tokens(x_t, t, inp=inp)          # denoiser + reset_net (:128-129)
-                    if steps_b is not None and sched is not None:
+                    if steps_b is not None and remask is not None:
+                        ops.psample_step_conf_listed_remask(logits, x_t, unmasked, t, temp, steps_b, sample_steps, self.STEP_STRIDE,
+                                                            sched[0], *remask, noise_a=sched[1], u=u, q=q, seed=seed, offset=off,
+                                                            philox_state=state, top_k=top_k, top_p=top_p)
+                    elif remask is not None:
+                        ops.psample_step_conf_remask(logits, x_t, unmasked, t, temp, sched[0], sample_steps, *remask, noise_a=sched[1],
+                                                     u=u, q=q, seed=seed, offset=off, philox_state=state,
+                                                     next_input=inp if t > 1 else None, top_k=top_k, top_p=top_p)
+                    elif steps_b is not None and sched is not None:
                         ops.psample_step_conf_listed_sched(logits, x_t, unmasked, t, temp, steps_b, sample_steps, self.STEP_STRIDE,
                                                            sched[0], sched[1], u, q, seed, off, philox_state=state, top_k=top_k,
                                                            top_p=top_p)
@@ -942,7 +1027,7 @@ class AbsorbingDiffusion(Sampler):
         ws[1] = v
 
     def _graph_key(self, dev, b, h, w, temp, sample_steps, form, conditional, score=False, top_k=None, top_p=None, confident=False,
-                   per_image_steps=False, scheduled=False):
+                   per_image_steps=False, scheduled=False, remask=False):
         # (the two step-tail switches beside the form they feed: the key changes wherever a switch does, also where the form does not)
         dn = self._denoise_fn
         weights = tuple((p.data_ptr(), p._version) for p in list(dn.parameters()) + list(dn.buffers())) + derived_epoch(dn)
@@ -956,22 +1041,26 @@ class AbsorbingDiffusion(Sampler):
                 conditional) + (('score',) if score else ()) + (('top-k',) if top_k is not None else ()) + \
             (('top-p',) if top_p is not None else ()) + (('confident',) if confident else ()) + \
             (('per-image-steps',) if per_image_steps else ()) + \
-            (('scheduled',) if scheduled else ())                   # (sample_steps is then S, the vector's maximum; both tables are inputs)
+            (('scheduled',) if scheduled else ()) + \
+            (('remask',) if remask else ())                         # (sample_steps is then S, the vector's maximum; the tables are inputs)
 
     def _graph_body(self, g, form, temp, sample_steps):
         """What a sampler graph captures: the start state, then the step loop on the graph's buffers, noise from its state
         (a score graph: its logp / step outputs zeroed first -- the loop writes them at the revealed positions only)."""
         self._fill_start(g.x_t, g.unmasked, g.start_in)
+        if g.remask is not None:
+            g.commit_conf = self._commit_conf_start(g.unmasked)     # (allocated inside the capture: the graph's own buffer)
         if g.target is not None:
             g.target[1].zero_()
             g.target[2].zero_()
         self._reverse_steps(g.x_t, g.unmasked, form, _Noise(state=g.state), temp if g.temps is None else g.temps, sample_steps,
                             act=g.act, need=g.need, inp=g.inp, target=g.target, top_k=g.topk,
                             **({} if g.topp is None else {'top_p': g.topp}), **({'confident': True} if g.confident else {}),
-                            **({} if g.steps is None else {'steps_b': g.steps}), **({} if g.sched is None else {'sched': g.sched}))
+                            **({} if g.steps is None else {'steps_b': g.steps}), **({} if g.sched is None else {'sched': g.sched}),
+                            **({} if g.remask is None else {'remask': (g.remask, g.commit_conf)}))
 
     def _sample_graphed(self, dev, b, h, w, form, temp, sample_steps, seed, start=None, target=None, top_k=None, top_p=None,
-                        confident=False, steps_b=None, sched=None):
+                        confident=False, steps_b=None, sched=None, remask=None):
         """Capture-once / replay-many form of ``_sample_eager``; same kernels, same results for the same seed.
         ``start = (codes, keep)``: the conditional form -- the start state is a graph INPUT (two static buffers filled before
         each replay; spk_completion_state is the first node in place of the two fills) and the graph has a key of its own.
@@ -988,12 +1077,15 @@ class AbsorbingDiffusion(Sampler):
         a per-image-steps graph -- one more marker, one more input (``steps``): one graph serves every vector with
         the same maximum.  ``sched`` (the two device tables [B, S + 1] of a scheduled sample_confident()): one
         more marker, two more inputs of fixed shape -- one graph serves every schedule and every noise scale; they come as the
-        host tensors they were built as and are copied straight into the graph's buffers."""
+        host tensors they were built as and are copied straight into the graph's buffers.  ``remask`` (the host table [B, S + 1] of
+        sample_confident(remask=); then with ``sched``): one more marker, one more input; commit_conf is a buffer of
+        the graph that every replay re-initialises from the start state."""
         dn = self._denoise_fn
         key = self._graph_key(dev, b, h, w, temp, sample_steps, form, start is not None, target is not None, top_k=top_k, top_p=top_p,
                               **({'confident': True} if confident else {}),
                               **({} if steps_b is None else {'per_image_steps': True}),
-                              **({} if sched is None else {'scheduled': True}))
+                              **({} if sched is None else {'scheduled': True}),
+                              **({} if remask is None else {'remask': True}))
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= 2:                              # at most two live graphs per sampler (e.g. dense and
@@ -1002,7 +1094,8 @@ class AbsorbingDiffusion(Sampler):
                               per_image_temp=isinstance(temp, torch.Tensor), top_k=top_k is not None,
                               top_p=top_p is not None, **({'confident': True} if confident else {}),
                               **({} if steps_b is None else {'per_image_steps': True}),
-                              **({} if sched is None else {'sched_steps': sample_steps}))
+                              **({} if sched is None else {'sched_steps': sample_steps}),
+                              **({} if remask is None else {'remask': True}))
             # warm-up on a side stream (weight packing, BN terms, allocator pools, this graph's own flag workspaces), then capture
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -1036,6 +1129,8 @@ class AbsorbingDiffusion(Sampler):
         if g.sched is not None:
             g.sched[0].copy_(sched[0])
             g.sched[1].copy_(sched[1])
+        if g.remask is not None:
+            g.remask.copy_(remask)
         if start is not None:
             g.start_in[0].copy_(start[0])
             g.start_in[1].copy_(start[1])
@@ -1188,11 +1283,11 @@ class DummyModel(nn.Module):
 
     @torch.no_grad()
     def sample_step(self, x_t, unmasked, t, temp, u=None, q=None, seed=0, offset=0, philox_state=None, pre1=None,
-                    want_next=True, want_logits=False, top_k=None, top_p=None, confident=False, sched=None):
+                    want_next=True, want_logits=False, top_k=None, top_p=None, confident=False, sched=None, remask=None):
         """One DENSE reverse step of the sampler on this denoiser (R/snn_model/vq_diffusion.py:113-140 with the call of
         :128-129 inside): x_t / unmasked are updated in place from the logits of ``self(x_t, t)`` (fresh LIF state, nothing
         written back).  ``pre1``: the first layer's (spikes, counts) for this step as returned by the previous call;
-        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation); ``confident``: the tail launch is the confidence-ordered one (spk_den_step_tail_conf); ``sched = (w, a, S)``: with ``confident``, its sibling under a reveal schedule and selection noise (spk_den_step_tail_conf_sched; ``u`` is then the Gumbel uniform).  Returns (pre1 for the next step or None, logits or None)."""
+        ``want_next``: also evaluate it for step t - 1; ``temp``: a number or a per-image fp32 device tensor; ``top_k``: int32 device tensor, one k per image (top-k truncation); ``top_p``: fp32 device tensor, one p per image (nucleus truncation); ``confident``: the tail launch is the confidence-ordered one (spk_den_step_tail_conf); ``sched = (w, a, S)``: with ``confident``, its sibling under a reveal schedule and selection noise (spk_den_step_tail_conf_sched; ``u`` is then the Gumbel uniform); ``remask = (r, commit_conf, mask_id)``: with ``sched``, its sibling with remasking (spk_den_step_tail_conf_remask).  Returns (pre1 for the next step or None, logits or None)."""
         functional.reset_net(self)
         inp = None if pre1 is not None else ops.den_build_input(x_t, int(t))
         x, cnt5, x1, cnt1, which, impl, collapse = self._trunk(inp, False, pre1=pre1)
@@ -1206,6 +1301,11 @@ class DummyModel(nn.Module):
         if top_p is not None:
             trunc['top_p'] = top_p
         with ops.timed('den.tail'):
+            if confident and sched is not None and remask is not None:
+                return ops.den_step_tail_conf_remask(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, sched[0], sched[2], *remask,
+                                                     T=self.n_steps, K=conv6.out_channels, noise_a=sched[1], u=u, q=q, seed=seed,
+                                                     offset=offset, philox_state=philox_state, conv1=nxt, want_logits=want_logits,
+                                                     **trunc)
             if confident and sched is not None:
                 return ops.den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, int(t), temp, sched[0], sched[2],
                                                     T=self.n_steps, K=conv6.out_channels, noise_a=sched[1], u=u, q=q, seed=seed,

@@ -77,7 +77,7 @@ def complete_images_top_p(model, sampler, images, keep, top_p, temp=1.0, sample_
 
 @torch.no_grad()
 def complete_images_confident(model, sampler, images, keep, sample_steps=None, temp=1.0, T=16, paste=True, top_k=None, top_p=None,
-                              positions_per_step=None, schedule=None, selection_noise=None):
+                              positions_per_step=None, schedule=None, selection_noise=None, remask=None):
     """``complete_images`` with the unknown tokens revealed in the order of the denoiser's confidence (DESIGN.md §4.15;
     ``AbsorbingDiffusion.sample_confident``): every step commits the ceil(m / t) surest candidates of each image, m counting the
     positions still unknown, so a few steps serve a small hole.  ``temp`` / ``top_k`` / ``top_p`` as sample_confident() takes them.
@@ -91,7 +91,9 @@ def complete_images_confident(model, sampler, images, keep, sample_steps=None, t
     (the ``n_known`` vector, B int32) ahead of the sampler call -- the only synchronisation of this function.
     ``schedule`` / ``selection_noise``: handed to sample_confident() as given -- how many of the unknown tokens a
     step commits ('cosine': few at first, most at the end) and how much annealed Gumbel noise their order carries; both None:
-    the call made before.  The known tokens come back unchanged under every schedule and noise scale."""
+    the call made before.  The known tokens come back unchanged under every schedule and noise scale.
+    ``remask``: handed to sample_confident() as given -- how many of the tokens earlier steps filled in each step
+    returns to the masked state; the known tokens are never remasked and come back unchanged.  None: the call made before."""
     if positions_per_step is not None:
         if sample_steps is not None:
             raise ValueError("complete_images_confident: give sample_steps or positions_per_step, not both")
@@ -99,7 +101,8 @@ def complete_images_confident(model, sampler, images, keep, sample_steps=None, t
             raise ValueError(f"complete_images_confident: positions_per_step must be an int >= 1, got {positions_per_step!r}")
     return _complete(model, sampler, images, keep, temp, sample_steps, T, paste, top_k, top_p, confident=True,
                      positions_per_step=positions_per_step,
-                     **({} if schedule is None and selection_noise is None else {'schedule': schedule, 'selection_noise': selection_noise}))
+                     **({} if schedule is None and selection_noise is None else {'schedule': schedule, 'selection_noise': selection_noise}),
+                     **({} if remask is None else {'remask': remask}))
 
 
 def steps_for_holes(n_unknown, positions_per_step):

@@ -88,7 +88,7 @@ def _per_image(v):
 
 
 def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps=None, T=16, paste=True, top_k=None, top_p=None,
-                            confident=False, positions_per_step=None, schedule=None, selection_noise=None):
+                            confident=False, positions_per_step=None, schedule=None, selection_noise=None, remask=None):
     """``spkdiff.complete.complete_images`` of one job over the ranks: every rank holds the whole job's ``images`` / ``keep``,
     completes its ``shard_range`` of them as a shard of the job (``set_shard``: shared key, counters on the global image index,
     so the images do not depend on the split) and one gather returns all uint8 images [total, C, H, W] on every rank.
@@ -102,7 +102,9 @@ def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps
     image is completed as its own count alone completes it, so the images still do not depend on the split.  ``schedule`` /
     ``selection_noise`` (with ``confident``): as sample_confident() takes them -- one value for the job, or one per
     image of the whole job (a list of per-image schedules, a list of noise scales), sliced like ``temp``; an image's tables are its
-    own, so the split still changes nothing."""
+    own, so the split still changes nothing.  ``remask`` (with ``confident``): as sample_confident() takes it -- one
+    int or one table for the job, or one per image of the whole job (a list of B entries or a 2-D array), sliced like ``temp``;
+    remasking draws no new noise, so the split still changes nothing."""
     from .complete import complete_images, complete_images_confident, complete_images_top_k, complete_images_top_p
     per_image, per_image_k, per_image_p = _per_image(temp), _per_image(top_k), _per_image(top_p)
     per_image_s = confident and (isinstance(sample_steps, (list, tuple)) or getattr(sample_steps, 'ndim', 0) == 1)
@@ -114,6 +116,10 @@ def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps
     per_image_w = getattr(schedule, 'ndim', 0) == 2 or (isinstance(schedule, (list, tuple)) and any(
         v is None or isinstance(v, (str, list, tuple)) or getattr(v, 'ndim', 0) >= 1 for v in schedule))
     per_image_n = _per_image(selection_noise)
+    if remask is not None and not confident:
+        raise ValueError("complete_images_sharded: remask belongs to confident=True")
+    per_image_r = getattr(remask, 'ndim', 0) == 2 or (isinstance(remask, (list, tuple)) and any(
+        v is None or isinstance(v, (list, tuple)) or getattr(v, 'ndim', 0) >= 1 for v in remask))
 
     def generate_local(lo, hi):
         tl = temp[lo:hi] if per_image else temp
@@ -125,7 +131,8 @@ def complete_images_sharded(model, sampler, images, keep, temp=1.0, sample_steps
                                              positions_per_step=positions_per_step,
                                              **({} if schedule is None and selection_noise is None else
                                                 {'schedule': schedule[lo:hi] if per_image_w else schedule,
-                                                 'selection_noise': selection_noise[lo:hi] if per_image_n else selection_noise})
+                                                 'selection_noise': selection_noise[lo:hi] if per_image_n else selection_noise}),
+                                             **({} if remask is None else {'remask': remask[lo:hi] if per_image_r else remask})
                                              ).images_u8
         if top_p is not None:
             return complete_images_top_p(model, sampler, images[lo:hi], keep[lo:hi], top_p[lo:hi] if per_image_p else top_p, temp=tl,

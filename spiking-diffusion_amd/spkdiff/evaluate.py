@@ -213,7 +213,7 @@ def temperature_sweep_top_p(model, sampler, temps, n_per_temp, top_p, sample_ste
 
 @torch.no_grad()
 def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1.0, top_k=None, top_p=None, schedule=None,
-                     selection_noise=None):
+                     selection_noise=None, remask=None):
     """"How few steps are enough?" as ONE job: ``n_per_steps`` confidence-ordered samples for every entry of
     ``steps`` (integers >= 1) -- image ``g * n_per_steps + j`` of the job runs ``steps[g]`` steps -- through
     ``AbsorbingDiffusion.sample_confident`` with per-image step counts.  Returns (uint8 images [len(steps), n_per_steps, C, H, W],
@@ -223,7 +223,9 @@ def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1
     ``g * n_per_steps + j`` under the sweep's key, so neither ``batch`` nor the grouping changes an image.  ``temp`` / ``top_k`` /
     ``top_p``: one value for the whole job, as sample_confident() takes a number.  ``schedule`` (None, 'linear' or 'cosine': every
     image gets the named table of its own step count) and ``selection_noise`` (one tau >= 0, annealed over each image's own steps):
-    DESIGN.md §4.17, handed to every call; both None: the calls made before.  ``n_samples`` / ``global_first`` of the sampler are
+    DESIGN.md §4.17, handed to every call; both None: the calls made before.  ``remask`` (None or one int r >= 0: up to r tokens
+    per image return to the masked state at every step t >= 2 of the image's own run; a table fits one step count): DESIGN.md §4.18,
+    handed to every call.  ``n_samples`` / ``global_first`` of the sampler are
     restored."""
     n = int(n_per_steps)
     try:
@@ -237,6 +239,10 @@ def step_count_sweep(model, sampler, steps, n_per_steps, batch=256, T=16, temp=1
     if not (schedule is None or isinstance(schedule, str)):
         raise ValueError(f"step_count_sweep: schedule is None, 'linear' or 'cosine' (a table fits one step count), got {schedule!r}")
     sched = {} if schedule is None and selection_noise is None else {'schedule': schedule, 'selection_noise': selection_noise}
+    if remask is not None:
+        if isinstance(remask, bool) or not hasattr(remask, '__index__'):
+            raise ValueError(f"step_count_sweep: remask is None or one integer >= 0 (a table fits one step count), got {remask!r}")
+        sched['remask'] = remask
     if getattr(sampler, "noise_source", "philox") != "philox":
         raise ValueError("step_count_sweep: one job in several calls needs the counter-based noise (noise_source = 'philox')")
     sv = sv.to(torch.int32).cpu().repeat_interleave(n)

@@ -2127,10 +2127,11 @@ def pscore_step(logits, x0, x_t, unmasked, t, temp, logp, step=None, u=None, see
 
 
 def _den_step_tail(what, cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset, philox_state, conv1, want_logits,
-                   top_k, top_p, conf_outs=None, sched=None):
-    """The body of ``den_step_tail`` and its two confidence-ordered siblings (``what``: the caller's name; its entry point is
+                   top_k, top_p, conf_outs=None, sched=None, remask=None):
+    """The body of ``den_step_tail`` and its three confidence-ordered siblings (``what``: the caller's name; its entry point is
     ``spk_`` + that).  ``conf_outs``: None -- the plain family, launched by the form of its temperature, inside an ``active_set``
-    scope too -- or the (x0_hat, conf) of a confidence-ordered tail; ``sched``: None or its (sched_w, S, noise_a, score)."""
+    scope too -- or the (x0_hat, conf) of a confidence-ordered tail; ``sched``: None or its (sched_w, S, noise_a, score);
+    ``remask``: None or, with ``sched``, its (remask_r, commit_conf, mask_id, remasked)."""
     cnt5 = _dev(cnt5, "cnt5", torch.uint8)
     cnt1 = _dev(cnt1, "cnt1", torch.uint8)
     B, nch5, H, W, _ = cnt5.shape
@@ -2147,6 +2148,8 @@ def _den_step_tail(what, cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q
     if sched is not None:
         sched_w, S, noise_a, score = sched
         sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, images, S, t, n, what)
+    if remask is not None:
+        remask = _remask_args(*remask, images, S, n, int(K), what)
     wq, scale, bias_d = packed6
     _token_state(x_t, unmasked, n, "[B,1,h,w]")
     u, q = _step_noise(u, q, philox_state, n, int(K))
@@ -2171,6 +2174,8 @@ def _den_step_tail(what, cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q
         tail += (_p(_x0_hat_out(conf_outs[0], n)), _p(_conf_out(conf_outs[1], n)))
         if sched is not None:
             tail += (_p(sched_w), _p(noise_a), int(S), _p(score))
+        if remask is not None:
+            tail += (_p(remask[0]), _p(remask[1]), remask[2], _p(remask[3]))
         check(getattr(lib, name)(*head, _p(temp_b), _p(top_k), _p(top_p), *tail, _stream(cnt5)), name)
     return (None if x1 is None else (x1, c1o)), logits
 
@@ -2233,10 +2238,11 @@ def _x0_hat_out(x0_hat, n):
 
 
 def _psample_conf(what, logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state, top_k, top_p, next_input=None,
-                  listed=None, sched=None):
-    """The body of the four ``psample_step_conf*`` wrappers (``what``: the caller's name; its entry point is ``spk_`` + that).
+                  listed=None, sched=None, remask=None):
+    """The body of the six ``psample_step_conf*`` wrappers (``what``: the caller's name; its entry point is ``spk_`` + that).
     ``listed``: None -- the dense form, which may write ``next_input`` -- or the (steps_b, S, step_stride) of the update on the list
-    of the enclosing ``active_set`` scope, whose logits lie by slot; ``sched``: None or (sched_w, S, noise_a, score)."""
+    of the enclosing ``active_set`` scope, whose logits lie by slot; ``sched``: None or (sched_w, S, noise_a, score); ``remask``:
+    None or, with ``sched``, (remask_r, commit_conf, mask_id, remasked)."""
     logits = _dev(logits, "logits", torch.float32)
     B, K = logits.shape[0], logits.shape[1]
     HW = logits[0, 0].numel()
@@ -2255,10 +2261,14 @@ def _psample_conf(what, logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_h
     if sched is not None:
         sched_w, S, noise_a, score = sched
         sched_w, noise_a, score = _sched_args(sched_w, noise_a, score, images, S, t, n, what)
+    if remask is not None:
+        remask = _remask_args(*remask, images, S, n, K, what)
     _token_state(x_t, unmasked, n, "(updated in place)")
     u, q = _step_noise(u, q, philox_state, n, K)
     if sched is not None:                           # (the listed form has its S among the list's arguments)
         tail += (_p(sched_w), _p(noise_a), int(S), _p(score)) if listed is None else (_p(sched_w), _p(noise_a), _p(score))
+    if remask is not None:
+        tail += (_p(remask[0]), _p(remask[1]), remask[2], _p(remask[3]))
     name = "spk_" + what
     check(getattr(lib, name)(_p(logits), _p(x_t), _p(unmasked), int(t), _p(temp_b), _p(top_k), _p(top_p), _p(u), _p(q), int(seed),
                              offset, _p(philox_state), _p(_x0_hat_out(x0_hat, n)), _p(_conf_out(conf, n)), B, HW, K, *tail,
@@ -2381,6 +2391,63 @@ def den_step_tail_conf_sched(cnt5, cnt1, packed6, x_t, unmasked, t, temp, sched_
     launch.  The sibling's arguments, checks and results plus the tables and the optional ``score`` of psample_step_conf_sched."""
     return _den_step_tail("den_step_tail_conf_sched", cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset,
                           philox_state, conv1, want_logits, top_k, top_p, conf_outs=(x0_hat, conf), sched=(sched_w, S, noise_a, score))
+
+
+def _remask_args(remask_r, commit_conf, mask_id, remasked, B, S, n, K, what):
+    """The added arguments of a ``_remask`` token update: ``remask_r`` a contiguous int32 device tensor [B, S + 1]
+    (the entry points read uint32: counts >= 0 have the same bits in both), ``commit_conf`` a contiguous fp32 device tensor with one
+    entry per position (read and written in place), both taken as given; ``mask_id`` an integer outside [0, K); ``remasked`` None
+    or a contiguous uint8 / bool device tensor with one entry per position."""
+    B, S = int(B), int(S)
+    if (not isinstance(remask_r, torch.Tensor) or remask_r.dtype != torch.int32 or not remask_r.is_cuda or
+            not remask_r.is_contiguous() or tuple(remask_r.shape) != (B, S + 1)):
+        got = f"{remask_r.dtype} {tuple(remask_r.shape)} on '{remask_r.device}'" if isinstance(remask_r, torch.Tensor) else repr(type(remask_r))
+        raise ValueError(f"{what}: remask_r must be a contiguous int32 device tensor [B = {B}, S + 1 = {S + 1}], got {got}")
+    if (not isinstance(commit_conf, torch.Tensor) or commit_conf.dtype != torch.float32 or not commit_conf.is_cuda or
+            not commit_conf.is_contiguous() or commit_conf.numel() != n):
+        raise ValueError(f"{what}: commit_conf must be a contiguous fp32 device tensor with one entry per position (updated in place)")
+    if isinstance(mask_id, bool) or not hasattr(mask_id, "__index__") or 0 <= mask_id.__index__() < int(K):
+        raise ValueError(f"{what}: mask_id is an integer outside the classes 0 .. K - 1 = {int(K) - 1}, got {mask_id!r}")
+    if remasked is not None and (not isinstance(remasked, torch.Tensor) or remasked.dtype not in (torch.uint8, torch.bool) or
+                                 not remasked.is_cuda or not remasked.is_contiguous() or remasked.numel() != n):
+        raise ValueError(f"{what}: remasked must be a contiguous uint8 / bool device tensor with one entry per position")
+    return remask_r, commit_conf, mask_id.__index__(), remasked
+
+
+def psample_step_conf_remask(logits, x_t, unmasked, t, temp, sched_w, S, remask_r, commit_conf, mask_id, noise_a=None, u=None, q=None,
+                             seed=0, offset=0, x0_hat=None, conf=None, score=None, remasked=None, philox_state=None, next_input=None,
+                             top_k=None, top_p=None):
+    """``psample_step_conf_sched`` with remasking (spk_psample_step_conf_remask): after the reveal, the
+    min(remask_r[i][t], c) least trusted of image i's c earlier commits -- those with the smallest ``commit_conf``, ties to the higher
+    position; positions holding +inf, the tokens the run started with, are never revisited -- return to the masked state (x_t =
+    ``mask_id``, unmasked = 0) and draw again at the next step; nothing is remasked at t = 1.  ``commit_conf`` (fp32, one entry per
+    position, in place) receives the confidence of every position this step reveals; ``remask_r``: int32 [B, S + 1] on the device
+    (spkdiff.schedules.remask_row builds rows); ``remasked``: optional uint8 output, 1 where this step remasked (written for the
+    images with a masked position at entry).  The reveal and ``x0_hat`` / ``conf`` / ``score`` are the sibling's bit for bit."""
+    return _psample_conf("psample_step_conf_remask", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf, philox_state,
+                         top_k, top_p, next_input, sched=(sched_w, S, noise_a, score), remask=(remask_r, commit_conf, mask_id, remasked))
+
+
+def psample_step_conf_listed_remask(logits, x_t, unmasked, t, temp, steps_b, S, step_stride, sched_w, remask_r, commit_conf, mask_id,
+                                    noise_a=None, u=None, q=None, seed=0, offset=0, x0_hat=None, conf=None, score=None, remasked=None,
+                                    philox_state=None, top_k=None, top_p=None):
+    """``psample_step_conf_listed_sched`` with remasking (spk_psample_step_conf_listed_remask): the added arguments
+    of psample_step_conf_remask, all indexed by image; an image off the list, or with t above its own step count, is left as it is,
+    ``commit_conf`` included."""
+    return _psample_conf("psample_step_conf_listed_remask", logits, x_t, unmasked, t, temp, u, q, seed, offset, x0_hat, conf,
+                         philox_state, top_k, top_p, listed=(steps_b, S, step_stride), sched=(sched_w, S, noise_a, score),
+                         remask=(remask_r, commit_conf, mask_id, remasked))
+
+
+def den_step_tail_conf_remask(cnt5, cnt1, packed6, x_t, unmasked, t, temp, sched_w, S, remask_r, commit_conf, mask_id, *, T, K,
+                              noise_a=None, u=None, q=None, seed=0, offset=0, philox_state=None, conv1=None, want_logits=False,
+                              top_k=None, top_p=None, x0_hat=None, conf=None, score=None, remasked=None):
+    """``den_step_tail_conf_sched`` with remasking (spk_den_step_tail_conf_remask): conv6 on the counts, the token
+    update of ``psample_step_conf_remask`` and -- with ``conv1`` -- the next step's first layer, which reads ``mask_id`` at a
+    remasked position; one launch.  The sibling's arguments, checks and results plus the added ones of psample_step_conf_remask."""
+    return _den_step_tail("den_step_tail_conf_remask", cnt5, cnt1, packed6, x_t, unmasked, t, temp, T, K, u, q, seed, offset,
+                          philox_state, conv1, want_logits, top_k, top_p, conf_outs=(x0_hat, conf), sched=(sched_w, S, noise_a, score),
+                          remask=(remask_r, commit_conf, mask_id, remasked))
 
 
 def q_sample(x_0, t, u, num_timesteps, mask_id):

@@ -5,7 +5,10 @@ uploads the result.
 
 A table row belongs to one image and is indexed by the loop's t = 0 .. S.  An image that runs e <= S steps of its own joins the
 loop at t = e, so its row is the table of a run of e steps in entries 0 .. e; the entries above e are never read and repeat the
-last one."""
+last one.
+
+Remasking adds a third table of the same shape, the per-step remask counts (``remask_row``: zeros above e), and the
+count trajectory of a run that reveals and remasks (``run_counts_remask``)."""
 import math
 
 W_MAX = 1 << 24                # the largest weight a schedule may hold (the kernels multiply it by m <= 64 in 64-bit arithmetic)
@@ -100,6 +103,60 @@ def reveal_counts(m0, w):
         n = reveal_count(m, w[t - 1], w[t])
         out.append(n)
         m -= n
+    return out
+
+
+def remask_row(remask, e, S, what="remask"):
+    """Row of S + 1 remask counts for an image that runs e = min(its steps, S) steps, placed as ``weights_row``
+    places a schedule row: ``remask`` is None / 0 (nothing), an integer r >= 0 (up to r tokens at every step 2 <= t <= e) or a
+    sequence of e + 1 non-negative integers indexed by t whose entries 0 and 1 are 0 (S + 1 is taken too: entries above e must be
+    0, they are never read).  Entries above e are 0."""
+    e, S = _steps(e), _steps(S)
+    if e > S:
+        raise ValueError(f"{what}: an image runs at most the loop's S = {S} steps, got {e}")
+    if remask is None:
+        remask = 0
+    if isinstance(remask, bool) or isinstance(remask, (str, float)):
+        raise ValueError(f"{what}: an integer >= 0 or a table of e + 1 integers >= 0, got {remask!r}")
+    if hasattr(remask, "__index__") and getattr(remask, "ndim", 0) == 0:
+        r = remask.__index__()
+        if not 0 <= r <= 0x7FFFFFFF:
+            raise ValueError(f"{what}: a count is an integer >= 0, got {r}")
+        row = [0, 0] + [r] * (e - 1)
+    else:
+        try:
+            row = list(remask)
+        except TypeError:
+            raise ValueError(f"{what}: an integer >= 0 or a table of e + 1 integers >= 0, got {remask!r}") from None
+        for v in row:
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 0 <= v.__index__() <= 0x7FFFFFFF:
+                raise ValueError(f"{what}: a count is an integer >= 0, got {v!r}")
+        row = [v.__index__() for v in row]
+        if len(row) not in (e + 1, S + 1):
+            raise ValueError(f"{what}: a table for {e} steps holds {e + 1} counts (t = 0 .. {e}), got {len(row)}")
+        if any(row[:2]) or any(row[e + 1:]):
+            raise ValueError(f"{what}: the entries at t = 0 and t = 1 are 0 (the last step reveals what is left and remasks nothing), "
+                             f"and so are those above the image's {e} steps, got {row}")
+        row = row[:e + 1]
+    return row + [0] * (S + 1 - len(row))
+
+
+def run_counts_remask(m0, w, r):
+    """The counts of a whole run with remasking: ``w`` a table of e + 1 weights, ``r`` one of e + 1 remask counts,
+    ``m0`` the positions masked at the start -> list of e pairs (n_t, r_t) for t = e .. 1.  The revisable count at entry of step t
+    is m0 - m_t, so n_t = reveal_count(m_t, w[t - 1], w[t]), r_t = min(r[t], m0 - m_t) for t >= 2 and m_t > 0, else 0, and
+    m_(t-1) = m_t - n_t + r_t: the n sum to m0 plus the sum of the r."""
+    w = check_weights(w)
+    r = remask_row(r, len(w) - 1, len(w) - 1) if len(w) >= 2 else []
+    if len(w) < 2:
+        raise ValueError("run_counts_remask: a table holds at least two weights (t = 0, 1)")
+    m0 = int(m0)
+    m, out = m0, []
+    for t in range(len(w) - 1, 0, -1):
+        n = reveal_count(m, w[t - 1], w[t])
+        rt = min(r[t], m0 - m) if (t >= 2 and m > 0) else 0
+        out.append((n, rt))
+        m = m - n + rt
     return out
 
 
