@@ -1094,6 +1094,47 @@ long long spk_ssim_mse_ws_bytes(int N, int C, int H, int W, int window_size);
 int spk_ssim_mse(const float* img1, const float* img2, const float* window2d, double* ssim_sum_out, double* sq_sum_out,
                  void* ws_buf, int N, int C, int H, int W, int window_size, spk_stream_t stream);
 
+/* ---- sample quality: feature moments and polynomial-kernel sums (csrc/feature_stats.hip) ----------------------------- */
+/* The arithmetic R/main.py's last stage runs after its feature network (R/metric/Fid_score.py: mean and covariance for the
+ * Frechet distance; torchmetrics' KernelInceptionDistance: a polynomial-kernel MMD), on any fp32 feature matrix, on the fp64
+ * matrix cores (v_mfma_f64_16x16x4_f64).  The fp32 features are widened to fp64 in registers: every product is exact and
+ * only the accumulation rounds.  No allocation, no synchronisation, fixed-order reductions, no floating-point atomics;
+ * capturable in a hipGraph; two calls give bit-equal results.
+ *
+ * spk_feature_moments_acc: x fp32 [n, d] with row_stride >= d elements between rows; sum_inout fp64 [d] and gram_inout fp64
+ *   [d, d] (contiguous) are updated in place:  sum += sum over rows of x,  gram += x^T x.
+ *   Every element of gram is ONE chain owned by one wave: acc = gram_in; for k0 = 0, 4, 8, ...: acc = mfma(rows k0 .. k0 + 3,
+ *   acc); rows at or beyond n are fed as zeros.  No split over n, no dependence on the grid: update(A); update(B) is bit-equal
+ *   to update(cat(A, B)) when A has a multiple of 4 rows.  Every element of sum is a sequential fp64 chain over the rows in
+ *   order.  The upper 16x16 tiles are computed and mirrored: gram is written as a full, bit-symmetric matrix (and is read as
+ *   one: the state is this entry point's own).  A non-finite x[r, c] reaches sum[c] and row and column c of gram, nothing
+ *   else.  1 <= d <= SPK_FEATURE_MAX_D (SPK_ERR_UNSUPPORTED beyond), any n >= 0; n = 0 launches nothing.  Two launches.
+ *
+ * spk_poly_kernel_sums: X fp32 [n_x, d], Y fp32 [n_y, d] (contiguous); ix int32 [S, p] and iy int32 [S, q] DEVICE tables of
+ *   row numbers (rows may repeat); a NULL ix / iy means rows 0 .. p - 1 / 0 .. q - 1 and needs S = 1.  For every subset s
+ *     out[2 s]     = sum_{i < p, j < q} (gamma * <X[ix[s, i]], Y[iy[s, j]]> + coef)^degree
+ *     out[2 s + 1] = sum_{i < min(p, q)} of the terms (i, i) when `symmetric` is set (the caller passes Y = X, iy = ix: the
+ *                    diagonal of the Gram matrix), else 0.
+ *   gamma_coef_host: HOST fp64 [2] = {gamma, coef}, read before the call returns (the binding passes no fp64 by value).
+ *   v = gamma * dot + coef is one fp64 product and one sum; the power is r = v; r = r * v (degree - 1 times).  The dot product
+ *   is a chain of fp64 MFMAs over d in steps of 4 from zero.  The p x q Gram matrix is never written: each 16x16 tile is
+ *   raised to the power in registers and reduced (fixed butterfly) to one pair of fp64 partials in ws; a second launch adds each
+ *   subset's partials in a fixed order.  A non-finite feature reaches the subsets that name its row and no other.  A table is
+ *   device memory, so the host cannot check it: an entry outside [0, n) is the caller's error; the kernel reads no row for it
+ *   and that subset's results are NaN.  (spkdiff.ops checks a table that is still on the host: ValueError.)
+ *   ws: spk_poly_kernel_sums_ws_bytes(S, p, q) bytes (or the SPK_ERR_* code the call would return), 8-byte aligned, this call's
+ *   alone while it is in flight; nothing is expected of its contents.  SPK_ERR_ARG: null X / Y / out / ws, S < 1, p < 1, q < 1,
+ *   p > n_x or q > n_y without a table, a NULL table with S > 1, degree outside 1 .. SPK_POLY_KERNEL_MAX_DEGREE, a short ws;
+ *   SPK_ERR_UNSUPPORTED: d outside 1 .. SPK_FEATURE_MAX_D, S > 65535 or 2^31 macro tiles and more. */
+#define SPK_FEATURE_MAX_D 4096
+#define SPK_POLY_KERNEL_MAX_DEGREE 8
+int spk_feature_moments_acc(const float* x, long long n, int d, long long row_stride, double* sum_inout, double* gram_inout,
+                            spk_stream_t stream);
+long long spk_poly_kernel_sums_ws_bytes(int S, int p, int q);
+int spk_poly_kernel_sums(const float* X, long long n_x, const float* Y, long long n_y, int d, const int* ix_or_null,
+                         const int* iy_or_null, int S, int p, int q, const double* gamma_coef_host, int degree, int symmetric,
+                         double* out, void* ws, long long ws_bytes, spk_stream_t stream);
+
 /* ---- the plain-CNN VQVAE baseline, eval path (csrc/ann_vqvae.hip) ---------------------------------------------------- */
 /* R/snn_model/vae_model.py:548-672 (main.py --model vq-vae).  fp32 products and accumulation (fmaf, one fixed order per
  * output), deterministic, image i's result independent of B; no allocation, no synchronisation, capturable in a hipGraph.

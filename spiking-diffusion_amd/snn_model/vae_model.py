@@ -259,6 +259,15 @@ class SNN_VQVAE(nn.Module):
         L = images.shape[-1] // 4
         return idx.reshape(images.shape[0], L, L)
 
+    @torch.no_grad()
+    def encode_features(self, images, T=16):
+        """images [B,C,H,W] already normalised (images - 0.5) -> fp32 [B, h*w*D]: the encoder's read-out the quantiser searches
+        on (``_quantize_ptc(want_xm=True)``: position-major, D values per position), flattened per image -- the feature space of
+        ``spkdiff.evaluate.sample_quality_eval``.  Same launches as ``encode_images``."""
+        z_ptc = self.encoder.snn_convs.run(images, IN_TINV, final='ptc', T=T, stateful=False)['ptc']
+        _, _, xm = self.vq_layer._quantize_ptc(z_ptc, want_xm=True, want_zq=False)
+        return xm.reshape(images.shape[0], -1)
+
     def _decoder_takes_s32(self, T, h, w):
         """Will the decoder's first layer take nibble-packed spikes (the fp6 transposed-convolution kernel, csrc/vae_fp6.hip)?"""
         blocks = self.decoder.snn_convs._blocks()

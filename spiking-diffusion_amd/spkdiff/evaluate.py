@@ -11,7 +11,11 @@ own reverse process (``AbsorbingDiffusion.score``), again with one read at the e
 
 ``temperature_sweep`` is the sampling sweep of R/main.py:379-443 (per temperature: many ``abdiff.sample(temp=tem)`` calls of 16
 images, decoded) run as ONE job with a per-image temperature; ``step_count_sweep`` is its counterpart over the
-step count of confidence-ordered decoding, one job with a per-image step count."""
+step count of confidence-ordered decoding, one job with a per-image step count.
+
+``sample_quality_eval`` scores generated images against data: the Frechet distance between Gaussian fits (``FeatureStats``,
+``frechet_distance``) and the kernel distance of KID (``kernel_distance``) -- the arithmetic of R/main.py:445-529 after its feature
+network -- on a feature space of this project's own, in fp64 on the matrix cores."""
 from __future__ import annotations
 
 import math
@@ -316,3 +320,282 @@ def token_nll_eval(model, sampler, batches, temp=1.0, sample_steps=None, orders=
                 "orders": int(orders), "temps": [float(v) for v in tv.tolist()]}
     nats = -float(host.item()) / (n_images * int(orders))
     return {"bits_per_dim": nats / (math.log(2) * h * w), "nats_per_image": nats, "n_images": n_images, "orders": int(orders)}
+
+
+# ---- sample quality: Frechet and kernel distances on a feature space ----------------------------------------
+class FeatureStats:
+    """Streaming first and second moments of a feature set: ``n``, ``sum`` fp64 [d] and ``gram`` = sum of x x^T fp64 [d, d].  The
+    state is additive -- ``merge`` adds another instance's, which is what a sharded job reduces -- and mean and covariance follow
+    from it.  ``update`` takes fp32 [n, d]: a device tensor goes through ``ops.feature_moments`` (fp64 matrix cores: exact
+    products, one accumulation chain per element, so the result depends on the row order and the split of the stream into
+    updates only through the chain contract of DESIGN.md §4.19), a CPU tensor through torch's fp64 operators.  No host
+    synchronisation inside ``update`` (``n`` is counted from shapes)."""
+
+    def __init__(self, d, device="cpu"):
+        d = int(d)
+        if not 1 <= d <= ops.FEATURE_MAX_D:
+            raise ValueError(f"FeatureStats: d must be in 1 .. {ops.FEATURE_MAX_D}, got {d}")
+        self.d, self.device, self.n = d, torch.device(device), 0
+        self.sum = torch.zeros(d, dtype=torch.float64, device=self.device)
+        self.gram = torch.zeros((d, d), dtype=torch.float64, device=self.device)
+
+    def update(self, features):
+        if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[1] != self.d:
+            raise ValueError(f"FeatureStats.update: features must be [n, {self.d}], got {tuple(getattr(features, 'shape', ()))}")
+        if features.dtype != torch.float32:
+            raise ValueError(f"FeatureStats.update: features must be fp32, got {features.dtype}")
+        if features.device.type != self.device.type:
+            raise ValueError(f"FeatureStats.update: features are on '{features.device}', the state on '{self.device}'")
+        if self.device.type == "cuda":
+            ops.feature_moments(features, self.sum, self.gram)
+        elif features.shape[0]:
+            f = features.double()
+            self.sum += f.sum(dim=0)
+            self.gram += f.T @ f
+        self.n += int(features.shape[0])
+        return self
+
+    def merge(self, other):
+        if not isinstance(other, FeatureStats) or other.d != self.d:
+            raise ValueError("FeatureStats.merge: needs a FeatureStats of the same d")
+        self.sum += other.sum.to(self.device)
+        self.gram += other.gram.to(self.device)
+        self.n += other.n
+        return self
+
+    def mean(self):
+        """fp64 [d] on the state's device."""
+        if self.n < 1:
+            raise ValueError("FeatureStats.mean: no features yet")
+        return self.sum / self.n
+
+    def cov(self):
+        """The unbiased covariance, fp64 [d, d] on the state's device: (gram - sum sum^T / n) * (1 / (n - 1)), the value
+        ``np.cov(rowvar=False)`` gives (it, too, multiplies by the reciprocal).  One pass: the subtraction cancels
+        (mean / std)^2 of the leading digits, which fp64 affords for features of order one."""
+        if self.n < 2:
+            raise ValueError(f"FeatureStats.cov: needs n >= 2, has {self.n}")
+        return (self.gram - torch.outer(self.sum, self.sum) / self.n) * (1.0 / (self.n - 1))
+
+
+def _moments_np(a, what):
+    import numpy as np
+    if isinstance(a, FeatureStats):
+        if a.n < 2:
+            raise ValueError(f"frechet_distance: {what} has n = {a.n}; a covariance needs n >= 2")
+        mu, sigma = a.mean().cpu().numpy(), a.cov().cpu().numpy()
+    else:
+        mu, sigma = a
+        mu = np.atleast_1d(np.asarray(mu.cpu() if isinstance(mu, torch.Tensor) else mu, dtype=np.float64))
+        sigma = np.atleast_2d(np.asarray(sigma.cpu() if isinstance(sigma, torch.Tensor) else sigma, dtype=np.float64))
+    if mu.ndim != 1 or sigma.shape != (mu.shape[0], mu.shape[0]):
+        raise ValueError(f"frechet_distance: {what} must be (mu [d], sigma [d, d]), got {mu.shape} and {sigma.shape}")
+    if not (np.isfinite(mu).all() and np.isfinite(sigma).all()):
+        raise ValueError(f"frechet_distance: {what} has non-finite moments")
+    return mu, sigma
+
+
+def frechet_distance(a, b, convention="exact"):
+    """The Frechet distance between the Gaussians fitted to two feature sets.  ``a``, ``b``: ``FeatureStats`` or ``(mu, sigma)``
+    pairs.  The d x d eigenproblems run on the host in fp64 (numpy); they are not the hot path.
+
+    ``'exact'``: |mu1 - mu2|^2 + tr C1 + tr C2 - 2 sum sqrt(lambda(sqrt(C1) C2 sqrt(C1))), eigenvalues clipped at 0 -- the
+    distance itself (tr sqrt(C1 C2) by a symmetric eigenproblem).
+    ``'reference'``: the formula of R/metric/Fid_score.py:116-172, whose own ``sqrtm(A) = U sqrt(S) V`` from an SVD is applied
+    to the non-symmetric C1 C2; it equals the distance only when C1 and C2 commute and is kept for parity with
+    what main.py would print.
+
+    ValueError on non-finite moments or n < 2.  For n <= d the covariance has rank at most n - 1: sqrt(C1) C2 sqrt(C1) then has at
+    most n - 1 non-zero eigenvalues, the cross term is under-estimated and the value is biased upwards by an amount that depends on
+    n, so distances are comparable only between sets of the same size (the same holds, less visibly, for every finite n)."""
+    import numpy as np
+    mu1, s1 = _moments_np(a, "a")
+    mu2, s2 = _moments_np(b, "b")
+    if mu1.shape != mu2.shape:
+        raise ValueError(f"frechet_distance: the two sets have d = {mu1.shape[0]} and {mu2.shape[0]}")
+    diff = mu1 - mu2
+    if convention == "exact":
+        lam, V = np.linalg.eigh((s1 + s1.T) / 2)
+        root = (V * np.sqrt(np.clip(lam, 0.0, None))) @ V.T
+        M = root @ s2 @ root
+        tr_covmean = float(np.sqrt(np.clip(np.linalg.eigvalsh((M + M.T) / 2), 0.0, None)).sum())
+    elif convention == "reference":
+        U, S, Vh = np.linalg.svd(s1.dot(s2))
+        tr_covmean = float(np.trace(U.dot(np.diag(np.sqrt(S))).dot(Vh)))
+    else:
+        raise ValueError(f"frechet_distance: convention is 'exact' or 'reference', got {convention!r}")
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2 * tr_covmean)
+
+
+def kernel_subsets(n_x, n_y, subsets, subset_size, seed=0):
+    """The subset tables of ``kernel_distance``: (ix int32 [subsets, subset_size], iy likewise) on the host, a function of the
+    arguments alone.  One seeded host generator; for s = 0, 1, ...: the first ``subset_size`` entries of a permutation of n_x, then
+    of a permutation of n_y (without replacement, as torchmetrics' KernelInceptionDistance draws)."""
+    subsets, m = int(subsets), int(subset_size)
+    if subsets < 1 or m < 2:
+        raise ValueError(f"kernel_distance: needs subsets >= 1 and subset_size >= 2, got {subsets}, {subset_size}")
+    if m > min(n_x, n_y):
+        raise ValueError(f"kernel_distance: subset_size {m} is larger than a set ({n_x} and {n_y} samples)")
+    g = torch.Generator().manual_seed(int(seed))
+    ix = torch.empty((subsets, m), dtype=torch.int32)
+    iy = torch.empty((subsets, m), dtype=torch.int32)
+    for s in range(subsets):
+        ix[s] = torch.randperm(n_x, generator=g)[:m]
+        iy[s] = torch.randperm(n_y, generator=g)[:m]
+    return ix, iy
+
+
+def _poly_sums_host(X, Y, ix, iy, gamma, coef, degree, symmetric):
+    """``ops.poly_kernel_sums`` restated with torch's fp64 operators for CPU tensors (the materialised Gram matrix per subset)."""
+    out = torch.zeros((1 if ix is None else ix.shape[0], 2), dtype=torch.float64)
+    Xd, Yd = X.double(), Y.double()
+    for s in range(out.shape[0]):
+        v = gamma * ((Xd if ix is None else Xd[ix[s].long()]) @ (Yd if iy is None else Yd[iy[s].long()]).T) + coef
+        k = v
+        for _ in range(degree - 1):
+            k = k * v
+        out[s, 0] = k.sum()
+        if symmetric:
+            out[s, 1] = torch.diagonal(k).sum()
+    return out
+
+
+def kernel_distance(fx, fy, subsets=100, subset_size=1000, degree=3, gamma=None, coef=1.0, seed=0):
+    """The kernel distance of KID on any feature space: (mean, std) over ``subsets`` random subsets of ``subset_size`` samples a
+    side of the unbiased MMD^2 under k(a, b) = (gamma <a, b> + coef)^degree,
+        (sum k_xx + sum k_yy - tr k_xx - tr k_yy) / (m (m - 1)) - 2 sum k_xy / m^2,
+    with the defaults main.py's ``KernelInceptionDistance()`` runs with (gamma None: 1 / d); the std is the unbiased one
+    (``torch.std``; 0 for a single value).  fx, fy fp32 [n, d].  Device tensors: the subset tables (``kernel_subsets``) are
+    uploaded once and three ``ops.poly_kernel_sums`` calls serve all subsets, no Gram matrix is written, one host read at the end;
+    CPU tensors: torch fp64 operators.  ``subsets=None``: the full-set estimate (each k_xx / k_yy term over its own n (n - 1),
+    k_xy over n_x n_y), std 0.  ``subset_size`` larger than either set raises, as the torchmetrics class does.  The estimator is
+    unbiased, not non-negative: a set against itself gives 2 (sum k - m tr k) / (m^2 (m - 1)) <= 0, not 0."""
+    for t, name in ((fx, "fx"), (fy, "fy")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError(f"kernel_distance: {name} must be an fp32 [n, d] tensor")
+    d = int(fx.shape[1])
+    if fy.shape[1] != d:
+        raise ValueError(f"kernel_distance: fx has d = {d} and fy d = {int(fy.shape[1])}")
+    if not 1 <= d <= ops.FEATURE_MAX_D:
+        raise ValueError(f"kernel_distance: d must be in 1 .. {ops.FEATURE_MAX_D}, got {d}")
+    if isinstance(degree, bool) or not hasattr(degree, "__index__") or not 1 <= int(degree) <= ops.POLY_KERNEL_MAX_DEGREE:
+        raise ValueError(f"kernel_distance: degree must be an integer in 1 .. {ops.POLY_KERNEL_MAX_DEGREE}, got {degree!r}")
+    if fx.device != fy.device:
+        raise ValueError("kernel_distance: fx and fy must be on one device")
+    n_x, n_y = int(fx.shape[0]), int(fy.shape[0])
+    degree, gamma, coef = int(degree), (1.0 / d if gamma is None else float(gamma)), float(coef)
+    if subsets is None:
+        if min(n_x, n_y) < 2:
+            raise ValueError("kernel_distance: needs at least two samples a side")
+        ix = iy = None
+        mx, my = n_x, n_y
+    else:
+        ix, iy = kernel_subsets(n_x, n_y, subsets, subset_size, seed)
+        mx = my = int(subset_size)
+    if fx.is_cuda:
+        if ix is not None:
+            ix, iy = ix.to(fx.device), iy.to(fx.device)
+        kw = dict(gamma=gamma, coef=coef, degree=degree)
+        sxx = ops.poly_kernel_sums(fx, fx, ix, ix, symmetric=True, **kw)
+        syy = ops.poly_kernel_sums(fy, fy, iy, iy, symmetric=True, **kw)
+        sxy = ops.poly_kernel_sums(fx, fy, ix, iy, symmetric=False, **kw)
+    else:
+        sxx = _poly_sums_host(fx, fx, ix, ix, gamma, coef, degree, True)
+        syy = _poly_sums_host(fy, fy, iy, iy, gamma, coef, degree, True)
+        sxy = _poly_sums_host(fx, fy, ix, iy, gamma, coef, degree, False)
+    vals = mmd2_from_sums(sxx, syy, sxy, mx, my)
+    mean = vals.mean()
+    std = vals.std() if vals.numel() > 1 else torch.zeros_like(mean)
+    mean, std = torch.stack((mean, std)).cpu().tolist()
+    return mean, std
+
+
+def mmd2_from_sums(sxx, syy, sxy, mx, my):
+    """fp64 [S]: the unbiased MMD^2 of every subset from the three [S, 2] results of ``ops.poly_kernel_sums`` (mx, my samples a
+    side), in this order of operations: ((xx - tr_xx) / (mx (mx - 1)) + (yy - tr_yy) / (my (my - 1))) - 2 xy / (mx my) -- for
+    mx = my the two quotients share the divisor, as in the formula above."""
+    if mx == my:
+        return ((sxx[:, 0] - sxx[:, 1]) + (syy[:, 0] - syy[:, 1])) / (mx * (mx - 1)) - 2 * sxy[:, 0] / (mx * mx)
+    return (sxx[:, 0] - sxx[:, 1]) / (mx * (mx - 1)) + (syy[:, 0] - syy[:, 1]) / (my * (my - 1)) - 2 * sxy[:, 0] / (mx * my)
+
+
+KID_DEFAULTS = dict(subsets=100, subset_size=1000, degree=3, gamma=None, coef=1.0, seed=0)
+
+
+def _feature_fn(model, features, T):
+    """images fp32 [B,C,H,W] in [0, 1] on the device -> fp32 [B, d]."""
+    if callable(features):
+        return features
+    if features == "encoder":
+        if not hasattr(model, "encode_features"):
+            raise ValueError(f"sample_quality_eval: {type(model).__name__} has no encode_features (the 'encoder' feature space is "
+                             "the SNN_VQVAE encoder's read-out); use features='pixels' or a callable images -> [B, d]")
+        return lambda im: model.encode_features((im - 0.5).contiguous(), T)
+    if features == "pixels":
+        return lambda im: im.reshape(im.shape[0], -1).contiguous()
+    raise ValueError(f"sample_quality_eval: features is 'encoder', 'pixels' or a callable images -> [B, d], got {features!r}")
+
+
+def sample_quality_eval(model, sampler, real_batches, n_samples, draw=None, features="encoder", batch=256, T=16, kid=KID_DEFAULTS,
+                        sample_steps=None):
+    """How close are the sampler's images to data?  Frechet and kernel distances between ``real_batches`` (as for
+    ``reconstruction_eval``: images in [0, 1] or (images, labels)) and ``n_samples`` generated images, on a feature space this
+    project owns.  ``draw``: a callable (sampler, b) -> tokens of b images (any ``sample_*`` method fits in a
+    lambda); None: ``sampler.sample(1.0, sample_steps)``.  The job runs in calls of at most ``batch`` images, each a shard of the
+    job under ONE noise key, decoded with ``model.decode_tokens``.  ``features``: 'encoder' (``model.encode_features``: the
+    read-out the quantiser searches on), 'pixels' (the uint8 image divided by 255, flattened; real images are rounded to the
+    same grid) or a callable images in [0, 1] -> fp32 [B, d].  Both sides go through the uint8 image, so the real side sees the decoder's
+    quantisation too.  One ``FeatureStats`` per side; the features themselves are kept only when ``kid`` is not None (a dict of
+    ``kernel_distance`` arguments over ``KID_DEFAULTS``).  One host read per distance at the end.  Returns {"fd",
+    "fd_reference_convention", "kd_mean", "kd_std" (None without kid), "n_real", "n_generated", "d"}."""
+    device = next(model.parameters()).device
+    if device.type != "cuda":
+        raise RuntimeError("spkdiff: sample_quality_eval runs the sampler and the metrics on a ROCm device; there is no CPU path")
+    fn = _feature_fn(model, features, T)
+    n_samples, step = int(n_samples), int(batch)
+    if n_samples < 2 or step < 1:
+        raise ValueError("sample_quality_eval: needs n_samples >= 2 and batch >= 1")
+    if getattr(sampler, "noise_source", "philox") != "philox":
+        raise ValueError("sample_quality_eval: one job in several calls needs the counter-based noise (noise_source = 'philox')")
+    if kid is not None:
+        kid = {**KID_DEFAULTS, **kid}
+    if draw is None:
+        draw = lambda s, b: s.sample(1.0, sample_steps)      # noqa: E731
+    stats, kept = {}, {"real": [], "generated": []}
+
+    def take(side, u8):
+        f = fn(u8.float() / 255)
+        if f.dim() != 2 or f.dtype != torch.float32:
+            raise ValueError(f"sample_quality_eval: the feature function must return fp32 [B, d], got {f.dtype} {tuple(f.shape)}")
+        if side not in stats:
+            stats[side] = FeatureStats(f.shape[1], device)
+        stats[side].update(f)
+        if kid is not None:
+            kept[side].append(f)
+
+    with torch.no_grad():
+        for b in real_batches:
+            images = (b[0] if isinstance(b, (tuple, list)) else b).to(device).float()
+            take("real", (images.clamp(0, 1) * 255 + 0.5).to(torch.uint8))      # rounded: data that came from uint8 returns to it
+        if "real" not in stats:
+            raise ValueError("sample_quality_eval: no real batches")
+        keep = (sampler.n_samples, sampler.global_first)
+        try:
+            sampler.set_shard(0, min(step, n_samples))
+            with sampler._one_key():
+                for first in range(0, n_samples, step):
+                    count = min(step, n_samples - first)
+                    sampler.set_shard(first, count)
+                    tok = draw(sampler, count)
+                    tok = tok.reshape(count, tok.shape[-2], tok.shape[-1])
+                    take("generated", model.decode_tokens(tok, T, want_u8=True)[1])
+        finally:
+            sampler.n_samples, sampler.global_first = keep
+        real, gen = stats["real"], stats["generated"]
+        if real.d != gen.d:
+            raise ValueError(f"sample_quality_eval: real features have d = {real.d}, generated d = {gen.d}")
+        res = {"fd": frechet_distance(real, gen, "exact"), "fd_reference_convention": frechet_distance(real, gen, "reference"),
+               "kd_mean": None, "kd_std": None, "n_real": real.n, "n_generated": gen.n, "d": real.d}
+        if kid is not None:
+            res["kd_mean"], res["kd_std"] = kernel_distance(torch.cat(kept["real"]), torch.cat(kept["generated"]), **kid)
+    return res

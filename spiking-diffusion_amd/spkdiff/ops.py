@@ -5,6 +5,7 @@ All tensors must live on a ROCm device ("cuda"); CPU tensors are rejected -- the
 """
 from __future__ import annotations
 
+import ctypes
 from typing import NamedTuple
 
 import torch
@@ -1767,6 +1768,107 @@ def ssim_mse_ws(N, C, H, W, window_size, device):
     if nbytes < 0:
         check(nbytes, "spk_ssim_mse_ws_bytes")
     return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+FEATURE_MAX_D = _C["SPK_FEATURE_MAX_D"]                    # widest feature matrix of feature_moments / poly_kernel_sums
+POLY_KERNEL_MAX_DEGREE = _C["SPK_POLY_KERNEL_MAX_DEGREE"]
+
+
+def feature_moments(x, sum, gram):
+    """x fp32 [n, d] (device; rows may be strided, the columns of a row are contiguous), ``sum`` fp64 [d] and ``gram`` fp64 [d, d]
+    (contiguous device state, updated in place): sum += x.sum(0), gram += x^T x on the fp64 matrix cores
+    (spk_feature_moments_acc: exact products, one accumulation chain per element, deterministic, no host synchronisation).
+    n = 0 is a no-op.  Returns (sum, gram)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError(f"spkdiff: feature_moments: x is on '{getattr(x, 'device', type(x))}'; there is no CPU path")
+    if x.dtype != torch.float32 or x.dim() != 2:
+        raise ValueError(f"feature_moments: x must be fp32 [n, d], got {x.dtype} {tuple(x.shape)}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if d < 1:
+        raise ValueError("feature_moments: d must be >= 1")
+    if n > 1 and (x.stride(1) != 1 or x.stride(0) < d):
+        x = x.contiguous()
+    elif n <= 1 and d > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    stride = int(x.stride(0)) if n > 1 else d
+    for t, name, shape in ((sum, "sum", (d,)), (gram, "gram", (d, d))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == x.device and t.dtype == torch.float64
+                and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"feature_moments: {name} must be a contiguous fp64 {list(shape)} tensor on {x.device} (it is the "
+                             f"state the call updates in place)")
+    check(lib.spk_feature_moments_acc(_p(x), n, d, stride, _p(sum), _p(gram), _stream(x)), "spk_feature_moments_acc")
+    return sum, gram
+
+
+def _index_table(t, name, rows, device):
+    """An index table of poly_kernel_sums as a contiguous int32 [S, count] device tensor.  A table still on the host is checked
+    here (every entry in [0, rows)) and uploaded; a device table is the caller's contract (the kernel reads no row for a bad
+    entry and that subset's sums are NaN)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"poly_kernel_sums: {name} must be an int32 [S, count] tensor")
+    if not t.is_cuda:
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= rows):
+            raise ValueError(f"poly_kernel_sums: {name} names a row outside [0, {rows})")
+        t = t.to(torch.int32).to(device)
+    elif t.dtype != torch.int32:
+        raise ValueError(f"poly_kernel_sums: a device {name} must be int32")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def poly_kernel_sums_ws(S, p, q, device):
+    """A workspace for poly_kernel_sums calls of this shape (one pair of fp64 partials per 16x16 tile and subset)."""
+    nbytes = int(lib.spk_poly_kernel_sums_ws_bytes(S, p, q))
+    if nbytes < 0:
+        check(nbytes, "spk_poly_kernel_sums_ws_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def poly_kernel_sums(X, Y, ix=None, iy=None, p=None, q=None, gamma=None, coef=1.0, degree=3, symmetric=False, ws=None, out=None):
+    """X fp32 [n_x, d], Y fp32 [n_y, d] (device); ``ix`` int32 [S, p] / ``iy`` int32 [S, q] tables of row numbers (None: rows
+    0 .. p - 1 / 0 .. q - 1, one subset; p / q default to all rows) -> out fp64 [S, 2]:
+    out[s, 0] = sum_{i, j} (gamma <X[ix[s, i]], Y[iy[s, j]]> + coef)^degree, out[s, 1] = the sum of the (i, i) terms when
+    ``symmetric`` (pass Y = X and iy = ix), else 0.  gamma None: 1 / d.  One call serves all S subsets; the p x q Gram matrix is
+    never written (spk_poly_kernel_sums: fp64 matrix cores, fixed-order sums, deterministic, no host synchronisation).  ``ws``: a
+    workspace of ``poly_kernel_sums_ws`` to reuse (this call's alone while it is in flight)."""
+    for t, name in ((X, "X"), (Y, "Y")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"spkdiff: poly_kernel_sums: {name} is on '{getattr(t, 'device', type(t))}'; there is no CPU path")
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise ValueError(f"poly_kernel_sums: {name} must be fp32 [n, d], got {t.dtype} {tuple(t.shape)}")
+    if X.shape[1] != Y.shape[1] or X.device != Y.device:
+        raise ValueError(f"poly_kernel_sums: X {tuple(X.shape)} and Y {tuple(Y.shape)} must share d and the device")
+    X = X if X.is_contiguous() else X.contiguous()
+    Y = Y if Y.is_contiguous() else Y.contiguous()
+    n_x, n_y, d = int(X.shape[0]), int(Y.shape[0]), int(X.shape[1])
+    if ix is not None:
+        ix = _index_table(ix, "ix", n_x, X.device)
+    if iy is not None:
+        iy = _index_table(iy, "iy", n_y, X.device)
+    if (ix is None) != (iy is None) and (ix if ix is not None else iy).shape[0] != 1:
+        raise ValueError("poly_kernel_sums: one table alone needs S = 1")
+    if ix is not None and iy is not None and ix.shape[0] != iy.shape[0]:
+        raise ValueError(f"poly_kernel_sums: ix has {ix.shape[0]} subsets and iy {iy.shape[0]}")
+    S = int(ix.shape[0]) if ix is not None else int(iy.shape[0]) if iy is not None else 1
+    p = int(ix.shape[1]) if ix is not None else n_x if p is None else int(p)
+    q = int(iy.shape[1]) if iy is not None else n_y if q is None else int(q)
+    gc = (ctypes.c_double * 2)(1.0 / d if gamma is None else float(gamma), float(coef))
+    nbytes = int(lib.spk_poly_kernel_sums_ws_bytes(S, p, q))
+    if nbytes < 0:
+        check(nbytes, "spk_poly_kernel_sums_ws_bytes")
+    if ws is None:
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=X.device)
+    elif not (ws.is_cuda and ws.device == X.device and ws.is_contiguous() and ws.data_ptr() % 8 == 0
+              and ws.numel() * ws.element_size() >= nbytes):
+        raise ValueError(f"poly_kernel_sums: ws must be a contiguous 8-byte aligned device buffer of at least {nbytes} bytes")
+    if out is None:
+        out = torch.empty((S, 2), dtype=torch.float64, device=X.device)
+    elif not (out.is_cuda and out.device == X.device and out.dtype == torch.float64 and out.is_contiguous()
+              and tuple(out.shape) == (S, 2)):
+        raise ValueError(f"poly_kernel_sums: out must be a contiguous fp64 [{S}, 2] device tensor")
+    check(lib.spk_poly_kernel_sums(_p(X), n_x, _p(Y), n_y, d, _p(ix), _p(iy), S, p, q, ctypes.addressof(gc), int(degree),
+                                   int(bool(symmetric)), _p(out), _p(ws), ws.numel() * ws.element_size(), _stream(X)),
+          "spk_poly_kernel_sums")
+    return out
 
 
 def _vq_train_ws(device):
